@@ -67,7 +67,12 @@ def parse():
                     "(extra `pyramid8` object; off by default so that a profile of the default command sees one launch "
                     "shape per kernel)")
     ap.add_argument("--no-pyramid", action="store_true", help="accepted for older scripts; the default already")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step returned "
+                    "(rank 0's shard) as DIR/<name>.npy for comparing two builds output for output (dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def usable_cores():
@@ -140,6 +145,68 @@ def measured_counters(kernel, frames):
         return None, None, None
 
 
+DUMP_FRAMES = 64           # frames of the stream sampled by --dump-outputs: ~25 MB at 2000 keypoints per image
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir):
+    """Writes the FrontendResult of the last timed step as out_dir/<name>.npy, float64 (every value is an integer below
+    2^53, so exact), for a fixed seeded sample of frames (`frames`, indices into the rank's stream; image rows 2f, 2f + 1,
+    stereo rows f, track rows f for f < n_frames - 1).  Descriptors are split into eight 32-bit words.  Keypoint slots at
+    or past their image's kp_count hold no result and are written as -1, so that two builds compare equal on everything
+    a caller may read."""
+    import numpy as np
+    F, dev = res.n_frames, res.kp_keys.device
+    frames = np.sort(np.random.default_rng(0).choice(F, size=min(F, DUMP_FRAMES), replace=False))
+    tracked = frames[frames < F - 1]
+    images = np.stack([2 * frames, 2 * frames + 1], 1).ravel()
+
+    def rows(t, idx):
+        return t[torch.from_numpy(idx).to(dev)].cpu().numpy()
+
+    count = rows(res.kp_count, images)
+    valid = np.arange(res.kp_keys.shape[1])[None, :] < count[:, None]          # [image, slot]
+    stereo_valid, track_valid = valid[0::2], valid[0::2][frames < F - 1]      # query image = left image of frame f
+
+    def masked(a, ok):
+        a = a.astype(np.float64)
+        a[~ok] = -1.0                                # ok: [row, slot], leading axes of a
+        return a
+
+    out = {
+        "frames": frames.astype(np.float64),
+        "kp_count": count.astype(np.float64),
+        "cand_count": rows(res.cand_count, images).astype(np.float64),
+        "kp_keys": rows(res.kp_keys, images).astype(np.float64),
+        "desc": masked(rows(res.desc, images).view(np.uint32), valid),
+        "angle": masked(rows(res.angle, images), valid),
+        "stereo_idx": masked(rows(res.stereo_idx, frames), stereo_valid),
+        "stereo_dist": masked(rows(res.stereo_dist, frames), stereo_valid),
+        "track_idx": masked(rows(res.track_idx, tracked), track_valid),
+        "track_dist": masked(rows(res.track_dist, tracked), track_valid),
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def native_oracle():
+    """The -O3 -march=native build of the C port for the cpu_baseline legs, made on this machine in a private temporary
+    directory (removed once loaded): the checkout bench.py runs from need not be writable.  It becomes the oracle module's
+    native library, so every O.lib(native=True) of this process (oracle/ba_port.py included) uses it."""
+    import ctypes
+    import tempfile
+    from oracle import oracle as O
+    if O._native is None:
+        with tempfile.TemporaryDirectory(prefix="vus_oracle_native_") as d:
+            path = os.path.join(d, "libvus_oracle_native.so")
+            O.build("native", f"NATIVE_LIB={path}")
+            O._native = ctypes.CDLL(path)
+    return O._native
+
+
 def cpu_baseline_frontend(t0, cores, requested_frames):
     """M1 on the host CPU.  OpenCV (the engine the reference's nodelet runs) if this machine has it, else the C port
     (-O3 -march=native build made here, OpenMP over images).  1 thread and all usable cores, median of 5 after a
@@ -169,7 +236,7 @@ def cpu_baseline_frontend(t0, cores, requested_frames):
             return out
         except Exception as e:
             out["cv2_error"] = str(e)
-    lib = O.lib(native=True)
+    lib = native_oracle()
 
     def run(n, threads):
         lib.vus_oracle_set_threads(threads)
@@ -216,6 +283,7 @@ def cpu_baseline_ba(seq, cores, gpu_seconds):
             return out
         except Exception as e:
             out["gtsam_error"] = str(e)
+    native_oracle()                                                # BAPort(native=True) loads it through O.lib
     pk = ba_pack.pack_observations(torch.from_numpy(seq["obs_pose"]), torch.from_numpy(seq["obs_point"]),
                                    torch.from_numpy(seq["meas"]), n_kf, nL)
     st = ba_pack.build_structure(pk)
@@ -320,6 +388,7 @@ def main():
             pending.append(vdist.gather_tracks_start(*vdist.owned_track_records(res, n_owned), n_stream, world, rank))
             while len(pending) > 1:
                 vdist.gather_tracks_finish(pending.pop(0))
+        return res
 
     def drain():
         while pending:
@@ -341,12 +410,15 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        res = step()
     drain()
     barrier()
     dt = time.perf_counter() - t0
     fe.stage_hook = None
     fe.check_overflow()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(res, a.dump_outputs)
+    del res
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

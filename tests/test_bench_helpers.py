@@ -4,6 +4,7 @@ import json
 import os
 import types
 
+import numpy as np
 import pytest
 
 import bench
@@ -46,18 +47,86 @@ def test_measured_counters_reads_the_committed_pmc_summary():
     assert bench.measured_counters("hamming_track", 10)[0] > 0
 
 
+DUMP_NAMES = ("frames", "kp_count", "cand_count", "kp_keys", "desc", "angle", "stereo_idx", "stereo_dist", "track_idx",
+              "track_dist")
+
+
+def test_dump_outputs_writes_a_seeded_sample_of_the_last_step(tmp_path):
+    """bench.dump_outputs on a stand-in FrontendResult (CPU tensors, 100 frames, 6 keypoint slots): a fixed sample of
+    DUMP_FRAMES frames, image rows 2f / 2f + 1, float64 with every integer exact, descriptors as 32-bit words, and -1 in
+    every slot at or past the image's kp_count."""
+    import torch
+    F, K = 100, 6
+    g = torch.Generator().manual_seed(1)
+    res = types.SimpleNamespace(
+        n_frames=F, kp_count=torch.randint(0, K + 1, (2 * F,), dtype=torch.int32, generator=g),
+        cand_count=torch.randint(0, 1 << 20, (2 * F,), dtype=torch.int32, generator=g),
+        kp_keys=torch.randint(-(1 << 31), 1 << 31, (2 * F, K), dtype=torch.int32, generator=g),
+        desc=torch.randint(-(1 << 63), (1 << 63) - 1, (2 * F, K, 4), dtype=torch.int64, generator=g),
+        angle=torch.randint(0, 30, (2 * F, K), dtype=torch.uint8, generator=g),
+        stereo_idx=torch.randint(-1, K, (F, K), dtype=torch.int32, generator=g),
+        stereo_dist=torch.randint(0, 257, (F, K), dtype=torch.int32, generator=g),
+        track_idx=torch.randint(-1, K, (F - 1, K), dtype=torch.int32, generator=g),
+        track_dist=torch.randint(0, 257, (F - 1, K), dtype=torch.int32, generator=g))
+    bench.dump_outputs(res, str(tmp_path / "a"))
+    bench.dump_outputs(res, str(tmp_path / "b"))
+    d = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in DUMP_NAMES}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in DUMP_NAMES)
+    assert all(a.dtype == np.float64 for a in d.values())
+    for n in DUMP_NAMES:                                                      # the sample does not change between runs
+        assert np.array_equal(d[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    f = d["frames"].astype(np.int64)
+    assert len(f) == bench.DUMP_FRAMES and (np.diff(f) > 0).all() and 0 <= f[0] and f[-1] < F
+    img = np.stack([2 * f, 2 * f + 1], 1).ravel()
+    cnt = res.kp_count.numpy()[img]
+    valid = np.arange(K)[None, :] < cnt[:, None]
+    assert np.array_equal(d["kp_count"], cnt) and np.array_equal(d["cand_count"], res.cand_count.numpy()[img])
+    assert np.array_equal(d["kp_keys"], res.kp_keys.numpy()[img])
+    words = res.desc.numpy()[img].view(np.uint32)
+    assert np.array_equal(d["desc"][valid], words[valid]) and (d["desc"][~valid] == -1).all()
+    assert np.array_equal(d["angle"][valid], res.angle.numpy()[img][valid]) and (d["angle"][~valid] == -1).all()
+    sv = valid[0::2]
+    for n in ("stereo_idx", "stereo_dist"):
+        assert np.array_equal(d[n][sv], getattr(res, n).numpy()[f][sv]) and (d[n][~sv] == -1).all()
+    t = f < F - 1
+    for n in ("track_idx", "track_dist"):
+        assert d[n].shape == (t.sum(), K)
+        assert np.array_equal(d[n][sv[t]], getattr(res, n).numpy()[f[t]][sv[t]]) and (d[n][~sv[t]] == -1).all()
+
+
+def test_native_oracle_is_built_outside_the_checkout():
+    """The cpu_baseline legs' -march=native C port is built in a temporary directory, not in oracle/ (the checkout
+    bench.py runs from need not be writable), and it is what O.lib(native=True) returns afterwards (oracle/ba_port.py).
+    A fresh process: the oracle module of this one may already hold a native library."""
+    import subprocess
+    import sys
+    before = sorted(os.listdir(os.path.join(ROOT, "oracle")))
+    code = ("import bench; from oracle import oracle as O; lib = bench.native_oracle(); "
+            "assert O.lib(native=True) is lib and bench.native_oracle() is lib; lib.vus_oracle_set_threads(1)")
+    r = subprocess.run([sys.executable, "-B", "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(os.path.join(ROOT, "oracle"))) == before
+
+
 @pytest.mark.gpu
-def test_bench_command_line_contract_on_a_small_stream(gpu):
+def test_bench_command_line_contract_on_a_small_stream(gpu, tmp_path):
     """`python bench.py` end to end (the driver's command, with a small stream so that it takes seconds): ONE JSON line
     with the contract's keys, the roofline object of the dominant kernel and the BA legs."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "24", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900,
+                       cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
     j = json.loads(lines[0])
+    # the last timed step's outputs: all 24 frames (fewer than DUMP_FRAMES), every image at its 2000 keypoints
+    d = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in DUMP_NAMES}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert np.array_equal(d["frames"], np.arange(24)) and d["kp_count"].shape == (48,) and (d["kp_count"] == 2000).all()
+    assert d["desc"].shape == (48, 2000, 8) and d["track_idx"].shape == (23, 2000)
+    assert (d["stereo_idx"] >= 0).mean() > 0.1 and (d["track_idx"] >= 0).mean() > 0.1
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in j, k
