@@ -509,4 +509,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 #ifdef __cplusplus
 }
 #endif
+
+/* Robust noise models of the stereo factors (Huber, Cauchy, Tukey, Geman-McClure, Welsch): vus_ba_loss and the
+ * `_robust` twins of vus_ba_linearize / vus_ba_eval_step / vus_ba_error, plus vus_ba_stereo_weights. */
+#include "vus_robust.h"
 #endif /* VUS_H */

@@ -44,6 +44,11 @@ SIGNATURES = {
     "vus_ba_band_solve_multi": [_P, c_int, c_int, _P, c_int, _P, _P],
     "vus_ba_band_solve_split": [_P, c_int, c_int, _P, _P, _P, _P, _P],
     "vus_ba_band_solve_multi_split": [_P, c_int, c_int, _P, c_int, _P, _P, _P],
+    # robust noise models of the stereo factors (include/vus_robust.h)
+    "vus_ba_linearize_robust": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_eval_step_robust": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_error_robust": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_stereo_weights": [_P, _P, _P, _P, _P, _P],
     # graph packing (csrc/pack.hip)
     "vus_imu_preintegrate": [_P, _P, c_int, _P, _P, _P, _P],      # host pointers
     "vus_keys_to_indices": [_P, c_int, _P, _P, _P, _P, ctypes.c_longlong, _P],

@@ -28,6 +28,34 @@ class _CProblem(ctypes.Structure):
                 ("prior_T", c_void_p), ("prior_w", c_void_p), ("pose_stride", c_int)]
 
 
+class _CLoss(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("k", c_double)]
+
+
+# VUS_LOSS_* of include/vus_robust.h: robust noise models of the stereo factors (GTSAM mEstimator, Block reweighting)
+LOSS_KINDS = {"gaussian": 0, "huber": 1, "cauchy": 2, "tukey": 3, "geman_mcclure": 4, "welsch": 5}
+
+
+def robust_loss(loss):
+    """None, a kind name / VUS_LOSS_* number with its parameter `(kind, k)`, or an object with `.kind` and `.k`
+    (gtsam.noiseModel.mEstimator.*) -> (kind number, k); (0, 0.0) is the plain Gaussian model."""
+    if loss is None:
+        return 0, 0.0
+    kind, k = (loss.kind, loss.k) if hasattr(loss, "kind") else loss
+    if isinstance(kind, str):
+        if kind.lower() not in LOSS_KINDS:
+            raise ValueError(f"unknown robust loss {kind!r} (one of {', '.join(LOSS_KINDS)})")
+        kind = LOSS_KINDS[kind.lower()]
+    kind, k = int(kind), float(k)
+    if not 0 <= kind <= 5:
+        raise ValueError(f"unknown robust loss kind {kind}")
+    if kind == 0:
+        return 0, 0.0
+    if not (math.isfinite(k) and k > 0.0):
+        raise ValueError(f"robust loss parameter k={k} must be finite and > 0")
+    return kind, k
+
+
 class _CTiles(ctypes.Structure):
     _fields_ = [("band", c_int), ("n_tiles", c_int), ("n_units", c_int), ("n_entries", c_int),
                 ("unit_ptr", c_void_p), ("entries", c_void_p), ("order", c_void_p)]
@@ -62,6 +90,7 @@ class LMReport:
     lambda_hist: List[float] = field(default_factory=list)
     seconds: float = 0.0
     setup_seconds: float = 0.0
+    stereo_weights: Optional[tuple] = None     # gtsam shim, robust stereo factors: (pose keys, landmark keys, final w)
 
 
 def _i32(t):
@@ -115,10 +144,11 @@ def build_tiles_device(pk, band):
 
 
 class StereoBAProblem:
-    """Packed, device-resident stereo BA problem (vus_ba_problem + vus_ba_tiles)."""
+    """Packed, device-resident stereo BA problem (vus_ba_problem + vus_ba_tiles).  `loss`: robust noise model of the
+    stereo factors (robust_loss(): None = Gaussian, or e.g. ("cauchy", 2.0) with k in whitened units)."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None,
-                 prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1):
+                 prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None):
         _lib.require_gpu()
         _lib.load()
         dev = torch.device(device)
@@ -148,6 +178,9 @@ class StereoBAProblem:
         self.K = to_dev(K, torch.float64)
         assert self.K.numel() == 6
         self.sigma = float(sigma)
+        self.loss = robust_loss(loss)
+        self.robust = self.loss[0] != 0           # the Gaussian model keeps today's entry points
+        self.c_loss = _CLoss(*self.loss)
         if prior_pose is None or len(prior_pose) == 0:
             self.prior_pose = torch.zeros(0, dtype=torch.int32, device=dev)
             self.prior_T = torch.zeros((0, 12), dtype=torch.float64, device=dev)
@@ -218,15 +251,33 @@ class StereoBASolver:
     def _pp(self):
         return ctypes.addressof(self.P.c_problem)
 
+    def _loss_args(self, name):
+        """(entry point, trailing arguments): the `_robust` twin with the problem's vus_ba_loss for a robust model"""
+        return (name + "_robust", (ctypes.addressof(self.P.c_loss),)) if self.P.robust else (name, ())
+
     def error(self, poses, points) -> float:
-        _lib.call("vus_ba_error", self._pp(), _lib.ptr(poses), _lib.ptr(points), _lib.ptr(self.scal),
-                  _lib.ptr(self.work), _lib.current_stream_ptr())
+        """Nonlinear error of the stereo factors (sum of rho(d) under a robust model) and priors."""
+        fn, extra = self._loss_args("vus_ba_error")
+        _lib.call(fn, self._pp(), _lib.ptr(poses), _lib.ptr(points), _lib.ptr(self.scal),
+                  _lib.ptr(self.work), _lib.current_stream_ptr(), *extra)
         return float(self.scal[0].item())
 
     def linearize(self, poses, points):
+        """scal[0] = the linear system's error at delta = 0 (0.5 sum w d^2 under a robust model)."""
         p = _lib.ptr
-        _lib.call("vus_ba_linearize", self._pp(), p(poses), p(points), p(self.W), p(self.V), p(self.gl),
-                  p(self.Hpp), p(self.gp), p(self.scal), p(self.work), _lib.current_stream_ptr())
+        fn, extra = self._loss_args("vus_ba_linearize")
+        _lib.call(fn, self._pp(), p(poses), p(points), p(self.W), p(self.V), p(self.gl),
+                  p(self.Hpp), p(self.gp), p(self.scal), p(self.work), _lib.current_stream_ptr(), *extra)
+
+    def stereo_weights(self, poses, points) -> torch.Tensor:
+        """Robust weight w(d) of every stereo observation at (poses, points), in the problem's INPUT row order (all ones
+        under the Gaussian model): inliers near 1, gross outliers near 0."""
+        w = torch.empty(self.P.n_obs, dtype=torch.float64, device=self.P.device)
+        _lib.call("vus_ba_stereo_weights", self._pp(), ctypes.addressof(self.P.c_loss), _lib.ptr(poses), _lib.ptr(points),
+                  _lib.ptr(w), _lib.current_stream_ptr())
+        out = torch.empty_like(w)
+        out[self.P.pk["perm"].to(torch.int64)] = w               # perm: L-order row -> input row
+        return out
 
     def schur(self, lam: float, Y=None):
         """Y: optional [n_obs,18] buffer that receives W Vinv (L-order); the kernel forms it on the fly and needs no
@@ -269,8 +320,9 @@ class StereoBASolver:
 
     def eval_step(self, poses, points):
         p = _lib.ptr
-        _lib.call("vus_ba_eval_step", self._pp(), p(poses), p(points), p(self.dp), p(self.dl), p(self.new_poses),
-                  p(self.new_points), p(self.scal[1:]), p(self.work), _lib.current_stream_ptr())
+        fn, extra = self._loss_args("vus_ba_eval_step")
+        _lib.call(fn, self._pp(), p(poses), p(points), p(self.dp), p(self.dl), p(self.new_poses),
+                  p(self.new_points), p(self.scal[1:]), p(self.work), _lib.current_stream_ptr(), *extra)
 
     # -- Levenberg-Marquardt ----------------------------------------------------------------------
     def optimize(self, poses: torch.Tensor, points: torch.Tensor, params: Optional[LMParams] = None,

@@ -269,12 +269,61 @@ __device__ __forceinline__ double sym3(const double* v, int r, int c) {
   return v[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
 }
 
+// Robust noise model (include/vus_robust.h): weight w and loss rho of a stereo factor from its squared whitened
+// residual norm d2 = d^2.  Every kernel that reweights a factor calls this on the same d2 expression, so W / V (lin_points),
+// Hpp / gp (lin_poses) and the linear error (eval_points) describe one weighted system.
+template <int LOSS>
+__device__ __forceinline__ void robust_weight(double d2, double k, double& w, double& rho) {
+  const double k2 = k * k;
+  if (LOSS == VUS_LOSS_HUBER) {
+    const double d = sqrt(d2);
+    w = d <= k ? 1.0 : k / d;
+    rho = d <= k ? 0.5 * d2 : k * d - 0.5 * k2;
+  } else if (LOSS == VUS_LOSS_CAUCHY) {
+    w = k2 / (k2 + d2);
+    rho = 0.5 * k2 * log1p(d2 / k2);
+  } else if (LOSS == VUS_LOSS_TUKEY) {
+    const double t = 1.0 - d2 / k2;
+    w = d2 <= k2 ? t * t : 0.0;
+    rho = d2 <= k2 ? (k2 / 6.0) * (1.0 - t * t * t) : k2 / 6.0;
+  } else if (LOSS == VUS_LOSS_GEMAN_MCCLURE) {
+    const double s = k2 + d2;
+    w = (k2 * k2) / (s * s);
+    rho = 0.5 * k2 * d2 / s;
+  } else if (LOSS == VUS_LOSS_WELSCH) {
+    w = exp(-d2 / k2);
+    rho = -0.5 * k2 * expm1(-d2 / k2);
+  } else {
+    w = 1.0;
+    rho = 0.5 * d2;
+  }
+}
+
+// IRLS (Block reweighting): scale a factor's whitened residual and Jacobian rows by sqrt(w), w from its own residual
+template <int LOSS, bool WITH_H1, bool WITH_H2>
+__device__ __forceinline__ void robust_reweight(double k, double* r, double* H1, double* H2) {
+  double w, rho;
+  robust_weight<LOSS>(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], k, w, rho);
+  const double s = sqrt(w);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) r[q] *= s;
+  if (WITH_H1)
+#pragma unroll
+    for (int q = 0; q < 18; ++q) H1[q] *= s;
+  if (WITH_H2)
+#pragma unroll
+    for (int q = 0; q < 9; ++q) H2[q] *= s;
+}
+
 // ---------------------------------------------------------------------------------------------
-// linearisation
+// linearisation (LOSS = VUS_LOSS_*: the Gaussian instance is the plain statement, a robust one reweights every factor
+// before the products; loss_k = the mEstimator's parameter, unused by the Gaussian instance)
+template <int LOSS>
 __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                          const double* __restrict__ points,
                                                          double* __restrict__ W, double* __restrict__ V,
-                                                         double* __restrict__ gl, double* __restrict__ err_part) {
+                                                         double* __restrict__ gl, double* __restrict__ err_part,
+                                                         double loss_k) {
   const int lane = threadIdx.x & 63;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= P.n_points) return;
@@ -287,7 +336,8 @@ __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const
     load12(poses + 12 * (size_t)P.obs_pose[a], T);
     const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
     stereo_factor<true, true>(T, p, m, K, r, H1, H2);
-    e += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, true>(loss_k, r, H1, H2);
+    e += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);      // robust: 0.5 w d^2, the linear error at delta = 0
     double* Wa = W + 18 * (size_t)a;
 #pragma unroll
     for (int rr = 0; rr < 6; ++rr)
@@ -315,9 +365,11 @@ __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const
   }
 }
 
+template <int LOSS>
 __global__ __launch_bounds__(256) void lin_poses_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                         const double* __restrict__ points,
-                                                        double* __restrict__ Hpp, double* __restrict__ gp) {
+                                                        double* __restrict__ Hpp, double* __restrict__ gp,
+                                                        double loss_k) {
   __shared__ double s_part[4][27];
   const int i = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -335,6 +387,7 @@ __global__ __launch_bounds__(256) void lin_poses_kernel(vus_ba_problem P, const 
     const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
     double r[3], H1[18];
     stereo_factor<true, false>(T, p, m, K, r, H1, nullptr);
+    if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, false>(loss_k, r, H1, nullptr);
     int u = 0;
 #pragma unroll
     for (int rr = 0; rr < 6; ++rr)
@@ -2530,13 +2583,15 @@ __global__ void retract_kernel(int n_poses, int n_points, int ps, const double* 
 
 // per point: part_lin[j] = 0.5 sum |r + H1 dp + H2 dl|^2 at the old values,
 //            part_new[j] = 0.5 sum |r|^2 at the new values
-template <bool WITH_LIN>
+// robust LOSS: r, H1, H2 at the old values reweighted by sqrt(w(old)) (the linearisation point), part_new = sum rho
+template <bool WITH_LIN, int LOSS = VUS_LOSS_GAUSSIAN>
 __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                           const double* __restrict__ points,
                                                           const double* __restrict__ dp, const double* __restrict__ dl,
                                                           const double* __restrict__ new_poses,
                                                           const double* __restrict__ new_points,
-                                                          double* __restrict__ part_lin, double* __restrict__ part_new) {
+                                                          double* __restrict__ part_lin, double* __restrict__ part_new,
+                                                          double loss_k) {
   const int lane = threadIdx.x & 63;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= P.n_points) return;
@@ -2557,11 +2612,18 @@ __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, cons
     double T[12], r[3];
     load12(new_poses + 12 * (size_t)i, T);
     stereo_factor<false, false>(T, pn, m, K, r, nullptr, nullptr);
-    e_new += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    if (LOSS == VUS_LOSS_GAUSSIAN) {
+      e_new += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    } else {
+      double w, rho;
+      robust_weight<LOSS>(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], loss_k, w, rho);
+      e_new += rho;
+    }
     if (WITH_LIN) {
       double H1[18], H2[9];
       load12(poses + 12 * (size_t)i, T);
       stereo_factor<true, true>(T, po, m, K, r, H1, H2);
+      if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, true>(loss_k, r, H1, H2);
       const double* d = dp + 6 * (size_t)pose_stride(P) * i;
 #pragma unroll
       for (int rr = 0; rr < 3; ++rr) {
@@ -2600,6 +2662,120 @@ int check_problem(const vus_ba_problem* P) {
 
 inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
 
+// w [n_obs] (L-order) of every stereo observation at (poses, points), thread / observation
+template <int LOSS>
+__global__ __launch_bounds__(256) void stereo_weights_kernel(vus_ba_problem P, const double* __restrict__ poses,
+                                                             const double* __restrict__ points, double* __restrict__ w_out,
+                                                             double loss_k) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= P.n_obs) return;
+  const Calib K = load_calib(P.K, P.inv_sigma);
+  const int j = P.obs_point[a];
+  const double p[3] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
+  const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
+  double T[12], r[3], w, rho;
+  load12(poses + 12 * (size_t)P.obs_pose[a], T);
+  stereo_factor<false, false>(T, p, m, K, r, nullptr, nullptr);
+  robust_weight<LOSS>(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], loss_k, w, rho);
+  w_out[a] = w;
+}
+
+int check_loss(const vus_ba_loss* L) {
+  VUS_REQUIRE(L != nullptr, "loss is null");
+  VUS_REQUIRE(L->kind >= VUS_LOSS_GAUSSIAN && L->kind <= VUS_LOSS_WELSCH, "unknown loss kind %d", L->kind);
+  VUS_REQUIRE(L->kind == VUS_LOSS_GAUSSIAN || (L->k > 0.0 && L->k <= 1.7976931348623157e308),
+              "loss parameter k=%g must be finite and > 0", L->k);
+  return VUS_OK;
+}
+
+// one instance of F<LOSS> per kind, chosen at run time (the loss was validated by check_loss)
+template <template <int> class F, typename... A>
+int dispatch_loss(const vus_ba_loss* L, A... args) {
+  switch (L->kind) {
+    case VUS_LOSS_HUBER: return F<VUS_LOSS_HUBER>::run(L->k, args...);
+    case VUS_LOSS_CAUCHY: return F<VUS_LOSS_CAUCHY>::run(L->k, args...);
+    case VUS_LOSS_TUKEY: return F<VUS_LOSS_TUKEY>::run(L->k, args...);
+    case VUS_LOSS_GEMAN_MCCLURE: return F<VUS_LOSS_GEMAN_MCCLURE>::run(L->k, args...);
+    case VUS_LOSS_WELSCH: return F<VUS_LOSS_WELSCH>::run(L->k, args...);
+    default: return F<VUS_LOSS_GAUSSIAN>::run(0.0, args...);
+  }
+}
+
+template <int LOSS>
+struct ErrorOp {
+  static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* err,
+                 double* work, void* stream) {
+    if (int rc = check_problem(P)) return rc;
+    VUS_REQUIRE(poses && (points || !P->n_points) && err && work, "null buffer");
+    hipStream_t st = vus::as_stream(stream);
+    const int nL = P->n_points;
+    if (nL > 0)
+      eval_points_kernel<false, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
+                                                                  nullptr, work, k);
+    priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, nullptr, nullptr, work + nL, 1);
+    reduce_partials_kernel<<<1, 1024, 0, st>>>(work, nL + 1, err);
+    VUS_CHECK_LAUNCH("ba_error");
+    return VUS_OK;
+  }
+};
+
+template <int LOSS>
+struct LinearizeOp {
+  static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* W, double* V,
+                 double* gl, double* Hpp, double* gp, double* err, double* work, void* stream) {
+    if (int rc = check_problem(P)) return rc;
+    // a graph without landmarks (priors only) has empty per-landmark / per-observation arrays: those may be null
+    VUS_REQUIRE(poses && Hpp && gp && err && work, "null buffer");
+    VUS_REQUIRE((points && V && gl) || !P->n_points, "null landmark buffer");
+    VUS_REQUIRE(W || !P->n_obs, "null observation buffer");
+    hipStream_t st = vus::as_stream(stream);
+    const int nL = P->n_points;
+    if (nL > 0) lin_points_kernel<LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k);
+    lin_poses_kernel<LOSS><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k);
+    priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, Hpp, gp, work + nL, 0);
+    reduce_partials_kernel<<<1, 1024, 0, st>>>(work, nL + 1, err);
+    VUS_CHECK_LAUNCH("ba_linearize");
+    return VUS_OK;
+  }
+};
+
+template <int LOSS>
+struct EvalStepOp {
+  static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, const double* dp,
+                 const double* dl, double* new_poses, double* new_points, double* out, double* work, void* stream) {
+    if (int rc = check_problem(P)) return rc;
+    VUS_REQUIRE(poses && dp && new_poses && out && work, "null buffer");
+    VUS_REQUIRE((points && dl && new_points) || !P->n_points, "null landmark buffer");
+    hipStream_t st = vus::as_stream(stream);
+    const int nP = P->n_poses, nL = P->n_points;
+    retract_kernel<<<cdiv(nP > nL ? nP : (nL < 65536 ? nL : 65536), 256) + 1, 256, 0, st>>>(nP, nL, pose_stride(*P), poses, points,
+                                                                                             dp, dl, new_poses, new_points);
+    double* part_lin = work;
+    double* part_new = work + (nL + 1);
+    if (nL > 0)
+      eval_points_kernel<true, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, dp, dl, new_poses, new_points, part_lin,
+                                                                 part_new, k);
+    priors_kernel<<<1, 64, 0, st>>>(*P, poses, dp, nullptr, nullptr, part_lin + nL, 2);
+    priors_kernel<<<1, 64, 0, st>>>(*P, new_poses, nullptr, nullptr, nullptr, part_new + nL, 1);
+    reduce_partials_kernel<<<1, 1024, 0, st>>>(part_lin, nL + 1, out);
+    reduce_partials_kernel<<<1, 1024, 0, st>>>(part_new, nL + 1, out + 1);
+    VUS_CHECK_LAUNCH("ba_eval_step");
+    return VUS_OK;
+  }
+};
+
+template <int LOSS>
+struct WeightsOp {
+  static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* w, void* stream) {
+    if (int rc = check_problem(P)) return rc;
+    VUS_REQUIRE(poses && ((points && w) || !P->n_obs), "null buffer");
+    if (P->n_obs > 0)
+      stereo_weights_kernel<LOSS><<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k);
+    VUS_CHECK_LAUNCH("ba_stereo_weights");
+    return VUS_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" long long vus_ba_work_doubles(const vus_ba_problem* P) {
@@ -2609,35 +2785,32 @@ extern "C" long long vus_ba_work_doubles(const vus_ba_problem* P) {
 
 extern "C" int vus_ba_error(const vus_ba_problem* P, const double* poses, const double* points, double* err,
                             double* work, void* stream) {
-  if (int rc = check_problem(P)) return rc;
-  VUS_REQUIRE(poses && (points || !P->n_points) && err && work, "null buffer");
-  hipStream_t st = vus::as_stream(stream);
-  const int nL = P->n_points;
-  if (nL > 0)
-    eval_points_kernel<false><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
-                                                          nullptr, work);
-  priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, nullptr, nullptr, work + nL, 1);
-  reduce_partials_kernel<<<1, 1024, 0, st>>>(work, nL + 1, err);
-  VUS_CHECK_LAUNCH("ba_error");
-  return VUS_OK;
+  return ErrorOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, err, work, stream);
+}
+
+extern "C" int vus_ba_error_robust(const vus_ba_problem* P, const double* poses, const double* points, double* err,
+                                   double* work, void* stream, const vus_ba_loss* loss) {
+  if (int rc = check_loss(loss)) return rc;
+  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream);
 }
 
 extern "C" int vus_ba_linearize(const vus_ba_problem* P, const double* poses, const double* points, double* W,
                                 double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
                                 void* stream) {
-  if (int rc = check_problem(P)) return rc;
-  // a graph without landmarks (priors only) has empty per-landmark / per-observation arrays: those may be null
-  VUS_REQUIRE(poses && Hpp && gp && err && work, "null buffer");
-  VUS_REQUIRE((points && V && gl) || !P->n_points, "null landmark buffer");
-  VUS_REQUIRE(W || !P->n_obs, "null observation buffer");
-  hipStream_t st = vus::as_stream(stream);
-  const int nL = P->n_points;
-  if (nL > 0) lin_points_kernel<<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work);
-  lin_poses_kernel<<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp);
-  priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, Hpp, gp, work + nL, 0);
-  reduce_partials_kernel<<<1, 1024, 0, st>>>(work, nL + 1, err);
-  VUS_CHECK_LAUNCH("ba_linearize");
-  return VUS_OK;
+  return LinearizeOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, W, V, gl, Hpp, gp, err, work, stream);
+}
+
+extern "C" int vus_ba_linearize_robust(const vus_ba_problem* P, const double* poses, const double* points, double* W,
+                                       double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
+                                       void* stream, const vus_ba_loss* loss) {
+  if (int rc = check_loss(loss)) return rc;
+  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream);
+}
+
+extern "C" int vus_ba_stereo_weights(const vus_ba_problem* P, const vus_ba_loss* loss, const double* poses,
+                                     const double* points, double* w, void* stream) {
+  if (int rc = check_loss(loss)) return rc;
+  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream);
 }
 
 extern "C" int vus_ba_schur(const vus_ba_problem* P, const vus_ba_tiles* T, double lambda, const double* W, const double* V,
@@ -3314,24 +3487,14 @@ extern "C" int vus_ba_backsub(const vus_ba_problem* P, const double* W, const do
 extern "C" int vus_ba_eval_step(const vus_ba_problem* P, const double* poses, const double* points, const double* dp,
                                 const double* dl, double* new_poses, double* new_points, double* out, double* work,
                                 void* stream) {
-  if (int rc = check_problem(P)) return rc;
-  VUS_REQUIRE(poses && dp && new_poses && out && work, "null buffer");
-  VUS_REQUIRE((points && dl && new_points) || !P->n_points, "null landmark buffer");
-  hipStream_t st = vus::as_stream(stream);
-  const int nP = P->n_poses, nL = P->n_points;
-  retract_kernel<<<cdiv(nP > nL ? nP : (nL < 65536 ? nL : 65536), 256) + 1, 256, 0, st>>>(nP, nL, pose_stride(*P), poses, points, dp, dl,
-                                                                                           new_poses, new_points);
-  double* part_lin = work;
-  double* part_new = work + (nL + 1);
-  if (nL > 0)
-    eval_points_kernel<true><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, dp, dl, new_poses, new_points, part_lin,
-                                                         part_new);
-  priors_kernel<<<1, 64, 0, st>>>(*P, poses, dp, nullptr, nullptr, part_lin + nL, 2);
-  priors_kernel<<<1, 64, 0, st>>>(*P, new_poses, nullptr, nullptr, nullptr, part_new + nL, 1);
-  reduce_partials_kernel<<<1, 1024, 0, st>>>(part_lin, nL + 1, out);
-  reduce_partials_kernel<<<1, 1024, 0, st>>>(part_new, nL + 1, out + 1);
-  VUS_CHECK_LAUNCH("ba_eval_step");
-  return VUS_OK;
+  return EvalStepOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, dp, dl, new_poses, new_points, out, work, stream);
+}
+
+extern "C" int vus_ba_eval_step_robust(const vus_ba_problem* P, const double* poses, const double* points,
+                                       const double* dp, const double* dl, double* new_poses, double* new_points,
+                                       double* out, double* work, void* stream, const vus_ba_loss* loss) {
+  if (int rc = check_loss(loss)) return rc;
+  return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream);
 }
 
 #ifdef VUS_TIMING

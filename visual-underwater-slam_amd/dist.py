@@ -189,7 +189,7 @@ class ShardedStereoBASolver:
     landmarks, band forced to the global band) and inserts the collectives."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
-                 prior_sigmas=None, device="cuda:0"):
+                 prior_sigmas=None, device="cuda:0", loss=None):
         from .ba import StereoBAProblem, StereoBASolver
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -201,7 +201,7 @@ class ShardedStereoBASolver:
         if self.rank != 0:                      # priors are counted once, on rank 0
             prior_pose, prior_T, prior_sigmas = None, None, None
         self.problem = StereoBAProblem(op, ol, m, n_poses, self.hi - self.lo, K, sigma, prior_pose, prior_T,
-                                       prior_sigmas, device=device, band=band)
+                                       prior_sigmas, device=device, band=band, loss=loss)
         self.solver = _ShardSolver(self.problem, self.world)
 
     def optimize(self, poses, points, params=None):

@@ -291,11 +291,144 @@ class _Unit(_NoiseModel):
         return _Unit(np.ones(int(dim)))
 
 
+class _MEstimator:
+    """gtsam.noiseModel.mEstimator.Base: a robust loss rho(d) of the whitened residual norm d and its IRLS weight
+    w(d) = rho'(d) / d, GTSAM's default Block reweighting (one weight per factor).  `kind` is the VUS_LOSS_* number of
+    include/vus_robust.h, `k` the parameter in whitened units."""
+    kind = 0
+    _name = "Gaussian"
+
+    def __init__(self, k, reweight=None):
+        k = float(k)
+        if not (math.isfinite(k) and k > 0.0):
+            raise RuntimeError(f"mEstimator.{self._name}: parameter {k} must be finite and > 0")
+        if reweight not in (None, 1, "Block"):
+            raise NotImplementedError("only the Block reweight scheme (gtsam's default) is supported")
+        self.k = k
+
+    @classmethod
+    def Create(cls, k, reweight=None):
+        return cls(k, reweight)
+
+    def modelParameter(self):
+        return self.k
+
+    def weight(self, d):
+        return float(self._wl(abs(float(d)))[0])
+
+    def sqrtWeight(self, d):
+        return math.sqrt(self.weight(d))
+
+    def loss(self, d):
+        return float(self._wl(abs(float(d)))[1])
+
+    def _wl(self, d):
+        raise NotImplementedError
+
+    def equals(self, other, tol=1e-9):
+        return type(other) is type(self) and abs(other.k - self.k) <= tol
+
+    def __repr__(self):
+        return f"mEstimator.{self._name}({self.k:g})"
+
+
+class _Huber(_MEstimator):
+    kind, _name = 1, "Huber"
+
+    def _wl(self, d):
+        k = self.k
+        return (1.0, 0.5 * d * d) if d <= k else (k / d, k * d - 0.5 * k * k)
+
+
+class _Cauchy(_MEstimator):
+    kind, _name = 2, "Cauchy"
+
+    def _wl(self, d):
+        k2 = self.k * self.k
+        return k2 / (k2 + d * d), 0.5 * k2 * math.log1p(d * d / k2)
+
+
+class _Tukey(_MEstimator):
+    kind, _name = 3, "Tukey"
+
+    def _wl(self, d):
+        c2 = self.k * self.k
+        if d > self.k:
+            return 0.0, c2 / 6.0
+        t = 1.0 - d * d / c2
+        return t * t, c2 / 6.0 * (1.0 - t * t * t)
+
+
+class _GemanMcClure(_MEstimator):
+    kind, _name = 4, "GemanMcClure"
+
+    def _wl(self, d):
+        c2, d2 = self.k * self.k, d * d
+        return c2 * c2 / ((c2 + d2) * (c2 + d2)), 0.5 * c2 * d2 / (c2 + d2)
+
+
+class _Welsch(_MEstimator):
+    kind, _name = 5, "Welsch"
+
+    def _wl(self, d):
+        x = d * d / (self.k * self.k)
+        return math.exp(-x), -0.5 * self.k * self.k * math.expm1(-x)
+
+
+class _mEstimator:  # namespace (gtsam.noiseModel.mEstimator)
+    Base = _MEstimator
+    Huber = _Huber
+    Cauchy = _Cauchy
+    Tukey = _Tukey
+    GemanMcClure = _GemanMcClure
+    Welsch = _Welsch
+
+
+class _Robust(_NoiseModel):
+    """gtsam.noiseModel.Robust.Create(mEstimator, noise): the whitening of `noise` followed by IRLS reweighting with the
+    mEstimator (Block scheme).  The GPU optimizer supports it on stereo factors over an isotropic noise model."""
+
+    def __init__(self, robust: _MEstimator, noise: _NoiseModel):
+        if not isinstance(robust, _MEstimator):
+            raise RuntimeError("Robust.Create: the first argument must be a noiseModel.mEstimator")
+        if not isinstance(noise, _NoiseModel) or isinstance(noise, _Robust):
+            raise RuntimeError("Robust.Create: the second argument must be a Gaussian noise model")
+        super().__init__(noise.sigmas())
+        self._robust, self._noise = robust, noise
+
+    @staticmethod
+    def Create(robust, noise):
+        return _Robust(robust, noise)
+
+    def robust(self):
+        return self._robust
+
+    def noise(self):
+        return self._noise
+
+    def is_isotropic(self):
+        return self._noise.is_isotropic()
+
+
+def _refuse_robust(model, what):
+    if isinstance(model, _Robust):
+        raise NotImplementedError(f"{what}: a noiseModel.Robust model is supported on stereo factors only "
+                                  "(GenericStereoFactor3D, StereoFactorBlock); use a Gaussian noise model here")
+
+
+def _stereo_model_key(model):
+    """What makes two stereo noise models the same model: sigmas, robust kind and parameter."""
+    rob = model._robust if isinstance(model, _Robust) else None
+    return (tuple(model._sigmas.tolist()), rob.kind if rob else 0, rob.k if rob else 0.0)
+
+
 class noiseModel:  # namespace, as in gtsam
     Base = _NoiseModel
     Diagonal = _Diagonal
     Isotropic = _Isotropic
     Unit = _Unit
+    Robust = _Robust
+    mEstimator = _mEstimator
 
 
 class _ConstantBias:
@@ -392,6 +525,7 @@ class PriorFactorPose3(_PriorFactor):
     def __init__(self, key, prior: Pose3, model: _NoiseModel):           # batch.py:281
         if model.dim() != 6:
             raise RuntimeError("PriorFactorPose3 needs a 6-dimensional noise model")
+        _refuse_robust(model, "PriorFactorPose3")
         super().__init__(key, Pose3(prior), model)
 
 
@@ -400,6 +534,7 @@ class PriorFactorVector(_PriorFactor):
         prior = np.asarray(prior, dtype=float).reshape(-1).copy()
         if model.dim() != prior.size:
             raise RuntimeError("PriorFactorVector: noise model dimension differs from the vector's")
+        _refuse_robust(model, "PriorFactorVector")
         super().__init__(key, prior, model)
 
 
@@ -508,6 +643,7 @@ class DvlVelocityFactor(_Factor):
 
     def __init__(self, model: _NoiseModel, velKey: int, poseKey: int, measured):
         super().__init__([velKey, poseKey])
+        _refuse_robust(model, "DvlVelocityFactor")
         if model.dim() != 3 or not model.is_isotropic():
             raise NotImplementedError("DvlVelocityFactor needs an isotropic 3-dimensional noise model (batch.py:98)")
         self._model = model
@@ -898,7 +1034,7 @@ class NonlinearFactorGraph:
             m, K = factor._model, factor._K
             if self._st_model is None:
                 self._st_model, self._st_K = m, K
-            elif (m is not self._st_model and not np.array_equal(m._sigmas, self._st_model._sigmas)) or \
+            elif (m is not self._st_model and _stereo_model_key(m) != _stereo_model_key(self._st_model)) or \
                     (K is not self._st_K and not K.equals(self._st_K)):
                 self._st_mixed = True
             self._st_meas.extend(factor._measured._m)
@@ -942,7 +1078,8 @@ class NonlinearFactorGraph:
         return sorted(out)
 
     def error(self, values: Values) -> float:
-        """0.5 * sum of squared whitened residuals, evaluated on the GPU."""
+        """0.5 * sum of squared whitened residuals (sum of rho(d) for stereo factors under a noiseModel.Robust),
+        evaluated on the GPU."""
         from .optimizer import graph_error
         return graph_error(self, values)
 

@@ -145,18 +145,22 @@ def _pack_graph(graph, values, device=None):
                    ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias)
     meas, pkeys, lkeys = [], [], []
     imu_f, dvl_f = [], []
-    model_sigma, calib = None, None
+    from . import _Robust
+    model_sigma, calib, loss = None, None, None
     prior_pose, prior_vec = [], []
     single_m, single_p, single_l = [], [], []
 
     def check_model(model, K):
-        nonlocal model_sigma, calib
+        nonlocal model_sigma, calib, loss
         if not model.is_isotropic():
-            raise NotImplementedError("stereo factors need an isotropic noise model (batch.py:118 uses Isotropic.Sigma(3, 10))")
+            raise NotImplementedError("stereo factors need an isotropic noise model (batch.py:118 uses Isotropic.Sigma(3, 10)), "
+                                      "optionally wrapped in noiseModel.Robust")
         s = float(model.sigmas()[0])
+        rob = model.robust() if isinstance(model, _Robust) else None
+        lo = (rob.kind, rob.k) if rob is not None else None          # (VUS_LOSS_* kind, k) of a robust model
         if model_sigma is None:
-            model_sigma, calib = s, K
-        elif s != model_sigma or not K.equals(calib):
+            model_sigma, calib, loss = s, K, lo
+        elif s != model_sigma or lo != loss or not K.equals(calib):
             raise NotImplementedError("all stereo factors of one graph must share one noise model and one Cal3_S2Stereo")
 
     # single GenericStereoFactor3D objects were recorded column-wise when they were added (NonlinearFactorGraph._record):
@@ -266,7 +270,7 @@ def _pack_graph(graph, values, device=None):
     if len(set(aux.keys)) != len(aux.keys):
         raise NotImplementedError("several prior factors on one vector variable are not supported")
     return dict(meas=meas, pose_idx=pose_idx, lm_idx=lm_idx, pose_keys=pose_keys, lm_keys=lm_keys, poses=poses,
-                points=points, sigma=model_sigma if model_sigma is not None else 1.0,
+                points=points, sigma=model_sigma if model_sigma is not None else 1.0, loss=loss,
                 K=calib.vector6() if calib is not None else np.array([1.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
                 prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav)
@@ -331,7 +335,8 @@ def _build_solver(pg, device="cuda:0"):
     nav = pg.get("nav")
     prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], len(pg["pose_keys"]), len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
-                           prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=2 if nav else 1)
+                           prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=2 if nav else 1,
+                           loss=pg.get("loss"))
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
         return prob, NavBASolver(prob, nf)
@@ -394,6 +399,11 @@ class LevenbergMarquardtOptimizer:
             poses, points, rep = sv.optimize(torch.from_numpy(pg["poses"]).to(dev), torch.from_numpy(pg["points"]).to(dev),
                                              self._params._to_lm(), aux=aux)
         mark("lm")
+        rep.stereo_weights = None
+        if prob.robust:           # final IRLS weights per stereo factor, identified by its (pose key, landmark key)
+            w = sv.stereo_weights(poses, points).cpu().numpy()
+            pi, li = (np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x, dtype=np.int64) for x in (pg["pose_idx"], pg["lm_idx"]))
+            rep.stereo_weights = (pg["pose_keys"][pi], np.asarray(pg["lm_keys"])[li], w)
         poses, points = poses.cpu().numpy(), points.cpu().numpy()
         out = Values(self._initial)
         if nav:
@@ -430,5 +440,6 @@ class LevenbergMarquardtOptimizer:
         return self._params.lambdaInitial if self._report is None else self._report.final_lambda
 
     def report(self):
-        """EXTENSION: the LMReport of the last optimize() (error / lambda history, timings)."""
+        """EXTENSION: the LMReport of the last optimize() (error / lambda history, timings).  With robust stereo factors
+        its `stereo_weights` = (pose keys, landmark keys, w) holds every stereo factor's final weight w(d); else None."""
         return self._report

@@ -222,6 +222,28 @@ def ba_sequence(n_kf, n_lm, obs_per_kf, seed=SEED, line_len=None, kf_step=0.25, 
     }
 
 
+def inject_outliers(seq, frac, px_range=(50.0, 300.0), seed=SEED):
+    """Gross data-association errors, as brute-force Hamming matching without RANSAC makes them: a seeded fraction
+    `frac` of the rows of seq["meas"] (uL, uR, v) is replaced by a measurement shifted along the image row by a
+    uniform |offset| in px_range with a random sign.  uL and uR move together, so the v-row and the disparity stay
+    those of a real stereo match and the observation stays in front of the camera.  seq["meas"] is replaced by the
+    corrupted copy (the original array is not written); returns the boolean outlier mask over its rows."""
+    meas = np.array(seq["meas"], dtype=np.float64, copy=True)
+    n = len(meas)
+    n_out = int(round(float(frac) * n))
+    i = np.arange(n, dtype=np.int64)
+    mask = np.zeros(n, dtype=bool)
+    mask[np.argsort(_hash_uniform(i, seed ^ 0x7A11), kind="stable")[:n_out]] = True
+    lo, hi = float(px_range[0]), float(px_range[1])
+    mag = lo + (hi - lo) * _hash_uniform(i, seed ^ 0x7A12)
+    sign = np.where(_hash_uniform(i, seed ^ 0x7A13) < 0.5, -1.0, 1.0)
+    off = np.where(mask, sign * mag, 0.0)
+    meas[:, 0] += off
+    meas[:, 1] += off
+    seq["meas"] = meas
+    return mask
+
+
 # ---------------------------------------------------------------------------------------------
 # Stereo + IMU + DVL sequence (BASELINE.json configs[0]; IMU constants of /root/reference/batch.py:88,183-185,290)
 IMU_DT = 0.005
