@@ -513,4 +513,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Robust noise models of the stereo factors (Huber, Cauchy, Tukey, Geman-McClure, Welsch): vus_ba_loss and the
  * `_robust` twins of vus_ba_linearize / vus_ba_eval_step / vus_ba_error, plus vus_ba_stereo_weights. */
 #include "vus_robust.h"
+
+/* Marginal covariances (gtsam.Marginals): block-band selected inversion of the factor, landmark covariances, the
+ * shared-bias border -- vus_ba_band_selinv, vus_ba_point_check, vus_ba_point_covariance, vus_nav_border_covariance. */
+#include "vus_marginals.h"
 #endif /* VUS_H */

@@ -207,6 +207,88 @@ class StereoBAProblem:
         self.setup_seconds = time.perf_counter() - t0
 
 
+class IndeterminantSystem(RuntimeError):
+    """The information matrix at the linearisation point is not positive definite.  `kind` is "point" (landmark `index`
+    has a singular 3 x 3 information block, e.g. every observation of it fails cheirality), "node" (the reduced camera
+    system failed at camera-side node `index`) or "bias" (the shared-bias border is singular)."""
+
+    def __init__(self, kind, index):
+        super().__init__(f"indeterminant linear system at {kind} {index}")
+        self.kind, self.index = kind, int(index)
+
+
+class BAMarginals:
+    """Marginal covariances at one linearisation point (StereoBASolver.marginals / NavBASolver.marginals), device tensors:
+      Sigma     [n_nodes, band + 1, 36]  the band of the camera-side covariance (entry (i, s) = block (i, i - s)),
+                                         border-corrected on inertial graphs
+      pose_cov  [n_poses, 6, 6]          tangent order (rot, trans), body frame
+      point_cov [n_points, 3, 3] or None world frame, indexed by the problem's landmark index
+    and on inertial graphs vel_cov [n_poses, 3, 3], bias_cov [6, 6] (acc, gyro), node_bias_cov [n_nodes, 6, 6]."""
+
+    def __init__(self, solver, values, Sigma, pose_cov, point_cov, U=None, vel_cov=None, bias_cov=None, node_bias_cov=None):
+        self.solver, self._values = solver, values
+        self.band, self.pose_stride = solver.P.band, solver.P.pose_stride
+        self.Sigma, self.pose_cov, self.point_cov = Sigma, pose_cov, point_cov
+        self.U, self.vel_cov, self.bias_cov, self.node_bias_cov = U, vel_cov, bias_cov, node_bias_cov
+
+    def joint(self, nodes, bias=False):
+        """Joint covariance [6m (+6), 6m (+6)] of the camera-side nodes `nodes` (pose i is node pose_stride * i), in the
+        order given, with the shared bias appended last when `bias` (inertial graphs).  From the band when the nodes lie
+        within `band` of each other, otherwise exactly from columns of S^-1 (a fresh lambda = 0 factorisation per 8
+        columns, plus the border correction on inertial graphs)."""
+        nodes = [int(q) for q in nodes]
+        m = len(nodes)
+        if bias and self.bias_cov is None:
+            raise ValueError("bias=True needs an inertial graph (NavBASolver.marginals)")
+        out = np.zeros((6 * m + 6 * bool(bias),) * 2)
+        if m and max(nodes) - min(nodes) <= self.band:
+            idx = torch.tensor([[max(a, b), max(a, b) - min(a, b)] for a in nodes for b in nodes], device=self.Sigma.device)
+            blocks = self.Sigma[idx[:, 0], idx[:, 1]].reshape(m, m, 6, 6).cpu().numpy()
+            for x, a in enumerate(nodes):
+                for y, b in enumerate(nodes):
+                    out[6 * x:6 * x + 6, 6 * y:6 * y + 6] = blocks[x, y] if a >= b else blocks[y, x].T
+        elif m:
+            out[:6 * m, :6 * m] = self.solver._exact_covariance_columns(self._values, nodes, self.U, self.node_bias_cov)
+        if bias:
+            nb = self.node_bias_cov[torch.tensor(nodes, dtype=torch.int64, device=self.Sigma.device)].cpu().numpy()
+            out[:6 * m, 6 * m:] = nb.reshape(6 * m, 6) if m else 0.0
+            out[6 * m:, :6 * m] = out[:6 * m, 6 * m:].T
+            out[6 * m:, 6 * m:] = self.bias_cov.cpu().numpy()
+        return out
+
+    def joint_full(self, nodes, points=(), bias=False):
+        """Joint covariance of camera-side nodes, landmarks (the problem's landmark indices) and, with `bias`, the shared
+        bias, in the order nodes (6 each), bias (6), landmarks (3 each).  A landmark is l = -sum_k Y_kl^T x_k + e_l with
+        e_l ~ N(0, V_l^-1) independent of the rest (Y = W V^-1 at lambda = 0), so the joint is M G M^T + diag(V_l^-1),
+        G = the band's joint of every node involved.  Served when those nodes -- the requested ones and every pose
+        observing a requested landmark -- lie within `band` of each other; otherwise NotImplementedError."""
+        nodes, points = [int(q) for q in nodes], [int(j) for j in points]
+        if not points:
+            return self.joint(nodes, bias)
+        rows = self.solver._point_rows(self._values, points)
+        alln = sorted(set(nodes).union(*[set(r[1]) for r in rows]))
+        if alln[-1] - alln[0] > self.band:
+            raise NotImplementedError(
+                f"joint covariance with landmarks: the camera-side nodes involved span {alln[-1] - alln[0]} nodes "
+                f"({alln[0]} .. {alln[-1]}), more than the band of {self.band}; only joints inside one band window are served")
+        G = self.joint(alln, bias)
+        pos = {q: x for x, q in enumerate(alln)}
+        m, nb = len(nodes), 6 * len(alln)
+        r_lm = 6 * m + 6 * bool(bias)
+        M = np.zeros((r_lm + 3 * len(points), G.shape[0]))
+        for x, q in enumerate(nodes):
+            M[6 * x:6 * x + 6, 6 * pos[q]:6 * pos[q] + 6] = np.eye(6)
+        if bias:
+            M[6 * m:6 * m + 6, nb:nb + 6] = np.eye(6)
+        for t, (Y, onodes, _) in enumerate(rows):
+            for y, q in zip(Y, onodes):
+                M[r_lm + 3 * t:r_lm + 3 * t + 3, 6 * pos[q]:6 * pos[q] + 6] -= y.T
+        C = M @ G @ M.T
+        for t, (_, _, Vi) in enumerate(rows):
+            C[r_lm + 3 * t:r_lm + 3 * t + 3, r_lm + 3 * t:r_lm + 3 * t + 3] += Vi
+        return 0.5 * (C + C.T)
+
+
 class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
 
@@ -323,6 +405,124 @@ class StereoBASolver:
         fn, extra = self._loss_args("vus_ba_eval_step")
         _lib.call(fn, self._pp(), p(poses), p(points), p(self.dp), p(self.dl), p(self.new_poses),
                   p(self.new_points), p(self.scal[1:]), p(self.work), _lib.current_stream_ptr(), *extra)
+
+    # -- marginal covariances (gtsam.Marginals) ---------------------------------------------------------------------
+    def _check_points(self):
+        """Refuse a landmark whose information block is not positive definite before it is inverted at lambda = 0."""
+        if self.P.n_points == 0:
+            return
+        bad = torch.empty(1, dtype=torch.int32, device=self.P.device)
+        _lib.call("vus_ba_point_check", _lib.ptr(self.V), self.P.n_points, _lib.ptr(bad), _lib.current_stream_ptr())
+        j = int(bad.item())
+        if j != 0x7F7F7F7F:
+            raise IndeterminantSystem("point", j)
+
+    def _factor_status(self):
+        """Status of the last factorisation: True to redo it (window kernel fallback), raises on a non-PD system."""
+        status = int(self.status.item())
+        if status < 0:
+            if self._window_expired(status):
+                return True
+            raise RuntimeError("vus_ba_band_solve: the cooperative back-substitution timed out (status %d)" % status)
+        if status > 0:
+            raise IndeterminantSystem("node", (status - 1) // 6)
+        return False
+
+    def _marginal_factor(self, values):
+        """Linearise at `values` with no damping and leave the ONE-SIDED factor of S (lambda = 0) in Sband."""
+        poses, points = values
+        self.linearize(poses, points)
+        self._check_points()
+        p = _lib.ptr
+        while True:
+            self.schur(0.0)
+            _lib.call("vus_ba_band_solve", p(self.Sband), self.P.n_nodes, self.P.band, p(self.gs), p(self.dp),
+                      p(self.status), _lib.current_stream_ptr())
+            if not self._factor_status():
+                return
+
+    def _selinv(self):
+        nN, B = self.P.n_nodes, self.P.band
+        nw = int(_lib.load().vus_ba_band_selinv_work_doubles(nN, B))
+        if getattr(self, "_selinv_work", None) is None:       # allocated on the first marginals() call, then reused
+            self._selinv_work = torch.empty((nw,), dtype=torch.float64, device=self.P.device)
+        Sigma = torch.empty_like(self.Sband)
+        _lib.call("vus_ba_band_selinv", _lib.ptr(self.Sband), nN, B, _lib.ptr(Sigma), _lib.ptr(self._selinv_work), nw,
+                  _lib.current_stream_ptr())
+        return Sigma
+
+    def _point_rows(self, values, points):
+        """Per landmark j of `points`: (Y rows [m, 6, 3] = W V^-1 at lambda = 0, the camera-side nodes of its observations,
+        V_j^-1) at `values`, from a fresh stereo linearisation (robust weights included)."""
+        self.linearize(values[0], values[-1])
+        ptr = self.P.pk["point_ptr"].cpu().numpy()
+        obs_pose = self.P.pk["obs_pose"]
+        out = []
+        for j in points:
+            a, b = int(ptr[j]), int(ptr[j + 1])
+            v = self.V[j].cpu().numpy()
+            Vi = np.linalg.inv(np.array([[v[0], v[1], v[2]], [v[1], v[3], v[4]], [v[2], v[4], v[5]]]))
+            W = self.W[a:b].cpu().numpy().reshape(-1, 6, 3)
+            onodes = [self.P.pose_stride * int(k) for k in obs_pose[a:b].cpu().numpy()]
+            out.append(([w @ Vi for w in W], onodes, Vi))
+        return out
+
+    def _point_cov(self, Sigma):
+        nL = self.P.n_points
+        cov = torch.empty((nL, 9), dtype=torch.float64, device=self.P.device)
+        if nL:
+            _lib.call("vus_ba_point_covariance", self._pp(), ctypes.addressof(self.P.c_tiles), _lib.ptr(self.W),
+                      _lib.ptr(self.Vinv), _lib.ptr(Sigma), self.P.band, _lib.ptr(cov), _lib.current_stream_ptr())
+        return cov.reshape(nL, 3, 3)
+
+    def _pose_blocks(self, Sigma, nodes):
+        return Sigma[nodes, 0].reshape(-1, 6, 6)
+
+    def marginals(self, poses, points, points_cov=True) -> BAMarginals:
+        """Marginal covariances at (poses, points) -- which need not be an optimum -- with the robust weights of that
+        point and no damping: S at lambda = 0, its one-sided factor, the selected inversion of the band and the landmark
+        covariances.  Raises IndeterminantSystem when the information matrix is not positive definite.  Reuses the
+        solver's workspace; a later optimize() is unaffected."""
+        values = (poses.to(torch.float64).contiguous(), points.to(torch.float64).contiguous())
+        self._marginal_factor(values)
+        Sigma = self._selinv()
+        nodes = torch.arange(self.P.n_poses, device=self.P.device) * self.P.pose_stride
+        pc = self._point_cov(Sigma) if points_cov else None
+        return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, nodes), pc)
+
+    def _exact_covariance_columns(self, values, nodes, U=None, Snb=None):
+        """The joint covariance of `nodes` from exact columns of S^-1: vus_ba_band_solve_multi with at most 8 unit
+        right-hand sides per call, each after a fresh lambda = 0 Schur step (the solve factorises Sband in place)."""
+        nN = self.P.n_nodes
+        cols = [6 * q + c for q in nodes for c in range(6)]
+        got = np.zeros((len(cols), 6 * nN))
+        p = _lib.ptr
+        self._linearize_all(values)
+        for c0 in range(0, len(cols), 8):
+            chunk = cols[c0:c0 + 8]
+            while True:
+                self._assemble_zero()
+                rhs = torch.zeros((len(chunk), 6 * nN), dtype=torch.float64, device=self.P.device)
+                rhs[torch.arange(len(chunk)), torch.tensor(chunk)] = 1.0
+                _lib.call("vus_ba_band_solve_multi", p(self.Sband), nN, self.P.band, p(rhs), len(chunk), p(self.status),
+                          _lib.current_stream_ptr())
+                if not self._factor_status():
+                    break
+            got[c0:c0 + len(chunk)] = rhs.cpu().numpy()
+        J = got[:, cols].T
+        if U is not None:           # + U_i Sc^-1 U_k^T = -Sigma_nb(i) U_k^T
+            Ui = U.cpu().numpy()[:, cols].T                                   # [6m, 6]
+            nb = Snb[torch.tensor(nodes, dtype=torch.int64, device=Snb.device)].cpu().numpy().reshape(-1, 6)
+            J = J - nb @ Ui.T
+        return 0.5 * (J + J.T)
+
+    def _linearize_all(self, values):
+        poses, points = values
+        self.linearize(poses, points)
+        self._check_points()
+
+    def _assemble_zero(self):
+        self.schur(0.0)
 
     # -- Levenberg-Marquardt ----------------------------------------------------------------------
     def optimize(self, poses: torch.Tensor, points: torch.Tensor, params: Optional[LMParams] = None,
@@ -514,6 +714,44 @@ class NavBASolver(StereoBASolver):
         _lib.call("vus_nav_eval_step", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(bias), p(self.dp), p(self.db),
                   p(self.new_poses), p(self.new_vels), p(self.new_bias), p(self.nav_scal[1:]), p(self.nav_work),
                   _lib.current_stream_ptr())
+
+    def _linearize_all(self, values):
+        poses, vels, bias, points = values
+        self.linearize(poses, points)
+        self._check_points()
+        self.nav_linearize(poses, vels, bias)
+
+    def _assemble_zero(self):
+        self.schur(0.0)
+        self.nav_assemble(0.0)
+
+    def marginals(self, poses, vels, bias, points, points_cov=True) -> BAMarginals:
+        """StereoBASolver.marginals for the whole graph: the camera-side band of A^-1 (poses and velocity nodes, one-sided
+        7-right-hand-side solve at lambda = 0), then the shared-bias border (vus_nav_border_covariance), then the landmark
+        covariances from the corrected band."""
+        c = lambda x: x.to(torch.float64).contiguous()
+        values = (c(poses), c(vels), c(bias), c(points))
+        self._linearize_all(values)
+        p, st = _lib.ptr, _lib.current_stream_ptr()
+        while True:
+            self._assemble_zero()
+            _lib.call("vus_ba_band_solve_multi", p(self.Sband), self.P.n_nodes, self.P.band, p(self.rhs), 7, p(self.status), st)
+            if not self._factor_status():
+                break
+        Sigma = self._selinv()
+        nN, nP = self.P.n_nodes, self.P.n_poses
+        f64 = dict(dtype=torch.float64, device=self.P.device)
+        Snb, Sbb, ok = torch.empty((nN, 36), **f64), torch.empty((36,), **f64), torch.empty((1,), **f64)
+        _lib.call("vus_nav_border_covariance", nN, self.P.band, p(self.rhs), p(self.Scb), p(self.Sbb), p(Sigma), p(Snb),
+                  p(Sbb), p(ok), st)
+        if float(ok.item()) != 1.0:
+            raise IndeterminantSystem("bias", 0)
+        U = self.rhs[1:7].clone()
+        pose_nodes = torch.arange(nP, device=self.P.device) * 2
+        pc = self._point_cov(Sigma) if points_cov else None
+        vel = Sigma[pose_nodes + 1, 0].reshape(nP, 6, 6)[:, :3, :3]
+        return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, pose_nodes), pc, U=U, vel_cov=vel,
+                           bias_cov=Sbb.reshape(6, 6), node_bias_cov=Snb.reshape(nN, 6, 6))
 
     def optimize(self, poses, vels, bias, points, params: Optional[LMParams] = None):
         """Returns (poses, vels, bias, points, LMReport); inputs untouched."""

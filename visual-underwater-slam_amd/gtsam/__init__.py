@@ -1106,3 +1106,4 @@ class NonlinearFactorGraph:
 
 
 from .optimizer import LevenbergMarquardtParams, LevenbergMarquardtOptimizer  # noqa: E402
+from .marginals import Marginals, JointMarginal, KeyVector, IndeterminantLinearSystemException  # noqa: E402
