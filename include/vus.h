@@ -345,7 +345,8 @@ int vus_ba_tiles_fill(const vus_ba_problem* P, int band, const int* lm_base, int
  *   Vinv [n_points,6] = (V + lambda I)^-1 (upper triangle);  Y [n_obs,18] = W Vinv (L-order), OPTIONAL output
  *   (NULL: not written; the kernel forms the rows it needs on the fly);
  *   S band [n_nodes, band_nodes + 1, 36], entry (i, s) = the 6 x 6 block (i, i - s), = Hpp + lambda I - sum_j Y W^T: every
- *   stored block is written (none accumulated into), diagonal blocks whole;  gs [n_nodes,6] = gp - sum Y gl.
+ *   stored block is written (none accumulated into), diagonal blocks whole, blocks no landmark spans zero (also when
+ *   band_nodes exceeds pose_stride * T->band);  gs [n_nodes,6] = gp - sum Y gl.
  * band_nodes: the half-bandwidth of Sband's storage in NODES (>= pose_stride * T->band).  counter: one int of device
  * scratch (the unit queue).  Replaces what GTSAM's elimination does inside optimize(), batch.py:337. */
 int vus_ba_schur(const vus_ba_problem* P, const vus_ba_tiles* T, double lambda, const double* W, const double* V,

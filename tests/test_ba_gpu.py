@@ -61,10 +61,11 @@ def test_kernels_match_oracle_stage_by_stage(gpu, oracle, size):
         nPq, Bq = prob.n_poses, prob.band                            # diagonal blocks come out whole and symmetric
         D = Sg[:, 0].reshape(nPq, 6, 6)
         assert np.array_equal(D, D.transpose(0, 2, 1))
+        gs1 = sv.gs.cpu().numpy().copy()
         sv.schur(lam)
         torch.cuda.synchronize()
         assert np.array_equal(sv.Sband.cpu().numpy(), Sg)            # fixed summation order: bit-identical from run to run
-        assert np.array_equal(sv.gs.cpu().numpy(), sv.gs.cpu().numpy())
+        assert np.array_equal(sv.gs.cpu().numpy(), gs1)
         # band solve: compare the solution (and the factor on the lower triangles)
         sv.band_solve()
         torch.cuda.synchronize()
@@ -101,6 +102,39 @@ def test_kernels_match_oracle_stage_by_stage(gpu, oracle, size):
         assert relerr(sv.new_points.cpu().numpy(), npt) < 1e-9
         assert np.isclose(float(sv.scal[1]), lin_err, rtol=1e-7)
         assert np.isclose(float(sv.scal[2]), new_err, rtol=1e-7)
+
+
+def test_schur_writes_every_block_of_a_band_wider_than_its_tiles(gpu, oracle):
+    """vus_ba_schur at pose_stride 1 with band_nodes beyond the tile distances the units cover (8 * ceil(T->band / 8)):
+    every stored block is written -- a NaN-filled band comes back finite and equal to the oracle's, zeros beyond the
+    problem's own band included.  The Python solvers always pass band_nodes = T->band; a C caller need not."""
+    import ctypes
+    from visual_underwater_slam_amd import _lib
+    from visual_underwater_slam_amd.ba import StereoBAProblem, StereoBASolver
+    s = synth.nav_sequence(80, 1600, 80)           # the stereo part of a navigation graph: tile band ~25 of 80 poses
+    nP, nL = 80, len(s["points_gt"])
+    prob = StereoBAProblem(s["obs_pose"], s["obs_point"], s["meas"], nP, nL, s["K"], s["sigma"], prior_pose=[0],
+                           prior_T=s["poses_gt"][:1], prior_sigmas=s["prior_sigmas"][None])
+    sv = StereoBASolver(prob)
+    pk = ba_pack.pack_observations(torch.from_numpy(s["obs_pose"]), torch.from_numpy(s["obs_point"]),
+                                   torch.from_numpy(s["meas"]), nP, nL)
+    P = oracle.BAProblem(pk, s["K"], s["sigma"], (np.array([0], np.int32), s["poses_gt"][:1], s["prior_sigmas"][None]))
+    tb = prob.tiles["band"]
+    poses, points = torch.from_numpy(s["poses_init"]).cuda(), torch.from_numpy(s["points_init"]).cuda()
+    lin = oracle.ba_linearize(P, s["poses_init"], s["points_init"])
+    sv.linearize(poses, points)
+    p = _lib.ptr
+    for wide in (tb + 1, 8 * ((tb + 7) // 8) + 1, 8 * ((tb + 7) // 8) + 9):
+        assert wide < nP
+        Sb = torch.full((nP, wide + 1, 36), float("nan"), dtype=torch.float64, device="cuda")
+        gs = torch.full((nP, 6), float("nan"), dtype=torch.float64, device="cuda")
+        _lib.call("vus_ba_schur", sv._pp(), ctypes.addressof(prob.c_tiles), 1e-3, p(sv.W), p(sv.V), p(sv.gl), p(sv.Hpp),
+                  p(sv.gp), p(sv.Vinv), None, p(Sb), wide, p(gs), p(sv._unit_counter), _lib.current_stream_ptr())
+        torch.cuda.synchronize()
+        sch = oracle.ba_schur(P, wide, 1e-3, lin)
+        Sg = Sb.cpu().numpy()
+        assert np.isfinite(Sg).all(), (wide, tb, np.argwhere(~np.isfinite(Sg))[:3])
+        assert relerr(Sg, sch["Sband"]) < 1e-10 and relerr(gs.cpu().numpy(), sch["gs"]) < 1e-10
 
 
 def test_band_solve_reports_indefinite_system(gpu, oracle):

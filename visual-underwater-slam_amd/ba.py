@@ -169,7 +169,8 @@ class StereoBAProblem:
         self.pose_stride = int(pose_stride)
         self.n_nodes = self.pose_stride * int(n_poses)
         if self.pose_stride > 1:        # node layout with velocity nodes: pose blocks are 2 nodes apart,
-            st["band"] = max(self.pose_stride * st["band"], 3)     # inertial factors reach 3 nodes back
+            # inertial factors reach 3 nodes back, but no further than the graph's first node (a single keyframe: 1)
+            st["band"] = min(max(self.pose_stride * st["band"], 3), self.n_nodes - 1)
         if band is not None:            # landmark-sharded solve: every rank allocates the global band
             if band < st["band"]:
                 raise ValueError(f"band={band} is smaller than this problem's own band {st['band']}")

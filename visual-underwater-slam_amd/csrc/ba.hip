@@ -2831,15 +2831,18 @@ extern "C" int vus_ba_schur(const vus_ba_problem* P, const vus_ba_tiles* T, doub
   VUS_REQUIRE(T->unit_ptr && T->order && (T->entries || T->n_entries == 0), "tile lists are null");
   hipStream_t st = vus::as_stream(stream);
   // With velocity nodes between the poses (ps = 2) the blocks the tile pairs do not cover belong to the inertial
-  // factors and start from zero.  With ps = 1 every stored block (i, k), 0 <= k <= i, i - k <= band, is WRITTEN by its
-  // tile pair (nothing is accumulated into); the slots left of pose 0 (k < 0) of the first band rows are never read by
-  // the solvers (csrc/band_index.h masks them) and only kept finite.
-  if (ps > 1) {
+  // factors and start from zero.  With ps = 1 every stored block (i, k), 0 <= k <= i, i - k <= band_nodes, within the
+  // pose distances the units reach (tile distances up to ceil(T->band / 8): 8 ceil(T->band / 8) poses) is WRITTEN by
+  // its tile pair (nothing is accumulated into); a wider storage band is zeroed first, since no landmark spans the
+  // blocks beyond.  The slots left of pose 0 (k < 0) of the first band rows are never read by the solvers
+  // (csrc/band_index.h masks them) and only kept finite.
+  const bool beyond_units = band_nodes > 8 * ((T->band + 7) / 8);
+  if (ps > 1 || beyond_units)
     VUS_CHECK_HIP(hipMemsetAsync(Sband, 0, sizeof(double) * 36 * (size_t)nP * ps * (band_nodes + 1), st));
+  if (ps > 1)
     VUS_CHECK_HIP(hipMemsetAsync(gs, 0, sizeof(double) * 6 * (size_t)nP * ps, st));
-  } else if (band_nodes > 0) {
+  else if (band_nodes > 0 && !beyond_units)
     band_head_zero_kernel<<<min(band_nodes, nP), 256, 0, st>>>(Sband, nP, band_nodes);
-  }
   VUS_CHECK_HIP(hipMemsetAsync(counter, 0, sizeof(int), st));
   if (nL > 0) vinv_kernel<<<cdiv(nL, 256), 256, 0, st>>>(nL, lambda, V, Vinv);
   if (nO > 0 && Y != nullptr) ymul_kernel<<<cdiv(nO, 256), 256, 0, st>>>(*P, W, Vinv, Y);   // optional output only

@@ -252,9 +252,11 @@ IMU_ACC_COV, IMU_GYRO_COV, IMU_INT_COV = 8.999999999999999e-08, 1.21846967914683
 
 
 def nav_sequence(n_kf, n_lm, obs_per_kf, seed=SEED, kf_period=0.2, pose_sigma_t=0.05, pose_sigma_r=0.01,
-                 meas_sigma=1.0, dvl_sigma=0.0, rest_start=False):
+                 meas_sigma=1.0, dvl_sigma=0.0, rest_start=False, yaw_rate=None):
     """Down-looking stereo rig on a smooth meandering track with a 200 Hz IMU (dt = 0.005, batch.py:290)
-    and a DVL (body-frame velocity).  The keyframe states are produced by integrating the sampled IMU
+    and a DVL (body-frame velocity).  `yaw_rate` (rad/s) adds a steady turn of the heading about the vertical on top of
+    the meander, so that a long enough track carries the absolute heading through +-pi; None leaves the sequence as it
+    was.  The keyframe states are produced by integrating the sampled IMU
     signals with the same discrete model the preintegration uses, so the inertial factors are exactly
     consistent with the ground truth; the images see landmarks 2-6 m below the vehicle.
 
@@ -268,6 +270,8 @@ def nav_sequence(n_kf, n_lm, obs_per_kf, seed=SEED, kf_period=0.2, pose_sigma_t=
 
     def desired(t):
         yaw = 0.35 * np.sin(0.15 * t)
+        if yaw_rate is not None:
+            yaw = yaw + yaw_rate * t
         pitch, roll = 0.04 * np.sin(0.5 * t), 0.03 * np.sin(0.37 * t + 1.0)
         cy, sy, cp, sp, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
         Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]])
