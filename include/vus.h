@@ -267,7 +267,8 @@ typedef struct vus_ba_problem {
   const double* prior_T;   /* [n_priors,12] prior mean */
   const double* prior_w;   /* [n_priors,6] 1/sigma per tangent coordinate (rot xyz, trans xyz) */
   int pose_stride;         /* camera-side node layout: pose i is node pose_stride*i (0 or 1: poses only;
-                              2: node 2i = X(i), node 2i+1 = V(i) padded to 6, for graphs with vus_nav_factors).
+                              2: node 2i = X(i), node 2i+1 = V(i) padded to 6, for graphs with vus_nav_factors;
+                              3: node 3i = X(i), 3i+1 = V(i), 3i+2 = B(i), for graphs with vus_navb_factors).
                               Everything indexed "by node" (Sband rows, gs, dp) uses 6 doubles per node. */
 } vus_ba_problem;
 
@@ -518,4 +519,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Marginal covariances (gtsam.Marginals): block-band selected inversion of the factor, landmark covariances, the
  * shared-bias border -- vus_ba_band_selinv, vus_ba_point_check, vus_ba_point_covariance, vus_nav_border_covariance. */
 #include "vus_marginals.h"
+
+/* Inertial graphs with one IMU bias per keyframe (pose_stride 3): vus_navb_factors and vus_navb_linearize / _assemble /
+ * _eval_step / _error. */
+#include "vus_nav_bias.h"
 #endif /* VUS_H */

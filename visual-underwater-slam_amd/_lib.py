@@ -61,6 +61,11 @@ SIGNATURES = {
     "vus_nav_border_solve": [c_int, _P, _P, _P, _P, c_double, _P, _P, _P],
     "vus_nav_eval_step": [_P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "vus_nav_error": [_P, c_int, _P, _P, _P, _P, _P, _P],
+    # one IMU bias per keyframe (include/vus_nav_bias.h)
+    "vus_navb_linearize": [_P, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_navb_assemble": [c_int, c_int, c_double, _P, _P, _P, _P, _P],
+    "vus_navb_eval_step": [_P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_navb_error": [_P, c_int, _P, _P, _P, _P, _P, _P],
     # marginal covariances (include/vus_marginals.h)
     "vus_ba_band_selinv": [_P, c_int, c_int, _P, _P, ctypes.c_longlong, _P],
     "vus_ba_point_check": [_P, c_int, _P, _P],
@@ -113,6 +118,8 @@ def load():
     lib.vus_ba_get_tuning.restype = c_int
     lib.vus_nav_work_doubles.argtypes = [_P]
     lib.vus_nav_work_doubles.restype = ctypes.c_longlong
+    lib.vus_navb_work_doubles.argtypes = [_P]
+    lib.vus_navb_work_doubles.restype = ctypes.c_longlong
     lib.vus_ba_band_selinv_work_doubles.argtypes = [c_int, c_int]
     lib.vus_ba_band_selinv_work_doubles.restype = ctypes.c_longlong
     _lib = lib

@@ -168,9 +168,13 @@ class StereoBAProblem:
         self.n_poses, self.n_points, self.n_obs = int(n_poses), int(n_points), pk["n_obs"]
         self.pose_stride = int(pose_stride)
         self.n_nodes = self.pose_stride * int(n_poses)
-        if self.pose_stride > 1:        # node layout with velocity nodes: pose blocks are 2 nodes apart,
+        if self.pose_stride == 2:       # node layout with velocity nodes: pose blocks are 2 nodes apart,
             # inertial factors reach 3 nodes back, but no further than the graph's first node (a single keyframe: 1)
             st["band"] = min(max(self.pose_stride * st["band"], 3), self.n_nodes - 1)
+        elif self.pose_stride == 3:     # velocity and bias nodes (NavBiasBASolver): an ImuFactor reaches 4 nodes back
+            st["band"] = min(max(self.pose_stride * st["band"], 4), self.n_nodes - 1)
+        elif self.pose_stride > 3:
+            raise ValueError(f"pose_stride={self.pose_stride}: 1, 2 or 3")
         if band is not None:            # landmark-sharded solve: every rank allocates the global band
             if band < st["band"]:
                 raise ValueError(f"band={band} is smaller than this problem's own band {st['band']}")
@@ -224,10 +228,13 @@ class BAMarginals:
                                          border-corrected on inertial graphs
       pose_cov  [n_poses, 6, 6]          tangent order (rot, trans), body frame
       point_cov [n_points, 3, 3] or None world frame, indexed by the problem's landmark index
-    and on inertial graphs vel_cov [n_poses, 3, 3], bias_cov [6, 6] (acc, gyro), node_bias_cov [n_nodes, 6, 6]."""
+    and on inertial graphs vel_cov [n_poses, 3, 3], bias_cov [6, 6] (acc, gyro), node_bias_cov [n_nodes, 6, 6]; with one
+    bias per keyframe (NavBiasBASolver) biases_cov [n_poses, 6, 6] instead of the last two (B(i) is node 3i + 2)."""
 
-    def __init__(self, solver, values, Sigma, pose_cov, point_cov, U=None, vel_cov=None, bias_cov=None, node_bias_cov=None):
+    def __init__(self, solver, values, Sigma, pose_cov, point_cov, U=None, vel_cov=None, bias_cov=None, node_bias_cov=None,
+                 biases_cov=None):
         self.solver, self._values = solver, values
+        self.biases_cov = biases_cov
         self.band, self.pose_stride = solver.P.band, solver.P.pose_stride
         self.Sigma, self.pose_cov, self.point_cov = Sigma, pose_cov, point_cov
         self.U, self.vel_cov, self.bias_cov, self.node_bias_cov = U, vel_cov, bias_cov, node_bias_cov
@@ -834,3 +841,137 @@ class NavBASolver(StereoBASolver):
         rep.seconds = time.perf_counter() - t0
         rep.final_error, rep.final_lambda = current, lam
         return poses, vels, bias, points, rep
+
+
+# ---------------------------------------------------------------------------------------------
+# graphs with one IMU bias per keyframe (include/vus_nav_bias.h): GTSAM's usual visual-inertial graph
+class _CNavBias(ctypes.Structure):
+    _fields_ = _CNav._fields_ + [("n_bbetween", c_int), ("bb_i", c_void_p), ("bb_j", c_void_p), ("bb_meas", c_void_p),
+                                 ("bb_w", c_void_p), ("n_bprior", c_int), ("bp_idx", c_void_p), ("bp_mean", c_void_p),
+                                 ("bp_w", c_void_p)]
+
+
+class NavBiasFactors:
+    """Device-resident vus_navb_factors.  imu, dvl, vprior as NavFactors (ImuFactor f uses bias B(imu_i[f]));
+    bbetween = (i, j, meas [n,6], sigmas [n,6]) for BetweenFactorConstantBias(B(i), B(j = i + 1)), bprior = (idx,
+    mean [n,6], sigmas [n,6]) for PriorFactorConstantBias.  Diagonal noise models; 6-vectors in the order (acc, gyro)."""
+
+    def __init__(self, gravity, imu=None, dvl=None, vprior=None, bbetween=None, bprior=None, device="cuda:0"):
+        dev = torch.device(device)
+        z = []
+        h = lambda x, shape: np.asarray(x, dtype=np.float64).reshape(shape)
+        hi = lambda x: np.asarray(x, dtype=np.int64).reshape(-1)
+        self.imu_i_h = hi(imu[0] if imu else z)
+        imu_j = hi(imu[1] if imu else z)
+        if self.imu_i_h.size and bool((imu_j - self.imu_i_h != 1).any()):
+            raise NotImplementedError("ImuFactor between non-consecutive poses is not supported")
+        self.bb_i_h, bb_j = hi(bbetween[0] if bbetween else z), hi(bbetween[1] if bbetween else z)
+        if self.bb_i_h.size and bool((bb_j - self.bb_i_h != 1).any()):
+            raise NotImplementedError("BetweenFactorConstantBias between non-consecutive biases is not supported")
+        self.bp_idx_h = hi(bprior[0] if bprior else z)
+
+        def t(x, dt):
+            return torch.from_numpy(np.ascontiguousarray(x)).to(device=dev, dtype=dt).contiguous()
+        self.imu_i, self.imu_j = t(self.imu_i_h, torch.int32), t(imu_j, torch.int32)
+        self.imu_pim = t(h(imu[2] if imu else z, (-1, 148)), torch.float64)
+        self.imu_W = t(h(imu[3] if imu else z, (-1, 81)), torch.float64)
+        self.dvl_pose = t(hi(dvl[0] if dvl else z), torch.int32)
+        self.dvl_meas = t(h(dvl[1] if dvl else z, (-1, 3)), torch.float64)
+        self.dvl_w = t(1.0 / h(dvl[2] if dvl else z, (-1,)), torch.float64)
+        self.vp_idx = t(hi(vprior[0] if vprior else z), torch.int32)
+        self.vp_v = t(h(vprior[1] if vprior else z, (-1, 3)), torch.float64)
+        self.vp_w = t(1.0 / h(vprior[2] if vprior else z, (-1, 3)), torch.float64)
+        self.bb_i, self.bb_j = t(self.bb_i_h, torch.int32), t(bb_j, torch.int32)
+        self.bb_meas = t(h(bbetween[2] if bbetween else z, (-1, 6)), torch.float64)
+        self.bb_w = t(1.0 / h(bbetween[3] if bbetween else z, (-1, 6)), torch.float64)
+        self.bp_idx = t(self.bp_idx_h, torch.int32)
+        self.bp_mean = t(h(bprior[1] if bprior else z, (-1, 6)), torch.float64)
+        self.bp_w = t(1.0 / h(bprior[2] if bprior else z, (-1, 6)), torch.float64)
+        pp = lambda x: _lib.ptr(x) if x.numel() else None
+        self.c = _CNavBias(self.imu_i.numel(), pp(self.imu_i), pp(self.imu_j), pp(self.imu_pim), pp(self.imu_W),
+                           (c_double * 3)(*[float(g) for g in gravity]), self.dvl_pose.numel(), pp(self.dvl_pose),
+                           pp(self.dvl_meas), pp(self.dvl_w), self.vp_idx.numel(), pp(self.vp_idx), pp(self.vp_v),
+                           pp(self.vp_w), self.bb_i.numel(), pp(self.bb_i), pp(self.bb_j), pp(self.bb_meas), pp(self.bb_w),
+                           self.bp_idx.numel(), pp(self.bp_idx), pp(self.bp_mean), pp(self.bp_w))
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+    def unconstrained_biases(self, n_poses):
+        """Biases with neither a prior nor a between-factor: their information comes from ImuFactors alone, if any."""
+        seen = np.zeros(n_poses, bool)
+        for a in (self.bb_i_h, self.bb_i_h + 1, self.bp_idx_h):
+            seen[a[(a >= 0) & (a < n_poses)]] = True
+        return np.nonzero(~seen)[0]
+
+
+class NavBiasBASolver(NavBASolver):
+    """LM over poses, velocities, ONE IMU BIAS PER KEYFRAME and landmarks (GTSAM's usual visual-inertial graph).  The
+    problem must have been built with pose_stride=3: node 3i = X(i), 3i+1 = V(i) padded to 6, 3i+2 = B(i).  There is no
+    border; every lambda trial is one single-right-hand-side band solve (two-sided on long graphs).  optimize() is
+    NavBASolver's loop, with `bias` the [n_poses, 6] per-keyframe biases."""
+
+    def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors):
+        if problem.pose_stride != 3:
+            raise ValueError("NavBiasBASolver needs a StereoBAProblem built with pose_stride=3")
+        StereoBASolver.__init__(self, problem)
+        self.N = nav
+        dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.Snav = torch.empty((nN, 5, 36), **f64)
+        self.gnav = torch.empty((nN, 6), **f64)
+        self.new_vels = torch.empty((nP, 3), **f64)
+        self.new_bias = torch.empty((nP, 6), **f64)
+        self.nav_scal = torch.zeros((4,), **f64)
+        self.nav_work = torch.empty((int(_lib.load().vus_navb_work_doubles(nav.addr())),), **f64)
+
+    def nav_error(self, poses, vels, biases) -> float:
+        p = _lib.ptr
+        _lib.call("vus_navb_error", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.nav_scal),
+                  p(self.nav_work), _lib.current_stream_ptr())
+        return float(self.nav_scal[0].item())
+
+    def nav_linearize(self, poses, vels, biases):
+        p = _lib.ptr
+        _lib.call("vus_navb_linearize", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.Snav),
+                  p(self.gnav), p(self.nav_scal), p(self.nav_work), _lib.current_stream_ptr())
+
+    def nav_assemble(self, lam):
+        p = _lib.ptr
+        _lib.call("vus_navb_assemble", self.P.n_nodes, self.P.band, float(lam), p(self.Snav), p(self.gnav),
+                  p(self.Sband), p(self.gs), _lib.current_stream_ptr())
+
+    def nav_solve(self, lam):
+        self.band_solve()
+
+    def nav_eval_step(self, poses, vels, biases):
+        p = _lib.ptr
+        _lib.call("vus_navb_eval_step", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.dp),
+                  p(self.new_poses), p(self.new_vels), p(self.new_bias), p(self.nav_scal[1:]), p(self.nav_work),
+                  _lib.current_stream_ptr())
+
+    def marginals(self, poses, vels, biases, points, points_cov=True) -> BAMarginals:
+        """Marginal covariances at (poses, vels, biases, points): the one-sided factor of the whole camera-side system at
+        lambda = 0 and its selected inversion -- no border step, every bias is a band node.  The BAMarginals carries
+        vel_cov [n, 3, 3] and biases_cov [n, 6, 6] (B(i) is node 3i + 2, for joint()).  Raises IndeterminantSystem("bias",
+        i) for a bias B(i) with neither a prior nor a between-factor."""
+        c = lambda x: x.to(torch.float64).contiguous()
+        values = (c(poses), c(vels), c(biases), c(points))
+        free = self.N.unconstrained_biases(self.P.n_poses)
+        if len(free):
+            raise IndeterminantSystem("bias", int(free[0]))
+        self._linearize_all(values)
+        p, st = _lib.ptr, _lib.current_stream_ptr()
+        while True:
+            self._assemble_zero()
+            _lib.call("vus_ba_band_solve", p(self.Sband), self.P.n_nodes, self.P.band, p(self.gs), p(self.dp),
+                      p(self.status), st)
+            if not self._factor_status():
+                break
+        Sigma = self._selinv()
+        nP = self.P.n_poses
+        nodes = torch.arange(nP, device=self.P.device) * 3
+        pc = self._point_cov(Sigma) if points_cov else None
+        return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, nodes), pc,
+                           vel_cov=Sigma[nodes + 1, 0].reshape(nP, 6, 6)[:, :3, :3],
+                           biases_cov=Sigma[nodes + 2, 0].reshape(nP, 6, 6))

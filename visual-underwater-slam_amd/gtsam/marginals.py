@@ -53,6 +53,8 @@ class Marginals:
         QR = 1
 
     CHOLESKY, QR = Factorization.CHOLESKY, Factorization.QR
+    _bias_keys: List[int] = []          # one bias per keyframe: B(i) of keyframe i (empty on the other graphs)
+    _bias_idx: Dict[int, int] = {}
 
     def __init__(self, graph, values, factorization=None, device="cuda:0"):
         import torch
@@ -73,6 +75,7 @@ class Marginals:
         self._lm_keys = [int(k) for k in np.asarray(pg["lm_keys"].cpu() if hasattr(pg["lm_keys"], "cpu") else pg["lm_keys"]).tolist()]
         self._vel_keys = [int(k) for k in nav["vel_keys"]] if nav else []
         self._bias_key = int(nav["bias_key"]) if nav and nav["bias_key"] is not None else None
+        self._bias_keys = [int(k) for k in nav["bias_keys"]] if nav and nav.get("per_keyframe") else []
         try:
             if nav:
                 m = sv.marginals(t(pg["poses"]), t(nav["vels"]), t(nav["bias"]), t(pg["points"]))
@@ -85,19 +88,23 @@ class Marginals:
         self._point_cov = m.point_cov.cpu().numpy() if m.point_cov is not None else np.zeros((0, 3, 3))
         self._vel_cov = m.vel_cov.cpu().numpy() if m.vel_cov is not None else None
         self._bias_cov = m.bias_cov.cpu().numpy() if m.bias_cov is not None else None
+        self._biases_cov = m.biases_cov.cpu().numpy() if m.biases_cov is not None else None
         self._aux: Dict[int, np.ndarray] = {int(k): np.diag(1.0 / np.asarray(w, float) ** 2) for k, w in zip(aux.keys, aux.w)}
         self._pose_idx = {k: i for i, k in enumerate(self._pose_keys)}
         self._lm_idx = {k: j for j, k in enumerate(self._lm_keys)}
         self._vel_idx = {k: i for i, k in enumerate(self._vel_keys)}
+        self._bias_idx = {k: i for i, k in enumerate(self._bias_keys)}
 
     def _key_of(self, kind, index):
         if kind == "point":
             return self._lm_keys[index]
         if kind == "bias":
+            if self._bias_keys:                      # one bias per keyframe: the index is the keyframe's
+                return self._bias_keys[index]
             return self._bias_key if self._bias_key is not None else -1
-        ps = 2 if self._vel_keys else 1
+        ps = (3 if self._bias_keys else 2) if self._vel_keys else 1
         i, r = divmod(index, ps)
-        return self._vel_keys[i] if r else self._pose_keys[i]
+        return (self._pose_keys, self._vel_keys, self._bias_keys)[r][i]
 
     def _missing(self, key):
         return RuntimeError(f"Attempting to at the key \"{_sym.key_string(int(key))}\", which does not exist in the Values.")
@@ -112,6 +119,8 @@ class Marginals:
             return self._vel_cov[self._vel_idx[key]].copy()
         if self._bias_key is not None and key == self._bias_key:
             return self._bias_cov.copy()
+        if key in self._bias_idx:
+            return self._biases_cov[self._bias_idx[key]].copy()
         if key in self._aux:
             return self._aux[key].copy()
         raise self._missing(key)
@@ -126,9 +135,11 @@ class Marginals:
         if len(keys) == 1:
             c = self.marginalCovariance(keys[0])
             return JointMarginal(keys, [c.shape[0]], c)
-        cam = [k for k in keys if k in self._pose_idx or k in self._vel_idx]
+        cam = [k for k in keys if k in self._pose_idx or k in self._vel_idx or k in self._bias_idx]
         lms = [k for k in keys if k in self._lm_idx]
-        nodes = [self._stride * self._pose_idx[k] if k in self._pose_idx else 2 * self._vel_idx[k] + 1 for k in cam]
+        nodes = [self._stride * self._pose_idx[k] if k in self._pose_idx else
+                 self._stride * self._vel_idx[k] + 1 if k in self._vel_idx else self._stride * self._bias_idx[k] + 2
+                 for k in cam]
         with_bias = self._bias_key is not None and self._bias_key in keys
         if lms:
             # from the band: landmarks need every pose observing them inside one band window with the other keys

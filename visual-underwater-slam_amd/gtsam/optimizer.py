@@ -142,9 +142,10 @@ def _pack_graph(graph, values, device=None):
     The per-observation key -> index mapping (a sort of every landmark key) runs on `device` with torch when one
     is given (2 M observations: ~3 ms on the GPU against ~0.3 s in numpy), else in numpy (CPU tests)."""
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
-                   ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias)
+                   ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias, PriorFactorConstantBias,
+                   BetweenFactorConstantBias)
     meas, pkeys, lkeys = [], [], []
-    imu_f, dvl_f = [], []
+    imu_f, dvl_f, bias_f = [], [], []
     from . import _Robust
     model_sigma, calib, loss = None, None, None
     prior_pose, prior_vec = [], []
@@ -180,6 +181,8 @@ def _pack_graph(graph, values, device=None):
             imu_f.append(f)
         elif isinstance(f, DvlVelocityFactor):
             dvl_f.append(f)
+        elif isinstance(f, (PriorFactorConstantBias, BetweenFactorConstantBias)):
+            bias_f.append(f)
         elif isinstance(f, CustomFactor):
             low = lower_reference_dvl_factor(f)
             if low is not None:
@@ -256,8 +259,8 @@ def _pack_graph(graph, values, device=None):
             raise RuntimeError(f"Attempting to at the key \"{_sym.key_string(k)}\", which does not exist in the Values.")
         pr_idx.append(j); pr_T.append(f._prior.flat12()); pr_s.append(f._model.sigmas())
     nav = None
-    if imu_f or dvl_f:
-        nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec)
+    if imu_f or dvl_f or bias_f:
+        nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f)
     aux = _AuxPriors()
     for f in prior_vec:
         k = f._keys[0]
@@ -276,9 +279,10 @@ def _pack_graph(graph, values, device=None):
                 prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav)
 
 
-def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec):
+def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=()):
     """Velocity / bias side of the graph (batch.py:274-293): every pose X(i) needs a velocity V(i) with the same
-    index; one shared bias key (batch.py:238 passes B(0) to every ImuFactor)."""
+    index; either one shared bias key (batch.py:238 passes B(0) to every ImuFactor) or, when the graph has bias factors
+    or several bias keys, one bias B(i) per keyframe (_pack_bias_walk)."""
     from . import _ConstantBias
     pidx = {int(k): i for i, k in enumerate(pose_keys.tolist())}
     vel_keys = []
@@ -292,10 +296,13 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec):
     if vels.shape[1] != 3:
         raise RuntimeError("velocity variables must be 3-vectors")
     bias_keys = sorted({f._keys[4] for f in imu_f})
-    if len(bias_keys) > 1:
-        raise NotImplementedError("several IMU bias variables are not supported (batch.py uses the single B(0))")
-    bias_key = bias_keys[0] if bias_keys else None
+    per_keyframe = bool(bias_f) or len(bias_keys) > 1
+    if per_keyframe:
+        bias_keys, biases, bbetween, bprior = _pack_bias_walk(values, pose_keys, imu_f, bias_f)
+    bias_key = bias_keys[0] if bias_keys and not per_keyframe else None
     bias = values.atConstantBias(bias_key).vector() if bias_key is not None else np.zeros(6)
+    if per_keyframe:
+        bias = biases
     imu_i, imu_j, pims, Ws, grav = [], [], [], [], None
     for f in imu_f:
         ki, kvi, kj, kvj, _ = f._keys
@@ -320,7 +327,9 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec):
             vp_i.append(vidx[k]); vp_v.append(f._prior); vp_s.append(f._model.sigmas())
         else:
             rest.append(f)
-    nav = dict(vel_keys=vel_keys, bias_key=bias_key, vels=vels, bias=bias,
+    nav = dict(vel_keys=vel_keys, bias_key=bias_key, vels=vels, bias=bias, per_keyframe=per_keyframe,
+               bias_keys=bias_keys if per_keyframe else None, bbetween=bbetween if per_keyframe else None,
+               bprior=bprior if per_keyframe else None,
                gravity=grav if grav is not None else np.array([0.0, 0.0, -9.81]),
                imu=(np.asarray(imu_i, np.int32), np.asarray(imu_j, np.int32), np.asarray(pims, float).reshape(-1, 148),
                     np.asarray(Ws, float).reshape(-1, 81)) if imu_f else None,
@@ -330,13 +339,75 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec):
     return nav, rest
 
 
+def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
+    """One bias per keyframe (GTSAM's ImuFactorsExample): B(i) for every X(i), ImuFactor(X(i), V(i), X(i+1), V(i+1), B(i)),
+    BetweenFactorConstantBias only between consecutive biases, PriorFactorConstantBias with a diagonal or isotropic
+    model.  Returns (bias keys, biases [n, 6], bbetween = (i, j, meas, sigmas) or None, bprior = (idx, mean, sigmas) or
+    None).  Anything else is refused with the reason."""
+    from . import PriorFactorConstantBias, _Robust
+    n = len(pose_keys)
+    pidx = {int(k): i for i, k in enumerate(pose_keys.tolist())}
+    bias_keys = [_sym.symbol("b", _sym.symbolIndex(int(k))) for k in pose_keys.tolist()]
+    bidx = {k: i for i, k in enumerate(bias_keys)}
+    name = _sym.key_string
+    per_key = {}
+    for f in imu_f:
+        per_key.setdefault(f._keys[4], []).append(f)
+    shared = [k for k, fs in per_key.items() if len(fs) > 1]
+    if shared:
+        raise NotImplementedError(
+            f"the graph mixes one shared bias ({name(shared[0])} in {len(per_key[shared[0]])} ImuFactors) with per-keyframe "
+            "biases (bias factors or several bias keys): give each ImuFactor the bias B(i) of its earlier keyframe")
+    for k in bias_keys:
+        if not values.exists(k):
+            raise RuntimeError(f"per-keyframe biases: the bias {name(k)} of keyframe {name(pose_keys[bidx[k]])} is missing "
+                               f"(Attempting to at the key \"{name(k)}\", which does not exist in the Values.)")
+    for f in imu_f:
+        i = pidx.get(f._keys[0])
+        if i is not None and f._keys[4] != bias_keys[i]:
+            raise NotImplementedError(f"ImuFactor({name(f._keys[0])}, .., {name(f._keys[2])}) uses the bias "
+                                      f"{name(f._keys[4])}; with per-keyframe biases it must use {name(bias_keys[i])}, the "
+                                      "bias of its earlier keyframe")
+    bb_i, bb_m, bb_s, bp_i, bp_m, bp_s = [], [], [], [], [], []
+    for f in bias_f:
+        what = type(f).__name__
+        if isinstance(f._model, _Robust):
+            raise NotImplementedError(f"{what} on {', '.join(name(k) for k in f._keys)}: robust noise models on bias factors "
+                                      "are not supported")
+        if f._model.dim() != 6:
+            raise RuntimeError(f"{what}: needs a 6-dimensional noise model")
+        for k in f._keys:
+            if k not in bidx:
+                raise NotImplementedError(f"{what} on {name(k)}: not the bias B(i) of a keyframe X(i)")
+        if isinstance(f, PriorFactorConstantBias):
+            bp_i.append(bidx[f._keys[0]]); bp_m.append(f._prior.vector()); bp_s.append(f._model.sigmas())
+        else:
+            a, b = bidx[f._keys[0]], bidx[f._keys[1]]
+            if b != a + 1:
+                raise NotImplementedError(f"BetweenFactorConstantBias({name(f._keys[0])}, {name(f._keys[1])}): only "
+                                          "consecutive biases B(i), B(i+1) can be joined")
+            bb_i.append(a); bb_m.append(f._measured.vector()); bb_s.append(f._model.sigmas())
+    biases = np.stack([values.atConstantBias(k).vector() for k in bias_keys])
+    bbetween = (np.asarray(bb_i, np.int32), np.asarray(bb_i, np.int32) + 1, np.asarray(bb_m, float).reshape(-1, 6),
+                np.asarray(bb_s, float).reshape(-1, 6)) if bb_i else None
+    bprior = (np.asarray(bp_i, np.int32), np.asarray(bp_m, float).reshape(-1, 6),
+              np.asarray(bp_s, float).reshape(-1, 6)) if bp_i else None
+    assert len(biases) == n
+    return bias_keys, biases, bbetween, bprior
+
+
 def _build_solver(pg, device="cuda:0"):
-    from ..ba import StereoBAProblem, StereoBASolver, NavBASolver, NavFactors
+    from ..ba import StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors
     nav = pg.get("nav")
+    walk = bool(nav) and nav.get("per_keyframe", False)
     prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], len(pg["pose_keys"]), len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
-                           prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=2 if nav else 1,
+                           prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=(3 if walk else 2) if nav else 1,
                            loss=pg.get("loss"))
+    if walk:
+        nf = NavBiasFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], bbetween=nav["bbetween"],
+                            bprior=nav["bprior"], device=device)
+        return prob, NavBiasBASolver(prob, nf)
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
         return prob, NavBASolver(prob, nf)
@@ -411,6 +482,8 @@ class LevenbergMarquardtOptimizer:
                 out.update(k, v)
             if nav["bias_key"] is not None:
                 out.update(nav["bias_key"], _ConstantBias(bias[:3], bias[3:]))
+            for k, b in zip(nav["bias_keys"] or (), bias.reshape(-1, 6) if nav["per_keyframe"] else ()):
+                out.update(k, _ConstantBias(b[:3], b[3:]))
         out._store_rows("pose3", pg["pose_keys"], poses)
         out._store_rows("point3", pg["lm_keys"], points)
         if aux is not None:

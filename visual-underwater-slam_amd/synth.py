@@ -252,11 +252,14 @@ IMU_ACC_COV, IMU_GYRO_COV, IMU_INT_COV = 8.999999999999999e-08, 1.21846967914683
 
 
 def nav_sequence(n_kf, n_lm, obs_per_kf, seed=SEED, kf_period=0.2, pose_sigma_t=0.05, pose_sigma_r=0.01,
-                 meas_sigma=1.0, dvl_sigma=0.0, rest_start=False, yaw_rate=None):
+                 meas_sigma=1.0, dvl_sigma=0.0, rest_start=False, yaw_rate=None, bias_walk_sigma=None):
     """Down-looking stereo rig on a smooth meandering track with a 200 Hz IMU (dt = 0.005, batch.py:290)
     and a DVL (body-frame velocity).  `yaw_rate` (rad/s) adds a steady turn of the heading about the vertical on top of
     the meander, so that a long enough track carries the absolute heading through +-pi; None leaves the sequence as it
-    was.  The keyframe states are produced by integrating the sampled IMU
+    was.  `bias_walk_sigma` (acc, gyro) -- two scalars or one for both -- gives the IMU a bias that drifts as a random
+    walk, one step of that sigma per keyframe from zero at keyframe 0: the samples between keyframes i and i + 1 carry
+    bias i, and the result gains biases_gt [n_kf, 6] (acc, gyro); None leaves the sequence as it was (the samples are
+    bias-free and no key is added).  The keyframe states are produced by integrating the sampled IMU
     signals with the same discrete model the preintegration uses, so the inertial factors are exactly
     consistent with the ground truth; the images see landmarks 2-6 m below the vehicle.
 
@@ -305,6 +308,14 @@ def nav_sequence(n_kf, n_lm, obs_per_kf, seed=SEED, kf_period=0.2, pose_sigma_t=
             vk = vk + g * IMU_DT + (Rk @ ab) * IMU_DT
             Rk = Rk @ so3_expmap(om * IMU_DT)
         poses[i, :9], poses[i, 9:], vels[i] = Rk.reshape(-1), pk, vk
+    biases = None
+    if bias_walk_sigma is not None:     # the states integrate the true signals; the samples carry the bias on top
+        sa, sg = np.broadcast_to(np.asarray(bias_walk_sigma, dtype=float), (2,))
+        steps = _hash_normal(6 * n_kf, seed ^ 0x8888).reshape(n_kf, 6) * np.array([sa] * 3 + [sg] * 3)
+        steps[0] = 0.0
+        biases = np.cumsum(steps, axis=0)
+        if n_kf > 1:
+            imu[:, :, :6] += biases[:-1, None, :]
     # landmarks below the track
     fx, fy, cx, cy = INTRINSIC
     j = np.arange(n_lm, dtype=np.int64)
@@ -357,12 +368,15 @@ def nav_sequence(n_kf, n_lm, obs_per_kf, seed=SEED, kf_period=0.2, pose_sigma_t=
     dvl = np.einsum("nji,nj->ni", poses[:, :9].reshape(-1, 3, 3), vels)       # R^T v
     if dvl_sigma > 0:
         dvl = dvl + dvl_sigma * _hash_normal(3 * n_kf, seed ^ 0x7777).reshape(n_kf, 3)
-    return {
+    out = {
         "poses_gt": poses, "poses_init": poses_init, "points_gt": pts, "points_init": pts_init,
         "vels_gt": vels, "imu": imu, "dvl": dvl, "gravity": g,
         "obs_pose": obs_p.astype(np.int32), "obs_point": obs_l.astype(np.int32), "meas": meas,
         "K": np.array([fx, fy, 0.0, cx, cy, BASELINE_M]), "sigma": STEREO_SIGMA, "prior_sigmas": np.array(PRIOR_SIGMAS),
     }
+    if biases is not None:
+        out["biases_gt"] = biases
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
