@@ -178,7 +178,7 @@ def test_stage_by_stage_at_scale(gpu, oracle, scale_case, band_tuning):
     if n_kf >= 171:
         assert sv.use_split and n_nodes >= 2 * prob.band + sv.SPLIT_MIN_EXTRA      # the two-sided solve
     if n_kf >= 600:
-        assert n_part > 1024                     # reduce_kernel over the error partials: more than one pass
+        assert n_part > 1024                     # reduce_partials_kernel over the error partials: more than one pass
     modes = (None, 0, 1, 2, 3) if n_kf == SIZES[-1] else (None,)
     stage_by_stage(oracle, s, P, N, prob, sv, 1e-4, band_tuning, modes)
 

@@ -437,17 +437,19 @@ class StereoBASolver:
         return False
 
     def _marginal_factor(self, values):
-        """Linearise at `values` with no damping and leave the ONE-SIDED factor of S (lambda = 0) in Sband."""
-        poses, points = values
-        self.linearize(poses, points)
-        self._check_points()
-        p = _lib.ptr
+        """Linearise at `values` with no damping and leave the ONE-SIDED factor of S (lambda = 0) in Sband, redoing the
+        factorisation after a window-kernel fallback."""
+        self._linearize_all(values)
         while True:
-            self.schur(0.0)
-            _lib.call("vus_ba_band_solve", p(self.Sband), self.P.n_nodes, self.P.band, p(self.gs), p(self.dp),
-                      p(self.status), _lib.current_stream_ptr())
+            self._assemble_zero()
+            self._factor_zero()
             if not self._factor_status():
                 return
+
+    def _factor_zero(self):
+        p = _lib.ptr
+        _lib.call("vus_ba_band_solve", p(self.Sband), self.P.n_nodes, self.P.band, p(self.gs), p(self.dp),
+                  p(self.status), _lib.current_stream_ptr())
 
     def _selinv(self):
         nN, B = self.P.n_nodes, self.P.band
@@ -533,6 +535,33 @@ class StereoBASolver:
         self.schur(0.0)
 
     # -- Levenberg-Marquardt ----------------------------------------------------------------------
+    # The stages of one LM iteration over a tuple of state tensors; the inertial solvers extend them.
+    _NEW_STATE = ("new_poses", "new_points")      # the buffers a trial writes, one per state tensor
+
+    def _lm_error(self, state) -> float:
+        return self.error(*state)
+
+    def _lm_linearize(self, state):
+        self.linearize(*state)
+
+    def _lm_solve(self, lam):
+        self.schur(lam)
+        self.band_solve()
+        self.backsub()
+
+    def _lm_eval(self, state):
+        """Evaluate the trial step; (status, [linearised error at 0, at the step, new error]) from ONE blocking read."""
+        self.eval_step(*state)
+        rec = self._trial.cpu()
+        return int(rec[4:].view(torch.int32)[0]), [float(x) for x in rec[:3]]
+
+    def _lm_swap(self, state):
+        """Accept the trial: its buffers become the state, the old state tensors the next trial's buffers."""
+        new = tuple(getattr(self, n) for n in self._NEW_STATE)
+        for n, old in zip(self._NEW_STATE, state):
+            setattr(self, n, old)
+        return new
+
     def optimize(self, poses: torch.Tensor, points: torch.Tensor, params: Optional[LMParams] = None,
                  aux=None):
         """poses [nP,12], points [nL,3] float64 on the GPU; returns optimised copies and an LMReport.
@@ -543,28 +572,27 @@ class StereoBASolver:
             raise NotImplementedError("diagonalDamping=True is not implemented (gtsam default is False)")
         if not prm.useFixedLambdaFactor:
             raise NotImplementedError("useFixedLambdaFactor=False is not implemented (gtsam default is True)")
-        poses = poses.to(torch.float64).contiguous().clone()
-        points = points.to(torch.float64).contiguous().clone()
+        state, rep = self._levenberg_marquardt((poses, points), prm, aux)
+        return (*state, rep)
+
+    def _levenberg_marquardt(self, state, prm, aux=None):
+        """GTSAM's iterate / tryLambda / checkConvergence over copies of `state`; returns (state, LMReport)."""
+        state = tuple(x.to(torch.float64).contiguous().clone() for x in state)
         rep = LMReport(setup_seconds=self.P.setup_seconds)
         torch.cuda.synchronize(self.P.device)
         t0 = time.perf_counter()
         lam = prm.lambdaInitial
-        current = self.error(poses, points) + (aux.error() if aux else 0.0)
+        current = self._lm_error(state) + (aux.error() if aux else 0.0)
         rep.initial_error = current
         if current <= prm.errorTol or prm.maxIterations <= 0:
             rep.status, rep.final_error, rep.final_lambda = 0, current, lam
-            return poses, points, rep
+            return state, rep
         while rep.iterations < prm.maxIterations:
-            self.linearize(poses, points)                         # iterate(): linearise once
-            new_error, stop_search, accepted = current, False, False
-            lin0 = None
+            self._lm_linearize(state)                             # iterate(): linearise once
+            new_error, stop_search, accepted, lin0 = current, False, False, None
             while True:                                           # tryLambda
-                self.schur(lam)
-                self.band_solve()
-                self.backsub()
-                self.eval_step(poses, points)
-                rec = self._trial.cpu()                           # the trial's ONE blocking read
-                sc, status = rec[:4], int(rec[4:].view(torch.int32)[0])
+                self._lm_solve(lam)
+                status, sc = self._lm_eval(state)
                 if status < 0:
                     if self._window_expired(status):              # the band is spoilt: redo this trial launch by launch
                         continue
@@ -572,21 +600,20 @@ class StereoBASolver:
                 rep.tries += 1
                 a_lin, a_new = aux.try_lambda(lam) if aux else (0.0, 0.0)
                 if lin0 is None:
-                    lin0 = float(sc[0]) + (aux.error() if aux else 0.0)
+                    lin0 = sc[0] + (aux.error() if aux else 0.0)
                 success = False
-                if status == 0 and math.isfinite(float(sc[1])) and math.isfinite(float(sc[2])):
-                    lin_change = lin0 - (float(sc[1]) + a_lin)
+                lin1, new1 = sc[1] + a_lin, sc[2] + a_new
+                if status == 0 and math.isfinite(lin1) and math.isfinite(new1):
+                    lin_change = lin0 - lin1
                     if lin_change >= 0.0:
-                        new_err = float(sc[2]) + a_new
-                        cost_change = current - new_err
+                        cost_change = current - new1
                         if lin_change > 2.220446049250313e-16 * lin0:
                             success = cost_change / lin_change > prm.minModelFidelity
                         if abs(cost_change) < prm.relativeErrorTol * current:
                             stop_search = True
                         if success:
-                            poses, self.new_poses = self.new_poses, poses
-                            points, self.new_points = self.new_points, points
-                            new_error = new_err
+                            state = self._lm_swap(state)
+                            new_error = new1
                             if aux:
                                 aux.accept()
                 if success:
@@ -609,21 +636,19 @@ class StereoBASolver:
                 abs_dec = current - new_error
                 converged = (abs_dec / current <= prm.relativeErrorTol) or (abs_dec <= prm.absoluteErrorTol)
             current = new_error
-            if rep.status == 2:
-                break
-            if converged:
-                rep.status = 0
-                break
-            if not math.isfinite(current):
+            if rep.status == 2 or converged or not math.isfinite(current):
+                if converged and rep.status != 2:
+                    rep.status = 0
                 break
         torch.cuda.synchronize(self.P.device)
         rep.seconds = time.perf_counter() - t0
         rep.final_error, rep.final_lambda = current, lam
-        return poses, points, rep
+        return state, rep
 
 
 # ---------------------------------------------------------------------------------------------
-# graphs with inertial / velocity factors
+# graphs with inertial / velocity factors, in two node layouts: one shared IMU bias
+# (vus_nav_*, pose_stride 2) and one bias per keyframe (include/vus_nav_bias.h vus_navb_*, pose_stride 3)
 class _CNav(ctypes.Structure):
     _fields_ = [("n_imu", c_int), ("imu_i", c_void_p), ("imu_j", c_void_p), ("imu_pim", c_void_p), ("imu_W", c_void_p),
                 ("gravity", c_double * 3), ("n_dvl", c_int), ("dvl_pose", c_void_p), ("dvl_meas", c_void_p),
@@ -631,69 +656,180 @@ class _CNav(ctypes.Structure):
                 ("vprior_w", c_void_p)]
 
 
-class NavFactors:
-    """Device-resident vus_nav_factors.  imu = (i, j, pim [n,148], W [n,81]); dvl = (pose, meas [n,3], sigma [n]);
-    vprior = (idx, v [n,3], sigmas [n,3]).  ImuFactors must join consecutive poses (j = i + 1)."""
+class _CNavBias(ctypes.Structure):
+    _fields_ = _CNav._fields_ + [("n_bbetween", c_int), ("bb_i", c_void_p), ("bb_j", c_void_p), ("bb_meas", c_void_p),
+                                 ("bb_w", c_void_p), ("n_bprior", c_int), ("bp_idx", c_void_p), ("bp_mean", c_void_p),
+                                 ("bp_w", c_void_p)]
 
-    def __init__(self, gravity, imu=None, dvl=None, vprior=None, device="cuda:0"):
-        dev = torch.device(device)
 
-        def t(x, dt, shape):
-            return torch.as_tensor(x).to(device=dev, dtype=dt).reshape(shape).contiguous()
+class _InertialFactors:
+    """The device tensors both factor structs share (IMU, DVL, velocity priors) and the _CNav prefix of the struct."""
+    _IMU_REFUSAL = "ImuFactor between non-consecutive poses is not supported"
+
+    def __init__(self, gravity, imu, dvl, vprior, device):
+        self.dev = torch.device(device)
         z = []
-        self.imu_i = t(imu[0] if imu else z, torch.int32, (-1,))
-        self.imu_j = t(imu[1] if imu else z, torch.int32, (-1,))
-        self.imu_pim = t(imu[2] if imu else z, torch.float64, (-1, 148))
-        self.imu_W = t(imu[3] if imu else z, torch.float64, (-1, 81))
-        if self.imu_i.numel() and bool((self.imu_j - self.imu_i != 1).any()):
-            raise NotImplementedError("ImuFactor between non-consecutive poses is not supported (batch.py:238 joins i-1 and i)")
-        self.dvl_pose = t(dvl[0] if dvl else z, torch.int32, (-1,))
-        self.dvl_meas = t(dvl[1] if dvl else z, torch.float64, (-1, 3))
-        self.dvl_w = (1.0 / t(dvl[2], torch.float64, (-1,))).contiguous() if dvl else t(z, torch.float64, (-1,))
-        self.vp_idx = t(vprior[0] if vprior else z, torch.int32, (-1,))
-        self.vp_v = t(vprior[1] if vprior else z, torch.float64, (-1, 3))
-        self.vp_w = (1.0 / t(vprior[2], torch.float64, (-1, 3))).contiguous() if vprior else t(z, torch.float64, (-1, 3))
-        pp = lambda x: _lib.ptr(x) if x.numel() else None
-        self.c = _CNav(self.imu_i.numel(), pp(self.imu_i), pp(self.imu_j), pp(self.imu_pim), pp(self.imu_W),
-                       (c_double * 3)(*[float(g) for g in gravity]), self.dvl_pose.numel(), pp(self.dvl_pose),
-                       pp(self.dvl_meas), pp(self.dvl_w), self.vp_idx.numel(), pp(self.vp_idx), pp(self.vp_v), pp(self.vp_w))
+        self.imu_i, self.imu_j = self._pair(imu, self._IMU_REFUSAL)
+        self.imu_pim = self._t(imu[2] if imu else z, torch.float64, (-1, 148))
+        self.imu_W = self._t(imu[3] if imu else z, torch.float64, (-1, 81))
+        self.dvl_pose = self._t(dvl[0] if dvl else z, torch.int32, (-1,))
+        self.dvl_meas = self._t(dvl[1] if dvl else z, torch.float64, (-1, 3))
+        self.dvl_w = self._inv(dvl[2] if dvl else z, (-1,))
+        self.vp_idx = self._t(vprior[0] if vprior else z, torch.int32, (-1,))
+        self.vp_v = self._t(vprior[1] if vprior else z, torch.float64, (-1, 3))
+        self.vp_w = self._inv(vprior[2] if vprior else z, (-1, 3))
+        self._c_prefix = (self.imu_i.numel(), self._pp(self.imu_i), self._pp(self.imu_j), self._pp(self.imu_pim),
+                          self._pp(self.imu_W), (c_double * 3)(*[float(g) for g in gravity]), self.dvl_pose.numel(),
+                          self._pp(self.dvl_pose), self._pp(self.dvl_meas), self._pp(self.dvl_w), self.vp_idx.numel(),
+                          self._pp(self.vp_idx), self._pp(self.vp_v), self._pp(self.vp_w))
         self.n_factors = self.imu_i.numel() + self.dvl_pose.numel() + self.vp_idx.numel()
+
+    def _t(self, x, dt, shape):
+        return torch.as_tensor(x).to(device=self.dev, dtype=dt).reshape(shape).contiguous()
+
+    def _inv(self, sigma, shape):
+        """1/sigma on the device: the whitening weight of a diagonal noise model"""
+        return (1.0 / self._t(sigma, torch.float64, shape)).contiguous()
+
+    def _pair(self, fac, refusal):
+        """(i, j) index tensors of a factor that must join consecutive variables (j = i + 1)"""
+        i = self._t(fac[0] if fac else [], torch.int32, (-1,))
+        j = self._t(fac[1] if fac else [], torch.int32, (-1,))
+        if i.numel() and bool((j - i != 1).any()):
+            raise NotImplementedError(refusal)
+        return i, j
+
+    @staticmethod
+    def _pp(x):
+        return _lib.ptr(x) if x.numel() else None
 
     def addr(self):
         return ctypes.addressof(self.c)
 
 
-class NavBASolver(StereoBASolver):
-    """LM over poses, velocities, one shared IMU bias and landmarks.  The problem must have been built with
-    pose_stride=2 (velocity nodes interleaved); the bias is a 6-wide border eliminated after a
-    7-right-hand-side band solve."""
+class NavFactors(_InertialFactors):
+    """Device-resident vus_nav_factors.  imu = (i, j, pim [n,148], W [n,81]); dvl = (pose, meas [n,3], sigma [n]);
+    vprior = (idx, v [n,3], sigmas [n,3]).  ImuFactors must join consecutive poses (j = i + 1)."""
+    _IMU_REFUSAL = "ImuFactor between non-consecutive poses is not supported (batch.py:238 joins i-1 and i)"
 
-    def __init__(self, problem: StereoBAProblem, nav: NavFactors):
-        if problem.pose_stride != 2:
-            raise ValueError("NavBASolver needs a StereoBAProblem built with pose_stride=2")
+    def __init__(self, gravity, imu=None, dvl=None, vprior=None, device="cuda:0"):
+        super().__init__(gravity, imu, dvl, vprior, device)
+        self.c = _CNav(*self._c_prefix)
+
+
+class NavBiasFactors(_InertialFactors):
+    """Device-resident vus_navb_factors.  imu, dvl, vprior as NavFactors (ImuFactor f uses bias B(imu_i[f]));
+    bbetween = (i, j, meas [n,6], sigmas [n,6]) for BetweenFactorConstantBias(B(i), B(j = i + 1)), bprior = (idx,
+    mean [n,6], sigmas [n,6]) for PriorFactorConstantBias.  Diagonal noise models; 6-vectors in the order (acc, gyro)."""
+
+    def __init__(self, gravity, imu=None, dvl=None, vprior=None, bbetween=None, bprior=None, device="cuda:0"):
+        super().__init__(gravity, imu, dvl, vprior, device)
+        z = []
+        self.bb_i, self.bb_j = self._pair(bbetween, "BetweenFactorConstantBias between non-consecutive biases is not "
+                                                    "supported")
+        self.bb_meas = self._t(bbetween[2] if bbetween else z, torch.float64, (-1, 6))
+        self.bb_w = self._inv(bbetween[3] if bbetween else z, (-1, 6))
+        self.bp_idx = self._t(bprior[0] if bprior else z, torch.int32, (-1,))
+        self.bp_mean = self._t(bprior[1] if bprior else z, torch.float64, (-1, 6))
+        self.bp_w = self._inv(bprior[2] if bprior else z, (-1, 6))
+        pp = self._pp
+        self.c = _CNavBias(*self._c_prefix, self.bb_i.numel(), pp(self.bb_i), pp(self.bb_j), pp(self.bb_meas),
+                           pp(self.bb_w), self.bp_idx.numel(), pp(self.bp_idx), pp(self.bp_mean), pp(self.bp_w))
+
+    def unconstrained_biases(self, n_poses):
+        """Biases with neither a prior nor a between-factor: their information comes from ImuFactors alone, if any."""
+        seen = np.zeros(n_poses, bool)
+        bb_i, bp_idx = self.bb_i.cpu().numpy().astype(np.int64), self.bp_idx.cpu().numpy().astype(np.int64)
+        for a in (bb_i, bb_i + 1, bp_idx):
+            seen[a[(a >= 0) & (a < n_poses)]] = True
+        return np.nonzero(~seen)[0]
+
+
+class _InertialBASolver(StereoBASolver):
+    """LM over poses, velocities, IMU biases and landmarks: the stereo solver plus the inertial factors of one node
+    layout.  A subclass names its pose_stride, Snav's block diagonals, its entry points (`_ABI`) and its bias shape."""
+    POSE_STRIDE = SDIAG = None
+    _ABI = None
+    _NEW_STATE = ("new_poses", "new_vels", "new_bias", "new_points")     # state = (poses, vels, bias, points)
+
+    def __init__(self, problem: StereoBAProblem, nav, bias_rows):
+        if problem.pose_stride != self.POSE_STRIDE:
+            raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
         super().__init__(problem)
-        self.band_rhs = 7
-        self._alloc_band_work()
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
         f64 = dict(dtype=torch.float64, device=dev)
-        self.Snav = torch.empty((nN, 4, 36), **f64)
-        self.Scb = torch.empty((nN, 36), **f64)
-        self.Sbb = torch.empty((36,), **f64)
+        self.Snav = torch.empty((nN, self.SDIAG, 36), **f64)
         self.gnav = torch.empty((nN, 6), **f64)
-        self.gb = torch.empty((6,), **f64)
-        self.rhs = torch.empty((7, nN * 6), **f64)
-        self.db = torch.empty((6,), **f64)
         self.new_vels = torch.empty((nP, 3), **f64)
-        self.new_bias = torch.empty((6,), **f64)
+        self.new_bias = torch.empty((6,) if bias_rows is None else (bias_rows, 6), **f64)
         self.nav_scal = torch.zeros((4,), **f64)
-        self.nav_work = torch.empty((int(_lib.load().vus_nav_work_doubles(nav.addr())),), **f64)
+        self.nav_work = torch.empty((int(getattr(_lib.load(), self._ABI + "_work_doubles")(nav.addr())),), **f64)
 
     def nav_error(self, poses, vels, bias) -> float:
         p = _lib.ptr
-        _lib.call("vus_nav_error", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(bias), p(self.nav_scal),
+        _lib.call(self._ABI + "_error", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(bias), p(self.nav_scal),
                   p(self.nav_work), _lib.current_stream_ptr())
         return float(self.nav_scal[0].item())
+
+    def _linearize_all(self, values):
+        poses, vels, bias, points = values
+        self.linearize(poses, points)
+        self._check_points()
+        self.nav_linearize(poses, vels, bias)
+
+    def _assemble_zero(self):
+        self.schur(0.0)
+        self.nav_assemble(0.0)
+
+    def _lm_error(self, state):
+        poses, vels, bias, points = state
+        return self.error(poses, points) + self.nav_error(poses, vels, bias)
+
+    def _lm_linearize(self, state):
+        poses, vels, bias, points = state
+        self.linearize(poses, points)
+        self.nav_linearize(poses, vels, bias)
+
+    def _lm_solve(self, lam):
+        self.schur(lam)
+        self.nav_assemble(lam)
+        self.nav_solve(lam)
+        self.backsub()
+
+    def _lm_eval(self, state):
+        poses, vels, bias, points = state
+        self.eval_step(poses, points)
+        self.nav_eval_step(poses, vels, bias)
+        rec, nsc = self._trial.cpu(), self.nav_scal.cpu()         # stereo scalars + status, then the inertial scalars
+        return int(rec[4:].view(torch.int32)[0]), [float(rec[k]) + float(nsc[k]) for k in range(3)]
+
+    def optimize(self, poses, vels, bias, points, params: Optional[LMParams] = None):
+        """Returns (poses, vels, bias, points, LMReport); inputs untouched."""
+        prm = params or LMParams()
+        if prm.diagonalDamping or not prm.useFixedLambdaFactor:
+            raise NotImplementedError("only the gtsam defaults diagonalDamping=False, useFixedLambdaFactor=True")
+        state, rep = self._levenberg_marquardt((poses, vels, bias, points), prm)
+        return (*state, rep)
+
+
+class NavBASolver(_InertialBASolver):
+    """LM over poses, velocities, one shared IMU bias and landmarks.  The problem must have been built with
+    pose_stride=2 (velocity nodes interleaved); the bias is a 6-wide border eliminated after a
+    7-right-hand-side band solve."""
+    POSE_STRIDE, SDIAG, _ABI = 2, 4, "vus_nav"
+
+    def __init__(self, problem: StereoBAProblem, nav: NavFactors):
+        super().__init__(problem, nav, None)
+        self.band_rhs = 7
+        self._alloc_band_work()
+        nN = problem.n_nodes
+        f64 = dict(dtype=torch.float64, device=problem.device)
+        self.Scb = torch.empty((nN, 36), **f64)
+        self.Sbb = torch.empty((36,), **f64)
+        self.gb = torch.empty((6,), **f64)
+        self.rhs = torch.empty((7, nN * 6), **f64)
+        self.db = torch.empty((6,), **f64)
 
     def nav_linearize(self, poses, vels, bias):
         p = _lib.ptr
@@ -723,15 +859,10 @@ class NavBASolver(StereoBASolver):
                   p(self.new_poses), p(self.new_vels), p(self.new_bias), p(self.nav_scal[1:]), p(self.nav_work),
                   _lib.current_stream_ptr())
 
-    def _linearize_all(self, values):
-        poses, vels, bias, points = values
-        self.linearize(poses, points)
-        self._check_points()
-        self.nav_linearize(poses, vels, bias)
-
-    def _assemble_zero(self):
-        self.schur(0.0)
-        self.nav_assemble(0.0)
+    def _factor_zero(self):
+        p = _lib.ptr
+        _lib.call("vus_ba_band_solve_multi", p(self.Sband), self.P.n_nodes, self.P.band, p(self.rhs), 7, p(self.status),
+                  _lib.current_stream_ptr())
 
     def marginals(self, poses, vels, bias, points, points_cov=True) -> BAMarginals:
         """StereoBASolver.marginals for the whole graph: the camera-side band of A^-1 (poses and velocity nodes, one-sided
@@ -739,15 +870,10 @@ class NavBASolver(StereoBASolver):
         covariances from the corrected band."""
         c = lambda x: x.to(torch.float64).contiguous()
         values = (c(poses), c(vels), c(bias), c(points))
-        self._linearize_all(values)
-        p, st = _lib.ptr, _lib.current_stream_ptr()
-        while True:
-            self._assemble_zero()
-            _lib.call("vus_ba_band_solve_multi", p(self.Sband), self.P.n_nodes, self.P.band, p(self.rhs), 7, p(self.status), st)
-            if not self._factor_status():
-                break
+        self._marginal_factor(values)
         Sigma = self._selinv()
         nN, nP = self.P.n_nodes, self.P.n_poses
+        p, st = _lib.ptr, _lib.current_stream_ptr()
         f64 = dict(dtype=torch.float64, device=self.P.device)
         Snb, Sbb, ok = torch.empty((nN, 36), **f64), torch.empty((36,), **f64), torch.empty((1,), **f64)
         _lib.call("vus_nav_border_covariance", nN, self.P.band, p(self.rhs), p(self.Scb), p(self.Sbb), p(Sigma), p(Snb),
@@ -761,175 +887,16 @@ class NavBASolver(StereoBASolver):
         return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, pose_nodes), pc, U=U, vel_cov=vel,
                            bias_cov=Sbb.reshape(6, 6), node_bias_cov=Snb.reshape(nN, 6, 6))
 
-    def optimize(self, poses, vels, bias, points, params: Optional[LMParams] = None):
-        """Returns (poses, vels, bias, points, LMReport); inputs untouched."""
-        prm = params or LMParams()
-        if prm.diagonalDamping or not prm.useFixedLambdaFactor:
-            raise NotImplementedError("only the gtsam defaults diagonalDamping=False, useFixedLambdaFactor=True")
-        c = lambda x: x.to(torch.float64).contiguous().clone()
-        poses, vels, bias, points = c(poses), c(vels), c(bias), c(points)
-        rep = LMReport(setup_seconds=self.P.setup_seconds)
-        torch.cuda.synchronize(self.P.device)
-        t0 = time.perf_counter()
-        lam = prm.lambdaInitial
-        current = self.error(poses, points) + self.nav_error(poses, vels, bias)
-        rep.initial_error = current
-        if current <= prm.errorTol or prm.maxIterations <= 0:
-            rep.status, rep.final_error, rep.final_lambda = 0, current, lam
-            return poses, vels, bias, points, rep
-        while rep.iterations < prm.maxIterations:
-            self.linearize(poses, points)
-            self.nav_linearize(poses, vels, bias)
-            new_error, stop_search, accepted, lin0 = current, False, False, None
-            while True:
-                self.schur(lam)
-                self.nav_assemble(lam)
-                self.nav_solve(lam)
-                self.backsub()
-                self.eval_step(poses, points)
-                self.nav_eval_step(poses, vels, bias)
-                rec = self._trial.cpu()                           # stereo scalars + status, then the inertial scalars
-                sc, status, nsc = rec[:4], int(rec[4:].view(torch.int32)[0]), self.nav_scal.cpu()
-                if status < 0:
-                    if self._window_expired(status):
-                        continue
-                    raise RuntimeError("vus_ba_band_solve: the cooperative back-substitution timed out (status %d)" % status)
-                rep.tries += 1
-                if lin0 is None:
-                    lin0 = float(sc[0]) + float(nsc[0])
-                success = False
-                lin1, new1 = float(sc[1]) + float(nsc[1]), float(sc[2]) + float(nsc[2])
-                if status == 0 and math.isfinite(lin1) and math.isfinite(new1):
-                    lin_change = lin0 - lin1
-                    if lin_change >= 0.0:
-                        cost_change = current - new1
-                        if lin_change > 2.220446049250313e-16 * lin0:
-                            success = cost_change / lin_change > prm.minModelFidelity
-                        if abs(cost_change) < prm.relativeErrorTol * current:
-                            stop_search = True
-                        if success:
-                            poses, self.new_poses = self.new_poses, poses
-                            points, self.new_points = self.new_points, points
-                            vels, self.new_vels = self.new_vels, vels
-                            bias, self.new_bias = self.new_bias, bias
-                            new_error = new1
-                if success:
-                    lam = max(prm.lambdaLowerBound, lam / prm.lambdaFactor)
-                    accepted = True
-                    break
-                if stop_search:
-                    break
-                lam *= prm.lambdaFactor
-                if lam >= prm.lambdaUpperBound:
-                    rep.status = 2
-                    break
-            rep.err_hist.append(new_error)
-            rep.lambda_hist.append(lam)
-            rep.outer += 1
-            rep.iterations += int(accepted)
-            if new_error <= prm.errorTol:
-                converged = True
-            else:
-                abs_dec = current - new_error
-                converged = (abs_dec / current <= prm.relativeErrorTol) or (abs_dec <= prm.absoluteErrorTol)
-            current = new_error
-            if rep.status == 2 or converged or not math.isfinite(current):
-                if converged and rep.status != 2:
-                    rep.status = 0
-                break
-        torch.cuda.synchronize(self.P.device)
-        rep.seconds = time.perf_counter() - t0
-        rep.final_error, rep.final_lambda = current, lam
-        return poses, vels, bias, points, rep
 
-
-# ---------------------------------------------------------------------------------------------
-# graphs with one IMU bias per keyframe (include/vus_nav_bias.h): GTSAM's usual visual-inertial graph
-class _CNavBias(ctypes.Structure):
-    _fields_ = _CNav._fields_ + [("n_bbetween", c_int), ("bb_i", c_void_p), ("bb_j", c_void_p), ("bb_meas", c_void_p),
-                                 ("bb_w", c_void_p), ("n_bprior", c_int), ("bp_idx", c_void_p), ("bp_mean", c_void_p),
-                                 ("bp_w", c_void_p)]
-
-
-class NavBiasFactors:
-    """Device-resident vus_navb_factors.  imu, dvl, vprior as NavFactors (ImuFactor f uses bias B(imu_i[f]));
-    bbetween = (i, j, meas [n,6], sigmas [n,6]) for BetweenFactorConstantBias(B(i), B(j = i + 1)), bprior = (idx,
-    mean [n,6], sigmas [n,6]) for PriorFactorConstantBias.  Diagonal noise models; 6-vectors in the order (acc, gyro)."""
-
-    def __init__(self, gravity, imu=None, dvl=None, vprior=None, bbetween=None, bprior=None, device="cuda:0"):
-        dev = torch.device(device)
-        z = []
-        h = lambda x, shape: np.asarray(x, dtype=np.float64).reshape(shape)
-        hi = lambda x: np.asarray(x, dtype=np.int64).reshape(-1)
-        self.imu_i_h = hi(imu[0] if imu else z)
-        imu_j = hi(imu[1] if imu else z)
-        if self.imu_i_h.size and bool((imu_j - self.imu_i_h != 1).any()):
-            raise NotImplementedError("ImuFactor between non-consecutive poses is not supported")
-        self.bb_i_h, bb_j = hi(bbetween[0] if bbetween else z), hi(bbetween[1] if bbetween else z)
-        if self.bb_i_h.size and bool((bb_j - self.bb_i_h != 1).any()):
-            raise NotImplementedError("BetweenFactorConstantBias between non-consecutive biases is not supported")
-        self.bp_idx_h = hi(bprior[0] if bprior else z)
-
-        def t(x, dt):
-            return torch.from_numpy(np.ascontiguousarray(x)).to(device=dev, dtype=dt).contiguous()
-        self.imu_i, self.imu_j = t(self.imu_i_h, torch.int32), t(imu_j, torch.int32)
-        self.imu_pim = t(h(imu[2] if imu else z, (-1, 148)), torch.float64)
-        self.imu_W = t(h(imu[3] if imu else z, (-1, 81)), torch.float64)
-        self.dvl_pose = t(hi(dvl[0] if dvl else z), torch.int32)
-        self.dvl_meas = t(h(dvl[1] if dvl else z, (-1, 3)), torch.float64)
-        self.dvl_w = t(1.0 / h(dvl[2] if dvl else z, (-1,)), torch.float64)
-        self.vp_idx = t(hi(vprior[0] if vprior else z), torch.int32)
-        self.vp_v = t(h(vprior[1] if vprior else z, (-1, 3)), torch.float64)
-        self.vp_w = t(1.0 / h(vprior[2] if vprior else z, (-1, 3)), torch.float64)
-        self.bb_i, self.bb_j = t(self.bb_i_h, torch.int32), t(bb_j, torch.int32)
-        self.bb_meas = t(h(bbetween[2] if bbetween else z, (-1, 6)), torch.float64)
-        self.bb_w = t(1.0 / h(bbetween[3] if bbetween else z, (-1, 6)), torch.float64)
-        self.bp_idx = t(self.bp_idx_h, torch.int32)
-        self.bp_mean = t(h(bprior[1] if bprior else z, (-1, 6)), torch.float64)
-        self.bp_w = t(1.0 / h(bprior[2] if bprior else z, (-1, 6)), torch.float64)
-        pp = lambda x: _lib.ptr(x) if x.numel() else None
-        self.c = _CNavBias(self.imu_i.numel(), pp(self.imu_i), pp(self.imu_j), pp(self.imu_pim), pp(self.imu_W),
-                           (c_double * 3)(*[float(g) for g in gravity]), self.dvl_pose.numel(), pp(self.dvl_pose),
-                           pp(self.dvl_meas), pp(self.dvl_w), self.vp_idx.numel(), pp(self.vp_idx), pp(self.vp_v),
-                           pp(self.vp_w), self.bb_i.numel(), pp(self.bb_i), pp(self.bb_j), pp(self.bb_meas), pp(self.bb_w),
-                           self.bp_idx.numel(), pp(self.bp_idx), pp(self.bp_mean), pp(self.bp_w))
-
-    def addr(self):
-        return ctypes.addressof(self.c)
-
-    def unconstrained_biases(self, n_poses):
-        """Biases with neither a prior nor a between-factor: their information comes from ImuFactors alone, if any."""
-        seen = np.zeros(n_poses, bool)
-        for a in (self.bb_i_h, self.bb_i_h + 1, self.bp_idx_h):
-            seen[a[(a >= 0) & (a < n_poses)]] = True
-        return np.nonzero(~seen)[0]
-
-
-class NavBiasBASolver(NavBASolver):
+class NavBiasBASolver(_InertialBASolver):
     """LM over poses, velocities, ONE IMU BIAS PER KEYFRAME and landmarks (GTSAM's usual visual-inertial graph).  The
     problem must have been built with pose_stride=3: node 3i = X(i), 3i+1 = V(i) padded to 6, 3i+2 = B(i).  There is no
-    border; every lambda trial is one single-right-hand-side band solve (two-sided on long graphs).  optimize() is
-    NavBASolver's loop, with `bias` the [n_poses, 6] per-keyframe biases."""
+    border; every lambda trial is one single-right-hand-side band solve (two-sided on long graphs).  optimize() is the
+    common inertial loop, with `bias` the [n_poses, 6] per-keyframe biases."""
+    POSE_STRIDE, SDIAG, _ABI = 3, 5, "vus_navb"
 
     def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors):
-        if problem.pose_stride != 3:
-            raise ValueError("NavBiasBASolver needs a StereoBAProblem built with pose_stride=3")
-        StereoBASolver.__init__(self, problem)
-        self.N = nav
-        dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.Snav = torch.empty((nN, 5, 36), **f64)
-        self.gnav = torch.empty((nN, 6), **f64)
-        self.new_vels = torch.empty((nP, 3), **f64)
-        self.new_bias = torch.empty((nP, 6), **f64)
-        self.nav_scal = torch.zeros((4,), **f64)
-        self.nav_work = torch.empty((int(_lib.load().vus_navb_work_doubles(nav.addr())),), **f64)
-
-    def nav_error(self, poses, vels, biases) -> float:
-        p = _lib.ptr
-        _lib.call("vus_navb_error", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.nav_scal),
-                  p(self.nav_work), _lib.current_stream_ptr())
-        return float(self.nav_scal[0].item())
+        super().__init__(problem, nav, problem.n_poses)
 
     def nav_linearize(self, poses, vels, biases):
         p = _lib.ptr
@@ -960,14 +927,7 @@ class NavBiasBASolver(NavBASolver):
         free = self.N.unconstrained_biases(self.P.n_poses)
         if len(free):
             raise IndeterminantSystem("bias", int(free[0]))
-        self._linearize_all(values)
-        p, st = _lib.ptr, _lib.current_stream_ptr()
-        while True:
-            self._assemble_zero()
-            _lib.call("vus_ba_band_solve", p(self.Sband), self.P.n_nodes, self.P.band, p(self.gs), p(self.dp),
-                      p(self.status), st)
-            if not self._factor_status():
-                break
+        self._marginal_factor(values)
         Sigma = self._selinv()
         nP = self.P.n_poses
         nodes = torch.arange(nP, device=self.P.device) * 3

@@ -28,7 +28,7 @@
 //                diag_invert + chol_backsolve (diagonal panels inverted in place, then the cooperative,
 //                flag-ordered sweep) / split_* (two-sided elimination: both ends of the band at once)
 //   backsub      wave / point      dl = -Vinv (gl + sum W^T dp)
-//   retract, eval_points, error_points, reduce_partials
+//   retract, eval_points, error_points, reduce_partials (the fixed-order sum, also behind nav.hip: vus::reduce_partials)
 #include <atomic>
 #include <cerrno>
 #include <cstdio>
@@ -454,6 +454,14 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(const double* __r
   if (threadIdx.x == 0) out[0] = s[0];
 }
 
+}  // namespace
+
+// the one host launcher of the fixed-order sum, also used by nav.hip (vus_common.h)
+void vus::reduce_partials(const double* part, int n, double* out, hipStream_t st) {
+  reduce_partials_kernel<<<1, 1024, 0, st>>>(part, n, out);
+}
+
+namespace {
 // ---------------------------------------------------------------------------------------------
 // damped landmark elimination
 __global__ void vinv_kernel(int n_points, double lambda, const double* __restrict__ V, double* __restrict__ Vinv) {
@@ -2660,8 +2668,6 @@ int check_problem(const vus_ba_problem* P) {
   return VUS_OK;
 }
 
-inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
-
 // w [n_obs] (L-order) of every stereo observation at (poses, points), thread / observation
 template <int LOSS>
 __global__ __launch_bounds__(256) void stereo_weights_kernel(vus_ba_problem P, const double* __restrict__ poses,
@@ -2713,7 +2719,7 @@ struct ErrorOp {
       eval_points_kernel<false, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
                                                                   nullptr, work, k);
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, nullptr, nullptr, work + nL, 1);
-    reduce_partials_kernel<<<1, 1024, 0, st>>>(work, nL + 1, err);
+    vus::reduce_partials(work, nL + 1, err, st);
     VUS_CHECK_LAUNCH("ba_error");
     return VUS_OK;
   }
@@ -2733,7 +2739,7 @@ struct LinearizeOp {
     if (nL > 0) lin_points_kernel<LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k);
     lin_poses_kernel<LOSS><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k);
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, Hpp, gp, work + nL, 0);
-    reduce_partials_kernel<<<1, 1024, 0, st>>>(work, nL + 1, err);
+    vus::reduce_partials(work, nL + 1, err, st);
     VUS_CHECK_LAUNCH("ba_linearize");
     return VUS_OK;
   }
@@ -2757,8 +2763,8 @@ struct EvalStepOp {
                                                                  part_new, k);
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, dp, nullptr, nullptr, part_lin + nL, 2);
     priors_kernel<<<1, 64, 0, st>>>(*P, new_poses, nullptr, nullptr, nullptr, part_new + nL, 1);
-    reduce_partials_kernel<<<1, 1024, 0, st>>>(part_lin, nL + 1, out);
-    reduce_partials_kernel<<<1, 1024, 0, st>>>(part_new, nL + 1, out + 1);
+    vus::reduce_partials(part_lin, nL + 1, out, st);
+    vus::reduce_partials(part_new, nL + 1, out + 1, st);
     VUS_CHECK_LAUNCH("ba_eval_step");
     return VUS_OK;
   }

@@ -405,8 +405,6 @@ __global__ void border_band_kernel(int n_nodes, int band, const double* __restri
   Sg[t] += acc;
 }
 
-inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
-
 struct SelinvPlan {
   int np, br, kc_max;
   size_t off_linv, off_x, off_part, off_m, total;

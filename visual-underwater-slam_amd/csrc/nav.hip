@@ -1,39 +1,230 @@
-// nav.hip -- camera-side navigation factors for gfx950:
-// gtsam.ImuFactor over preintegrated measurements (reference batch.py:237-239,289-293), the DVL
-// velocity factor (batch.py:196-250, with the correct Jacobians) and PriorFactorVector on velocities
-// (batch.py:282).  O(#keyframes) work next to the O(#observations) stereo kernels of ba.hip.
+// nav.hip -- inertial factors for gfx950, in both node layouts: gtsam.ImuFactor over
+// preintegrated measurements (reference batch.py:237-239,289-293), the DVL velocity factor (batch.py:196-250, with the
+// correct Jacobians), PriorFactorVector on velocities (batch.py:282) and, with one bias per keyframe,
+// BetweenFactorConstantBias and PriorFactorConstantBias.  O(#keyframes) work next to the O(#observations) stereo
+// kernels of ba.hip.
 //
-// Node layout (vus_ba_problem.pose_stride = 2): node 2i = X(i), node 2i+1 = V(i) padded to 6 dims
-// (dims 3..5 are inert: unit diagonal, zero right-hand side); the shared bias B(0) is a 6-wide BORDER of
-// the reduced camera system, eliminated after the band solve with 7 right-hand sides.
+// Two node layouts (vus_ba_problem.pose_stride), one set of factor kernels templated on the layout:
+//   SharedBias (stride 2, include/vus.h vus_nav_*): node 2i = X(i), node 2i+1 = V(i) padded to 6 dims (dims 3..5 are
+//     inert: unit diagonal, zero right-hand side); the shared bias B(0) is a 6-wide BORDER of the reduced camera
+//     system, eliminated after the band solve with 7 right-hand sides.  Snav has 4 block diagonals.
+//   PerKeyframeBias (stride 3, include/vus_nav_bias.h vus_navb_*): node 3i = X(i), 3i+1 = V(i) padded to 6, 3i+2 =
+//     B(i).  No border: each lambda trial is one single-right-hand-side band solve.  An ImuFactor's columns land on
+//     nodes 3i .. 3i+4, so Snav has 5 block diagonals.
 //
-// Factors are evaluated one per thread.  Their J^T J blocks on the camera side go in with f64 atomics (a block
-// receives at most two IMU factors, one DVL factor and one prior, so the sums differ between runs by the order of
-// at most four addends, ~1e-16 relative); the bias-bias block and the bias gradient, which every IMU factor
-// touches, are written per factor and reduced in a fixed order.
+// Factors are evaluated one per thread.  Their J^T J blocks on the camera side go in with f64 atomics (a block receives
+// a handful of addends, so two runs agree to ~1e-16 relative, not bitwise).  With the shared bias, the bias-bias block
+// and the bias gradient, which every IMU factor touches, are written per factor and reduced in a fixed order, and the
+// velocity priors are added by one sequential thread.
 #include <cmath>
 #include <cstring>
+#include <vector>
 #include "vus_common.h"
-#include "nav_device.h"
 
 namespace {
+
+// ---- device math: SO(3) helpers and the ImuFactor residual / Jacobian --------------------------------------------------
+constexpr int PIM_DT = 0, PIM_DR = 1, PIM_DP = 10, PIM_DV = 13, PIM_DR_DBG = 16, PIM_DP_DBA = 25, PIM_DP_DBG = 34,
+              PIM_DV_DBA = 43, PIM_DV_DBG = 52, PIM_BIAS = 61, PIM_N = 148;
+constexpr double kEps = 2.220446049250313e-16;
+constexpr double kPi = 3.14159265358979323846;
+
+__device__ __forceinline__ void skew(const double* w, double* S) {
+  S[0] = 0; S[1] = -w[2]; S[2] = w[1]; S[3] = w[2]; S[4] = 0; S[5] = -w[0]; S[6] = -w[1]; S[7] = w[0]; S[8] = 0;
+}
+__device__ __forceinline__ void mm(const double* A, const double* B, double* C) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+}
+__device__ __forceinline__ void mtm(const double* A, const double* B, double* C) {   // A^T B
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) C[3 * r + c] = A[r] * B[c] + A[3 + r] * B[3 + c] + A[6 + r] * B[6 + c];
+}
+__device__ __forceinline__ void mv(const double* A, const double* v, double* o) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) o[r] = A[3 * r] * v[0] + A[3 * r + 1] * v[1] + A[3 * r + 2] * v[2];
+}
+__device__ __forceinline__ void mtv(const double* A, const double* v, double* o) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) o[r] = A[r] * v[0] + A[3 + r] * v[1] + A[6 + r] * v[2];
+}
+
+__device__ void so3_exp(const double* w, double* R) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double W[9], WW[9];
+  skew(w, W);
+  if (th2 <= kEps) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = W[i] + (i % 4 == 0 ? 1.0 : 0.0);
+    return;
+  }
+  const double th = sqrt(th2), s = sin(th) / th, sh = sin(0.5 * th), c = 2.0 * sh * sh / th2;
+  mm(W, W, WW);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + s * W[i] + c * WW[i];
+}
+__device__ void so3_log(const double* R, double* w) {
+  const double tr = R[0] + R[4] + R[8];
+  if (tr + 1.0 < 1e-10) {
+    if (fabs(R[8] + 1.0) > 1e-5) { double k = kPi / sqrt(2.0 + 2.0 * R[8]); w[0] = k * R[2]; w[1] = k * R[5]; w[2] = k * (1.0 + R[8]); }
+    else if (fabs(R[4] + 1.0) > 1e-5) { double k = kPi / sqrt(2.0 + 2.0 * R[4]); w[0] = k * R[1]; w[1] = k * (1.0 + R[4]); w[2] = k * R[7]; }
+    else { double k = kPi / sqrt(2.0 + 2.0 * R[0]); w[0] = k * (1.0 + R[0]); w[1] = k * R[3]; w[2] = k * R[6]; }
+    return;
+  }
+  double mag;
+  const double tr3 = tr - 3.0;
+  if (tr3 < -1e-7) { const double th = acos((tr - 1.0) / 2.0); mag = th / (2.0 * sin(th)); }
+  else mag = 0.5 - tr3 / 12.0;
+  w[0] = mag * (R[7] - R[5]); w[1] = mag * (R[2] - R[6]); w[2] = mag * (R[3] - R[1]);
+}
+__device__ void so3_jr(const double* w, double* J) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double W[9], WW[9];
+  skew(w, W); mm(W, W, WW);
+  double a, b;
+  if (th2 < 1e-10) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
+  else { const double th = sqrt(th2); a = (1.0 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * W[i] + b * WW[i];
+}
+__device__ void so3_jr_inv(const double* w, double* J) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double W[9], WW[9];
+  skew(w, W); mm(W, W, WW);
+  double b;
+  if (th2 < 1e-10) b = 1.0 / 12.0 + th2 / 720.0;
+  else { const double th = sqrt(th2); b = 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th)); }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) + 0.5 * W[i] + b * WW[i];
+}
+
+// ImuFactor: unwhitened residual r[9] = (theta, p, v) and, when J != nullptr, the Jacobian J[9][24] with
+// columns pose_i(6) vel_i(3) pose_j(6) vel_j(3) bias(6).  Forster et al. 2017 / gtsam ImuFactor.
+__device__ void imu_factor(const double* Ti, const double* vi, const double* Tj, const double* vj, const double* bias,
+                           const double* pim, const double* g, double* r, double* J) {
+  const double dt = pim[PIM_DT];
+  double dba[3], dbg[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { dba[k] = bias[k] - pim[PIM_BIAS + k]; dbg[k] = bias[3 + k] - pim[PIM_BIAS + 3 + k]; }
+  double phi[3], Ephi[9], dRc[9], dPc[3], dVc[3], t3[3], t3b[3];
+  mv(pim + PIM_DR_DBG, dbg, phi);
+  so3_exp(phi, Ephi);
+  mm(pim + PIM_DR, Ephi, dRc);
+  mv(pim + PIM_DP_DBA, dba, t3); mv(pim + PIM_DP_DBG, dbg, t3b);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dPc[k] = pim[PIM_DP + k] + t3[k] + t3b[k];
+  mv(pim + PIM_DV_DBA, dba, t3); mv(pim + PIM_DV_DBG, dbg, t3b);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dVc[k] = pim[PIM_DV + k] + t3[k] + t3b[k];
+  const double* Ri = Ti; const double* pi = Ti + 9;
+  const double* Rj = Tj; const double* pj = Tj + 9;
+  double RjtRi[9], E[9], rR[3];
+  mtm(Rj, Ri, RjtRi);
+  mm(RjtRi, dRc, E);
+  so3_log(E, rR);
+  double RidP[3], RidV[3], dpw[3], dvw[3], rP[3], rV[3];
+  mv(Ri, dPc, RidP); mv(Ri, dVc, RidV);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    dpw[k] = pi[k] + vi[k] * dt + 0.5 * g[k] * dt * dt + RidP[k] - pj[k];
+    dvw[k] = vi[k] + g[k] * dt + RidV[k] - vj[k];
+  }
+  mtv(Rj, dpw, rP); mtv(Rj, dvw, rV);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { r[k] = rR[k]; r[3 + k] = rP[k]; r[6 + k] = rV[k]; }
+  if (!J) return;
+  for (int k = 0; k < 9 * 24; ++k) J[k] = 0.0;
+  double JrInv[9], JrInvNeg[9], M[9], M2[9], X[9], JrPhi[9];
+  const double nrR[3] = {-rR[0], -rR[1], -rR[2]};
+  so3_jr_inv(rR, JrInv);
+  so3_jr_inv(nrR, JrInvNeg);
+#define JSET(row0, col0, Mat, sgn)                                                         \
+  for (int a = 0; a < 3; ++a)                                                              \
+    for (int b = 0; b < 3; ++b) J[24 * ((row0) + a) + (col0) + b] = (sgn) * (Mat)[3 * a + b]
+  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[3 * a + b] = dRc[3 * b + a];
+  mm(JrInv, M, M2);
+  JSET(0, 0, M2, 1.0);
+  JSET(0, 9, JrInvNeg, -1.0);
+  so3_jr(phi, JrPhi);
+  mm(JrInv, JrPhi, M); mm(M, pim + PIM_DR_DBG, M2);
+  JSET(0, 21, M2, 1.0);
+  skew(dPc, X); mm(RjtRi, X, M);
+  JSET(3, 0, M, -1.0);
+  JSET(3, 3, RjtRi, 1.0);
+  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[3 * a + b] = Rj[3 * b + a] * dt;
+  JSET(3, 6, M, 1.0);
+  skew(rP, X);
+  JSET(3, 9, X, 1.0);
+  for (int a = 0; a < 3; ++a) J[24 * (3 + a) + 12 + a] = -1.0;
+  mm(RjtRi, pim + PIM_DP_DBA, M); JSET(3, 18, M, 1.0);
+  mm(RjtRi, pim + PIM_DP_DBG, M); JSET(3, 21, M, 1.0);
+  skew(dVc, X); mm(RjtRi, X, M);
+  JSET(6, 0, M, -1.0);
+  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[3 * a + b] = Rj[3 * b + a];
+  JSET(6, 6, M, 1.0);
+  skew(rV, X);
+  JSET(6, 9, X, 1.0);
+  JSET(6, 15, M, -1.0);
+  mm(RjtRi, pim + PIM_DV_DBA, M); JSET(6, 18, M, 1.0);
+  mm(RjtRi, pim + PIM_DV_DBG, M); JSET(6, 21, M, 1.0);
+#undef JSET
+}
+
+// ---- the two node layouts ---------------------------------------------------------------------------------------------
+// ImuFactor columns (pose_i, vel_i, pose_j, vel_j, bias) -> (node, dim); node -1 = the shared-bias border
+struct SharedBias {
+  using Factors = vus_nav_factors;
+  static constexpr int STRIDE = 2, SDIAG = 4;   // node stride, block diagonals of Snav
+  static constexpr bool BORDER = true;          // bias columns -> border; their step in mode 2 is db
+  __device__ static const double* imu_bias(const double* bias, int) { return bias; }
+  __device__ static void imu_col(int c, int i, int j, int& node, int& dim) {
+    if (c < 6) { node = 2 * i; dim = c; }
+    else if (c < 9) { node = 2 * i + 1; dim = c - 6; }
+    else if (c < 15) { node = 2 * j; dim = c - 9; }
+    else if (c < 18) { node = 2 * j + 1; dim = c - 15; }
+    else { node = -1; dim = c - 18; }
+  }
+};
+struct PerKeyframeBias {
+  using Factors = vus_navb_factors;
+  static constexpr int STRIDE = 3, SDIAG = 5;
+  static constexpr bool BORDER = false;         // bias columns -> node 3i+2; their step in mode 2 is dc
+  __device__ static const double* imu_bias(const double* biases, int i) { return biases + 6 * (size_t)i; }
+  __device__ static void imu_col(int c, int i, int, int& node, int& dim) {   // j = i + 1, checked on the host
+    if (c < 6) { node = 3 * i; dim = c; }
+    else if (c < 9) { node = 3 * i + 1; dim = c - 6; }
+    else if (c < 15) { node = 3 * i + 3; dim = c - 9; }
+    else if (c < 18) { node = 3 * i + 4; dim = c - 15; }
+    else { node = 3 * i + 2; dim = c - 18; }
+  }
+};
+
+// error partials that follow the IMU and DVL ones: velocity priors, plus the bias factors of the per-keyframe layout
+inline int n_diag(const vus_nav_factors& N) { return N.n_vprior; }
+inline int n_diag(const vus_navb_factors& N) { return N.n_vprior + N.n_bbetween + N.n_bprior; }
 
 // scratch record of one evaluated factor: whitened Jacobian rows followed by the whitened residual
 constexpr int IMU_REC = 9 * 25;   // Jw[9][24] | rw[9] stored as row a: 24 J entries + 1 residual
 constexpr int DVL_REC = 3 * 10;   // Jw[3][9]  | rw[3]
+constexpr int NAV_BIAS_PART = 42; // shared bias: 36 (Sbb) + 6 (gb) per IMU factor
 
 // mode 0: Jacobians + residual into the scratch records;  mode 1: error only (part[f]);
-// mode 2: linearised error 0.5 |rw + Jw d|^2 with d from (dc, db) AND nothing else (part[f]).
-__global__ void nav_imu_kernel(vus_nav_factors N, int n_poses, const double* __restrict__ poses,
-                               const double* __restrict__ vels, const double* __restrict__ bias,
-                               const double* __restrict__ dc, const double* __restrict__ db,
-                               double* __restrict__ rec, double* __restrict__ part, int mode) {
+// mode 2: linearised error 0.5 |rw + Jw d|^2 with d from the node step dc (and db for the border) (part[f]).
+template <class L>
+__global__ void nav_imu_kernel(typename L::Factors N, const double* __restrict__ poses, const double* __restrict__ vels,
+                               const double* __restrict__ bias, const double* __restrict__ dc,
+                               const double* __restrict__ db, double* __restrict__ rec, double* __restrict__ part,
+                               int mode) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= N.n_imu) return;
   const int i = N.imu_i[f], j = N.imu_j[f];
   double r[9], J[9 * 24];
-  imu_factor(poses + 12 * (size_t)i, vels + 3 * (size_t)i, poses + 12 * (size_t)j, vels + 3 * (size_t)j, bias,
-             N.imu_pim + PIM_N * (size_t)f, N.gravity, r, mode == 1 ? nullptr : J);
+  imu_factor(poses + 12 * (size_t)i, vels + 3 * (size_t)i, poses + 12 * (size_t)j, vels + 3 * (size_t)j,
+             L::imu_bias(bias, i), N.imu_pim + PIM_N * (size_t)f, N.gravity, r, mode == 1 ? nullptr : J);
   const double* W = N.imu_W + 81 * (size_t)f;
   double e = 0.0;
   for (int a = 0; a < 9; ++a) {
@@ -46,14 +237,9 @@ __global__ void nav_imu_kernel(vus_nav_factors N, int n_poses, const double* __r
         for (int k = 0; k < 9; ++k) jw += W[9 * a + k] * J[24 * k + c];
         if (mode == 0) out[c] = jw;
         else {
-          // step component of column c: pose_i, vel_i, pose_j, vel_j live in node layout, bias in db
-          double dcomp;
-          if (c < 6) dcomp = dc[6 * (size_t)(2 * i) + c];
-          else if (c < 9) dcomp = dc[6 * (size_t)(2 * i + 1) + c - 6];
-          else if (c < 15) dcomp = dc[6 * (size_t)(2 * j) + c - 9];
-          else if (c < 18) dcomp = dc[6 * (size_t)(2 * j + 1) + c - 15];
-          else dcomp = db[c - 18];
-          rw += jw * dcomp;
+          int node, dim;
+          L::imu_col(c, i, j, node, dim);
+          rw += jw * (L::BORDER && node < 0 ? db[dim] : dc[6 * (size_t)node + dim]);
         }
       }
       if (mode == 0) out[24] = rw;
@@ -63,7 +249,8 @@ __global__ void nav_imu_kernel(vus_nav_factors N, int n_poses, const double* __r
   part[f] = e;
 }
 
-__global__ void nav_dvl_kernel(vus_nav_factors N, const double* __restrict__ poses, const double* __restrict__ vels,
+template <class L>
+__global__ void nav_dvl_kernel(typename L::Factors N, const double* __restrict__ poses, const double* __restrict__ vels,
                                const double* __restrict__ dc, double* __restrict__ rec, double* __restrict__ part,
                                int mode) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,14 +273,15 @@ __global__ void nav_dvl_kernel(vus_nav_factors N, const double* __restrict__ pos
       for (int c = 0; c < 9; ++c) out[c] = Jw[c];
       out[9] = rw;
     } else if (mode == 2) {
-      for (int c = 0; c < 6; ++c) rw += Jw[c] * dc[6 * (size_t)(2 * i) + c];
-      for (int c = 0; c < 3; ++c) rw += Jw[6 + c] * dc[6 * (size_t)(2 * i + 1) + c];
+      for (int c = 0; c < 6; ++c) rw += Jw[c] * dc[6 * (size_t)(L::STRIDE * i) + c];
+      for (int c = 0; c < 3; ++c) rw += Jw[6 + c] * dc[6 * (size_t)(L::STRIDE * i + 1) + c];
     }
     e += 0.5 * rw * rw;
   }
   part[f] = e;
 }
 
+// shared bias: error of the velocity priors (accumulated by nav_vprior_accumulate_kernel)
 __global__ void nav_vprior_kernel(vus_nav_factors N, const double* __restrict__ vels, const double* __restrict__ dc,
                                   double* __restrict__ part, int mode) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -109,42 +297,94 @@ __global__ void nav_vprior_kernel(vus_nav_factors N, const double* __restrict__ 
   part[f] = e;
 }
 
-// column of an IMU factor -> (node, dim); node -1 = the bias border
-__device__ __forceinline__ void imu_col(int c, int i, int j, int& node, int& dim) {
-  if (c < 6) { node = 2 * i; dim = c; }
-  else if (c < 9) { node = 2 * i + 1; dim = c - 6; }
-  else if (c < 15) { node = 2 * j; dim = c - 9; }
-  else if (c < 18) { node = 2 * j + 1; dim = c - 15; }
-  else { node = -1; dim = c - 18; }
+// per-keyframe bias, the diagonal factors: velocity priors (3 coordinates on node 3i+1), bias between-factors (6
+// coordinates, nodes 3i+2 and 3i+5), bias priors (6 coordinates on node 3i+2).  One thread per factor; mode 0 also
+// accumulates (atomics).
+__global__ void navb_diag_kernel(vus_navb_factors N, const double* __restrict__ vels, const double* __restrict__ biases,
+                                 const double* __restrict__ dc, double* __restrict__ Snav, double* __restrict__ gnav,
+                                 double* __restrict__ part, int mode) {
+  constexpr int NB_SDIAG = PerKeyframeBias::SDIAG;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nv = N.n_vprior, nb = N.n_bbetween;
+  if (t >= nv + nb + N.n_bprior) return;
+  double e = 0.0;
+  if (t < nv) {
+    const int i = N.vprior_idx[t];
+    const size_t node = 3 * (size_t)i + 1;
+    for (int k = 0; k < 3; ++k) {
+      const double w = N.vprior_w[3 * (size_t)t + k];
+      double r = w * (vels[3 * (size_t)i + k] - N.vprior_v[3 * (size_t)t + k]);
+      if (mode == 0) {
+        unsafeAtomicAdd(&Snav[36 * (node * NB_SDIAG) + 7 * k], w * w);
+        unsafeAtomicAdd(&gnav[6 * node + k], w * r);
+      } else if (mode == 2) {
+        r += w * dc[6 * node + k];
+      }
+      e += 0.5 * r * r;
+    }
+  } else if (t < nv + nb) {
+    const int f = t - nv;
+    const int i = N.bb_i[f], j = N.bb_j[f];
+    const size_t ni = 3 * (size_t)i + 2, nj = 3 * (size_t)j + 2;
+    for (int k = 0; k < 6; ++k) {
+      const double w = N.bb_w[6 * (size_t)f + k];
+      double r = w * (biases[6 * (size_t)j + k] - biases[6 * (size_t)i + k] - N.bb_meas[6 * (size_t)f + k]);
+      if (mode == 0) {
+        unsafeAtomicAdd(&Snav[36 * (ni * NB_SDIAG) + 7 * k], w * w);
+        unsafeAtomicAdd(&Snav[36 * (nj * NB_SDIAG) + 7 * k], w * w);
+        unsafeAtomicAdd(&Snav[36 * (nj * NB_SDIAG + (nj - ni)) + 7 * k], -w * w);
+        unsafeAtomicAdd(&gnav[6 * ni + k], -w * r);
+        unsafeAtomicAdd(&gnav[6 * nj + k], w * r);
+      } else if (mode == 2) {
+        r += w * (dc[6 * nj + k] - dc[6 * ni + k]);
+      }
+      e += 0.5 * r * r;
+    }
+  } else {
+    const int f = t - nv - nb;
+    const int i = N.bp_idx[f];
+    const size_t node = 3 * (size_t)i + 2;
+    for (int k = 0; k < 6; ++k) {
+      const double w = N.bp_w[6 * (size_t)f + k];
+      double r = w * (biases[6 * (size_t)i + k] - N.bp_mean[6 * (size_t)f + k]);
+      if (mode == 0) {
+        unsafeAtomicAdd(&Snav[36 * (node * NB_SDIAG) + 7 * k], w * w);
+        unsafeAtomicAdd(&gnav[6 * node + k], w * r);
+      } else if (mode == 2) {
+        r += w * dc[6 * node + k];
+      }
+      e += 0.5 * r * r;
+    }
+  }
+  part[t] = e;
 }
 
-// One workgroup adds the factors' J^T J / J^T r one factor after the other (fixed order => reproducible).
-// Thread t < 576 owns entry (c1, c2) of the 24x24 block, threads 576..599 the gradient entries.
-// One workgroup per factor.  A camera-side block receives at most two IMU factors, one DVL factor and
-// one velocity prior, so these go in with f64 atomics; the bias-bias block and the bias gradient, which
-// EVERY IMU factor touches, are written per factor and reduced in a fixed order afterwards.
-constexpr int NAV_BIAS_PART = 42;   // 36 (Sbb) + 6 (gb) per IMU factor
-__global__ __launch_bounds__(640) void nav_accumulate_imu_kernel(vus_nav_factors N, const double* __restrict__ rec_imu,
-                                                                 double* __restrict__ Snav, double* __restrict__ Scb,
-                                                                 double* __restrict__ gnav,
+// One workgroup per IMU factor: thread t < 576 owns entry (c1, c2) of the 24x24 block, threads 576..599 the gradient.
+// Camera-side blocks go in with f64 atomics.  Shared bias: the node-bias coupling goes to Scb (atomics); the bias-bias
+// block and the bias gradient, which EVERY IMU factor touches, are written per factor to bias_part and reduced in a
+// fixed order afterwards (nav_bias_reduce_kernel).
+template <class L>
+__global__ __launch_bounds__(640) void nav_accumulate_imu_kernel(typename L::Factors N, const double* __restrict__ rec_imu,
+                                                                 double* __restrict__ Snav, double* __restrict__ gnav,
+                                                                 double* __restrict__ Scb,
                                                                  double* __restrict__ bias_part) {
   const int t = threadIdx.x, f = blockIdx.x;
   const int i = N.imu_i[f], j = N.imu_j[f];
   const double* R = rec_imu + IMU_REC * (size_t)f;
   if (t < 576) {
     const int c1 = t / 24, c2 = t - 24 * c1;
+    int n1, d1, n2, d2;
+    L::imu_col(c1, i, j, n1, d1);
+    L::imu_col(c2, i, j, n2, d2);
+    if (n1 < n2) return;                       // the upper triangle is the transpose of what the lower one stores
     double h = 0.0;
 #pragma unroll
     for (int a = 0; a < 9; ++a) h += R[25 * a + c1] * R[25 * a + c2];
-    int n1, d1, n2, d2;
-    imu_col(c1, i, j, n1, d1);
-    imu_col(c2, i, j, n2, d2);
-    if (n1 >= 0 && n2 >= 0) {
-      if (n1 >= n2 && n1 - n2 <= 3) unsafeAtomicAdd(&Snav[36 * ((size_t)n1 * 4 + (n1 - n2)) + 6 * d1 + d2], h);
-    } else if (n1 >= 0 && n2 < 0) {
-      unsafeAtomicAdd(&Scb[36 * (size_t)n1 + 6 * d1 + d2], h);
-    } else if (n1 < 0 && n2 < 0) {
-      bias_part[NAV_BIAS_PART * (size_t)f + 6 * d1 + d2] = h;
+    if (L::BORDER && n2 < 0) {
+      if (n1 >= 0) unsafeAtomicAdd(&Scb[36 * (size_t)n1 + 6 * d1 + d2], h);
+      else bias_part[NAV_BIAS_PART * (size_t)f + 6 * d1 + d2] = h;
+    } else if (!L::BORDER || n1 - n2 < L::SDIAG) {   // shared bias: imu_j is not checked on the host
+      unsafeAtomicAdd(&Snav[36 * ((size_t)n1 * L::SDIAG + (n1 - n2)) + 6 * d1 + d2], h);
     }
   } else if (t < 600) {
     const int c = t - 576;
@@ -152,9 +392,9 @@ __global__ __launch_bounds__(640) void nav_accumulate_imu_kernel(vus_nav_factors
 #pragma unroll
     for (int a = 0; a < 9; ++a) gsum += R[25 * a + c] * R[25 * a + 24];
     int n1, d1;
-    imu_col(c, i, j, n1, d1);
-    if (n1 >= 0) unsafeAtomicAdd(&gnav[6 * (size_t)n1 + d1], gsum);
-    else bias_part[NAV_BIAS_PART * (size_t)f + 36 + d1] = gsum;
+    L::imu_col(c, i, j, n1, d1);
+    if (L::BORDER && n1 < 0) bias_part[NAV_BIAS_PART * (size_t)f + 36 + d1] = gsum;
+    else unsafeAtomicAdd(&gnav[6 * (size_t)n1 + d1], gsum);
   }
 }
 
@@ -171,31 +411,33 @@ __global__ __launch_bounds__(64) void nav_bias_reduce_kernel(int n_imu, const do
   }
 }
 
-__global__ __launch_bounds__(128) void nav_accumulate_dvl_kernel(vus_nav_factors N, const double* __restrict__ rec_dvl,
+template <class L>
+__global__ __launch_bounds__(128) void nav_accumulate_dvl_kernel(typename L::Factors N, const double* __restrict__ rec_dvl,
                                                                  double* __restrict__ Snav, double* __restrict__ gnav) {
+  constexpr int S = L::STRIDE;
   const int t = threadIdx.x, f = blockIdx.x;
   const int i = N.dvl_pose[f];
   const double* R = rec_dvl + DVL_REC * (size_t)f;
   if (t < 81) {
     const int c1 = t / 9, c2 = t - 9 * c1;
+    const int n1 = c1 < 6 ? S * i : S * i + 1, d1 = c1 < 6 ? c1 : c1 - 6;
+    const int n2 = c2 < 6 ? S * i : S * i + 1, d2 = c2 < 6 ? c2 : c2 - 6;
+    if (n1 < n2) return;
     double h = 0.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) h += R[10 * a + c1] * R[10 * a + c2];
-    const int n1 = c1 < 6 ? 2 * i : 2 * i + 1, d1 = c1 < 6 ? c1 : c1 - 6;
-    const int n2 = c2 < 6 ? 2 * i : 2 * i + 1, d2 = c2 < 6 ? c2 : c2 - 6;
-    if (n1 >= n2) unsafeAtomicAdd(&Snav[36 * ((size_t)n1 * 4 + (n1 - n2)) + 6 * d1 + d2], h);
+    unsafeAtomicAdd(&Snav[36 * ((size_t)n1 * L::SDIAG + (n1 - n2)) + 6 * d1 + d2], h);
   } else if (t < 90) {
     const int c = t - 81;
     double gsum = 0.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) gsum += R[10 * a + c] * R[10 * a + 9];
-    const int n1 = c < 6 ? 2 * i : 2 * i + 1, d1 = c < 6 ? c : c - 6;
+    const int n1 = c < 6 ? S * i : S * i + 1, d1 = c < 6 ? c : c - 6;
     unsafeAtomicAdd(&gnav[6 * (size_t)n1 + d1], gsum);
   }
 }
 
-// velocity priors are diagonal: one thread per coordinate, no conflicts with each other; run after the
-// accumulate kernel (same stream)
+// shared bias: velocity priors are diagonal; run after the accumulate kernels (same stream)
 __global__ void nav_vprior_accumulate_kernel(vus_nav_factors N, const double* __restrict__ vels,
                                              double* __restrict__ Snav, double* __restrict__ gnav) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -208,19 +450,6 @@ __global__ void nav_vprior_accumulate_kernel(vus_nav_factors N, const double* __
       gnav[6 * (size_t)node + k] += w * r;
     }
   }
-}
-
-__global__ __launch_bounds__(1024) void reduce_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
-  __shared__ double s[1024];
-  double acc = 0;
-  for (int k = threadIdx.x; k < n; k += 1024) acc += part[k];
-  s[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = s[0];
 }
 
 __global__ void nav_assemble_kernel(int n_nodes, int band, double lambda, const double* __restrict__ Snav,
@@ -246,7 +475,29 @@ __global__ void nav_assemble_kernel(int n_nodes, int band, double lambda, const 
   rhs[(size_t)(1 + q) * 6 * n_nodes + 6 * (size_t)node + d] = Scb[t];
 }
 
-// (Sbb + lambda I - Scb^T Z) db = -gb - Scb^T z0;  dc = z0 - Z db.   One workgroup.
+__global__ void navb_assemble_kernel(int n_nodes, int band, double lambda, const double* __restrict__ Snav,
+                                     const double* __restrict__ gnav, double* __restrict__ Sband, double* __restrict__ gs) {
+  constexpr int NB_SDIAG = PerKeyframeBias::SDIAG;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 36 * n_nodes) return;
+  const int node = t / 36, e = t - 36 * node;
+  const int kind = node % 3;                  // 0 pose (damped by vus_ba_schur), 1 velocity, 2 bias
+  const int smax = min(NB_SDIAG - 1, min(band, node));
+  for (int s = 0; s <= smax; ++s) {
+    double v = Snav[36 * ((size_t)node * NB_SDIAG + s) + e];
+    if (s == 0 && e % 7 == 0) {
+      if (kind == 1) v += (e / 7 < 3) ? lambda : 1.0;   // velocity node: damping / padding
+      else if (kind == 2) v += lambda;
+    }
+    Sband[36 * ((size_t)node * (band + 1) + s) + e] += v;
+  }
+  if (e < 6) {
+    const size_t k = 6 * (size_t)node + e;
+    gs[k] += gnav[k];
+  }
+}
+
+// shared bias: (Sbb + lambda I - Scb^T Z) db = -gb - Scb^T z0;  dc = z0 - Z db.   One workgroup.
 __global__ __launch_bounds__(1024) void nav_border_kernel(int n_nodes, const double* __restrict__ rhs,
                                                           const double* __restrict__ Scb, const double* __restrict__ Sbb,
                                                           const double* __restrict__ gb, double lambda,
@@ -311,47 +562,133 @@ __global__ __launch_bounds__(1024) void nav_border_kernel(int n_nodes, const dou
   }
 }
 
+template <class L>
 __global__ void nav_retract_kernel(int n_poses, const double* __restrict__ vels, const double* __restrict__ bias,
                                    const double* __restrict__ dc, const double* __restrict__ db,
                                    double* __restrict__ new_vels, double* __restrict__ new_bias) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < 3 * n_poses) new_vels[t] = vels[t] + dc[6 * (size_t)(2 * (t / 3) + 1) + t % 3];
-  if (t < 6) new_bias[t] = bias[t] + db[t];
+  if (t < 3 * n_poses) new_vels[t] = vels[t] + dc[6 * (size_t)(L::STRIDE * (t / 3) + 1) + t % 3];
+  if constexpr (L::BORDER) {
+    if (t < 6) new_bias[t] = bias[t] + db[t];
+  } else {
+    if (t < 6 * n_poses) new_bias[t] = bias[t] + dc[6 * (size_t)(3 * (t / 6) + 2) + t % 6];
+  }
 }
 
-int check_nav(const vus_nav_factors* N, int n_poses) {
-  VUS_REQUIRE(N != nullptr, "nav factors are null");
-  VUS_REQUIRE(n_poses >= 1 && N->n_imu >= 0 && N->n_dvl >= 0 && N->n_vprior >= 0, "bad sizes");
+// ---- host side ---------------------------------------------------------------------------------------------------------
+// the pointer checks of the fields both factor structs share
+template <class F>
+int check_arrays(const F* N) {
   if (N->n_imu > 0) VUS_REQUIRE(N->imu_i && N->imu_j && N->imu_pim && N->imu_W, "imu arrays are null");
   if (N->n_dvl > 0) VUS_REQUIRE(N->dvl_pose && N->dvl_meas && N->dvl_w, "dvl arrays are null");
   if (N->n_vprior > 0) VUS_REQUIRE(N->vprior_idx && N->vprior_v && N->vprior_w, "velocity prior arrays are null");
   return VUS_OK;
 }
 
-inline int cdivi(long long a, int b) { return (int)((a + b - 1) / b); }
+// shared bias: sizes and pointers only (no read-back: this runs in every LM trial)
+int check_nav(const vus_nav_factors* N, int n_poses) {
+  VUS_REQUIRE(N != nullptr, "nav factors are null");
+  VUS_REQUIRE(n_poses >= 1 && N->n_imu >= 0 && N->n_dvl >= 0 && N->n_vprior >= 0, "bad sizes");
+  return check_arrays(N);
+}
 
-// error partials of all factor kinds into work[0 .. n_imu + n_dvl + n_vprior), then reduce into out[0]
-int nav_errors(const vus_nav_factors* N, int n_poses, const double* poses, const double* vels, const double* bias,
-               const double* dc, const double* db, int mode, double* rec_imu, double* rec_dvl, double* part,
-               double* out, hipStream_t st) {
-  if (N->n_imu > 0)
-    nav_imu_kernel<<<cdivi(N->n_imu, 64), 64, 0, st>>>(*N, n_poses, poses, vels, bias, dc, db, rec_imu, part, mode);
-  if (N->n_dvl > 0)
-    nav_dvl_kernel<<<cdivi(N->n_dvl, 64), 64, 0, st>>>(*N, poses, vels, dc, rec_dvl, part + N->n_imu, mode);
-  if (N->n_vprior > 0)
-    nav_vprior_kernel<<<cdivi(N->n_vprior, 64), 64, 0, st>>>(*N, vels, dc, part + N->n_imu + N->n_dvl, mode);
-  reduce_kernel<<<1, 1024, 0, st>>>(part, N->n_imu + N->n_dvl + N->n_vprior, out);
-  VUS_CHECK_LAUNCH("nav_errors");
+// a device index array, read back for the host-side checks
+int read_indices(const int* d, int n, std::vector<int>& out) {
+  out.resize(n > 0 ? n : 0);
+  if (n > 0) VUS_CHECK_HIP(hipMemcpy(out.data(), d, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
   return VUS_OK;
+}
+
+// per-keyframe bias: every size, pointer and index the kernels rely on, checked on the host before anything is launched
+int check_navb(const vus_navb_factors* N, int n_poses) {
+  VUS_REQUIRE(N != nullptr, "nav factors are null");
+  VUS_REQUIRE(n_poses >= 1, "n_poses=%d", n_poses);
+  VUS_REQUIRE(N->n_imu >= 0 && N->n_dvl >= 0 && N->n_vprior >= 0 && N->n_bbetween >= 0 && N->n_bprior >= 0,
+              "bad sizes: n_imu=%d n_dvl=%d n_vprior=%d n_bbetween=%d n_bprior=%d", N->n_imu, N->n_dvl, N->n_vprior,
+              N->n_bbetween, N->n_bprior);
+  if (int rc = check_arrays(N)) return rc;
+  if (N->n_bbetween > 0) VUS_REQUIRE(N->bb_i && N->bb_j && N->bb_meas && N->bb_w, "bias between-factor arrays are null");
+  if (N->n_bprior > 0) VUS_REQUIRE(N->bp_idx && N->bp_mean && N->bp_w, "bias prior arrays are null");
+  std::vector<int> a, b;
+  if (int rc = read_indices(N->imu_i, N->n_imu, a)) return rc;
+  if (int rc = read_indices(N->imu_j, N->n_imu, b)) return rc;
+  for (int f = 0; f < N->n_imu; ++f)
+    VUS_REQUIRE(a[f] >= 0 && a[f] + 1 < n_poses && b[f] == a[f] + 1,
+                "ImuFactor %d joins poses %d and %d: needs j = i + 1 < n_poses=%d", f, a[f], b[f], n_poses);
+  if (int rc = read_indices(N->bb_i, N->n_bbetween, a)) return rc;
+  if (int rc = read_indices(N->bb_j, N->n_bbetween, b)) return rc;
+  for (int f = 0; f < N->n_bbetween; ++f)
+    VUS_REQUIRE(a[f] >= 0 && a[f] + 1 < n_poses && b[f] == a[f] + 1,
+                "bias between-factor %d joins biases %d and %d: needs bb_j = bb_i + 1 < n_poses=%d", f, a[f], b[f], n_poses);
+  const struct { const int* p; int n; const char* what; } one[] = {
+      {N->dvl_pose, N->n_dvl, "dvl_pose"}, {N->vprior_idx, N->n_vprior, "vprior_idx"}, {N->bp_idx, N->n_bprior, "bp_idx"}};
+  for (const auto& o : one) {
+    if (int rc = read_indices(o.p, o.n, a)) return rc;
+    for (int f = 0; f < o.n; ++f)
+      VUS_REQUIRE(a[f] >= 0 && a[f] < n_poses, "%s[%d]=%d is out of range (n_poses=%d)", o.what, f, a[f], n_poses);
+  }
+  return VUS_OK;
+}
+
+// work layout: [records of the IMU factors | records of the DVL factors | error partials | 8 | bias partials (shared
+// bias only, NAV_BIAS_PART per IMU factor)]
+template <class F>
+long long errors_doubles(const F& N) {
+  return (long long)IMU_REC * N.n_imu + (long long)DVL_REC * N.n_dvl + N.n_imu + N.n_dvl + n_diag(N) + 8;
+}
+struct NavWork {
+  double *rec_imu, *rec_dvl, *part;
+};
+template <class F>
+NavWork split_work(const F* N, double* work) {
+  NavWork w;
+  w.rec_imu = work;
+  w.rec_dvl = w.rec_imu + (size_t)IMU_REC * N->n_imu;
+  w.part = w.rec_dvl + (size_t)DVL_REC * N->n_dvl;
+  return w;
+}
+
+// error partials of every factor kind into part[0 .. n_imu + n_dvl + n_diag), reduced into out[0]; mode 0 also writes
+// the IMU / DVL records and, per keyframe bias, accumulates the diagonal factors into (Snav, gnav)
+template <class L>
+int nav_errors(const typename L::Factors* N, const double* poses, const double* vels, const double* bias,
+               const double* dc, const double* db, int mode, const NavWork& w, double* Snav, double* gnav, double* out,
+               hipStream_t st) {
+  const int nd = n_diag(*N);
+  if (N->n_imu > 0)
+    nav_imu_kernel<L><<<cdiv(N->n_imu, 64), 64, 0, st>>>(*N, poses, vels, bias, dc, db, w.rec_imu, w.part, mode);
+  if (N->n_dvl > 0)
+    nav_dvl_kernel<L><<<cdiv(N->n_dvl, 64), 64, 0, st>>>(*N, poses, vels, dc, w.rec_dvl, w.part + N->n_imu, mode);
+  double* part_diag = w.part + N->n_imu + N->n_dvl;
+  if constexpr (L::BORDER) {
+    if (nd > 0) nav_vprior_kernel<<<cdiv(nd, 64), 64, 0, st>>>(*N, vels, dc, part_diag, mode);
+  } else {
+    if (nd > 0) navb_diag_kernel<<<cdiv(nd, 64), 64, 0, st>>>(*N, vels, bias, dc, Snav, gnav, part_diag, mode);
+  }
+  vus::reduce_partials(w.part, N->n_imu + N->n_dvl + nd, out, st);
+  VUS_CHECK_LAUNCH(L::BORDER ? "nav_errors" : "navb_errors");
+  return VUS_OK;
+}
+
+// new velocities and biases at the step, then the linearised error at the old values (out[0]) and the error at the new
+// ones (out[1])
+template <class L>
+int nav_eval_step(const typename L::Factors* N, int n_poses, const double* poses, const double* vels, const double* bias,
+                  const double* dc, const double* db, const double* new_poses, double* new_vels, double* new_bias,
+                  double* out, double* work, hipStream_t st) {
+  const long long n_retract = L::BORDER ? 3ll * n_poses + 6 : 6ll * n_poses;
+  nav_retract_kernel<L><<<cdiv(n_retract, 256), 256, 0, st>>>(n_poses, vels, bias, dc, db, new_vels, new_bias);
+  const NavWork w = split_work(N, work);
+  if (int rc = nav_errors<L>(N, poses, vels, bias, dc, db, 2, w, nullptr, nullptr, out, st)) return rc;
+  return nav_errors<L>(N, new_poses, new_vels, new_bias, nullptr, nullptr, 1, w, nullptr, nullptr, out + 1, st);
 }
 
 }  // namespace
 
-// work layout: [records of the IMU factors | records of the DVL factors | error partials | bias partials]
+// ---- shared bias (include/vus.h) -----------------------------------------------------------------------------------
 extern "C" long long vus_nav_work_doubles(const vus_nav_factors* N) {
   if (!N) return 0;
-  return (long long)IMU_REC * N->n_imu + (long long)DVL_REC * N->n_dvl + N->n_imu + N->n_dvl + N->n_vprior + 8 +
-         (long long)NAV_BIAS_PART * N->n_imu;
+  return errors_doubles(*N) + (long long)NAV_BIAS_PART * N->n_imu;
 }
 
 extern "C" int vus_nav_linearize(const vus_nav_factors* N, int n_poses, const double* poses, const double* vels,
@@ -361,21 +698,19 @@ extern "C" int vus_nav_linearize(const vus_nav_factors* N, int n_poses, const do
   VUS_REQUIRE(poses && vels && bias && Snav && Scb && Sbb && gnav && gb && err && work, "null buffer");
   hipStream_t st = vus::as_stream(stream);
   const size_t n_nodes = 2 * (size_t)n_poses;
-  VUS_CHECK_HIP(hipMemsetAsync(Snav, 0, sizeof(double) * 36 * 4 * n_nodes, st));
+  VUS_CHECK_HIP(hipMemsetAsync(Snav, 0, sizeof(double) * 36 * SharedBias::SDIAG * n_nodes, st));
   VUS_CHECK_HIP(hipMemsetAsync(Scb, 0, sizeof(double) * 36 * n_nodes, st));
   VUS_CHECK_HIP(hipMemsetAsync(Sbb, 0, sizeof(double) * 36, st));
   VUS_CHECK_HIP(hipMemsetAsync(gnav, 0, sizeof(double) * 6 * n_nodes, st));
   VUS_CHECK_HIP(hipMemsetAsync(gb, 0, sizeof(double) * 6, st));
-  double* rec_imu = work;
-  double* rec_dvl = rec_imu + (size_t)IMU_REC * N->n_imu;
-  double* part = rec_dvl + (size_t)DVL_REC * N->n_dvl;
-  if (int rc = nav_errors(N, n_poses, poses, vels, bias, nullptr, nullptr, 0, rec_imu, rec_dvl, part, err, st)) return rc;
-  double* bias_part = part + N->n_imu + N->n_dvl + N->n_vprior + 8;
+  const NavWork w = split_work(N, work);
+  if (int rc = nav_errors<SharedBias>(N, poses, vels, bias, nullptr, nullptr, 0, w, nullptr, nullptr, err, st)) return rc;
+  double* bias_part = work + errors_doubles(*N);
   if (N->n_imu > 0) {
-    nav_accumulate_imu_kernel<<<N->n_imu, 640, 0, st>>>(*N, rec_imu, Snav, Scb, gnav, bias_part);
+    nav_accumulate_imu_kernel<SharedBias><<<N->n_imu, 640, 0, st>>>(*N, w.rec_imu, Snav, gnav, Scb, bias_part);
     nav_bias_reduce_kernel<<<NAV_BIAS_PART, 64, 0, st>>>(N->n_imu, bias_part, Sbb, gb);
   }
-  if (N->n_dvl > 0) nav_accumulate_dvl_kernel<<<N->n_dvl, 128, 0, st>>>(*N, rec_dvl, Snav, gnav);
+  if (N->n_dvl > 0) nav_accumulate_dvl_kernel<SharedBias><<<N->n_dvl, 128, 0, st>>>(*N, w.rec_dvl, Snav, gnav);
   nav_vprior_accumulate_kernel<<<1, 64, 0, st>>>(*N, vels, Snav, gnav);
   VUS_CHECK_LAUNCH("nav_linearize");
   return VUS_OK;
@@ -386,8 +721,8 @@ extern "C" int vus_nav_assemble(int n_nodes, int band, double lambda, const doub
   VUS_REQUIRE(Snav && Scb && gnav && Sband && gs && rhs, "null buffer");
   VUS_REQUIRE(n_nodes >= 2 && (n_nodes & 1) == 0 && band >= 1 && lambda >= 0.0, "n_nodes=%d band=%d lambda=%g", n_nodes,
               band, lambda);
-  nav_assemble_kernel<<<cdivi(36ll * n_nodes, 256), 256, 0, vus::as_stream(stream)>>>(n_nodes, band, lambda, Snav, Scb,
-                                                                                    gnav, Sband, gs, rhs);
+  nav_assemble_kernel<<<cdiv(36ll * n_nodes, 256), 256, 0, vus::as_stream(stream)>>>(n_nodes, band, lambda, Snav, Scb,
+                                                                                   gnav, Sband, gs, rhs);
   VUS_CHECK_LAUNCH("nav_assemble");
   return VUS_OK;
 }
@@ -406,23 +741,70 @@ extern "C" int vus_nav_eval_step(const vus_nav_factors* N, int n_poses, const do
                                  double* new_vels, double* new_bias, double* out, double* work, void* stream) {
   if (int rc = check_nav(N, n_poses)) return rc;
   VUS_REQUIRE(poses && vels && bias && dc && db && new_poses && new_vels && new_bias && out && work, "null buffer");
-  hipStream_t st = vus::as_stream(stream);
-  nav_retract_kernel<<<cdivi(3ll * n_poses + 6, 256), 256, 0, st>>>(n_poses, vels, bias, dc, db, new_vels, new_bias);
-  double* rec_imu = work;
-  double* rec_dvl = rec_imu + (size_t)IMU_REC * N->n_imu;
-  double* part = rec_dvl + (size_t)DVL_REC * N->n_dvl;
-  if (int rc = nav_errors(N, n_poses, poses, vels, bias, dc, db, 2, rec_imu, rec_dvl, part, out, st)) return rc;
-  return nav_errors(N, n_poses, new_poses, new_vels, new_bias, nullptr, nullptr, 1, rec_imu, rec_dvl, part, out + 1, st);
+  return nav_eval_step<SharedBias>(N, n_poses, poses, vels, bias, dc, db, new_poses, new_vels, new_bias, out, work,
+                                   vus::as_stream(stream));
 }
 
 extern "C" int vus_nav_error(const vus_nav_factors* N, int n_poses, const double* poses, const double* vels,
                              const double* bias, double* err, double* work, void* stream) {
   if (int rc = check_nav(N, n_poses)) return rc;
   VUS_REQUIRE(poses && vels && bias && err && work, "null buffer");
-  double* rec_imu = work;
-  double* rec_dvl = rec_imu + (size_t)IMU_REC * N->n_imu;
-  double* part = rec_dvl + (size_t)DVL_REC * N->n_dvl;
-  return nav_errors(N, n_poses, poses, vels, bias, nullptr, nullptr, 1, rec_imu, rec_dvl, part, err, vus::as_stream(stream));
+  return nav_errors<SharedBias>(N, poses, vels, bias, nullptr, nullptr, 1, split_work(N, work), nullptr, nullptr, err,
+                                vus::as_stream(stream));
+}
+
+// ---- one bias per keyframe (include/vus_nav_bias.h) ---------------------------------------------------------------
+extern "C" long long vus_navb_work_doubles(const vus_navb_factors* N) {
+  if (!N) return 0;
+  return errors_doubles(*N);
+}
+
+extern "C" int vus_navb_linearize(const vus_navb_factors* N, int n_poses, const double* poses, const double* vels,
+                                  const double* biases, double* Snav, double* gnav, double* err, double* work,
+                                  void* stream) {
+  VUS_REQUIRE(poses && vels && biases && Snav && gnav && err && work, "null buffer");
+  if (int rc = check_navb(N, n_poses)) return rc;
+  hipStream_t st = vus::as_stream(stream);
+  const size_t n_nodes = 3 * (size_t)n_poses;
+  VUS_CHECK_HIP(hipMemsetAsync(Snav, 0, sizeof(double) * 36 * PerKeyframeBias::SDIAG * n_nodes, st));
+  VUS_CHECK_HIP(hipMemsetAsync(gnav, 0, sizeof(double) * 6 * n_nodes, st));
+  const NavWork w = split_work(N, work);
+  if (int rc = nav_errors<PerKeyframeBias>(N, poses, vels, biases, nullptr, nullptr, 0, w, Snav, gnav, err, st)) return rc;
+  if (N->n_imu > 0)
+    nav_accumulate_imu_kernel<PerKeyframeBias><<<N->n_imu, 640, 0, st>>>(*N, w.rec_imu, Snav, gnav, nullptr, nullptr);
+  if (N->n_dvl > 0) nav_accumulate_dvl_kernel<PerKeyframeBias><<<N->n_dvl, 128, 0, st>>>(*N, w.rec_dvl, Snav, gnav);
+  VUS_CHECK_LAUNCH("navb_linearize");
+  return VUS_OK;
+}
+
+extern "C" int vus_navb_assemble(int n_nodes, int band, double lambda, const double* Snav, const double* gnav,
+                                 double* Sband, double* gs, void* stream) {
+  VUS_REQUIRE(Snav && gnav && Sband && gs, "null buffer");
+  VUS_REQUIRE(n_nodes >= 3 && n_nodes % 3 == 0, "n_nodes=%d is not 3 * n_poses", n_nodes);
+  VUS_REQUIRE(band >= (n_nodes - 1 < 4 ? n_nodes - 1 : 4) && band < n_nodes, "band=%d for %d nodes: needs min(4, n_nodes - 1) "
+              "<= band < n_nodes", band, n_nodes);
+  VUS_REQUIRE(lambda >= 0.0 && std::isfinite(lambda), "lambda=%g", lambda);
+  navb_assemble_kernel<<<cdiv(36ll * n_nodes, 256), 256, 0, vus::as_stream(stream)>>>(n_nodes, band, lambda, Snav, gnav,
+                                                                                    Sband, gs);
+  VUS_CHECK_LAUNCH("navb_assemble");
+  return VUS_OK;
+}
+
+extern "C" int vus_navb_eval_step(const vus_navb_factors* N, int n_poses, const double* poses, const double* vels,
+                                  const double* biases, const double* dc, const double* new_poses, double* new_vels,
+                                  double* new_biases, double* out, double* work, void* stream) {
+  VUS_REQUIRE(poses && vels && biases && dc && new_poses && new_vels && new_biases && out && work, "null buffer");
+  if (int rc = check_navb(N, n_poses)) return rc;
+  return nav_eval_step<PerKeyframeBias>(N, n_poses, poses, vels, biases, dc, nullptr, new_poses, new_vels, new_biases,
+                                        out, work, vus::as_stream(stream));
+}
+
+extern "C" int vus_navb_error(const vus_navb_factors* N, int n_poses, const double* poses, const double* vels,
+                              const double* biases, double* err, double* work, void* stream) {
+  VUS_REQUIRE(poses && vels && biases && err && work, "null buffer");
+  if (int rc = check_navb(N, n_poses)) return rc;
+  return nav_errors<PerKeyframeBias>(N, poses, vels, biases, nullptr, nullptr, 1, split_work(N, work), nullptr, nullptr,
+                                     err, vus::as_stream(stream));
 }
 
 // ---- host side: IMU preintegration (gtsam does it in C++ inside integrateMeasurement; the Python restatement of it,

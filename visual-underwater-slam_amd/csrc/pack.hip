@@ -19,7 +19,6 @@
 
 namespace {
 
-inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __global__ void iota_kernel(int* __restrict__ a, int n) {

@@ -1,4 +1,4 @@
-// vus_common.h -- shared host-side helpers of libvus_hip.so (error reporting, launch checks).
+// vus_common.h -- shared host-side helpers of libvus_hip.so (error reporting, launch checks, the fixed-order sum).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -13,7 +13,13 @@ int fail(int code, const char* fmt, ...);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// out[0] = sum of part[0..n) in a fixed order: one workgroup of reduce_partials_kernel (ba.hip), launched on st
+void reduce_partials(const double* part, int n, double* out, hipStream_t st);
+
 }  // namespace vus
+
+// workgroups of size b that cover a items
+inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
 
 #define VUS_REQUIRE(cond, ...)                                    \
   do {                                                            \
