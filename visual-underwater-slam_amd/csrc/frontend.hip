@@ -1814,131 +1814,159 @@ TileGrid tile_grid(int n_img, int H, int W) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Ungated brute-force matcher on the matrix cores.  With the descriptor bits as +-1 int8 values,
+// Ungated brute-force matcher on the matrix cores.  With the descriptor bits as +-1 values,
 // dot(q, t) = 256 - 2 * Hamming(q, t) exactly, so argmin Hamming = argmax dot: the 2000 x 2000 x 256-bit
-// all-pairs problem of one image pair is an int8 GEMM (v_mfma_i32_32x32x32_i8; the VALU version is
-// bound by the v_bcnt issue rate).  Rows of a 32x32 tile = train descriptors (A operand, expanded into
-// LDS once per 128-train chunk and shared by the four waves), columns = the wave's 32 queries (B
-// operand, expanded once into registers).  A and B use the same lane -> k map, so only the C layout
-// (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) matters.  Epilogue: one key per
-// value, (dot << 16) | (0xFFFF - train index), running signed max = smallest distance, ties to the
-// lowest train index -- the brute-force result, bit for bit.
+// all-pairs problem of one image pair is a GEMM (the VALU version is bound by the v_bcnt issue rate).
+// +-1 is exact in FP4 (E2M1: +1.0 = 0x2, -1.0 = 0xA), so the product runs on the block-scaled FP4 MFMA
+// v_mfma_scale_f32_32x32x64_f8f6f4: the cycles of the int8 32x32x32 form at twice the K, four MFMAs per
+// 32x32 tile over K = 256.  Rows of a tile = train descriptors (A operand, expanded into LDS once per
+// HM_CHUNK-train chunk and shared by the four waves; the next chunk's words are loaded while the current one's
+// tiles run), columns = the wave's 32 * HM_QT queries (B operand, expanded once into registers).  A and B use the same lane -> k map, so only the C layout
+// (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) matters.
+//
+// Keys.  Every accumulator is an integer of magnitude < 2^24, exact in f32 in any summation order: the
+// B block scale 2^HM_KEY_SHIFT (= HM_CHUNK) puts the factor HM_CHUNK on the dot product, and the C input of
+// a tile's first MFMA is HM_CHUNK - 1 - row, so a value is HM_CHUNK * dot + (HM_CHUNK - 1 - row).  Within
+// a chunk the running best is kept in f32 as (best chunk key + 32 * tile), chunk key = HM_CHUNK * dot +
+// (HM_CHUNK - 1 - local train index): one max3 tree per tile and column tile, seeded with the previous
+// best + 32.  Once per chunk it becomes the global key (dot << 16) | (0xFFFF - train index), running
+// signed max = smallest distance, ties to the lowest train index -- the brute-force result, bit for bit.
 typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef int v16i_t __attribute__((ext_vector_type(16)));
+typedef int v8i_t __attribute__((ext_vector_type(8)));
+typedef float v16f_t __attribute__((ext_vector_type(16)));
 #ifndef VUS_HM_CHUNK
 #define VUS_HM_CHUNK 128
 #endif
-constexpr int HM_CHUNK = VUS_HM_CHUNK;        // trains expanded per LDS chunk
-constexpr int HM_ROWB = 272;         // bytes per expanded row: 256 + 16 (bank spread of the b128 reads)
-
-// 4 descriptor bits -> 4 bytes of +1 (bit set) / -1
-__device__ __forceinline__ int spread_pm1(uint32_t nib) {
-  const uint32_t sp = (nib * 0x00204081u) & 0x01010101u;
-  return (int)~(sp * 0xFEu);
-}
+constexpr int HM_CHUNK = VUS_HM_CHUNK;   // trains expanded per LDS chunk
+constexpr int HM_KEY_SHIFT = HM_CHUNK == 256 ? 8 : HM_CHUNK == 128 ? 7 : HM_CHUNK == 64 ? 6 : -1;
+static_assert(HM_KEY_SHIFT > 0, "HM_CHUNK must be 64, 128 or 256");
+constexpr int HM_ROWB = 144;             // bytes per expanded row: 128 + 16 (bank spread of the b128 reads)
+constexpr int HM_SCALE_A = 0x7F7F7F7F;   // E8M0 block scales, every byte the same: 2^0 (trains) ...
+constexpr int HM_SCALE_B = (int)(0x01010101u * (0x7F + HM_KEY_SHIFT));   // ... and 2^HM_KEY_SHIFT (queries)
 
 #ifndef VUS_HM_QT
-#define VUS_HM_QT 2
+#define VUS_HM_QT 4
 #endif
-constexpr int HM_QT = VUS_HM_QT;             // 32-query column tiles per wave (A fragments and the chunk expansion are shared)
+constexpr int HM_QT = VUS_HM_QT;         // 32-query column tiles per wave (A fragments and the chunk expansion are shared)
 constexpr int HM_QWG = 4 * 32 * HM_QT;   // queries per workgroup
 
-// 4 descriptor bits -> 4 bytes of +32 (bit set) / -32: the QUERY operand carries the factor 32 of the epilogue's key
-__device__ __forceinline__ int spread_pm32(uint32_t nib) {
-  const uint32_t sp = (nib * 0x00204081u) & 0x01010101u;
-  return (int)((sp * 0xC0u) ^ 0xE0E0E0E0u);
+// 8 descriptor bits (the low byte of b) -> 8 FP4 nibbles, -1.0 (0xA) for a set bit and +1.0 (0x2) for a clear one.
+// The sign is flipped for both operands alike, so every product is unchanged.
+__device__ __forceinline__ int spread_fp4(uint32_t b) {
+  uint32_t x = (b | b << 12) & 0x000F000Fu;         // bits 0-3 -> 0-3, bits 4-7 -> 16-19
+  x = (x | x << 6) & 0x03030303u;                   // bit pairs -> bits 0-1 of each byte
+  return (int)(((x << 3 | x << 6) & 0x88888888u) | 0x22222222u);   // bit 0 -> 3, bit 1 -> 7: sign bits of the nibbles
 }
 
-// best key of one 32x32 tile for this lane's query.  The accumulators ARE the keys (dot << 5) | (31 - row): the factor
-// 32 rides on the query operand (+-32 instead of +-1) and the row term is the accumulators' initial value (round 4: the
-// 32 v_lshl_or per tile that formed the keys were a third of the epilogue's vector instructions, and the epilogue, not the
-// matrix pipe, was the longer of the two per tile).  A max3 tree, then one conversion to the global key
-// (dot << 16) | (0xFFFF - train index).
-__device__ __forceinline__ int tile_best(const v16i_t& acc, int tb) {
-  int k[16];
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) k[reg] = acc[reg];
-  const int m0 = max3i(k[0], k[1], k[2]), m1 = max3i(k[3], k[4], k[5]), m2 = max3i(k[6], k[7], k[8]),
-            m3 = max3i(k[9], k[10], k[11]), m4 = max3i(k[12], k[13], k[14]);
-  const int m = max(max3i(m0, m1, m2), max3i(m3, m4, k[15]));
-  const int row = 31 - (m & 31);
-  return (m >> 5) * 65536 + (0xFFFF - (tb + row));
+// one descriptor word (32 bits) -> the 32 FP4 values of one lane's operand of one MFMA: four lookups in the block's
+// 256-entry byte table (one v_lshlrev_b32_sdwa + one ds_read_b32 per byte instead of eight VALU instructions)
+__device__ __forceinline__ v4i_t spread_word(const uint32_t* lut, uint32_t w) {
+  return v4i_t{(int)lut[w & 0xFFu], (int)lut[(w >> 8) & 0xFFu], (int)lut[(w >> 16) & 0xFFu], (int)lut[w >> 24]};
 }
 
-__global__ __launch_bounds__(256) void hamming_match_mfma_kernel(const uint32_t* __restrict__ desc32,
-                                                                 const int* __restrict__ kp_count, int max_kp,
-                                                                 const int* __restrict__ q_index,
-                                                                 const int* __restrict__ t_index, int max_dist,
-                                                                 int32_t* __restrict__ idx_out,
-                                                                 int32_t* __restrict__ dist_out) {
+__device__ __forceinline__ v8i_t fp4_operand(v4i_t v) {   // FP4 reads dwords 0-3 of the builtin's 8-dword operand
+  return v8i_t{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
+}
+
+__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+
+// running chunk best of one column tile after one more tile: max over the 16 keys of this lane's rows and prev + 32
+__device__ __forceinline__ float tile_best(const v16f_t& acc, float prev) {
+  const float m0 = max3f(acc[0], acc[1], acc[2]), m1 = max3f(acc[3], acc[4], acc[5]), m2 = max3f(acc[6], acc[7], acc[8]),
+              m3 = max3f(acc[9], acc[10], acc[11]), m4 = max3f(acc[12], acc[13], acc[14]),
+              m5 = max3f(acc[15], prev + 32.0f, m0);
+  return max3f(max3f(m1, m2, m3), m4, m5);
+}
+
+// waves_per_eu(3): 166 registers, no spill, 3 waves per SIMD (172 and 2 waves without the hint: 0.38 vs 0.36 ms)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void hamming_match_mfma_kernel(
+    const uint32_t* __restrict__ desc32, const int* __restrict__ kp_count, int max_kp, const int* __restrict__ q_index,
+    const int* __restrict__ t_index, int max_dist, int32_t* __restrict__ idx_out, int32_t* __restrict__ dist_out) {
   __shared__ __attribute__((aligned(16))) uint8_t s_t[HM_CHUNK * HM_ROWB];
+  __shared__ uint32_t s_lut[256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  s_lut[tid] = spread_fp4(tid);
+  __syncthreads();
   const int r = lane & 31, h = lane >> 5;
   const int p = blockIdx.y;
   const int qi = q_index[p], ti = t_index[p];
-  const int nq = kp_count[qi], nt = kp_count[ti];
-  const int q0 = blockIdx.x * HM_QWG + 32 * HM_QT * wave + r;   // column tile c holds query q0 + 32 c
-  // B fragments: k-step ks, lane half h <-> descriptor bits [32 ks + 16 h, +16)
-  v4i_t bq[HM_QT][8];
+  const int nq = kp_count[qi];
+  const int wq0 = blockIdx.x * HM_QWG + 32 * HM_QT * wave;   // first query of this wave
+  const int q0 = wq0 + r;                                     // column tile c holds query q0 + 32 c
+  // a workgroup without queries skips the trains; a wave without queries only helps expand them
+  const int nt = blockIdx.x * HM_QWG < nq ? kp_count[ti] : 0;
+  const bool wave_busy = wq0 < nq;
+  // B fragments: MFMA ks, lane half h <-> descriptor word 2 ks + h
+  v4i_t bq[HM_QT][4];
 #pragma unroll
   for (int c = 0; c < HM_QT; ++c) {
     const int q = q0 + 32 * c;
-    const uint32_t* dq = desc32 + ((size_t)qi * max_kp + min(q, max_kp - 1)) * 8;
+    const uint32_t* dq = desc32 + ((size_t)qi * max_kp + min(q, max_kp - 1)) * 8 + h;
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const uint32_t bits = (q < nq ? dq[ks] : 0u) >> (16 * h);
-#pragma unroll
-      for (int n = 0; n < 4; ++n) bq[c][ks][n] = spread_pm32((bits >> (4 * n)) & 0xFu);
-    }
+    for (int ks = 0; ks < 4; ++ks) bq[c][ks] = spread_word(s_lut, dq[2 * ks]);   // a column past nq is never written
   }
-  // initial value of a tile's accumulators: 31 - (row of the value inside this lane's sixteen), row = (reg & 3) + 8 (reg >> 2)
-  v16i_t cinit;
+  // initial value of a tile's accumulators: HM_CHUNK - 1 - (row of the value inside this lane's sixteen)
+  v16f_t cinit;
 #pragma unroll
-  for (int reg = 0; reg < 16; ++reg) cinit[reg] = 31 - ((reg & 3) + 8 * (reg >> 2));
+  for (int reg = 0; reg < 16; ++reg) cinit[reg] = (float)(HM_CHUNK - 1 - ((reg & 3) + 8 * (reg >> 2)));
   int best[HM_QT];
 #pragma unroll
   for (int c = 0; c < HM_QT; ++c) best[c] = INT_MIN;
+  // the chunk's (train, 32-bit word) items of this thread, loaded one chunk ahead; a row past nt loads row nt - 1, whose
+  // keys the epilogue masks
   const uint32_t* dt = desc32 + (size_t)ti * max_kp * 8;
+  constexpr int HM_ITEMS = HM_CHUNK * 8 / 256;
+  uint32_t xw[HM_ITEMS];
+#pragma unroll
+  for (int u = 0; u < HM_ITEMS; ++u) xw[u] = nt > 0 ? dt[(size_t)min((tid + 256 * u) >> 3, nt - 1) * 8 + (tid & 7)] : 0u;
   for (int t0 = 0; t0 < nt; t0 += HM_CHUNK) {
     __syncthreads();
 #pragma unroll
-    for (int u = 0; u < HM_CHUNK * 8 / 256; ++u) {   // (train, 32-bit word) items
+    for (int u = 0; u < HM_ITEMS; ++u) {
       const int item = tid + 256 * u;
-      const int tr = item >> 3, wd = item & 7;
-      const uint32_t x = t0 + tr < nt ? dt[(size_t)(t0 + tr) * 8 + wd] : 0u;
-      v4i_t lo, hi;
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        lo[n] = spread_pm1((x >> (4 * n)) & 0xFu);
-        hi[n] = spread_pm1((x >> (16 + 4 * n)) & 0xFu);
-      }
-      v4i_t* dst = reinterpret_cast<v4i_t*>(s_t + tr * HM_ROWB + 32 * wd);
-      dst[0] = lo;
-      dst[1] = hi;
+      *reinterpret_cast<v4i_t*>(s_t + (item >> 3) * HM_ROWB + 16 * (item & 7)) = spread_word(s_lut, xw[u]);
     }
     __syncthreads();
+    if (t0 + HM_CHUNK < nt) {
+#pragma unroll
+      for (int u = 0; u < HM_ITEMS; ++u)
+        xw[u] = dt[(size_t)min(t0 + HM_CHUNK + ((tid + 256 * u) >> 3), nt - 1) * 8 + (tid & 7)];
+    }
+    if (!wave_busy) continue;
     const int ntile = min(HM_CHUNK, nt - t0 + 31) >> 5;
+    float cb[HM_QT];                                     // chunk best + 32 * tile
+#pragma unroll
+    for (int c = 0; c < HM_QT; ++c) cb[c] = -INFINITY;
     for (int tile = 0; tile < ntile; ++tile) {
       const uint8_t* arow = s_t + (32 * tile + r) * HM_ROWB + 16 * h;
-      v16i_t acc[HM_QT];
+      v16f_t acc[HM_QT];
 #pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const v4i_t a = *reinterpret_cast<const v4i_t*>(arow + 32 * ks);
+      for (int ks = 0; ks < 4; ++ks) {
+        const v8i_t a = fp4_operand(*reinterpret_cast<const v4i_t*>(arow + 32 * ks));
 #pragma unroll
         for (int c = 0; c < HM_QT; ++c)
-          acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[c][ks], ks == 0 ? cinit : acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, fp4_operand(bq[c][ks]), ks == 0 ? cinit : acc[c],
+                                                                   4, 4, 0, HM_SCALE_A, 0, HM_SCALE_B);
       }
-      const int tb = t0 + 32 * tile + 4 * h;            // train index of this lane's row 0
       if (t0 + 32 * tile + 32 > nt) {                   // wave-uniform: rows past the train count cannot win
+        const int tb = t0 + 32 * tile + 4 * h;          // train index of this lane's row 0
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
           if (tb + (reg & 3) + 8 * (reg >> 2) >= nt) {
 #pragma unroll
-            for (int c = 0; c < HM_QT; ++c) acc[c][reg] = -(1 << 20);
+            for (int c = 0; c < HM_QT; ++c) acc[c][reg] = -INFINITY;
           }
       }
 #pragma unroll
-      for (int c = 0; c < HM_QT; ++c) best[c] = max(best[c], tile_best(acc[c], tb));
+      for (int c = 0; c < HM_QT; ++c) cb[c] = tile_best(acc[c], cb[c]);
+    }
+    // chunk key -> global key (a lane half whose rows of the chunk all lie past nt keeps -inf)
+#pragma unroll
+    for (int c = 0; c < HM_QT; ++c) {
+      if (!(cb[c] > -INFINITY)) continue;
+      const int k = (int)(cb[c] - 32.0f * (ntile - 1));
+      const int train = t0 + 4 * h + (HM_CHUNK - 1 - (k & (HM_CHUNK - 1)));
+      best[c] = max(best[c], (k >> HM_KEY_SHIFT) * 65536 + (0xFFFF - train));
     }
   }
 #pragma unroll
@@ -2356,7 +2384,7 @@ extern "C" int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, 
     if (max_dy >= 0)
       hamming_match_kernel<true><<<grid, 256, 0, vus::as_stream(stream)>>>(
           desc, kp_keys, kp_count, max_kp, W, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out, dist_out);
-    else if (max_kp <= 65535)   // ungated: int8 GEMM formulation on the matrix cores
+    else if (max_kp <= 65535)   // ungated: FP4 GEMM formulation on the matrix cores
       hamming_match_mfma_kernel<<<dim3((max_kp + HM_QWG - 1) / HM_QWG, n_pairs), 256, 0, vus::as_stream(stream)>>>(
           reinterpret_cast<const uint32_t*>(desc), kp_count, max_kp, q_index, t_index, max_dist, idx_out, dist_out);
     else
