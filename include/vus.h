@@ -523,4 +523,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Inertial graphs with one IMU bias per keyframe (pose_stride 3): vus_navb_factors and vus_navb_linearize / _assemble /
  * _eval_step / _error. */
 #include "vus_nav_bias.h"
+
+/* BetweenFactor<Pose3> (odometry, loop closures) added to the reduced camera system: vus_between_factors and
+ * vus_between_check / _linearize / _assemble / _eval_step / _error. */
+#include "vus_between.h"
 #endif /* VUS_H */

@@ -1,0 +1,256 @@
+"""Dense f64 reference of BetweenFactorPose3 (include/vus_between.h): the residual and Jacobians in numpy on top of the
+oracle's pose_local / pose_retract twins, the between blocks added to the existing dense references (the oracle's
+stereo Schur twins, nav_ref, nav_bias_ref), and a dense LM with GTSAM's trial rules for pose graphs with or without
+stereo factors.  Test infrastructure only (a plain module, not a conftest)."""
+import math
+
+import numpy as np
+
+from robust_ref import weight_loss
+
+
+def flat_inv(T):
+    R, t = T[:9].reshape(3, 3), T[9:]
+    return np.concatenate([R.T.reshape(-1), -R.T @ t])
+
+
+def flat_mul(A, B):
+    Ra, ta, Rb, tb = A[:9].reshape(3, 3), A[9:], B[:9].reshape(3, 3), B[9:]
+    return np.concatenate([(Ra @ Rb).reshape(-1), ta + Ra @ tb])
+
+
+def skew(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def adjoint(T):
+    """Ad(T) in the tangent order (omega, v): [[R, 0], [[t]x R, R]]."""
+    R, t = T[:9].reshape(3, 3), T[9:]
+    A = np.zeros((6, 6))
+    A[:3, :3] = A[3:, 3:] = R
+    A[3:, :3] = skew(t) @ R
+    return A
+
+
+def residual(oracle, T1, T2, M):
+    """r = Log(M^-1 T1^-1 T2) = Local(M, T1^-1 T2)."""
+    return oracle.pose_local(M, flat_mul(flat_inv(T1), T2))
+
+
+def jacobians(T1, T2):
+    """H1 = -Ad(hx^-1), H2 = I (GTSAM's default BetweenFactor, the derivative of Local not applied)."""
+    hx = flat_mul(flat_inv(T1), T2)
+    return -adjoint(flat_inv(hx)), np.eye(6)
+
+
+class BetweenSet:
+    """Host description: i, j pose indices, meas [n, 12], sigmas [n, 6], losses [(kind, k)] (None = all Gaussian)."""
+
+    def __init__(self, i, j, meas, sigmas, losses=None):
+        self.i, self.j = np.asarray(i, np.int64), np.asarray(j, np.int64)
+        self.meas = np.asarray(meas, float).reshape(-1, 12)
+        self.w = 1.0 / np.asarray(sigmas, float).reshape(-1, 6)
+        self.losses = list(losses) if losses is not None else [(0, 0.0)] * len(self.i)
+
+    @property
+    def span(self):
+        return int(np.abs(self.i - self.j).max())
+
+    def device(self, n_poses, pose_stride=1, device="cuda:0"):
+        from visual_underwater_slam_amd.ba import BetweenFactors
+        return BetweenFactors(self.i, self.j, self.meas, 1.0 / self.w, n_poses, pose_stride=pose_stride,
+                              loss=list(self.losses), device=device)
+
+
+def _wl(kind, k, d2):
+    """(w, rho) of the robust table at the squared whitened norm d2 (Gaussian: 1, d2 / 2)."""
+    if kind == 0:
+        return 1.0, 0.5 * d2
+    w, rho = weight_loss(kind, k, np.array([math.sqrt(d2)]))
+    return float(w[0]), float(rho[0])
+
+
+def factors(oracle, G, poses):
+    """Per factor: (sqrt(w) W r, sqrt(w) W H1, sqrt(w) W H2, i, j, w, rho) at poses."""
+    out = []
+    for f in range(len(G.i)):
+        a, b = int(G.i[f]), int(G.j[f])
+        r = residual(oracle, poses[a], poses[b], G.meas[f])
+        H1, H2 = jacobians(poses[a], poses[b])
+        d2 = float(((G.w[f] * r) ** 2).sum())
+        w, rho = _wl(*G.losses[f], d2)
+        s = math.sqrt(w) * G.w[f]
+        out.append((s * r, s[:, None] * H1, s[:, None] * H2, a, b, w, rho))
+    return out
+
+
+def error(oracle, G, poses):
+    """Sum rho (0.5 |W r|^2 without a robust model)."""
+    return sum(f[6] for f in factors(oracle, G, poses))
+
+
+def system(oracle, G, poses, n_nodes, stride=1):
+    """The between factors' weighted normal equations over the camera-side nodes: H [6 n_nodes]^2, g, err at delta = 0
+    (0.5 sum w |W r|^2) and the factors."""
+    H, g, e = np.zeros((6 * n_nodes, 6 * n_nodes)), np.zeros(6 * n_nodes), 0.0
+    fac = factors(oracle, G, poses)
+    for rw, J1, J2, a, b, _, _ in fac:
+        e += 0.5 * float(rw @ rw)
+        cols = ((stride * a, J1), (stride * b, J2))
+        for na, Ja in cols:
+            g[6 * na:6 * na + 6] += Ja.T @ rw
+            for nb, Jb in cols:
+                H[6 * na:6 * na + 6, 6 * nb:6 * nb + 6] += Ja.T @ Jb
+    return H, g, e, fac
+
+
+def linear_error(fac, x, stride=1):
+    """0.5 sum w |W (r + H1 d1 + H2 d2)|^2 at the node step x [6 n_nodes]."""
+    e = 0.0
+    for rw, J1, J2, a, b, _, _ in fac:
+        v = rw + J1 @ x[6 * stride * a:6 * stride * a + 6] + J2 @ x[6 * stride * b:6 * stride * b + 6]
+        e += 0.5 * float(v @ v)
+    return e
+
+
+def prior_system(oracle, priors, poses):
+    """PriorFactorPose3 (r = -Local(x, prior) w, H = diag(w)) in numpy: H, g over poses, err."""
+    n = len(poses)
+    H, g, e = np.zeros((6 * n, 6 * n)), np.zeros(6 * n), 0.0
+    for i, T, w in zip(*priors):
+        r = -oracle.pose_local(poses[i], T) * w
+        H[6 * i:6 * i + 6, 6 * i:6 * i + 6] += np.diag(w * w)
+        g[6 * i:6 * i + 6] += w * r
+        e += 0.5 * float(r @ r)
+    return H, g, e
+
+
+def prior_error(oracle, priors, poses):
+    return sum(0.5 * float(((oracle.pose_local(poses[i], T) * w) ** 2).sum()) for i, T, w in zip(*priors))
+
+
+def stereo_dense(oracle, P, poses, points, band, lam):
+    """The oracle's stereo (+ prior) Schur complement at damping lam scattered to a dense [6n]^2 matrix, its gs, and the
+    pieces (lin, sch)."""
+    n = len(poses)
+    lin = oracle.ba_linearize(P, poses, points)
+    sch = oracle.ba_schur(P, band, lam, lin)
+    A, g = np.zeros((6 * n, 6 * n)), np.zeros(6 * n)
+    for i in range(n):
+        for sl in range(min(i, band) + 1):
+            blk = sch["Sband"][i, sl].reshape(6, 6)
+            k = i - sl
+            A[6 * i:6 * i + 6, 6 * k:6 * k + 6] += blk
+            if sl:
+                A[6 * k:6 * k + 6, 6 * i:6 * i + 6] += blk.T
+        g[6 * i:6 * i + 6] = sch["gs"][i]
+    return A, g, lin, sch
+
+
+def lm_optimize(oracle, G, poses, priors=None, P=None, points=None, band=None, max_iterations=100, lambda_initial=1e-5,
+                lambda_factor=10.0, lambda_upper=1e5, lambda_lower=0.0, min_model_fidelity=1e-3, rel_tol=1e-5,
+                abs_tol=1e-5, error_tol=0.0):
+    """Dense LM (GTSAM's iterate / tryLambda / convergence rules, as the oracle LM) over poses (pose_stride 1) with between
+    factors G and either the numpy pose priors `priors` = (idx, T [m,12], w [m,6]) (pose graph) or the oracle stereo problem
+    P (stereo + priors, landmarks back-substituted by the oracle twins).  Returns (poses, points, report)."""
+    n = len(poses)
+    poses = np.array(poses, float, copy=True)
+    points = None if points is None else np.array(points, float, copy=True)
+    rep = {"iterations": 0, "outer": 0, "tries": 0, "status": 1, "err_hist": [], "lambda_hist": [], "trials": []}
+
+    def total(po, pt):
+        e = error(oracle, G, po)
+        return e + (oracle.ba_error(P, po, pt) if P is not None else prior_error(oracle, priors, po))
+    lam = lambda_initial
+    current = total(poses, points)
+    rep["initial_error"] = current
+    while rep["iterations"] < max_iterations:
+        new_error, stop, accepted = current, False, False
+        Hb, gb, eb, fac = system(oracle, G, poses, n)
+        while True:
+            if P is not None:
+                A, g, lin, sch = stereo_dense(oracle, P, poses, points, band, lam)
+                lin0 = lin["err"] + eb
+            else:
+                A, g, e0 = prior_system(oracle, priors, poses)
+                A = A + lam * np.eye(6 * n)
+                lin0 = e0 + eb
+            A, g = A + Hb, g + gb
+            x = np.linalg.solve(A, -g)
+            dp = x.reshape(n, 6)
+            if P is not None:
+                dl = oracle.ba_backsub(P, lin, sch["Vinv"], dp)
+                npo, npt, lin_s, new_s = oracle.ba_eval_step(P, poses, points, dp, dl)
+            else:
+                npo = np.stack([oracle.pose_retract(poses[i], dp[i]) for i in range(n)])
+                npt = None
+                Hp, gp, ep = prior_system(oracle, priors, poses)
+                lin_s = ep + float(gp @ x) + 0.5 * float(x @ Hp @ x)
+                new_s = prior_error(oracle, priors, npo)
+            lin1 = lin_s + linear_error(fac, x)
+            new1 = new_s + error(oracle, G, npo)
+            rep["tries"] += 1
+            success = False
+            if math.isfinite(lin1) and math.isfinite(new1):
+                lin_change = lin0 - lin1
+                if lin_change >= 0.0:
+                    cost_change = current - new1
+                    if lin_change > 2.220446049250313e-16 * lin0:
+                        success = cost_change / lin_change > min_model_fidelity
+                    if abs(cost_change) < rel_tol * current:
+                        stop = True
+                    if success:
+                        poses, points, new_error = npo, npt, new1
+            rep["trials"].append((lam, success))
+            if success:
+                lam = max(lambda_lower, lam / lambda_factor)
+                accepted = True
+                break
+            if stop:
+                break
+            lam *= lambda_factor
+            if lam >= lambda_upper:
+                rep["status"] = 2
+                break
+        rep["err_hist"].append(new_error)
+        rep["lambda_hist"].append(lam)
+        rep["outer"] += 1
+        rep["iterations"] += int(accepted)
+        if new_error <= error_tol:
+            converged = True
+        else:
+            dec = current - new_error
+            converged = dec / current <= rel_tol or dec <= abs_tol
+        current = new_error
+        if rep["status"] == 2 or converged or not math.isfinite(current):
+            if converged and rep["status"] != 2:
+                rep["status"] = 0
+            break
+    rep["final_error"], rep["final_lambda"] = current, lam
+    return poses, points, rep
+
+
+def pose_graph(rng, n, closures=(), noise=0.0, step=1.0, loss=None):
+    """A planar-ish trajectory of n poses (ground truth), odometry between i-1 and i and the given (i, j) closures, measured
+    from the truth with optional tangent noise; initial poses = the truth perturbed.  Returns (truth [n,12], init [n,12],
+    BetweenSet, priors) with a prior on pose 0 at its truth."""
+    from visual_underwater_slam_amd.gtsam import Pose3, Rot3
+    truth = []
+    for k in range(n):
+        yaw = 0.15 * k
+        truth.append(Pose3(Rot3.Rz(yaw).compose(Rot3.Rx(0.05 * math.sin(k))), [step * math.cos(0.1 * k) * k, step * math.sin(0.1 * k) * k, 0.2 * math.sin(0.3 * k)]))
+    truth_f = np.stack([T.flat12() for T in truth])
+    pairs = [(k - 1, k) for k in range(1, n)] + list(closures)
+    meas = []
+    for a, b in pairs:
+        m = truth[a].between(truth[b])
+        if noise:
+            m = m.retract(noise * rng.standard_normal(6))
+        meas.append(m.flat12())
+    sig = np.tile([0.01, 0.01, 0.01, 0.05, 0.05, 0.05], (len(pairs), 1))
+    losses = None if loss is None else [(0, 0.0)] * (n - 1) + [loss] * len(closures)
+    G = BetweenSet([p[0] for p in pairs], [p[1] for p in pairs], np.array(meas), sig, losses)
+    init = np.stack([T.retract(0.05 * rng.standard_normal(6)).flat12() for T in truth])
+    init[0] = truth_f[0]
+    priors = (np.array([0]), truth_f[:1], np.array([[1e3] * 6]))
+    return truth_f, init, G, priors

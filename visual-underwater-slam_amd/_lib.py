@@ -71,6 +71,12 @@ SIGNATURES = {
     "vus_ba_point_check": [_P, c_int, _P, _P],
     "vus_ba_point_covariance": [_P, _P, _P, _P, _P, c_int, _P, _P],
     "vus_nav_border_covariance": [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    # BetweenFactor<Pose3> (include/vus_between.h)
+    "vus_between_check": [_P, c_int, _P],
+    "vus_between_linearize": [_P, _P, _P, _P, _P, _P],
+    "vus_between_assemble": [_P, _P, c_int, _P, _P, _P],
+    "vus_between_eval_step": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_between_error": [_P, _P, _P, _P, _P],
     # host-only tuning knobs of the band solve (tests, A/B timing)
     "vus_ba_set_tuning": [c_int, c_int],
 }
@@ -120,6 +126,8 @@ def load():
     lib.vus_nav_work_doubles.restype = ctypes.c_longlong
     lib.vus_navb_work_doubles.argtypes = [_P]
     lib.vus_navb_work_doubles.restype = ctypes.c_longlong
+    lib.vus_between_work_doubles.argtypes = [_P]
+    lib.vus_between_work_doubles.restype = ctypes.c_longlong
     lib.vus_ba_band_selinv_work_doubles.argtypes = [c_int, c_int]
     lib.vus_ba_band_selinv_work_doubles.restype = ctypes.c_longlong
     _lib = lib

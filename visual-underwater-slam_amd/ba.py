@@ -61,6 +61,78 @@ class _CTiles(ctypes.Structure):
                 ("unit_ptr", c_void_p), ("entries", c_void_p), ("order", c_void_p)]
 
 
+class _CBetween(ctypes.Structure):
+    _fields_ = [("n", c_int), ("n_nodes", c_int), ("pose_stride", c_int), ("node1", c_void_p), ("node2", c_void_p),
+                ("meas", c_void_p), ("w", c_void_p), ("loss_kind", c_void_p), ("loss_k", c_void_p), ("n_targets", c_int),
+                ("tgt_node", c_void_p),
+                ("tgt_s", c_void_p), ("tgt_ptr", c_void_p), ("tgt_terms", c_void_p)]
+
+
+def between_targets(node1, node2):
+    """The CSR of include/vus_between.h on the host: every 6 x 6 block (node, s) of the band that BetweenFactorPose3 terms
+    land in, ascending by (node, s), and per block its terms 4 f + kind in factor order (kind 0 J1^T J1 at (node1, 0),
+    1 J2^T J2 at (node2, 0), 2 J1^T J2 at (node1, node1 - node2) when node1 > node2, 3 its transpose at (node2,
+    node2 - node1) otherwise).  Returns (tgt_node, tgt_s, tgt_ptr, tgt_terms) as int32 arrays."""
+    n1, n2 = np.asarray(node1, np.int64), np.asarray(node2, np.int64)
+    f = np.arange(len(n1), dtype=np.int64)
+    hi = n1 > n2
+    node = np.concatenate([n1, n2, np.where(hi, n1, n2)])
+    sdiag = np.concatenate([np.zeros_like(n1), np.zeros_like(n2), np.abs(n1 - n2)])
+    term = np.concatenate([4 * f, 4 * f + 1, 4 * f + np.where(hi, 2, 3)])
+    order = np.lexsort((term, sdiag, node))
+    node, sdiag, term = node[order], sdiag[order], term[order]
+    first = np.ones(len(node), bool)
+    first[1:] = (node[1:] != node[:-1]) | (sdiag[1:] != sdiag[:-1])
+    starts = np.nonzero(first)[0]
+    ptr = np.append(starts, len(node))
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return i32(node[starts]), i32(sdiag[starts]), i32(ptr), i32(term)
+
+
+class BetweenFactors:
+    """Device-resident vus_between_factors: BetweenFactorPose3(X(i), X(j), meas, model) for i, j = `pose_i`, `pose_j`
+    (either order, several on one pair allowed, i != j), meas [n, 12] flat12 of the measured T_i^-1 T_j, sigmas [n, 6]
+    in the tangent order (omega, v).  `loss`: one robust model for all of them (robust_loss(): None = Gaussian) or a list
+    (not a tuple) of n, one per factor (Gaussian odometry next to robust loop closures).  Node of pose p = pose_stride p.
+    `span` = the widest pose distance, for StereoBAProblem(between_span=...)."""
+
+    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride=1, loss=None, device="cuda:0"):
+        pi, pj = np.asarray(pose_i, np.int64).reshape(-1), np.asarray(pose_j, np.int64).reshape(-1)
+        meas = np.asarray(meas, np.float64).reshape(-1, 12)
+        sig = np.asarray(sigmas, np.float64).reshape(-1, 6)
+        n = len(pi)
+        if n == 0 or not (len(pj) == len(meas) == len(sig) == n):
+            raise ValueError(f"between factors: {len(pi)} / {len(pj)} keys, {len(meas)} measurements, {len(sig)} sigmas")
+        if ((pi < 0) | (pi >= n_poses) | (pj < 0) | (pj >= n_poses)).any():
+            raise ValueError(f"between factors: a pose index outside [0, {n_poses})")
+        if (pi == pj).any():
+            f = int(np.nonzero(pi == pj)[0][0])
+            raise ValueError(f"BetweenFactorPose3 {f} joins pose {int(pi[f])} to itself")
+        if not (np.isfinite(sig).all() and (sig > 0).all()):
+            raise ValueError("between factors: sigmas must be finite and > 0")
+        self.n, self.n_poses, self.pose_stride = n, int(n_poses), int(pose_stride)
+        self.span = int(np.abs(pi - pj).max())
+        if isinstance(loss, list) and len(loss) != n:
+            raise ValueError(f"between factors: {len(loss)} robust models for {n} factors")
+        self.losses = [robust_loss(x) for x in loss] if isinstance(loss, list) else [robust_loss(loss)] * n
+        self.host = dict(i=pi, j=pj, meas=meas, sigmas=sig, losses=self.losses)
+        dev = torch.device(device)
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        ps = self.pose_stride
+        self.node1, self.node2 = t(ps * pi, torch.int32), t(ps * pj, torch.int32)
+        self.meas, self.w = t(meas, torch.float64), t(1.0 / sig, torch.float64)
+        self.loss_kind = t(np.array([k for k, _ in self.losses], np.int32), torch.int32)
+        self.loss_k = t(np.array([k for _, k in self.losses], np.float64), torch.float64)
+        tn, ts, tp, tt = between_targets(ps * pi, ps * pj)
+        self.tgt_node, self.tgt_s, self.tgt_ptr, self.tgt_terms = (t(a, torch.int32) for a in (tn, ts, tp, tt))
+        p = _lib.ptr
+        self.c = _CBetween(n, ps * self.n_poses, ps, p(self.node1), p(self.node2), p(self.meas), p(self.w),
+                           p(self.loss_kind), p(self.loss_k), len(tn), p(self.tgt_node), p(self.tgt_s), p(self.tgt_ptr), p(self.tgt_terms))
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+
 @dataclass
 class LMParams:
     """gtsam.LevenbergMarquardtParams() defaults."""
@@ -145,10 +217,12 @@ def build_tiles_device(pk, band):
 
 class StereoBAProblem:
     """Packed, device-resident stereo BA problem (vus_ba_problem + vus_ba_tiles).  `loss`: robust noise model of the
-    stereo factors (robust_loss(): None = Gaussian, or e.g. ("cauchy", 2.0) with k in whitened units)."""
+    stereo factors (robust_loss(): None = Gaussian, or e.g. ("cauchy", 2.0) with k in whitened units).  `between_span`: the
+    widest pose distance of a BetweenFactorPose3 (BetweenFactors.span); the band in poses is the larger of it and the
+    landmark span, scaled by pose_stride, so the tiles, Sband and the band-solve mode all follow the wider of the two."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None,
-                 prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None):
+                 prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None, between_span=0):
         _lib.require_gpu()
         _lib.load()
         dev = torch.device(device)
@@ -162,7 +236,7 @@ class StereoBAProblem:
         else:
             pk = ba_pack.pack_observations(to_dev(obs_pose, torch.int64), to_dev(obs_point, torch.int64),
                                            to_dev(meas, torch.float64), n_poses, n_points)
-        st = {"band": band_of(pk)}
+        st = {"band": max(band_of(pk), int(between_span))}
         self.pk = pk
         self.device = dev
         self.n_poses, self.n_points, self.n_obs = int(n_poses), int(n_points), pk["n_obs"]
@@ -300,7 +374,7 @@ class BAMarginals:
 class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
 
-    def __init__(self, problem: StereoBAProblem):
+    def __init__(self, problem: StereoBAProblem, between: Optional[BetweenFactors] = None):
         self.P = problem
         dev, nP, nL, nO, B = problem.device, problem.n_poses, problem.n_points, problem.n_obs, problem.band
         nN = problem.n_nodes                       # camera-side nodes (= poses unless velocity nodes are interleaved)
@@ -319,10 +393,23 @@ class StereoBASolver:
         self.new_points = torch.empty((nL, 3), **f64)
         self.work = torch.empty((2 * (nL + 1) + 8,), **f64)
         # one 40-byte record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised
-        # error at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word
-        self._trial = torch.zeros((5,), **f64)
+        # error at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word; with between
+        # factors [5..7] their three errors in the same order, [8] spare
+        self._trial = torch.zeros((5 if between is None else 9,), **f64)
         self.scal = self._trial[:4]
         self.status = self._trial[4:].view(torch.int32)[:1]
+        self.B = between
+        if between is not None:
+            if between.pose_stride != problem.pose_stride or between.n_poses != nP:
+                raise ValueError("BetweenFactors built for another problem (pose_stride / n_poses differ)")
+            if between.span * problem.pose_stride > B:
+                raise ValueError(f"a between factor spans {between.span} poses, more than the problem's band of {B} nodes: "
+                                 "build the StereoBAProblem with between_span=BetweenFactors.span")
+            self.btw_scal = self._trial[5:8]
+            self.btw_lin = torch.empty((between.n, 120), **f64)
+            self.btw_err = torch.empty((1,), **f64)
+            self.btw_work = torch.empty((int(_lib.load().vus_between_work_doubles(between.addr())),), **f64)
+            _lib.call("vus_between_check", between.addr(), B, _lib.current_stream_ptr())
         # two-sided band solve (vus_ba_band_solve_split): worth it once the chain of panel steps is much longer than
         # the band; its workspace (pose-reversed copy of the lower half + the middle system) is allocated once
         self.band_rhs = 1
@@ -413,6 +500,40 @@ class StereoBASolver:
         fn, extra = self._loss_args("vus_ba_eval_step")
         _lib.call(fn, self._pp(), p(poses), p(points), p(self.dp), p(self.dl), p(self.new_poses),
                   p(self.new_points), p(self.scal[1:]), p(self.work), _lib.current_stream_ptr(), *extra)
+
+    # -- between factors (include/vus_between.h); every hook is a no-op without them ---------------------------------
+    def between_error(self, poses) -> float:
+        """Error (sum rho under a robust model) of the between factors at poses; 0.0 without them."""
+        if self.B is None:
+            return 0.0
+        _lib.call("vus_between_error", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.btw_err), _lib.ptr(self.btw_work),
+                  _lib.current_stream_ptr())
+        return float(self.btw_err[0].item())
+
+    def between_linearize(self, poses):
+        """btw_lin = the per-factor products, btw_scal[0] = their linear error at delta = 0."""
+        if self.B is not None:
+            _lib.call("vus_between_linearize", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.btw_lin), _lib.ptr(self.btw_scal),
+                      _lib.ptr(self.btw_work), _lib.current_stream_ptr())
+
+    def between_assemble(self):
+        """Sband += the between blocks, gs += their gradient: after schur(), before an inertial assemble."""
+        if self.B is not None:
+            _lib.call("vus_between_assemble", self.B.addr(), _lib.ptr(self.btw_lin), self.P.band, _lib.ptr(self.Sband),
+                      _lib.ptr(self.gs), _lib.current_stream_ptr())
+
+    def between_eval_step(self, poses):
+        """btw_scal[1] = linearised error at the step dp, btw_scal[2] = error at new_poses (after eval_step)."""
+        if self.B is not None:
+            _lib.call("vus_between_eval_step", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.dp), _lib.ptr(self.new_poses),
+                      _lib.ptr(self.btw_scal[1:]), _lib.ptr(self.btw_work), _lib.current_stream_ptr())
+
+    def _trial_errors(self, rec):
+        """[linearise error, linearised error at the step, new error] of the stereo factors, priors and between factors
+        from one trial record"""
+        if self.B is None:
+            return [float(x) for x in rec[:3]]
+        return [float(rec[k]) + float(rec[5 + k]) for k in range(3)]
 
     # -- marginal covariances (gtsam.Marginals) ---------------------------------------------------------------------
     def _check_points(self):
@@ -530,30 +651,35 @@ class StereoBASolver:
         poses, points = values
         self.linearize(poses, points)
         self._check_points()
+        self.between_linearize(poses)
 
     def _assemble_zero(self):
         self.schur(0.0)
+        self.between_assemble()
 
     # -- Levenberg-Marquardt ----------------------------------------------------------------------
     # The stages of one LM iteration over a tuple of state tensors; the inertial solvers extend them.
     _NEW_STATE = ("new_poses", "new_points")      # the buffers a trial writes, one per state tensor
 
     def _lm_error(self, state) -> float:
-        return self.error(*state)
+        return self.error(*state) + self.between_error(state[0])
 
     def _lm_linearize(self, state):
         self.linearize(*state)
+        self.between_linearize(state[0])
 
     def _lm_solve(self, lam):
         self.schur(lam)
+        self.between_assemble()
         self.band_solve()
         self.backsub()
 
     def _lm_eval(self, state):
         """Evaluate the trial step; (status, [linearised error at 0, at the step, new error]) from ONE blocking read."""
         self.eval_step(*state)
+        self.between_eval_step(state[0])
         rec = self._trial.cpu()
-        return int(rec[4:].view(torch.int32)[0]), [float(x) for x in rec[:3]]
+        return int(rec[4:].view(torch.int32)[0]), self._trial_errors(rec)
 
     def _lm_swap(self, state):
         """Accept the trial: its buffers become the state, the old state tensors the next trial's buffers."""
@@ -752,10 +878,10 @@ class _InertialBASolver(StereoBASolver):
     _ABI = None
     _NEW_STATE = ("new_poses", "new_vels", "new_bias", "new_points")     # state = (poses, vels, bias, points)
 
-    def __init__(self, problem: StereoBAProblem, nav, bias_rows):
+    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None):
         if problem.pose_stride != self.POSE_STRIDE:
             raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
-        super().__init__(problem)
+        super().__init__(problem, between)
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
         f64 = dict(dtype=torch.float64, device=dev)
@@ -777,22 +903,26 @@ class _InertialBASolver(StereoBASolver):
         self.linearize(poses, points)
         self._check_points()
         self.nav_linearize(poses, vels, bias)
+        self.between_linearize(poses)
 
     def _assemble_zero(self):
         self.schur(0.0)
+        self.between_assemble()             # before nav_assemble: vus_nav_assemble copies -gs into its right-hand side
         self.nav_assemble(0.0)
 
     def _lm_error(self, state):
         poses, vels, bias, points = state
-        return self.error(poses, points) + self.nav_error(poses, vels, bias)
+        return self.error(poses, points) + self.nav_error(poses, vels, bias) + self.between_error(poses)
 
     def _lm_linearize(self, state):
         poses, vels, bias, points = state
         self.linearize(poses, points)
         self.nav_linearize(poses, vels, bias)
+        self.between_linearize(poses)
 
     def _lm_solve(self, lam):
         self.schur(lam)
+        self.between_assemble()
         self.nav_assemble(lam)
         self.nav_solve(lam)
         self.backsub()
@@ -801,8 +931,10 @@ class _InertialBASolver(StereoBASolver):
         poses, vels, bias, points = state
         self.eval_step(poses, points)
         self.nav_eval_step(poses, vels, bias)
-        rec, nsc = self._trial.cpu(), self.nav_scal.cpu()         # stereo scalars + status, then the inertial scalars
-        return int(rec[4:].view(torch.int32)[0]), [float(rec[k]) + float(nsc[k]) for k in range(3)]
+        self.between_eval_step(poses)
+        rec, nsc = self._trial.cpu(), self.nav_scal.cpu()         # stereo (+ between) scalars + status, then the inertial scalars
+        sc = self._trial_errors(rec)
+        return int(rec[4:].view(torch.int32)[0]), [sc[k] + float(nsc[k]) for k in range(3)]
 
     def optimize(self, poses, vels, bias, points, params: Optional[LMParams] = None):
         """Returns (poses, vels, bias, points, LMReport); inputs untouched."""
@@ -819,8 +951,8 @@ class NavBASolver(_InertialBASolver):
     7-right-hand-side band solve."""
     POSE_STRIDE, SDIAG, _ABI = 2, 4, "vus_nav"
 
-    def __init__(self, problem: StereoBAProblem, nav: NavFactors):
-        super().__init__(problem, nav, None)
+    def __init__(self, problem: StereoBAProblem, nav: NavFactors, between: Optional[BetweenFactors] = None):
+        super().__init__(problem, nav, None, between)
         self.band_rhs = 7
         self._alloc_band_work()
         nN = problem.n_nodes
@@ -895,8 +1027,8 @@ class NavBiasBASolver(_InertialBASolver):
     common inertial loop, with `bias` the [n_poses, 6] per-keyframe biases."""
     POSE_STRIDE, SDIAG, _ABI = 3, 5, "vus_navb"
 
-    def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors):
-        super().__init__(problem, nav, problem.n_poses)
+    def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors, between: Optional[BetweenFactors] = None):
+        super().__init__(problem, nav, problem.n_poses, between)
 
     def nav_linearize(self, poses, vels, biases):
         p = _lib.ptr

@@ -38,6 +38,7 @@
 #include <vector>
 #include "vus_common.h"
 #include "band_index.h"
+#include "se3_device.h"
 
 namespace {
 
@@ -86,114 +87,6 @@ int device_cu_count() {
   std::lock_guard<std::mutex> lock(mu);
   if (!cached[dev] && hipDeviceGetAttribute(&cached[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cached[dev] = 0;
   return cached[dev];
-}
-
-constexpr double kEps = 2.220446049250313e-16;
-constexpr double kPi = 3.14159265358979323846;
-
-// ---------------------------------------------------------------------------------------------
-// Lie-group helpers (gtsam Pose3 / Rot3 conventions; mirrored independently by the CPU oracle)
-__device__ void so3_expmap(const double* w, double* R) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  const double Wx[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-  if (th2 <= kEps) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = Wx[i] + (i % 4 == 0 ? 1.0 : 0.0);
-    return;
-  }
-  const double th = sqrt(th2);
-  const double s = sin(th) / th;
-  const double sh = sin(0.5 * th);
-  const double c = 2.0 * sh * sh / th2;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) {
-      double ww = 0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ww += Wx[3 * r + k] * Wx[3 * k + cc];
-      R[3 * r + cc] = (r == cc ? 1.0 : 0.0) + s * Wx[3 * r + cc] + c * ww;
-    }
-}
-
-__device__ void so3_logmap(const double* R, double* w) {
-  const double tr = R[0] + R[4] + R[8];
-  if (tr + 1.0 < 1e-10) {
-    if (fabs(R[8] + 1.0) > 1e-5) {
-      double k = kPi / sqrt(2.0 + 2.0 * R[8]);
-      w[0] = k * R[2]; w[1] = k * R[5]; w[2] = k * (1.0 + R[8]);
-    } else if (fabs(R[4] + 1.0) > 1e-5) {
-      double k = kPi / sqrt(2.0 + 2.0 * R[4]);
-      w[0] = k * R[1]; w[1] = k * (1.0 + R[4]); w[2] = k * R[7];
-    } else {
-      double k = kPi / sqrt(2.0 + 2.0 * R[0]);
-      w[0] = k * (1.0 + R[0]); w[1] = k * R[3]; w[2] = k * R[6];
-    }
-    return;
-  }
-  double mag;
-  const double tr3 = tr - 3.0;
-  if (tr3 < -1e-7) {
-    double th = acos((tr - 1.0) / 2.0);
-    mag = th / (2.0 * sin(th));
-  } else {
-    mag = 0.5 - tr3 / 12.0;
-  }
-  w[0] = mag * (R[7] - R[5]);
-  w[1] = mag * (R[2] - R[6]);
-  w[2] = mag * (R[3] - R[1]);
-}
-
-// out = T * Exp(xi)
-__device__ void pose_retract(const double* T, const double* xi, double* out) {
-  double Re[9], te[3];
-  so3_expmap(xi, Re);
-  const double* w = xi;
-  const double* v = xi + 3;
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  if (th2 > kEps) {
-    double wv = w[0] * v[0] + w[1] * v[1] + w[2] * v[2];
-    double c[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double Rc = Re[3 * r] * c[0] + Re[3 * r + 1] * c[1] + Re[3 * r + 2] * c[2];
-      te[r] = (c[r] - Rc + w[r] * wv) / th2;
-    }
-  } else {
-    te[0] = v[0]; te[1] = v[1]; te[2] = v[2];
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      out[3 * r + c] = T[3 * r] * Re[c] + T[3 * r + 1] * Re[3 + c] + T[3 * r + 2] * Re[6 + c];
-    out[9 + r] = T[9 + r] + (T[3 * r] * te[0] + T[3 * r + 1] * te[1] + T[3 * r + 2] * te[2]);
-  }
-}
-
-// xi = Logmap(T^-1 * T2)
-__device__ void pose_local(const double* T, const double* T2, double* xi) {
-  double R[9], t[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = T[r] * T2[c] + T[3 + r] * T2[3 + c] + T[6 + r] * T2[6 + c];
-    t[r] = T[r] * (T2[9] - T[9]) + T[3 + r] * (T2[10] - T[10]) + T[6 + r] * (T2[11] - T[11]);
-  }
-  double w[3];
-  so3_logmap(R, w);
-  const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  xi[0] = w[0]; xi[1] = w[1]; xi[2] = w[2];
-  if (th < 1e-10) {
-    xi[3] = t[0]; xi[4] = t[1]; xi[5] = t[2];
-    return;
-  }
-  const double k[3] = {w[0] / th, w[1] / th, w[2] / th};
-  const double WT[3] = {k[1] * t[2] - k[2] * t[1], k[2] * t[0] - k[0] * t[2], k[0] * t[1] - k[1] * t[0]};
-  const double WWT[3] = {k[1] * WT[2] - k[2] * WT[1], k[2] * WT[0] - k[0] * WT[2], k[0] * WT[1] - k[1] * WT[0]};
-  const double tn = tan(0.5 * th);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) xi[3 + r] = t[r] - (0.5 * th) * WT[r] + (1.0 - th / (2.0 * tn)) * WWT[r];
 }
 
 struct Calib {
@@ -267,36 +160,6 @@ __device__ __forceinline__ double sym3(const double* v, int r, int c) {
   // upper-triangle storage xx,xy,xz,yy,yz,zz
   const int lo = r < c ? r : c, hi = r < c ? c : r;
   return v[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
-}
-
-// Robust noise model (include/vus_robust.h): weight w and loss rho of a stereo factor from its squared whitened
-// residual norm d2 = d^2.  Every kernel that reweights a factor calls this on the same d2 expression, so W / V (lin_points),
-// Hpp / gp (lin_poses) and the linear error (eval_points) describe one weighted system.
-template <int LOSS>
-__device__ __forceinline__ void robust_weight(double d2, double k, double& w, double& rho) {
-  const double k2 = k * k;
-  if (LOSS == VUS_LOSS_HUBER) {
-    const double d = sqrt(d2);
-    w = d <= k ? 1.0 : k / d;
-    rho = d <= k ? 0.5 * d2 : k * d - 0.5 * k2;
-  } else if (LOSS == VUS_LOSS_CAUCHY) {
-    w = k2 / (k2 + d2);
-    rho = 0.5 * k2 * log1p(d2 / k2);
-  } else if (LOSS == VUS_LOSS_TUKEY) {
-    const double t = 1.0 - d2 / k2;
-    w = d2 <= k2 ? t * t : 0.0;
-    rho = d2 <= k2 ? (k2 / 6.0) * (1.0 - t * t * t) : k2 / 6.0;
-  } else if (LOSS == VUS_LOSS_GEMAN_MCCLURE) {
-    const double s = k2 + d2;
-    w = (k2 * k2) / (s * s);
-    rho = 0.5 * k2 * d2 / s;
-  } else if (LOSS == VUS_LOSS_WELSCH) {
-    w = exp(-d2 / k2);
-    rho = -0.5 * k2 * expm1(-d2 / k2);
-  } else {
-    w = 1.0;
-    rho = 0.5 * d2;
-  }
 }
 
 // IRLS (Block reweighting): scale a factor's whitened residual and Jacobian rows by sqrt(w), w from its own residual

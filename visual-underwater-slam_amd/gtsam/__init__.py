@@ -31,7 +31,7 @@ from .symbol_shorthand import symbol, symbolChr, symbolIndex  # noqa: F401
 __all__ = [
     "Point3", "Rot3", "Pose3", "Cal3_S2Stereo", "Cal3_S2", "StereoPoint2", "noiseModel", "imuBias",
     "GenericStereoFactor3D", "PriorFactorPose3", "PriorFactorVector", "PriorFactorPoint3",
-    "PriorFactorConstantBias", "BetweenFactorConstantBias", "ImuFactor", "CustomFactor", "DvlVelocityFactor",
+    "PriorFactorConstantBias", "BetweenFactorConstantBias", "BetweenFactorPose3", "ImuFactor", "CustomFactor", "DvlVelocityFactor",
     "PreintegrationParams", "PreintegratedImuMeasurements", "NavState", "ISAM2", "ConstantTwistScenario",
     "PinholeCameraCal3_S2",
     "NonlinearFactorGraph", "Values", "LevenbergMarquardtParams", "LevenbergMarquardtOptimizer",
@@ -178,6 +178,53 @@ class Pose3:
 
     def equals(self, other, tol=1e-9):
         return bool(np.allclose(self._R, other._R, atol=tol) and np.allclose(self._t, other._t, atol=tol))
+
+    # tangent space: (omega, v), retract T Exp(xi), local Log(T^-1 T2) -- the conventions of the GPU kernels
+    @staticmethod
+    def Expmap(xi):
+        xi = np.asarray(xi, dtype=float).reshape(6)
+        w, v = xi[:3], xi[3:]
+        R = Rot3.Expmap(w)._R
+        th2 = float(w @ w)
+        if th2 > np.finfo(float).eps:
+            c = np.cross(w, v)
+            t = (c - R @ c + w * float(w @ v)) / th2
+        else:
+            t = v.copy()
+        return Pose3(Rot3(R), t)
+
+    @staticmethod
+    def Logmap(T):
+        R, t = T._R, T._t
+        tr = float(np.trace(R))
+        if tr + 1.0 < 1e-10:                      # rotation by pi
+            if abs(R[2, 2] + 1.0) > 1e-5:
+                w = math.pi / math.sqrt(2.0 + 2.0 * R[2, 2]) * np.array([R[0, 2], R[1, 2], 1.0 + R[2, 2]])
+            elif abs(R[1, 1] + 1.0) > 1e-5:
+                w = math.pi / math.sqrt(2.0 + 2.0 * R[1, 1]) * np.array([R[0, 1], 1.0 + R[1, 1], R[2, 1]])
+            else:
+                w = math.pi / math.sqrt(2.0 + 2.0 * R[0, 0]) * np.array([1.0 + R[0, 0], R[1, 0], R[2, 0]])
+        else:
+            tr3 = tr - 3.0
+            if tr3 < -1e-7:
+                th = math.acos((tr - 1.0) / 2.0)
+                mag = th / (2.0 * math.sin(th))
+            else:
+                mag = 0.5 - tr3 / 12.0
+            w = mag * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+        th = float(np.linalg.norm(w))
+        if th < 1e-10:
+            return np.concatenate([w, t])
+        k = w / th
+        WT = np.cross(k, t)
+        v = t - (0.5 * th) * WT + (1.0 - th / (2.0 * math.tan(0.5 * th))) * np.cross(k, WT)
+        return np.concatenate([w, v])
+
+    def localCoordinates(self, other):
+        return Pose3.Logmap(self.between(other))
+
+    def retract(self, xi):
+        return self.compose(Pose3.Expmap(xi))
 
     def flat12(self):
         """Row-major R followed by t: the device layout of include/vus.h."""
@@ -551,6 +598,28 @@ class BetweenFactorConstantBias(_Factor):
     def __init__(self, key1, key2, measured, model):
         super().__init__([key1, key2])
         self._measured, self._model = measured, model
+
+
+class BetweenFactorPose3(_Factor):
+    """gtsam.BetweenFactorPose3(key1, key2, measured, model): error 0.5 |Log(measured^-1 (X1^-1 X2))|^2 in the whitening of
+    a 6-dimensional Diagonal / Isotropic / Unit model, optionally wrapped in noiseModel.Robust (include/vus_between.h).
+    Odometry (consecutive keys) and loop closures (any two keyframes) alike; the two keys must differ."""
+
+    def __init__(self, key1, key2, measured: Pose3, model: _NoiseModel):
+        super().__init__([key1, key2])
+        if model.dim() != 6:
+            raise RuntimeError("BetweenFactorPose3 needs a 6-dimensional noise model")
+        if self._keys[0] == self._keys[1]:
+            raise ValueError(f"BetweenFactorPose3: both keys are {symbol_shorthand.key_string(self._keys[0])}")
+        if not isinstance(measured, Pose3):
+            raise RuntimeError("BetweenFactorPose3: the measurement must be a Pose3")
+        self._measured, self._model = Pose3(measured), model
+
+    def measured(self):
+        return Pose3(self._measured)
+
+    def noiseModel(self):
+        return self._model
 
 
 class PreintegrationParams:

@@ -143,8 +143,9 @@ def _pack_graph(graph, values, device=None):
     is given (2 M observations: ~3 ms on the GPU against ~0.3 s in numpy), else in numpy (CPU tests)."""
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
                    ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias, PriorFactorConstantBias,
-                   BetweenFactorConstantBias)
+                   BetweenFactorConstantBias, BetweenFactorPose3)
     meas, pkeys, lkeys = [], [], []
+    between_f = []
     imu_f, dvl_f, bias_f = [], [], []
     from . import _Robust
     model_sigma, calib, loss = None, None, None
@@ -175,6 +176,8 @@ def _pack_graph(graph, values, device=None):
             single_m.append(f._measured._m); single_p.append(f._keys[0]); single_l.append(f._keys[1])
         elif isinstance(f, PriorFactorPose3):
             prior_pose.append(f)
+        elif isinstance(f, BetweenFactorPose3):
+            between_f.append(f)
         elif isinstance(f, PriorFactorVector):
             prior_vec.append(f)
         elif isinstance(f, ImuFactor):
@@ -258,6 +261,7 @@ def _pack_graph(graph, values, device=None):
         if j >= len(pose_keys) or pose_keys[j] != k:
             raise RuntimeError(f"Attempting to at the key \"{_sym.key_string(k)}\", which does not exist in the Values.")
         pr_idx.append(j); pr_T.append(f._prior.flat12()); pr_s.append(f._model.sigmas())
+    between = _pack_between(pose_keys, between_f) if between_f else None
     nav = None
     if imu_f or dvl_f or bias_f:
         nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f)
@@ -276,7 +280,27 @@ def _pack_graph(graph, values, device=None):
                 points=points, sigma=model_sigma if model_sigma is not None else 1.0, loss=loss,
                 K=calib.vector6() if calib is not None else np.array([1.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
-                prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav)
+                prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between)
+
+
+def _pack_between(pose_keys, between_f):
+    """BetweenFactorPose3 -> (i, j, meas [n, 12], sigmas [n, 6], losses [n], span): pose indices into the sorted Pose3 keys,
+    the measured poses, the diagonal sigmas, each factor's (VUS_LOSS_* kind, k) and the widest pose distance."""
+    from . import _Robust
+    bi, bj, bm, bs, bl = [], [], [], [], []
+    for f in between_f:
+        idx = []
+        for k in f._keys:
+            j = int(np.searchsorted(pose_keys, k))
+            if j >= len(pose_keys) or pose_keys[j] != k:
+                raise RuntimeError(f"Attempting to at the key \"{_sym.key_string(k)}\", which does not exist in the Values.")
+            idx.append(j)
+        rob = f._model.robust() if isinstance(f._model, _Robust) else None
+        bi.append(idx[0]); bj.append(idx[1]); bm.append(f._measured.flat12()); bs.append(f._model.sigmas())
+        bl.append((rob.kind, rob.k) if rob is not None else (0, 0.0))
+    bi, bj = np.asarray(bi, np.int32), np.asarray(bj, np.int32)
+    return dict(i=bi, j=bj, meas=np.asarray(bm, float).reshape(-1, 12), sigmas=np.asarray(bs, float).reshape(-1, 6),
+                losses=bl, span=int(np.abs(bi.astype(np.int64) - bj).max()))
 
 
 def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=()):
@@ -397,21 +421,27 @@ def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
 
 
 def _build_solver(pg, device="cuda:0"):
-    from ..ba import StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors
+    from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
+                      BetweenFactors)
     nav = pg.get("nav")
+    btw = pg.get("between")
     walk = bool(nav) and nav.get("per_keyframe", False)
-    prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], len(pg["pose_keys"]), len(pg["lm_keys"]),
+    stride = (3 if walk else 2) if nav else 1
+    n_poses = len(pg["pose_keys"])
+    prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
-                           prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=(3 if walk else 2) if nav else 1,
-                           loss=pg.get("loss"))
+                           prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
+                           loss=pg.get("loss"), between_span=btw["span"] if btw else 0)
+    bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
+                        loss=list(btw["losses"]), device=device) if btw else None
     if walk:
         nf = NavBiasFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], bbetween=nav["bbetween"],
                             bprior=nav["bprior"], device=device)
-        return prob, NavBiasBASolver(prob, nf)
+        return prob, NavBiasBASolver(prob, nf, bf)
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
-        return prob, NavBASolver(prob, nf)
-    return prob, StereoBASolver(prob)
+        return prob, NavBASolver(prob, nf, bf)
+    return prob, StereoBASolver(prob, bf)
 
 
 def graph_error(graph, values) -> float:
@@ -421,7 +451,7 @@ def graph_error(graph, values) -> float:
     prob, sv = _build_solver(pg)
     dev = prob.device
     poses = torch.from_numpy(pg["poses"]).to(dev)
-    e = sv.error(poses, torch.from_numpy(pg["points"]).to(dev))
+    e = sv.error(poses, torch.from_numpy(pg["points"]).to(dev)) + sv.between_error(poses)
     if pg.get("nav"):
         e += sv.nav_error(poses, torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev))
     return e + pg["aux"].error()
