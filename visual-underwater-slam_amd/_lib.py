@@ -71,6 +71,9 @@ SIGNATURES = {
     "vus_ba_point_check": [_P, c_int, _P, _P],
     "vus_ba_point_covariance": [_P, _P, _P, _P, _P, c_int, _P, _P],
     "vus_nav_border_covariance": [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    # block-tiled image planes of the single-level front-end (include/vus_tiled.h)
+    "vus_fast_detect_adaptive_tiled": [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P],
+    "vus_orient_rbrief_tiled": [_P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P],
     # BetweenFactor<Pose3> (include/vus_between.h)
     "vus_between_check": [_P, c_int, _P],
     "vus_between_linearize": [_P, _P, _P, _P, _P, _P],

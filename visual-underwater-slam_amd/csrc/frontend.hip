@@ -25,8 +25,10 @@
 //    choice, and the descriptor words come straight out of __ballot (lane = test bit);
 //  * hamming_match keeps the train descriptors in LDS (broadcast reads) and one query per lane.
 #include "vus_common.h"
+#include <type_traits>
 #define VUS_TABLE_QUAL __device__ constexpr
 #include "../../include/vus_orb_tables.h"
+#include "../../include/vus_tiled.h"
 
 namespace {
 
@@ -236,6 +238,8 @@ typedef int v4i32_t __attribute__((ext_vector_type(4)));
 
 // The tile's eight 16-column blocks go to the waves j_first, j_first + j_step, ... (all four waves: tid >> 6, 4; the
 // late form below: three waves, the fourth waits for the tile's global atomic meanwhile).
+// TILED: blur_out is block-tiled (include/vus_tiled.h; W % 16 == 0): a lane's 4 pixels lie in one 16-byte block row.
+template <bool TILED = false>
 __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* __restrict__ blur_out, int n, int H, int W,
                                                int x0, int y0, int tid, int j_first, int j_step) {
   static_assert(IMG_ROWS == 32 && TW % 16 == 0 && (IMG_DW * 4) % 8 == 0, "blur_tile_mfma: K = the 32 staged rows");
@@ -282,7 +286,9 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
 #ifdef VUS_BLUR_EXP_NOSTORE   // timing experiment: everything but the stores (a value nobody produces keeps the result live)
       if (v != 0x12345678u) continue;
 #endif
-      if (ly < TH && gy < H) {
+      if (TILED) {
+        if (ly < TH && gy < H && gx < W) __builtin_memcpy(blur_out + (size_t)n * H * W + vus_tiled_offset(gy, gx, W), &v, 4);
+      } else if (ly < TH && gy < H) {
         uint8_t* o = blur_out + ((size_t)n * H + gy) * W + gx;
         if (gx + 3 < W) {
           __builtin_memcpy(o, &v, 4);
@@ -306,12 +312,14 @@ extern "C" int vus_debug_fast_counters(unsigned long long* out, int reset) {
 #endif
 // One 128 x 24 tile of image n.  HIST (with DETECT): the non-max-suppression survivors of the tile are not listed but
 // counted by score into hist[256 n + score] (vus_fast_threshold_estimate's sample).
-template <bool WRITE_SCORE, bool DETECT, bool BLUR, bool HIST = false, bool REGIONS = false>
+// TILED (the late-smoothing detection launch only): blur_out is block-tiled (include/vus_tiled.h) and the tile's image
+// goes to raw_out, block-tiled as well -- from the staged tile, by the wave that waits for the candidate atomic.
+template <bool WRITE_SCORE, bool DETECT, bool BLUR, bool HIST = false, bool REGIONS = false, bool TILED = false>
 __device__ __forceinline__ void fast_tile_body(
     const uint8_t* __restrict__ img, int H, int W, int pitch, int thr, int border,
     uint8_t* __restrict__ score_out, uint8_t* __restrict__ blur_out,
     uint32_t* __restrict__ cand_keys, int cand_cap, int* __restrict__ cand_count, int* __restrict__ hist,
-    int n, int tile, int tiles_x) {
+    int n, int tile, int tiles_x, uint8_t* __restrict__ raw_out = nullptr) {
   __shared__ __attribute__((aligned(8))) uint32_t s_img[IMG_ROWS * IMG_DW];
   __shared__ uint32_t s_score[(WRITE_SCORE || DETECT) ? SC_ROWS * SC_DW : 1];
   // the strip pre-test's tables (s_mm, s_strip) share the horizontal-blur buffer of the VALU smoothing (not written
@@ -335,6 +343,7 @@ __device__ __forceinline__ void fast_tile_body(
   static_assert(IMG_ROWS * IMG_DW >= TW * TH / 4, "candidate list must fit in the image tile");
   static_assert(!LATE_BLUR || AUX_DW >= TW * TH / 4, "candidate list must fit in the strip tables' buffer");
   uint32_t* const s_keys = LATE_BLUR ? s_h : s_img;
+  static_assert(!TILED || LATE_BLUR, "the block-tiled planes are written by the late-smoothing detection launch");
 
   const int tid = threadIdx.x;
   const int x0 = (tile % tiles_x) * TW, y0 = (tile / tiles_x) * TH;
@@ -706,8 +715,26 @@ __device__ __forceinline__ void fast_tile_body(
       uint32_t* const list = cand_keys + (size_t)n * cand_cap + (REGIONS ? (size_t)(tile & (VUS_CAND_REGIONS - 1)) * rcap : 0);
       int* const counter = REGIONS ? reinterpret_cast<int*>(list) : &cand_count[n];
       if (LATE_BLUR) {
-        if (tid == NTHREADS - 64 && cnt > 0) s_base = atomicAdd(counter, cnt);
-        if (tid < NTHREADS - 64) blur_tile_mfma(s_img, blur_out, n, H, W, x0, y0, tid, tid >> 6, NTHREADS / 64 - 1);
+        const bool leader = tid == NTHREADS - 64 && cnt > 0;
+        int base = 0;
+        if (leader) base = atomicAdd(counter, cnt);
+        if (TILED && tid >= NTHREADS - 64) {
+          // the staged tile's interior, block-tiled: TH x TW / 16 rows of 16 bytes (whole blocks: x0 % 16 == 0,
+          // y0 % 8 == 0, W % 16 == 0, H % 8 == 0), three per lane, while the atomic is out
+          const uint8_t* s8 = reinterpret_cast<const uint8_t*>(s_img);
+          uint8_t* const ro = raw_out + (size_t)n * H * W;
+          for (int i = tid - (NTHREADS - 64); i < TH * (TW / 16); i += 64) {
+            const int ly = i / (TW / 16), cb = i - ly * (TW / 16);
+            const int gy = y0 + ly, gx = x0 + 16 * cb;
+            if (gy < H && gx < W) {
+              const uint8_t* sp = s8 + (ly + 4) * (4 * IMG_DW) + 8 + 16 * cb;   // 8-byte aligned
+              const uint2 a = *reinterpret_cast<const uint2*>(sp), b = *reinterpret_cast<const uint2*>(sp + 8);
+              *reinterpret_cast<uint4*>(ro + vus_tiled_offset(gy, gx, W)) = make_uint4(a.x, a.y, b.x, b.y);
+            }
+          }
+        }
+        if (leader) s_base = base;
+        if (tid < NTHREADS - 64) blur_tile_mfma<TILED>(s_img, blur_out, n, H, W, x0, y0, tid, tid >> 6, NTHREADS / 64 - 1);
       } else {
         if (tid == 0 && cnt > 0) s_base = atomicAdd(counter, cnt);
       }
@@ -736,6 +763,20 @@ __global__ __launch_bounds__(NTHREADS, VUS_FAST_WPE) void fast_tile_kernel(
   const int tile = slot - (slot / tiles_per_img) * tiles_per_img;
   fast_tile_body<WRITE_SCORE, DETECT, BLUR, false, REGIONS>(img, H, W, pitch, thr_img ? thr_img[n] : thr, border, score_out, blur_out,
                                                             cand_keys, cand_cap, cand_count, nullptr, n, tile, tiles_x);
+}
+
+// fast_tile_kernel<false, true, true, REGIONS> with both planes block-tiled (vus_fast_detect_adaptive_tiled)
+template <bool REGIONS>
+__global__ __launch_bounds__(NTHREADS, VUS_FAST_WPE) void fast_tile_tiled_kernel(
+    const uint8_t* __restrict__ img, int H, int W, int pitch, const int* __restrict__ thr_img, int border,
+    uint8_t* __restrict__ blur_out, uint8_t* __restrict__ raw_out, uint32_t* __restrict__ cand_keys, int cand_cap,
+    int* __restrict__ cand_count, int n_img, int tiles_x, int tiles_per_img) {
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int n = (slot / tiles_per_img) * 8 + xcd;
+  if (n >= n_img) return;
+  const int tile = slot - (slot / tiles_per_img) * tiles_per_img;
+  fast_tile_body<false, true, true, false, REGIONS, true>(img, H, W, pitch, thr_img[n], border, nullptr, blur_out, cand_keys,
+                                                          cand_cap, cand_count, nullptr, n, tile, tiles_x, raw_out);
 }
 
 // The regions of fast_tile_kernel<.., REGIONS>: counters zeroed before the launch ...
@@ -1043,6 +1084,70 @@ struct PatchRegs {
   }
 };
 
+// The same patch from a block-tiled plane (include/vus_tiled.h; W % 16 == 0, H % 8 == 0).  The patch starts at the
+// 8-byte boundary below x - RADIUS, so a lane's dwordx2 never leaves a 16-byte block row.  Pixel (y0 + r, xa + 8 c) of
+// vector (r, c) sits at
+//   tiled(y0 & ~7, xa & ~15)  +  16 (y0 & 7) + 16 r + f(q)  +  (p >> 3) (8 W - 128),   p = (y0 & 7) + r,  q = (xa & 8) + 8 c,
+//   f(q) = 128 (q >> 4) + (q & 8)
+// -- the first two terms wave-uniform, 16 r + f(q) a per-lane constant for each of the two values of xa & 8: four
+// vector instructions per vector (add, shift, select, multiply-add) on top of the plain form's load.
+template <int RADIUS, int DW>
+struct TiledPatchRegs {
+  static_assert(DW % 2 == 0, "row width must be a multiple of the vector width");
+  typedef typename PatchVec<2>::type vec_t;
+  static constexpr int ROWS = 2 * RADIUS + 1;
+  static constexpr int HW = DW / 2;             // vectors per row
+  static constexpr int N = ROWS * HW;
+  static constexpr int ITERS = (N + 63) / 64;
+  vec_t v[ITERS];
+  uint32_t row[ITERS];            // patch row of this lane's vectors
+  uint32_t off0[ITERS], off8[ITERS];   // 16 r + f(q) for xa & 8 == 0 / 8
+
+  __device__ __forceinline__ void init(int lane) {
+#pragma unroll
+    for (int u = 0; u < ITERS; ++u) {
+      const int t = min(lane + 64 * u, N - 1);
+      const uint32_t r = (uint32_t)(t / HW), q0 = 8u * (uint32_t)(t % HW), q8 = q0 + 8u;
+      row[u] = r;
+      off0[u] = 16u * r + 128u * (q0 >> 4) + (q0 & 8u);
+      off8[u] = 16u * r + 128u * (q8 >> 4) + (q8 & 8u);
+    }
+  }
+  __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int y, int x, int lane) {
+    const int xa = (x - RADIUS) & ~7, y0 = y - RADIUS;
+    const bool inside = y0 >= 0 && y + RADIUS < H && xa >= 0 && xa + 4 * DW <= W;
+    if (inside) {   // wave-uniform
+      const uint8_t* base = src + vus_tiled_offset(y0 & ~7, xa & ~15, W) + 16 * (y0 & 7);
+      const uint32_t ys = (uint32_t)(y0 & 7), ystep = 8u * (uint32_t)W - 128u;
+      const bool x8 = (xa & 8) != 0;
+#pragma unroll
+      for (int u = 0; u < ITERS; ++u) {
+        const uint32_t off = ((ys + row[u]) >> 3) * ystep + (x8 ? off8[u] : off0[u]);
+        v[u] = *reinterpret_cast<const vec_t*>(base + (size_t)off);
+      }
+    } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
+#pragma unroll
+      for (int u = 0; u < ITERS; ++u) {
+        const int t = min(lane + 64 * u, N - 1);
+        const int r = t / HW, c = t - r * HW;
+        const int gy = clampi(y0 + r, 0, H - 1), gx = xa + 8 * c;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          uint32_t w = 0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) w |= (uint32_t)src[vus_tiled_offset(gy, clampi(gx + 4 * k + b, 0, W - 1), W)] << (8 * b);
+          v[u][k] = w;
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void store(uint32_t* __restrict__ dst, int lane) const {
+#pragma unroll
+    for (int u = 0; u < ITERS; ++u)
+      if (lane + 64 * u < N) *reinterpret_cast<uint2*>(dst + 2 * (lane + 64 * u)) = make_uint2(v[u][0], v[u][1]);
+  }
+};
+
 // Cross-lane helpers of orient_rbrief (round 4, second pass).  A wave works on EIGHT keypoints at once; the per-lane
 // partial sums of their centroid moments (16 values) are folded with a reduce-scatter instead of 16 full wave
 // reductions: v_permlane32_swap / v_permlane16_swap (gfx950) exchange half-waves / odd-even rows of TWO registers in one
@@ -1098,17 +1203,17 @@ __device__ __forceinline__ uint32_t writelane_u32(uint32_t reg, uint32_t value, 
 struct RotOffTable {
   uint32_t v[VUS_N_ANGLE_BINS * 64 * 4];
 };
-constexpr RotOffTable make_rot_off_table() {
+constexpr RotOffTable make_rot_off_table(int row_bytes) {
   RotOffTable r{};
   for (int e = 0; e < VUS_N_ANGLE_BINS * 256; ++e) {
     const int bin = e / 256, test = e - 256 * bin, w = test >> 6, lane = test & 63;
-    const int oa = VUS_RBRIEF_ROT[4 * e + 1] * (4 * BR_DW) + VUS_RBRIEF_ROT[4 * e];
-    const int ob = VUS_RBRIEF_ROT[4 * e + 3] * (4 * BR_DW) + VUS_RBRIEF_ROT[4 * e + 2];
+    const int oa = VUS_RBRIEF_ROT[4 * e + 1] * row_bytes + VUS_RBRIEF_ROT[4 * e];
+    const int ob = VUS_RBRIEF_ROT[4 * e + 3] * row_bytes + VUS_RBRIEF_ROT[4 * e + 2];
     r.v[(bin * 64 + lane) * 4 + w] = ((uint32_t)oa & 0xFFFFu) | ((uint32_t)ob << 16);
   }
   return r;
 }
-__device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table = make_rot_off_table();
+__device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table = make_rot_off_table(4 * BR_DW);
 
 #ifndef VUS_OR_WPE
 #define VUS_OR_WPE 4
@@ -1121,16 +1226,35 @@ static_assert(OR_VW == 2 && OR_KP_PER_WAVE == 8, "orient_rbrief_kernel is writte
 constexpr int OR_NV = OR_ROWS * (OR_DW / OR_VW);   // 155 dwordx2 vectors of a centroid patch
 constexpr int OR_WT = 192;                         // weight entries per byte alignment: one per vector, padded to 3 x 64 lanes
 
+// Patch geometry of orient_rbrief_kernel per plane layout.  Row-major planes: patch rows start on the dword boundary
+// below x - radius (4 alignments).  Block-tiled planes (TiledPatchRegs): on the 8-byte boundary below it (8 alignments),
+// so the descriptor patch needs 44 of 48 bytes (12 dwords) per row; the centroid patch's 38 still fit its 40.
+template <bool TILED> struct OrGeom {
+  static constexpr int ALIGN = 4, OR_DW = ::OR_DW, BR_DW = ::BR_DW;
+  typedef PatchRegs<OR_R, OR_DW, OR_VW, false> Disc;
+  typedef PatchRegs<BR_R, BR_DW, OR_VW, false> Brief;
+};
+template <> struct OrGeom<true> {
+  static constexpr int ALIGN = 8, OR_DW = 10, BR_DW = 12;
+  typedef TiledPatchRegs<OR_R, OR_DW> Disc;
+  typedef TiledPatchRegs<BR_R, BR_DW> Brief;
+};
+static_assert(OrGeom<true>::OR_DW == OR_DW && 2 * OR_R + 1 + 7 <= 4 * OrGeom<true>::OR_DW && 2 * BR_R + 1 + 7 <= 4 * OrGeom<true>::BR_DW,
+              "tiled patch rows: 8-byte aligned starts, same centroid vectors");
+__device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table_tiled = make_rot_off_table(4 * OrGeom<true>::BR_DW);
+
 // The disc weights of orient_rbrief_kernel's s_w as a compile-time table: entry (sh, t) = weights of patch vector t (row
 // t / 5, dword pair t % 5) for a patch whose first column sits sh bytes into its first dword: .x/.y = (dx + 15) inside
 // the disc else 0 (u8 x 4) of the two dwords, .z/.w = 1 inside the disc else 0.
+template <int ALIGN>
 struct DiscWeightTable {
-  uint32_t v[4 * OR_WT * 4];
+  uint32_t v[ALIGN * OR_WT * 4];
 };
-constexpr DiscWeightTable make_disc_weight_table() {
+template <int ALIGN>
+constexpr DiscWeightTable<ALIGN> make_disc_weight_table() {
   constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-  DiscWeightTable r{};
-  for (int e = 0; e < 4 * OR_WT; ++e) {
+  DiscWeightTable<ALIGN> r{};
+  for (int e = 0; e < ALIGN * OR_WT; ++e) {
     const int sh = e / OR_WT, t = e - sh * OR_WT;
     if (t >= OR_NV) continue;
     const int row = t / (OR_DW / 2), c = t - row * (OR_DW / 2);
@@ -1146,7 +1270,8 @@ constexpr DiscWeightTable make_disc_weight_table() {
   }
   return r;
 }
-__device__ __attribute__((aligned(16))) const DiscWeightTable g_disc_weight_table = make_disc_weight_table();
+__device__ __attribute__((aligned(16))) const DiscWeightTable<4> g_disc_weight_table = make_disc_weight_table<4>();
+__device__ __attribute__((aligned(16))) const DiscWeightTable<8> g_disc_weight_table8 = make_disc_weight_table<8>();
 
 // One wave = eight consecutive keypoints of one image, in two phases.
 //  A. orientation of all eight: the 31-row image patches arrive in registers (3 dwordx2 per lane and keypoint, up to
@@ -1211,15 +1336,19 @@ __global__ __launch_bounds__(256) void orient_order_kernel(const uint32_t* __res
 // ORDERED: slot s of an image is served with keypoint order[s] (vus_orient_order: the image's keypoints grouped by 64 x 64
 // cell, the unused slots mapped to themselves), so that the eight keypoints of a wave and the 32 of a workgroup are
 // neighbours and their patch rows share lines in flight; the outputs go to the keypoint's own index.  A schedule only.
-template <bool EXACT, bool ORDERED>
+// TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W): the patches arrive through TiledPatchRegs,
+// phase B's LDS patch stays row-major (48-byte rows), so the test offsets and ballots are those of the plain form.
+template <bool EXACT, bool ORDERED, bool TILED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE, 8))) void orient_rbrief_kernel(
     const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int H, int W, int pitch,
     const uint32_t* __restrict__ kp_keys, const int* __restrict__ kp_count, int max_kp, const int* __restrict__ order,
     uint64_t* __restrict__ desc_out, uint8_t* __restrict__ angle_out, int n_img, int chunks_per_img) {
   // centroid weights per patch vector (two dwords), for the 4 possible byte alignments of the patch:
   // .x/.y = (dx + 15) inside the disc else 0 (u8 x 4) of the two dwords, .z/.w = 1 inside the disc else 0
-  __shared__ uint4 s_w[4 * OR_WT];
-  __shared__ __attribute__((aligned(8))) uint32_t s_blur[4][2][BR_ROWS * BR_DW];
+  typedef OrGeom<TILED> G;
+  static_assert(!(TILED && EXACT), "tiled planes are always read from aligned starts");
+  __shared__ uint4 s_w[G::ALIGN * OR_WT];
+  __shared__ __attribute__((aligned(8))) uint32_t s_blur[4][2][BR_ROWS * G::BR_DW];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // XCD-aware block -> (image, chunk) map: workgroups are dealt round-robin over the 8 XCDs, so all
@@ -1230,12 +1359,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
   const int chunk = slot - (slot / chunks_per_img) * chunks_per_img;
   if (n >= n_img) return;
   {   // the disc weights: a compile-time table, copied (deriving them per workgroup cost ~19 vector instructions per keypoint)
-    const uint4* wt = reinterpret_cast<const uint4*>(g_disc_weight_table.v);
+    const uint4* wt = reinterpret_cast<const uint4*>(TILED ? g_disc_weight_table8.v : g_disc_weight_table.v);
 #pragma unroll
-    for (int i = 0; i < 4 * OR_WT / 256; ++i) s_w[threadIdx.x + 256 * i] = wt[threadIdx.x + 256 * i];
+    for (int i = 0; i < G::ALIGN * OR_WT / 256; ++i) s_w[threadIdx.x + 256 * i] = wt[threadIdx.x + 256 * i];
   }
   const uint8_t* im = img + (size_t)n * H * pitch;
-  const uint8_t* bl = blur + (size_t)n * H * W;
+  const uint8_t* bl = blur + (size_t)n * H * W;   // TILED: both planes have H * W bytes per image
   const int base_i = (chunk * 4 + wave) * OR_KP_PER_WAVE;       // this wave's keypoints: base_i .. base_i + 7
   const int n_live = clampi(min(kp_count[n], max_kp) - base_i, 0, OR_KP_PER_WAVE);
   int my_y = 0, my_x = 0;                                         // lane k < 8: position of keypoint k
@@ -1254,11 +1383,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
     bin_cos[q] = VUS_ANGLE_COS[bq];
     bin_sin[q] = VUS_ANGLE_SIN[bq];
   }
-  PatchRegs<OR_R, OR_DW, OR_VW, EXACT> pr[OR_GRP];
-  PatchRegs<BR_R, BR_DW, OR_VW, EXACT> pb;
+  typename std::conditional<TILED, typename G::Disc, PatchRegs<OR_R, OR_DW, OR_VW, EXACT>>::type pr[OR_GRP];
+  typename std::conditional<TILED, typename G::Brief, PatchRegs<BR_R, BR_DW, OR_VW, EXACT>>::type pb;
+  if constexpr (TILED) {
 #pragma unroll
-  for (int kk = 0; kk < OR_GRP; ++kk) pr[kk].init(pitch, lane);
-  pb.init(W, lane);
+    for (int kk = 0; kk < OR_GRP; ++kk) pr[kk].init(lane);
+    pb.init(lane);
+  } else {
+#pragma unroll
+    for (int kk = 0; kk < OR_GRP; ++kk) pr[kk].init(pitch, lane);
+    pb.init(W, lane);
+  }
   int mom_dy[3];
 #pragma unroll
   for (int u = 0; u < 3; ++u) mom_dy[u] = min(lane + 64 * u, OR_NV - 1) / (OR_DW / 2) - OR_R;
@@ -1277,21 +1412,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
     for (int kk = 0; kk < OR_GRP; ++kk) {
       const int k = OR_GRP * g + kk;
 #ifndef VUS_OR_EXP_NORAW
-      if (k < n_live)
-        pr[kk].load(im, H, W, pitch, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
+      if (k < n_live) {
+        if constexpr (TILED) pr[kk].load(im, H, W, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
+        else pr[kk].load(im, H, W, pitch, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
+      }
 #else
       for (int u = 0; u < 3; ++u) pr[kk].v[u] = typename PatchVec<OR_VW>::type{(uint32_t)lane, (uint32_t)k};
 #endif
     }
-    if (g == 8 / OR_GRP - 1)   // the first descriptor patch joins the queue behind the last centroid patches
-      pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
+    if (g == 8 / OR_GRP - 1) {   // the first descriptor patch joins the queue behind the last centroid patches
+      if constexpr (TILED) pb.load(bl, H, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
+      else pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
+    }
 #pragma unroll
     for (int kk = 0; kk < OR_GRP; ++kk) {
       const int k = OR_GRP * g + kk;
       pa[k] = 0;
       pq[k] = 0;
       if (k < n_live) {
-        const int sh = EXACT ? 0 : (__builtin_amdgcn_readlane(my_x, k) - OR_R) & 3;
+        const int sh = EXACT ? 0 : (__builtin_amdgcn_readlane(my_x, k) - OR_R) & (G::ALIGN - 1);
         const uint4* wt = s_w + sh * OR_WT + lane;
         uint32_t sx = 0;
         int si = 0, sy = 0;
@@ -1348,7 +1487,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
 
   // ---- phase B: the descriptors
   uint32_t wlo = 0, whi = 0;   // lane 4k + w: word w of keypoint k
-  const uint4* rot = reinterpret_cast<const uint4*>(g_rot_off_table.v) + lane;
+  const uint4* rot = reinterpret_cast<const uint4*>(TILED ? g_rot_off_table_tiled.v : g_rot_off_table.v) + lane;
   uint4 to = rot[__builtin_amdgcn_readlane(my_bin, 0) * 64];
   for (int k = 0; k < n_live; ++k) {   // scalar loop
     uint32_t* patch = s_blur[wave][k & 1];
@@ -1357,13 +1496,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
     const int cx = __builtin_amdgcn_readlane(my_x, k);
     if (k + 1 < n_live) {
 #ifndef VUS_OR_EXP_NOBLUR
-      pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, k + 1), __builtin_amdgcn_readlane(my_x, k + 1), lane);
+      if constexpr (TILED) pb.load(bl, H, W, __builtin_amdgcn_readlane(my_y, k + 1), __builtin_amdgcn_readlane(my_x, k + 1), lane);
+      else pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, k + 1), __builtin_amdgcn_readlane(my_x, k + 1), lane);
 #endif
       to = rot[__builtin_amdgcn_readlane(my_bin, 8 * (k + 1)) * 64];
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // this wave's LDS operations execute in order
-    const int sh_blur = EXACT ? 0 : (cx - BR_R) & 3;   // patch column of x - radius
-    const uint8_t* c = reinterpret_cast<const uint8_t*>(patch) + BR_R * (4 * BR_DW) + BR_R + sh_blur;   // the keypoint inside the patch
+    const int sh_blur = EXACT ? 0 : (cx - BR_R) & (G::ALIGN - 1);   // patch column of x - radius
+    const uint8_t* c = reinterpret_cast<const uint8_t*>(patch) + BR_R * (4 * G::BR_DW) + BR_R + sh_blur;   // the keypoint inside the patch
     const uint32_t tw[4] = {cto.x, cto.y, cto.z, cto.w};
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -2271,6 +2411,40 @@ extern "C" int vus_fast_detect_adaptive(const uint8_t* img, int n_img, int H, in
   return VUS_OK;
 }
 
+// the planes of include/vus_tiled.h: whole 16 x 8 blocks, 16-byte aligned (the raw copy's dwordx4 stores)
+static int check_tiled_args(const void* a, const void* b, int H, int W) {
+  VUS_REQUIRE(a != nullptr && b != nullptr, "tiled plane pointer is null");
+  VUS_REQUIRE(W % VUS_TILE_BW == 0 && H % VUS_TILE_BH == 0, "tiled planes need W %% %d == 0 and H %% %d == 0 (got %dx%d)",
+              VUS_TILE_BW, VUS_TILE_BH, W, H);
+  VUS_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0, "tiled planes must be 16-byte aligned");
+  return VUS_OK;
+}
+
+extern "C" int vus_fast_detect_adaptive_tiled(const uint8_t* img, int n_img, int H, int W, int pitch, const int* thr_img,
+                                              int border, uint8_t* blur_tiled, uint8_t* img_tiled, uint32_t* cand_keys,
+                                              int cand_cap, int* cand_count, void* stream) {
+  if (int rc = check_image_args(img, n_img, H, W, pitch)) return rc;
+  if (int rc = check_tiled_args(blur_tiled, img_tiled, H, W)) return rc;
+  VUS_REQUIRE(cand_keys != nullptr && cand_count != nullptr && thr_img != nullptr, "null buffer");
+  VUS_REQUIRE(cand_cap >= 1 && border >= 0, "cand_cap=%d border=%d", cand_cap, border);
+  if (n_img == 0) return VUS_OK;
+  hipStream_t st = vus::as_stream(stream);
+  const TileGrid g = tile_grid(n_img, H, W);
+  static_assert(TW % VUS_TILE_BW == 0 && TH % VUS_TILE_BH == 0, "a detector tile is whole blocks");
+  // the same list scheme as vus_fast_detect_adaptive with a smoothing plane
+  if (cand_cap >= 64 * VUS_CAND_REGIONS) {
+    cand_region_zero_kernel<<<(n_img * VUS_CAND_REGIONS + 255) / 256, 256, 0, st>>>(cand_keys, cand_cap, n_img);
+    fast_tile_tiled_kernel<true><<<g.blocks, NTHREADS, 0, st>>>(img, H, W, pitch, thr_img, border, blur_tiled, img_tiled,
+                                                                cand_keys, cand_cap, cand_count, n_img, g.tiles_x, g.tiles_per_img);
+    cand_region_merge_kernel<<<n_img, 256, 0, st>>>(cand_keys, cand_cap, cand_count);
+  } else {
+    fast_tile_tiled_kernel<false><<<g.blocks, NTHREADS, 0, st>>>(img, H, W, pitch, thr_img, border, blur_tiled, img_tiled,
+                                                                 cand_keys, cand_cap, cand_count, n_img, g.tiles_x, g.tiles_per_img);
+  }
+  VUS_CHECK_LAUNCH("fast_detect_adaptive_tiled");
+  return VUS_OK;
+}
+
 extern "C" int vus_fast_detect_retry(const uint8_t* img, int n_img, int H, int W, int pitch, int thr, const int* thr_img,
                                      int max_kp, int border, uint32_t* cand_keys, int cand_cap, int* cand_count,
                                      int* retry_list, int* retry_count, void* stream) {
@@ -2360,6 +2534,27 @@ extern "C" int vus_orient_rbrief_ordered(const uint8_t* img, const uint8_t* blur
                                          uint64_t* desc_out, uint8_t* angle_out, void* stream) {
   VUS_REQUIRE(order != nullptr, "null buffer");
   return orient_launch(img, blur, n_img, H, W, pitch, kp_keys, kp_count, max_kp, order, desc_out, angle_out, stream);
+}
+
+extern "C" int vus_orient_rbrief_tiled(const uint8_t* img_tiled, const uint8_t* blur_tiled, int n_img, int H, int W,
+                                       const uint32_t* kp_keys, const int* kp_count, int max_kp, const int* order,
+                                       uint64_t* desc_out, uint8_t* angle_out, void* stream) {
+  if (int rc = check_image_args(img_tiled, n_img, H, W, W)) return rc;
+  if (int rc = check_tiled_args(img_tiled, blur_tiled, H, W)) return rc;
+  VUS_REQUIRE(kp_keys && kp_count && desc_out && angle_out, "null buffer");
+  VUS_REQUIRE(max_kp >= 1, "max_kp=%d", max_kp);
+  if (n_img == 0) return VUS_OK;
+  const int chunks = (max_kp + 4 * OR_KP_PER_WAVE - 1) / (4 * OR_KP_PER_WAVE);
+  const long long blocks = (long long)((n_img + 7) / 8) * 8 * chunks;
+  VUS_REQUIRE(blocks < (1ll << 31), "too many workgroups (%lld)", blocks);
+  if (order)
+    orient_rbrief_kernel<false, true, true><<<(unsigned)blocks, 256, 0, vus::as_stream(stream)>>>(
+        img_tiled, blur_tiled, H, W, W, kp_keys, kp_count, max_kp, order, desc_out, angle_out, n_img, chunks);
+  else
+    orient_rbrief_kernel<false, false, true><<<(unsigned)blocks, 256, 0, vus::as_stream(stream)>>>(
+        img_tiled, blur_tiled, H, W, W, kp_keys, kp_count, max_kp, order, desc_out, angle_out, n_img, chunks);
+  VUS_CHECK_LAUNCH("orient_rbrief_tiled");
+  return VUS_OK;
 }
 
 extern "C" int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, const int* kp_count,

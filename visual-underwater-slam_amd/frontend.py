@@ -18,6 +18,28 @@ import torch
 from . import _lib
 
 
+TILE_BW, TILE_BH = 16, 8   # block-tiled planes (include/vus_tiled.h): 16 x 8-pixel blocks of 128 bytes, raster order
+
+
+def tiled_supported(H: int, W: int) -> bool:
+    """The tiled entry points take whole blocks only."""
+    return H % TILE_BH == 0 and W % TILE_BW == 0
+
+
+def tile_planes(planes: torch.Tensor) -> torch.Tensor:
+    """[n, H, W] row-major -> [n, H * W] block-tiled (vus_tiled_offset of include/vus_tiled.h)."""
+    n, H, W = planes.shape
+    return (planes.reshape(n, H // TILE_BH, TILE_BH, W // TILE_BW, TILE_BW).permute(0, 1, 3, 2, 4)
+            .reshape(n, H * W).contiguous())
+
+
+def untile_planes(tiled: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """[n, H * W] block-tiled -> [n, H, W] row-major: the inverse of tile_planes."""
+    n = tiled.shape[0]
+    return (tiled.reshape(n, H // TILE_BH, W // TILE_BW, TILE_BH, TILE_BW).permute(0, 1, 3, 2, 4)
+            .reshape(n, H, W).contiguous())
+
+
 @dataclass
 class ImageProcessorParams:
     """Parameter names follow launch/stereo.launch:37-47 where the reference has one."""
@@ -133,7 +155,18 @@ class StereoOrbFrontend:
         self.device = torch.device(device)
         n_img, K, cap = 2 * self.max_frames, self.p.max_features, self.p.cand_cap
         dev = self.device
-        self.blur = torch.empty((n_img, H, W), dtype=torch.uint8, device=dev)
+        # the single-level adaptive path keeps the image and its smoothing block-tiled (include/vus_tiled.h): the
+        # orientation stage's patches then touch ~half the 128-byte lines.  `blur` stays a row-major [n, H, W] tensor
+        # on demand (a de-tiled copy, made when read).  Other paths, and sizes that are not whole 16 x 8 blocks, stay
+        # row-major.
+        self.tiled = bool(self.p.n_levels == 1 and self.p.adaptive_fast and self.p.grid_max_feature_num <= 0
+                          and tiled_supported(self.H, self.W))
+        if self.tiled:
+            self.blur_tiled = torch.empty((n_img, H * W), dtype=torch.uint8, device=dev)
+            self.img_tiled = torch.empty((n_img, H * W), dtype=torch.uint8, device=dev)
+            self._blur = None
+        else:
+            self._blur = torch.empty((n_img, H, W), dtype=torch.uint8, device=dev)
         self.cand_keys = torch.empty((n_img, cap), dtype=torch.int32, device=dev)
         self.cand_count = torch.zeros((n_img,), dtype=torch.int32, device=dev)
         self.kp_keys = torch.empty((n_img, K), dtype=torch.int32, device=dev)
@@ -177,7 +210,7 @@ class StereoOrbFrontend:
                 self.levels.append(dict(
                     H=h, W=w, quota=q,
                     img=None if l == 0 else torch.empty((n_img, h, w), dtype=torch.uint8, device=dev),
-                    blur=self.blur if l == 0 else torch.empty((n_img, h, w), dtype=torch.uint8, device=dev),
+                    blur=self._blur if l == 0 else torch.empty((n_img, h, w), dtype=torch.uint8, device=dev),
                     keys=torch.empty((n_img, q), dtype=torch.int32, device=dev),
                     count=torch.zeros((n_img,), dtype=torch.int32, device=dev),
                     desc=torch.empty((n_img, q, 4), dtype=torch.int64, device=dev),
@@ -201,14 +234,19 @@ class StereoOrbFrontend:
                 _lib.call("vus_fast_threshold_estimate", ptr(images), n_img, H, W, W, p.fast_threshold, p.border, K,
                           p.fast_sample_stride, ptr(self.fast_hist), ptr(self.fast_thr), st)
                 mark("fast_threshold")
-                _lib.call("vus_fast_detect_adaptive", ptr(images), n_img, H, W, W, ptr(self.fast_thr), p.border,
-                          ptr(self.blur), ptr(self.cand_keys), p.cand_cap, ptr(self.cand_count), st)
+                if self.tiled:   # both planes depend on the images only: complete before any retry
+                    _lib.call("vus_fast_detect_adaptive_tiled", ptr(images), n_img, H, W, W, ptr(self.fast_thr), p.border,
+                              ptr(self.blur_tiled), ptr(self.img_tiled), ptr(self.cand_keys), p.cand_cap,
+                              ptr(self.cand_count), st)
+                else:
+                    _lib.call("vus_fast_detect_adaptive", ptr(images), n_img, H, W, W, ptr(self.fast_thr), p.border,
+                              ptr(self._blur), ptr(self.cand_keys), p.cand_cap, ptr(self.cand_count), st)
                 _lib.call("vus_fast_detect_retry", ptr(images), n_img, H, W, W, p.fast_threshold, ptr(self.fast_thr), K,
                           p.border, ptr(self.cand_keys), p.cand_cap, ptr(self.cand_count), ptr(self.fast_retry_list),
                           ptr(self.fast_retry_count), st)
             else:
                 _lib.call("vus_fast_detect", ptr(images), n_img, H, W, W, p.fast_threshold, p.border,
-                          ptr(self.blur), ptr(self.cand_keys), p.cand_cap, ptr(self.cand_count), st)
+                          ptr(self._blur), ptr(self.cand_keys), p.cand_cap, ptr(self.cand_count), st)
             mark("fast_detect")
             if p.grid_max_feature_num > 0:
                 _lib.call("vus_select_grid", ptr(self.cand_keys), ptr(self.cand_count), n_img, p.cand_cap, H, W,
@@ -217,8 +255,11 @@ class StereoOrbFrontend:
                 _lib.call("vus_select_topk", ptr(self.cand_keys), ptr(self.cand_count), n_img, p.cand_cap, K,
                           ptr(self.kp_keys), ptr(self.kp_count), st)
             mark("select_topk")
-            self._orient(ptr(images), ptr(self.blur), n_img, H, W, ptr(self.kp_keys), ptr(self.kp_count), K, ptr(self.desc),
-                         ptr(self.angle), st)
+            if self.tiled:
+                self._orient_tiled(n_img, st)
+            else:
+                self._orient(ptr(images), ptr(self._blur), n_img, H, W, ptr(self.kp_keys), ptr(self.kp_count), K,
+                             ptr(self.desc), ptr(self.angle), st)
             mark("orient_rbrief")
         else:
             self._process_pyramid(images, n_img, st)
@@ -294,6 +335,24 @@ class StereoOrbFrontend:
                       desc_p, angle_p, st)
         else:
             _lib.call("vus_orient_rbrief", img_p, blur_p, n_img, h, w, w, keys_p, count_p, k, desc_p, angle_p, st)
+
+    def _orient_tiled(self, n_img, st):
+        """_orient of the single-level path on the block-tiled planes of vus_fast_detect_adaptive_tiled."""
+        H, W, K, ptr = self.H, self.W, self.p.max_features, _lib.ptr
+        order = None
+        if ((H + 63) // 64) * ((W + 63) // 64) <= 1024:
+            _lib.call("vus_orient_order", ptr(self.kp_keys), ptr(self.kp_count), n_img, K, H, W, ptr(self.kp_order), st)
+            order = ptr(self.kp_order)
+        _lib.call("vus_orient_rbrief_tiled", ptr(self.img_tiled), ptr(self.blur_tiled), n_img, H, W, ptr(self.kp_keys),
+                  ptr(self.kp_count), K, order, ptr(self.desc), ptr(self.angle), st)
+
+    @property
+    def blur(self) -> torch.Tensor:
+        """The 7 x 7 smoothing of the images of the last process(), row-major [n_img, H, W] (the full-resolution
+        level).  On the tiled path a de-tiled copy, made when read."""
+        if self.tiled:
+            return untile_planes(self.blur_tiled, self.H, self.W)
+        return self._blur
 
     def check_overflow(self, n_img=None):
         """Raises if any image since the last check produced more FAST candidates than cand_cap (one device
