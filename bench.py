@@ -11,10 +11,14 @@ shard plus a one-frame halo (dist.shard_frames), and the step ends with the all_
 records (dist.gather_tracks, RCCL): "scaling": "weak".
 
 The same JSON line carries `roofline` (dominant kernel: HBM reading + the VALU-issue reading that actually binds
-it), `cpu_baseline` (OpenCV if this machine has it, else the C port, on a bounded sample of the same stream, 1 thread
-and all usable cores) and `ba`: the second half of the metric, full-batch LM wall time at 2000 keyframes / 50k
-landmarks (configs[2]) with its own roofline, drop-in boundary timing and CPU baseline; with N > 1 ranks `ba_sharded`:
-the landmark-sharded LM of configs[4].
+it), read from the timed steps' stage times and the committed PMC summary.  A plain run stops there: it sets up,
+warms up, times the steps, writes --dump-outputs and prints the line.
+
+With --full the line also carries `cpu_baseline` (OpenCV if this machine has it, else the C port, on a bounded sample
+of the same stream, 1 thread and all usable cores), `pyramid8` if --pyramid is given, and `ba`: the second half of the
+metric, full-batch LM wall time at 2000 keyframes / 50k landmarks (configs[2]) with its own roofline, drop-in boundary
+timing (the first optimize() of a fresh process) and CPU baseline; with N > 1 ranks `ba_sharded`: the landmark-sharded
+LM of configs[4].  The --no-* options below trim a --full run.
 """
 import argparse
 import json
@@ -50,12 +54,15 @@ ALGO_BYTES_FRAME = 2 * H * W + 2 * KP * 16 + 2 * KP * 32 + 2 * KP * 32 + KP * 8 
 STAGES = ["fast_detect", "select_topk", "orient_rbrief", "hamming_stereo", "hamming_track"]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--frames", type=int, default=1000, help="frames per GPU (configs[1]: 1000)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the CPU baselines, the "
+                    "BA legs (first optimize() of a fresh process, end to end, full graphs; ba_sharded with N > 1 ranks) "
+                    "and --pyramid")
     ap.add_argument("--cpu-frames", type=int, default=0, help="bounded cpu_baseline sample (0: sized from the core count)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ba", action="store_true")
@@ -63,15 +70,17 @@ def parse():
     ap.add_argument("--no-object-graph", action="store_true", help="skip the per-object graph leg (~20 s of Python graph build)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the images -> trajectory leg")
     ap.add_argument("--ba-sharded-kf", type=int, default=10000, help="keyframes of the configs[4] leg run with N > 1 ranks")
-    ap.add_argument("--pyramid", action="store_true", help="also measure the same stream through the 8-level x1.2 pyramid "
-                    "(extra `pyramid8` object; off by default so that a profile of the default command sees one launch "
-                    "shape per kernel)")
+    ap.add_argument("--pyramid", action="store_true", help="with --full, also measure the same stream through the 8-level "
+                    "x1.2 pyramid (extra `pyramid8` object; off by default so that a profile of a --full run sees one "
+                    "launch shape per kernel)")
     ap.add_argument("--no-pyramid", action="store_true", help="accepted for older scripts; the default already")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step returned "
                     "(rank 0's shard) as DIR/<name>.npy for comparing two builds output for output (dump_outputs)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.pyramid and not a.full:
+        ap.error("--pyramid is a leg of --full")
     return a
 
 
@@ -349,11 +358,12 @@ def main():
     assert a.gpus == world, f"--gpus {a.gpus} but WORLD_SIZE={world} (launch with torch.distributed.run)"
     first_call = None
     under_profiler = "rocprofiler" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCP") for k in os.environ)
-    if world == 1 and not a.no_ba and not a.no_first_call and under_profiler:
-        # rocprofv3's preloaded tool may already have initialised the GPU in this process: starting a child from it is
-        # what the GPU pool forbids.  The figure comes from the plain run (profiles/bench_rNN.json).
+    probe_first_call = a.full and world == 1 and not a.no_ba and not a.no_first_call
+    if probe_first_call and under_profiler:
+        # rocprofv3's preloaded tool may already have initialised the GPU in this process, and no child process is
+        # started from one that has.  The figure comes from a --full run without the profiler (profiles/bench_rNN.json).
         first_call = {"skipped": "running under rocprofv3: no child process is started from a profiled process"}
-    elif world == 1 and not a.no_ba and not a.no_first_call:
+    elif probe_first_call:
         # batch.py:337 calls optimize() ONCE per process: measure that first call in a fresh child process, before this
         # process has made any GPU call of its own (the two never share the GPU)
         from visual_underwater_slam_amd import ba_bench as _bb
@@ -500,10 +510,11 @@ def main():
                                "note": "dense int8 MFMA peak = 2x the ~2.5 PFLOP/s bf16 peak (MI355X_MICROARCH.md, matrix cores)"}
     if world > 1:
         out["stage_ms"]["gather_tracks_and_rest"] = round(dt / a.steps * 1e3 - sum(stage_ms.values()), 4)
+    # the legs of --full; a plain run goes straight to the result line
     cores = usable_cores()
-    if rank == 0 and not a.no_cpu_baseline and world == 1:
+    if a.full and rank == 0 and not a.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_frontend(0, cores, a.cpu_frames)
-    if rank == 0 and a.pyramid and not a.no_pyramid and world == 1:
+    if a.full and rank == 0 and a.pyramid and not a.no_pyramid and world == 1:
         # extra figure, not the headline: the same stream through the 8-level x1.2 ORB pyramid
         # (2,853,088 px per image, per-level quotas summing to 2000 keypoints)
         del fe
@@ -525,7 +536,7 @@ def main():
     fe = None
     del images
     torch.cuda.empty_cache()
-    if not a.no_ba and world == 1:
+    if a.full and not a.no_ba and world == 1:
         from visual_underwater_slam_amd import ba_bench
         ba = ba_bench.run(device, with_object_graph=not a.no_object_graph)
         seq = ba.pop("_seq")
@@ -543,7 +554,7 @@ def main():
         if not a.no_cpu_baseline:
             ba["cpu_baseline"] = cpu_baseline_ba(seq, cores, ba["value"])
         out["ba"] = ba
-    if not a.no_ba and world > 1:
+    if a.full and not a.no_ba and world > 1:
         from visual_underwater_slam_amd import ba_bench
         r = ba_bench.run_sharded(device, world, rank, n_kf=a.ba_sharded_kf, n_lm=50 * a.ba_sharded_kf)
         t = torch.tensor([r["seconds"]], dtype=torch.float64, device=device if backend == "nccl" else "cpu")

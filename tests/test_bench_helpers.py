@@ -108,15 +108,47 @@ def test_native_oracle_is_built_outside_the_checkout():
     assert sorted(os.listdir(os.path.join(ROOT, "oracle"))) == before
 
 
+def test_full_is_off_by_default_and_pyramid_needs_it():
+    """A plain command line runs the headline alone; the legs beyond it (and --pyramid among them) ask for --full."""
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and not a.pyramid and (a.steps, a.warmup) == (3, 1)
+    assert bench.parse(["--full"]).full
+    assert bench.parse(["--full", "--pyramid"]).pyramid
+    with pytest.raises(SystemExit):
+        bench.parse(["--pyramid"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_only_the_headline(gpu, tmp_path):
+    """`python bench.py` without --full: ONE JSON line with the contract's keys and the front-end's roofline, the last
+    timed step's outputs under --dump-outputs, and none of the legs that --full adds."""
+    import subprocess, sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "24", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "stage_ms", "roofline"):
+        assert k in j, k
+    assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    for k in ("cpu_baseline", "pyramid8", "ba", "ba_sharded"):
+        assert k not in j, k
+    d = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in DUMP_NAMES}
+    assert np.array_equal(d["frames"], np.arange(24)) and (d["kp_count"] == 2000).all()
+    assert d["desc"].shape == (48, 2000, 8) and d["track_idx"].shape == (23, 2000)
+
+
 @pytest.mark.gpu
 def test_bench_command_line_contract_on_a_small_stream(gpu, tmp_path):
-    """`python bench.py` end to end (the driver's command, with a small stream so that it takes seconds): ONE JSON line
-    with the contract's keys, the roofline object of the dominant kernel and the BA legs."""
+    """`python bench.py --full` end to end (with a small stream so that it takes seconds): ONE JSON line with the
+    contract's keys, the roofline object of the dominant kernel and the BA legs."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "24", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900,
-                       cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--frames", "24", "--steps", "2",
+                        "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True,
+                       text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -139,10 +171,10 @@ def test_bench_command_line_contract_on_a_small_stream(gpu, tmp_path):
 
 @pytest.mark.gpu
 def test_bench_two_rank_rehearsal_over_gloo_on_the_one_gpu(gpu):
-    """The driver's multi-GPU command line -- torch.distributed.run, one rank per GPU, `bench.py --gpus N` -- rehearsed as
-    two ranks on the ONE visible GPU with VUS_BENCH_BACKEND=gloo (RCCL needs one device per rank): the frame-sharded
-    front-end with its gather, and the landmark-sharded LM with its reduce / broadcast, produce ONE JSON line from rank 0
-    that carries what an 8-GPU result needs to be interpreted (bytes per trial, per-stage times)."""
+    """The driver's multi-GPU command line -- torch.distributed.run, one rank per GPU, `bench.py --full --gpus N` --
+    rehearsed as two ranks on the ONE visible GPU with VUS_BENCH_BACKEND=gloo (RCCL needs one device per rank): the
+    frame-sharded front-end with its gather, and the landmark-sharded LM with its reduce / broadcast, produce ONE JSON
+    line from rank 0 that carries what an 8-GPU result needs to be interpreted (bytes per trial, per-stage times)."""
     import os
     import socket
     import subprocess
@@ -150,8 +182,8 @@ def test_bench_two_rank_rehearsal_over_gloo_on_the_one_gpu(gpu):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, VUS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--frames", "24", "--ba-sharded-kf", "300"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
+           "--warmup", "1", "--frames", "24", "--ba-sharded-kf", "300"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -7,12 +7,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-# 1. plain bench line (no profiler attached)
-python3 $ROOT/bench.py --pyramid > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err || true
+# 1. full bench line (no profiler attached)
+python3 $ROOT/bench.py --full --pyramid > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err || true
 # 2. rocprofv3 kernel trace + stats of the same command
-# (the default command: single-level headline; --pyramid would launch the same kernels at 8 sizes and blur the averages)
-rm -rf /tmp/prof_kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python3 $ROOT/bench.py > $OUT/bench_${TAG}_under_rocprof.json 2>/dev/null || true
-python3 $ROOT/tools/summarize_stats.py /tmp/prof_kt 40 | grep -v "at::native\|rocprim\|rocclr\|compute_cuda" > $OUT/kernel_stats_${TAG}.txt || true
+# (--full without --pyramid: single-level headline; --pyramid would launch the same kernels at 8 sizes and blur the averages)
+rm -rf $TMPDIR/prof_kt && rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/prof_kt -- python3 $ROOT/bench.py --full > $OUT/bench_${TAG}_under_rocprof.json 2>/dev/null || true
+python3 $ROOT/tools/summarize_stats.py $TMPDIR/prof_kt 40 | grep -v "at::native\|rocprim\|rocclr\|compute_cuda" > $OUT/kernel_stats_${TAG}.txt || true
 # 3. PMC passes (front-end kernels, 200 frames; separate passes as the guide prescribes)
 pmc() { name=$1; shift; rm -rf /tmp/pmc_$name; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmc_$name -- python3 $ROOT/bench.py --frames 200 --steps 2 --warmup 1 --no-cpu-baseline --no-ba --no-pyramid > /dev/null 2>&1 || true; }
 pmc sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR
