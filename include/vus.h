@@ -87,8 +87,10 @@ int vus_fast_detect(const uint8_t* img, int n_img, int H, int W, int pitch, int 
  *       a sub-list that outgrows cand_cap / 8 - 1 entries is reported as an overflow of the list (cand_count[n] >
  *       cand_cap, the unwritten tail = VUS_KEY_INVALID).
  *   vus_fast_detect_retry        the check: every image with thr_img[n] > thr and cand_count[n] < max_kp (the estimate
- *       was too high: s* may lie below thr_img[n]) is detected again at thr -- cand_count[n] reset, candidates
- *       rewritten; blur_out of the adaptive pass stays valid.  retry_list [n_img] scratch, retry_count[0] = how many.
+ *       was too high: s* may lie below thr_img[n]), and every image with cand_count[n] > cand_cap (an overflowed sub-list
+ *       or a true overflow), is detected again at thr into a single list -- cand_count[n] reset, candidates rewritten; a
+ *       true overflow stays one, with its true count.  blur_out of the adaptive pass stays valid.  retry_list [n_img]
+ *       scratch, retry_count[0] = how many.
  * After the three calls vus_select_topk gives exactly what it gives after vus_fast_detect(thr): bit-identical keys. */
 #ifndef VUS_FAST_MARGIN_NUM      /* overridable for A/B builds only: library and oracle must be built with the same pair */
 #define VUS_FAST_MARGIN_NUM 7    /* 1.75: on the configs[1] stream 0 of 1000 images fail the check (1.5: 18, 1.25: 130) and the */

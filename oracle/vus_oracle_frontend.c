@@ -200,7 +200,7 @@ int vus_fast_detect_retry_cpu(const uint8_t* img, int n_img, int H, int W, int p
   if (!img || !thr_img || !cand_keys || !cand_count || !retry_list || !retry_count) return VUS_E_INVALID;
   int m = 0;
   for (int n = 0; n < n_img; ++n)
-    if (thr_img[n] > thr && cand_count[n] < max_kp) {
+    if ((thr_img[n] > thr && cand_count[n] < max_kp) || cand_count[n] > cand_cap) {
       retry_list[m++] = n;
       int rc = vus_fast_detect_cpu(img + (size_t)n * H * pitch, 1, H, W, pitch, thr, border, NULL,
                                    cand_keys + (size_t)n * cand_cap, cand_cap, cand_count + n);

@@ -788,9 +788,11 @@ __global__ void cand_region_zero_kernel(uint32_t* __restrict__ cand_keys, int ca
 
 // ... and compacted after it, one workgroup per image: region r's keys (slots 1 .. of its part of the row) move down to
 // where region r - 1's ended -- always to lower addresses than anything still unread, a chunk read whole before it is
-// written -- and cand_count[n] becomes the total.  A region that overflowed its share of cand_cap (the image's candidates
-// would have to sit in every eighth tile for that to happen below cand_cap) is reported as an overflow of the list:
-// cand_count[n] > cand_cap, the unwritten tail filled with VUS_KEY_INVALID.
+// written -- and cand_count[n] becomes the total.  A region that overflowed its share of cand_cap is reported as an
+// overflow of the list: cand_count[n] > cand_cap, the unwritten tail filled with VUS_KEY_INVALID.  That happens well below
+// cand_cap whenever the candidates crowd into the tiles of one region: a textured patch inside a single 128-pixel tile
+// column is such a layout whenever tiles_x is a multiple of 8 (widths 897 .. 1024), and nearly so for tiles_x = 2, 4, 6.
+// vus_fast_detect_retry detects such an image again into a single list.
 __global__ __launch_bounds__(256) void cand_region_merge_kernel(uint32_t* __restrict__ cand_keys, int cand_cap, int* __restrict__ cand_count) {
   __shared__ int s_c[VUS_CAND_REGIONS];
   const int n = blockIdx.x, tid = threadIdx.x;
@@ -875,16 +877,17 @@ __global__ __launch_bounds__(256) void fast_pick_threshold_kernel(const int* __r
   if (lane == 0) thr_img[n] = best > floor ? best : thr;
 }
 
-// images whose adaptive pass yielded fewer than max_kp candidates although it ran above fast_threshold: listed,
-// their counts reset (one workgroup)
-__global__ __launch_bounds__(1024) void fast_retry_list_kernel(const int* __restrict__ thr_img, int thr, int max_kp, int n_img,
-                                                               int* __restrict__ cand_count, int* __restrict__ retry_list,
-                                                               int* __restrict__ retry_count) {
+// images whose adaptive pass yielded fewer than max_kp candidates although it ran above fast_threshold, and images whose
+// list overflowed (a sub-list that outgrew its share is reported as one, cand_region_merge_kernel; a true overflow stays
+// one, with its true count, after the single-list detection at fast_threshold): listed, their counts reset (one workgroup)
+__global__ __launch_bounds__(1024) void fast_retry_list_kernel(const int* __restrict__ thr_img, int thr, int max_kp, int cand_cap,
+                                                               int n_img, int* __restrict__ cand_count,
+                                                               int* __restrict__ retry_list, int* __restrict__ retry_count) {
   __shared__ int s_n;
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
   for (int n = threadIdx.x; n < n_img; n += 1024)
-    if (thr_img[n] > thr && cand_count[n] < max_kp) {
+    if ((thr_img[n] > thr && cand_count[n] < max_kp) || cand_count[n] > cand_cap) {
       retry_list[atomicAdd(&s_n, 1)] = n;
       cand_count[n] = 0;
     }
@@ -2455,7 +2458,7 @@ extern "C" int vus_fast_detect_retry(const uint8_t* img, int n_img, int H, int W
   if (n_img == 0) return VUS_OK;
   hipStream_t st = vus::as_stream(stream);
   const TileGrid g = tile_grid(n_img, H, W);
-  fast_retry_list_kernel<<<1, 1024, 0, st>>>(thr_img, thr, max_kp, n_img, cand_count, retry_list, retry_count);
+  fast_retry_list_kernel<<<1, 1024, 0, st>>>(thr_img, thr, max_kp, cand_cap, n_img, cand_count, retry_list, retry_count);
   int n_cu = 256;
   {
     int dev = 0;
