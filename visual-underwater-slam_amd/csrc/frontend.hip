@@ -1093,7 +1093,8 @@ struct PatchRegs {
 //   tiled(y0 & ~7, xa & ~15)  +  16 (y0 & 7) + 16 r + f(q)  +  (p >> 3) (8 W - 128),   p = (y0 & 7) + r,  q = (xa & 8) + 8 c,
 //   f(q) = 128 (q >> 4) + (q & 8)
 // -- the first two terms wave-uniform, 16 r + f(q) a per-lane constant for each of the two values of xa & 8: four
-// vector instructions per vector (add, shift, select, multiply-add) on top of the plain form's load.
+// vector instructions per vector (add, shift, bit-field extract, multiply-add) on top of the plain form's load.  The
+// three per-lane constants of a vector share ONE register (pk below): 6 bits of row, two 10-bit offsets.
 template <int RADIUS, int DW>
 struct TiledPatchRegs {
   static_assert(DW % 2 == 0, "row width must be a multiple of the vector width");
@@ -1102,18 +1103,17 @@ struct TiledPatchRegs {
   static constexpr int HW = DW / 2;             // vectors per row
   static constexpr int N = ROWS * HW;
   static constexpr int ITERS = (N + 63) / 64;
+  static_assert(ROWS + 7 < 64 && 16 * (ROWS - 1) + 128 * ((8 * HW) >> 4) + 8 < 1024, "pk fields: 6-bit row, 10-bit offsets");
   vec_t v[ITERS];
-  uint32_t row[ITERS];            // patch row of this lane's vectors
-  uint32_t off0[ITERS], off8[ITERS];   // 16 r + f(q) for xa & 8 == 0 / 8
+  uint32_t pk[ITERS];   // this lane's vectors: (patch row r) << 20 | (16 r + f(q), xa & 8 == 8) << 10 | (..., xa & 8 == 0)
 
   __device__ __forceinline__ void init(int lane) {
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) {
       const int t = min(lane + 64 * u, N - 1);
       const uint32_t r = (uint32_t)(t / HW), q0 = 8u * (uint32_t)(t % HW), q8 = q0 + 8u;
-      row[u] = r;
-      off0[u] = 16u * r + 128u * (q0 >> 4) + (q0 & 8u);
-      off8[u] = 16u * r + 128u * (q8 >> 4) + (q8 & 8u);
+      const uint32_t off0 = 16u * r + 128u * (q0 >> 4) + (q0 & 8u), off8 = 16u * r + 128u * (q8 >> 4) + (q8 & 8u);
+      pk[u] = r << 20 | off8 << 10 | off0;
     }
   }
   __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int y, int x, int lane) {
@@ -1121,11 +1121,11 @@ struct TiledPatchRegs {
     const bool inside = y0 >= 0 && y + RADIUS < H && xa >= 0 && xa + 4 * DW <= W;
     if (inside) {   // wave-uniform
       const uint8_t* base = src + vus_tiled_offset(y0 & ~7, xa & ~15, W) + 16 * (y0 & 7);
-      const uint32_t ys = (uint32_t)(y0 & 7), ystep = 8u * (uint32_t)W - 128u;
-      const bool x8 = (xa & 8) != 0;
+      const uint32_t ys = (uint32_t)(y0 & 7) << 20, ystep = 8u * (uint32_t)W - 128u;
+      const uint32_t sel = (xa & 8) != 0 ? 10u : 0u;
 #pragma unroll
-      for (int u = 0; u < ITERS; ++u) {
-        const uint32_t off = ((ys + row[u]) >> 3) * ystep + (x8 ? off8[u] : off0[u]);
+      for (int u = 0; u < ITERS; ++u) {   // (ys + r) >> 3 == (pk + ys) >> 23: the row field has room for ys + r < 64
+        const uint32_t off = ((pk[u] + ys) >> 23) * ystep + __builtin_amdgcn_ubfe(pk[u], sel, 10u);
         v[u] = *reinterpret_cast<const vec_t*>(base + (size_t)off);
       }
     } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
@@ -1221,10 +1221,16 @@ __device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table = make
 #ifndef VUS_OR_WPE
 #define VUS_OR_WPE 4
 #endif
+#ifndef VUS_OR_WPE_TILED
+#define VUS_OR_WPE_TILED 7   // the tiled instances (OrGeom<true>)
+#endif
 #ifndef VUS_OR_GRP
 #define VUS_OR_GRP 4
 #endif
-constexpr int OR_GRP = VUS_OR_GRP;   // centroid patches of this many keypoints are in flight together (4 or 8)
+#ifndef VUS_OR_GRP_TILED
+#define VUS_OR_GRP_TILED 2
+#endif
+constexpr int OR_GRP = VUS_OR_GRP;   // centroid patches of this many keypoints are in flight together (2, 4 or 8)
 static_assert(OR_VW == 2 && OR_KP_PER_WAVE == 8, "orient_rbrief_kernel is written for dwordx2 patch loads and 8 keypoints per wave");
 constexpr int OR_NV = OR_ROWS * (OR_DW / OR_VW);   // 155 dwordx2 vectors of a centroid patch
 constexpr int OR_WT = 192;                         // weight entries per byte alignment: one per vector, padded to 3 x 64 lanes
@@ -1234,11 +1240,19 @@ constexpr int OR_WT = 192;                         // weight entries per byte al
 // so the descriptor patch needs 44 of 48 bytes (12 dwords) per row; the centroid patch's 38 still fit its 40.
 template <bool TILED> struct OrGeom {
   static constexpr int ALIGN = 4, OR_DW = ::OR_DW, BR_DW = ::BR_DW;
+  static constexpr int WT_VEC4 = ALIGN * OR_WT;   // uint4 entries of s_w (DiscWeightTable<4>)
+  static constexpr int GRP = OR_GRP, BLUR_BUF = 2;   // BLUR_BUF: 1 or 2
   typedef PatchRegs<OR_R, OR_DW, OR_VW, false> Disc;
   typedef PatchRegs<BR_R, BR_DW, OR_VW, false> Brief;
 };
+constexpr int OR_WTD = 2 * OR_WT + 1;   // DiscWeightDwTable entries per byte alignment: a zero, then one per patch dword
 template <> struct OrGeom<true> {
   static constexpr int ALIGN = 8, OR_DW = 10, BR_DW = 12;
+  static constexpr int WT_VEC4 = 4 * OR_WTD * 2 / 4;   // uint4 entries of s_w (DiscWeightDwTable)
+  // 7 waves per SIMD: <= 72 VGPRs (phase A keeps 2 centroid patches in flight, not 4) and <= 23,405 B of LDS (the weights
+  // per dword; ONE descriptor patch buffer per wave -- the ballots of keypoint k have consumed its patch bytes before
+  // the patch of k + 1 is stored).  tests/test_orient_resources.py holds these figures.
+  static constexpr int GRP = VUS_OR_GRP_TILED, BLUR_BUF = 1;
   typedef TiledPatchRegs<OR_R, OR_DW> Disc;
   typedef TiledPatchRegs<BR_R, BR_DW> Brief;
 };
@@ -1274,14 +1288,56 @@ constexpr DiscWeightTable<ALIGN> make_disc_weight_table() {
   return r;
 }
 __device__ __attribute__((aligned(16))) const DiscWeightTable<4> g_disc_weight_table = make_disc_weight_table<4>();
-__device__ __attribute__((aligned(16))) const DiscWeightTable<8> g_disc_weight_table8 = make_disc_weight_table<8>();
+
+// The tiled form's disc weights, per dword instead of per dword pair (12 KB of LDS instead of the 24 KB of
+// DiscWeightTable<8>): entry (a, j), j >= 1 = {(dx + 15) inside the disc else 0, 1 inside else 0} (u8 x 4) of dword j - 1 of
+// the patch's rows laid end to end (10 dwords each), for a patch whose first column sits a bytes into its first dword;
+// entry (a, 0) and those past the last row are 0.  A patch that starts sh = 4 s + a bytes before its first column
+// weighs its dword d with entry (a, d + 1 - s), so vector t (dwords 2t, 2t + 1) reads entries 2t + 1 - s and 2t + 2 - s.
+// For s = 1 and t at a row start the first of them is the previous row's last dword (or entry 0): dx >= 18 there, 0 as
+// well.  Vectors t >= 155 (padding lanes) read entries past the last row.
+struct DiscWeightDwTable {
+  uint32_t v[4 * OR_WTD * 2];
+};
+constexpr DiscWeightDwTable make_disc_weight_dw_table() {
+  constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
+  DiscWeightDwTable r{};
+  for (int e = 0; e < 4 * OR_WTD; ++e) {
+    const int a = e / OR_WTD, d = e - a * OR_WTD - 1;
+    if (d < 0 || d >= OR_ROWS * OR_DW) continue;
+    const int row = d / OR_DW, col = d - row * OR_DW;
+    const int dy = row - OR_R, um = umax[dy < 0 ? -dy : dy];
+    for (int b = 0; b < 4; ++b) {
+      const int dx = 4 * col + b - a - OR_R;
+      if (dx >= -um && dx <= um) {
+        r.v[2 * e] |= (uint32_t)(dx + OR_R) << (8 * b);
+        r.v[2 * e + 1] |= 1u << (8 * b);
+      }
+    }
+  }
+  return r;
+}
+__device__ __attribute__((aligned(16))) const DiscWeightDwTable g_disc_weight_dw_table = make_disc_weight_dw_table();
+constexpr bool disc_weight_dw_table_matches() {   // the same weights as the per-pair table of all 8 alignments, every vector
+  constexpr DiscWeightTable<8> pair = make_disc_weight_table<8>();
+  constexpr DiscWeightDwTable dw = make_disc_weight_dw_table();
+  for (int sh = 0; sh < 8; ++sh)
+    for (int t = 0; t < OR_WT; ++t) {
+      const int e = (sh & 3) * OR_WTD + 2 * t + 1 - (sh >> 2);
+      const uint32_t* p = pair.v + 4 * (sh * OR_WT + t);
+      if (dw.v[2 * e] != p[0] || dw.v[2 * e + 2] != p[1] || dw.v[2 * e + 1] != p[2] || dw.v[2 * e + 3] != p[3]) return false;
+    }
+  return true;
+}
+static_assert(disc_weight_dw_table_matches(), "DiscWeightDwTable must weigh every vector as DiscWeightTable<8>");
+static_assert(sizeof(DiscWeightDwTable) == 16 * OrGeom<true>::WT_VEC4, "LDS copy of the tiled weights: whole uint4");
 
 // One wave = eight consecutive keypoints of one image, in two phases.
-//  A. orientation of all eight: the 31-row image patches arrive in registers (3 dwordx2 per lane and keypoint, up to
-//     12 in flight) and are multiplied right there with the disc weights (v_dot4_u32_u8; the weights of a lane's two
-//     dwords are ONE ds_read_b128): no LDS round trip for the patch.  Per-lane partial moments of the eight keypoints
+//  A. orientation of all eight: the 31-row image patches arrive in registers (3 dwordx2 per lane and keypoint, 3 GRP in
+//     flight) and are multiplied right there with the disc weights (v_dot4_u32_u8; the weights of a lane's two dwords
+//     are ONE LDS read): no LDS round trip for the patch.  Per-lane partial moments of the eight keypoints
 //     -> reduce-scatter (above) -> lane 8g + j holds m10 / m01 of keypoint g and ranks bins 4j .. 4j+3.
-//  B. descriptors, keypoint by keypoint: the 37-row patch of the smoothed image goes through LDS (double-buffered; the
+//  B. descriptors, keypoint by keypoint: the 37-row patch of the smoothed image goes through LDS (BLUR_BUF buffers; the
 //     next keypoint's rows and its bin's test offsets are in flight meanwhile), 8 byte reads + 4 compares per lane; the
 //     ballots are written into lanes 4k + w of one register pair, so the eight descriptors leave in ONE 256-byte store.
 // Round 4 first pass: one keypoint at a time, 232 vector instructions per keypoint (2.67 ms per 1000 stereo frames).
@@ -1342,16 +1398,17 @@ __global__ __launch_bounds__(256) void orient_order_kernel(const uint32_t* __res
 // TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W): the patches arrive through TiledPatchRegs,
 // phase B's LDS patch stays row-major (48-byte rows), so the test offsets and ballots are those of the plain form.
 template <bool EXACT, bool ORDERED, bool TILED = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE, 8))) void orient_rbrief_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS_OR_WPE_TILED : VUS_OR_WPE, 8))) void orient_rbrief_kernel(
     const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int H, int W, int pitch,
     const uint32_t* __restrict__ kp_keys, const int* __restrict__ kp_count, int max_kp, const int* __restrict__ order,
     uint64_t* __restrict__ desc_out, uint8_t* __restrict__ angle_out, int n_img, int chunks_per_img) {
   // centroid weights per patch vector (two dwords), for the 4 possible byte alignments of the patch:
   // .x/.y = (dx + 15) inside the disc else 0 (u8 x 4) of the two dwords, .z/.w = 1 inside the disc else 0
+  // (TILED: per dword, DiscWeightDwTable)
   typedef OrGeom<TILED> G;
   static_assert(!(TILED && EXACT), "tiled planes are always read from aligned starts");
-  __shared__ uint4 s_w[G::ALIGN * OR_WT];
-  __shared__ __attribute__((aligned(8))) uint32_t s_blur[4][2][BR_ROWS * G::BR_DW];
+  __shared__ uint4 s_w[G::WT_VEC4];
+  __shared__ __attribute__((aligned(8))) uint32_t s_blur[4][G::BLUR_BUF][BR_ROWS * G::BR_DW];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // XCD-aware block -> (image, chunk) map: workgroups are dealt round-robin over the 8 XCDs, so all
@@ -1362,9 +1419,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
   const int chunk = slot - (slot / chunks_per_img) * chunks_per_img;
   if (n >= n_img) return;
   {   // the disc weights: a compile-time table, copied (deriving them per workgroup cost ~19 vector instructions per keypoint)
-    const uint4* wt = reinterpret_cast<const uint4*>(TILED ? g_disc_weight_table8.v : g_disc_weight_table.v);
+    const uint4* wt = reinterpret_cast<const uint4*>(TILED ? g_disc_weight_dw_table.v : g_disc_weight_table.v);
 #pragma unroll
-    for (int i = 0; i < G::ALIGN * OR_WT / 256; ++i) s_w[threadIdx.x + 256 * i] = wt[threadIdx.x + 256 * i];
+    for (int i = 0; i < (G::WT_VEC4 + 255) / 256; ++i)
+      if (G::WT_VEC4 % 256 == 0 || threadIdx.x + 256 * i < G::WT_VEC4) s_w[threadIdx.x + 256 * i] = wt[threadIdx.x + 256 * i];
   }
   const uint8_t* im = img + (size_t)n * H * pitch;
   const uint8_t* bl = blur + (size_t)n * H * W;   // TILED: both planes have H * W bytes per image
@@ -1378,23 +1436,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
     my_y = (int)(pos / (uint32_t)W);
     my_x = (int)(pos - (uint32_t)my_y * (uint32_t)W);
   }
-  // the bins this lane ranks in phase A: 4 (lane & 7) + q
+  // the bins this lane ranks in phase A: 4 (lane & 7) + q (TILED: loaded after phase A's patches, 8 registers fewer
+  // while they are in flight)
   int bin_cos[4], bin_sin[4];
+  if constexpr (!TILED) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int bq = min(4 * (lane & 7) + q, VUS_N_ANGLE_BINS - 1);
-    bin_cos[q] = VUS_ANGLE_COS[bq];
-    bin_sin[q] = VUS_ANGLE_SIN[bq];
+    for (int q = 0; q < 4; ++q) {
+      const int bq = min(4 * (lane & 7) + q, VUS_N_ANGLE_BINS - 1);
+      bin_cos[q] = VUS_ANGLE_COS[bq];
+      bin_sin[q] = VUS_ANGLE_SIN[bq];
+    }
   }
-  typename std::conditional<TILED, typename G::Disc, PatchRegs<OR_R, OR_DW, OR_VW, EXACT>>::type pr[OR_GRP];
+  constexpr int GRP = G::GRP;
+  typename std::conditional<TILED, typename G::Disc, PatchRegs<OR_R, OR_DW, OR_VW, EXACT>>::type pr[GRP];
   typename std::conditional<TILED, typename G::Brief, PatchRegs<BR_R, BR_DW, OR_VW, EXACT>>::type pb;
   if constexpr (TILED) {
 #pragma unroll
-    for (int kk = 0; kk < OR_GRP; ++kk) pr[kk].init(lane);
+    for (int kk = 0; kk < GRP; ++kk) pr[kk].init(lane);
     pb.init(lane);
   } else {
 #pragma unroll
-    for (int kk = 0; kk < OR_GRP; ++kk) pr[kk].init(pitch, lane);
+    for (int kk = 0; kk < GRP; ++kk) pr[kk].init(pitch, lane);
     pb.init(W, lane);
   }
   int mom_dy[3];
@@ -1407,13 +1469,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
     return;
   }
 
-  // ---- phase A: centroid moments of the eight keypoints, four at a time
+  // ---- phase A: centroid moments of the eight keypoints, GRP at a time
   int pa[8], pq[8];   // per-lane partials of m10 and m01
 #pragma unroll
-  for (int g = 0; g < 8 / OR_GRP; ++g) {
+  for (int g = 0; g < 8 / GRP; ++g) {
 #pragma unroll
-    for (int kk = 0; kk < OR_GRP; ++kk) {
-      const int k = OR_GRP * g + kk;
+    for (int kk = 0; kk < GRP; ++kk) {
+      const int k = GRP * g + kk;
 #ifndef VUS_OR_EXP_NORAW
       if (k < n_live) {
         if constexpr (TILED) pr[kk].load(im, H, W, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
@@ -1423,23 +1485,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
       for (int u = 0; u < 3; ++u) pr[kk].v[u] = typename PatchVec<OR_VW>::type{(uint32_t)lane, (uint32_t)k};
 #endif
     }
-    if (g == 8 / OR_GRP - 1) {   // the first descriptor patch joins the queue behind the last centroid patches
+    if (g == 8 / GRP - 1) {   // the first descriptor patch joins the queue behind the last centroid patches
       if constexpr (TILED) pb.load(bl, H, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
       else pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
     }
 #pragma unroll
-    for (int kk = 0; kk < OR_GRP; ++kk) {
-      const int k = OR_GRP * g + kk;
+    for (int kk = 0; kk < GRP; ++kk) {
+      const int k = GRP * g + kk;
       pa[k] = 0;
       pq[k] = 0;
       if (k < n_live) {
         const int sh = EXACT ? 0 : (__builtin_amdgcn_readlane(my_x, k) - OR_R) & (G::ALIGN - 1);
-        const uint4* wt = s_w + sh * OR_WT + lane;
         uint32_t sx = 0;
         int si = 0, sy = 0;
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-          const uint4 w = wt[64 * u];
+          uint4 w;
+          if constexpr (TILED) {   // {moment, count} of the vector's two dwords: entries 2t + 1 - s, 2t + 2 - s
+            const uint2* wd = reinterpret_cast<const uint2*>(s_w) + (sh & 3) * OR_WTD + 1 - (sh >> 2) + 2 * lane;
+            const uint2 w0 = wd[128 * u], w1 = wd[128 * u + 1];
+            w = make_uint4(w0.x, w1.x, w0.y, w1.y);
+          } else {
+            w = s_w[sh * OR_WT + lane + 64 * u];
+          }
           sx = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.x, sx, false);
           sx = __builtin_amdgcn_udot4(pr[kk].v[u][1], w.y, sx, false);
           uint32_t rs = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.z, 0u, false);
@@ -1450,6 +1518,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
         pa[k] = (int)sx - OR_R * si;   // sum dx I over this lane's pixels
         pq[k] = sy;                    // sum dy I
       }
+    }
+  }
+  if constexpr (TILED) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int bq = min(4 * (lane & 7) + q, VUS_N_ANGLE_BINS - 1);
+      bin_cos[q] = VUS_ANGLE_COS[bq];
+      bin_sin[q] = VUS_ANGLE_SIN[bq];
     }
   }
   // reduce-scatter: afterwards the lanes of group g = lane / 8 hold the moments of keypoint g
@@ -1493,7 +1569,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VUS_OR_WPE,
   const uint4* rot = reinterpret_cast<const uint4*>(TILED ? g_rot_off_table_tiled.v : g_rot_off_table.v) + lane;
   uint4 to = rot[__builtin_amdgcn_readlane(my_bin, 0) * 64];
   for (int k = 0; k < n_live; ++k) {   // scalar loop
-    uint32_t* patch = s_blur[wave][k & 1];
+    uint32_t* patch = s_blur[wave][k & (G::BLUR_BUF - 1)];
     pb.store(patch, lane);
     const uint4 cto = to;
     const int cx = __builtin_amdgcn_readlane(my_x, k);
