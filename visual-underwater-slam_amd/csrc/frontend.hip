@@ -13,12 +13,20 @@
 //  * fast_detect stages a 144x32 byte tile (128x24 outputs + halo) in LDS once, as dwords, and
 //    derives score, non-max suppression and the 7x7 smoothing from it: the image is read from HBM
 //    once; the score map never goes to HBM (candidates leave the CU as 4-byte keys);
-//  * every thread works on strips of 4 adjacent pixels read with ds_read_b32/b64 and unpacked in
-//    registers (SDWA byte selects): byte-wide LDS reads made the first version LDS-issue bound;
-//  * scoring is two-pass: a 10-op necessary test (compass points N/S/E/W) on every pixel, survivors
-//    compacted into an LDS work list (DPP wave scan), then the exact score with v_min3/v_max3
-//    sliding windows on dense lanes; the smoothing uses v_dot4_u32_u8 on v_alignbyte windows.
-//    The integer min/max/SDWA ops issue at ~0.57x the fp32 rate on gfx950 (tools/ubench): the
+//  * the phases that walk the whole tile work on strips of 4 adjacent pixels read with ds_read_b32/b64
+//    and unpacked in registers (SDWA byte selects): byte-wide LDS reads made the first version
+//    LDS-issue bound.  The phases that walk a sparse list read the few bytes they need as bytes;
+//  * scoring is a two-stage necessary test, then the exact score.  Stage one is per strip, from the
+//    (min, max) of every staged dword recorded while staging; stage two is per pixel of the listed
+//    strips, on four opposite pairs of the circle (N/S, E/W, the two diagonals).  Survivors are
+//    compacted into an LDS work list (DPP wave scan) and the exact score runs on dense lanes, one
+//    pixel per lane, from 17 byte reads around the pixel (v_min3/v_max3 sliding windows);
+//  * non-max suppression runs over that survivor list, not over the tile: a list entry is the pixel's
+//    byte index in the LDS score tile, its eight neighbours are eight byte reads;
+//  * the 7x7 smoothing is two banded int8 GEMMs on the matrix cores (blur_tile_mfma).  In the
+//    detection launch it runs last, on three waves, while the fourth waits for the atomic that
+//    reserves the tile's slots in the candidate list;
+//  * the integer min/max/SDWA ops issue at ~0.57x the fp32 rate on gfx950 (tools/ubench): the
 //    kernel is VALU-issue bound, so the lever is instruction count, not bytes;
 //  * select_topk is an exact 4x8-bit MSB radix select + LDS bitonic sort, one workgroup per image;
 //  * orient_rbrief uses one 64-lane wave per keypoint: lane-strided disc moments, integer bin
@@ -32,71 +40,54 @@
 
 namespace {
 
-#ifndef VUS_TW
-#define VUS_TW 128
-#endif
-#ifndef VUS_TH
-#define VUS_TH 24
-#endif
-constexpr int TW = VUS_TW;              // output tile width  (1280 = 10 tiles of 128)
-constexpr int TH = VUS_TH;              // output tile height (720 = 30 tiles of 24)
-#ifndef VUS_AB_TILE   // tools/ab experiments only
-static_assert(TW == VUS_FAST_TILE_W && TH == VUS_FAST_TILE_H, "the sampling pattern of vus_fast_threshold_estimate is part of the ABI");
-#endif
+// ---- FAST tile kernels.  The -D knobs of this section: two occupancy knobs over the same code, two kinds of
+// instrumentation build.  None of them selects between algorithms.
 #ifndef VUS_FAST_WPE
 #define VUS_FAST_WPE 1    // second __launch_bounds__ argument of the tile kernels: waves per SIMD the compiler must allow
 #endif
-#ifndef VUS_NT
-#define VUS_NT 256
+#ifndef VUS_FAST_LDS_PAD
+#define VUS_FAST_LDS_PAD 0   // occupancy experiment (tools/ab): dynamic LDS nobody uses = fewer workgroups per CU, same code
 #endif
-constexpr int NTHREADS = VUS_NT;
-// LDS images are arrays of dwords = 4 horizontally adjacent pixels ("strips"); every phase reads
-// ds_read_b32/b64 and unpacks bytes in registers (byte-wide LDS reads cost ~3x the LDS cycles).
+#ifdef VUS_FAST_EXIT_AFTER   // timing builds only (tools/ab): the tile kernel stops after phase N (1 .. 5), results are wrong
+#define VUS_FAST_EXIT(N) do { if (VUS_FAST_EXIT_AFTER == (N)) return; } while (0)
+#else
+#define VUS_FAST_EXIT(N)
+#endif
+#ifdef VUS_FAST_DEBUG_COUNT   // counting build (tools/fast_counts.py): tiles, strips listed by pass 1a, pixels listed by pass 1b
+__device__ unsigned long long g_fast_dbg[4];
+extern "C" int vus_debug_fast_counters(unsigned long long* out, int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_dbg), sizeof(g_fast_dbg)) != hipSuccess) return -1;
+  if (reset) { unsigned long long z[4] = {0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_fast_dbg), z, sizeof(z)) != hipSuccess) return -1; }
+  return 0;
+}
+#endif
+
+// The tile shape is part of the ABI (the sampling pattern of vus_fast_threshold_estimate), and the kernel is written for
+// it: the smoothing takes the 32 staged rows as its K, the late phases give the last of the four waves a job of its own.
+constexpr int TW = VUS_FAST_TILE_W;     // output tile width  (1280 = 10 tiles of 128)
+constexpr int TH = VUS_FAST_TILE_H;     // output tile height (720 = 30 tiles of 24)
+constexpr int NTHREADS = 256;
+// LDS images are arrays of dwords = 4 horizontally adjacent pixels ("strips"); the phases that walk the tile read
+// ds_read_b32/b64 and unpack bytes in registers (byte-wide LDS reads cost ~3x the LDS cycles).
 constexpr int IMG_ROWS = TH + 8;        // image rows  y0-4 .. y0+TH+3
 constexpr int IMG_DW = (TW + 16) / 4;   // image cols  x0-8 .. x0+TW+7
 constexpr int SC_ROWS = TH + 2;         // score rows  y0-1 .. y0+TH
 constexpr int SC_DW = (TW + 8) / 4;     // score cols  x0-4 .. x0+TW+3
-constexpr int H_ROWS = TH + 6;          // horizontally smoothed rows y0-3 .. y0+TH+2
-constexpr int H_DW = TW / 2;            // two u16 per dword
-constexpr int STRIPS = TW / 4;
+constexpr int STRIPS = TW / 4;          // strips of an output row
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int min3i(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
 __device__ __forceinline__ int byte_of(uint32_t w, int i) { return (int)((w >> (8 * i)) & 0xFFu); }
 
-// FAST-9/16 score of pixel e (0..3) of a strip.  r[row][j]: 7 image rows x 3 dwords; the strip's
-// pixels are bytes 4..7 of each 12-byte row window.  Sliding-window min / max of the 16 circle
-// differences over every arc of 9:  w3[k] = op(d[k..k+2]),  w9[k] = op(w3[k], w3[k+3], w3[k+6]).
+// FAST-9/16 score of a pixel from the sixteen circle bytes read as BYTES around it (c = its address in the staged tile,
+// rb = bytes per staged row).  Sliding-window min / max of the 16 circle differences over every arc of 9:
+//   w3[k] = op(d[k..k+2]),  w9[k] = op(w3[k], w3[k+3], w3[k+6]).
 // Bright arcs need min(d) large, dark arcs need max(d) small (very negative).
-template <int E>
-__device__ __forceinline__ int fast_score_strip(const uint32_t (&r)[7][3]) {
-  constexpr int DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-  constexpr int DY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
-  const int p = byte_of(r[3][1], E);
-  int d[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int pos = 4 + E + DX[k];
-    d[k] = byte_of(r[3 + DY[k]][pos >> 2], pos & 3) - p;
-  }
-  int mn3[16], mx3[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    mn3[k] = min3i(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
-    mx3[k] = max3i(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
-  }
-  int best_bright = -(1 << 20), best_dark = 1 << 20;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    best_bright = max(best_bright, min3i(mn3[k], mn3[(k + 3) & 15], mn3[(k + 6) & 15]));
-    best_dark = min(best_dark, max3i(mx3[k], mx3[(k + 3) & 15], mx3[(k + 6) & 15]));
-  }
-  return max(best_bright, -best_dark) - 1;
-}
-
-// The same score from the sixteen circle bytes read as BYTES around the pixel (c = its address in the staged tile, rb = bytes
-// per staged row): 17 ds_read_u8 instead of 21 ds_read_b32 + 21 v_alignbyte that bring the pixel to a fixed byte first.
+// (Measured and not kept, round 4: the score from 7 x 3 dwords re-aligned with v_alignbyte so that the pixel sits at a
+// fixed byte -- 21 ds_read_b32 + 21 v_alignbyte against the 17 ds_read_u8 here: 2.92 against 2.89 ms per 1000 stereo
+// frames.  Round 3: the same windows on packed i16 pairs (b, 255 - b), one v_pk_min_i16 chain for bright and dark arcs --
+// 95 packed instructions + 17 v_not do not issue faster than the ~160 scalar ones: fast_detect 6.23 against 6.17 ms.)
 __device__ __forceinline__ int fast_score_bytes(const uint8_t* c, int rb) {
   constexpr int DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
   constexpr int DY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
@@ -119,90 +110,11 @@ __device__ __forceinline__ int fast_score_bytes(const uint8_t* c, int rb) {
   return max(best_bright, -best_dark) - 1;
 }
 
-// The same score on PACKED 16-bit pairs (round 3).  Lane pair (b, 255 - b) of every circle pixel --
-// one v_perm_b32 from the row dword and its complement -- so that ONE v_pk_min_i16 chain serves bright and dark arcs:
-//   min over an arc of b        = p + (bright arc's min d),      min over an arc of (255 - b) = 255 - max b,
-// and the windows double instead of tripling: w2, w4, w8, then w9 = min(w8[k], v[k+8]) -- 4 packed ops per position
-// instead of 2 x (min3 + min3/max) on scalars.  score = max(max_k w9.lo - p, max_k w9.hi - (255 - p)) - 1: identical.
-typedef short short2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int fast_score_pk(const uint32_t (&r)[7][3]) {     // pixel = byte 4 of the 12-byte windows
-  constexpr int DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-  constexpr int DY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
-  const int p = byte_of(r[3][1], 0);
-  uint32_t nr[7][2];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    nr[k][0] = ~r[k][0];
-    nr[k][1] = ~r[k][1];
-  }
-  short2_t v[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int pos = 4 + DX[k], row = 3 + DY[k], dw = pos >> 2, by = pos & 3;
-    // v_perm_b32: selector bytes 0-3 address src1 (the row), 4-7 src0 (its complement), 0x0c = constant zero
-    const uint32_t sel = (uint32_t)by | (0x0cu << 8) | ((uint32_t)(4 + by) << 16) | (0x0cu << 24);
-    v[k] = __builtin_bit_cast(short2_t, __builtin_amdgcn_perm(nr[row][dw], r[row][dw], sel));
-  }
-  short2_t w2[16], w4[16], w8[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) w2[k] = __builtin_elementwise_min(v[k], v[(k + 1) & 15]);
-#pragma unroll
-  for (int k = 0; k < 16; ++k) w4[k] = __builtin_elementwise_min(w2[k], w2[(k + 2) & 15]);
-#pragma unroll
-  for (int k = 0; k < 16; ++k) w8[k] = __builtin_elementwise_min(w4[k], w4[(k + 4) & 15]);
-  short2_t best = __builtin_elementwise_min(w8[0], v[8]);
-#pragma unroll
-  for (int k = 1; k < 16; ++k) best = __builtin_elementwise_max(best, __builtin_elementwise_min(w8[k], v[(k + 8) & 15]));
-  return max((int)best.x - p, (int)best.y - (255 - p)) - 1;
-}
-
-// Measured (MI355X, configs[1], A/B builds in one gpurun call, twice): fast_detect 6.23 / 6.25 ms packed against
-// 6.17 / 6.17 ms with the scalar v_min3 / v_max3 windows of fast_score_strip -- 95 packed instructions (64 v_pk_min_i16,
-// 15 v_pk_max_i16, 16 v_perm_b32) + 17 v_not do not issue faster than the ~160 scalar ones they replace.  Bit-exact
-// either way (tests/test_frontend_gpu.py); the scalar form stays the default.
-#ifndef VUS_FAST_PK
-#define VUS_FAST_PK 0
-#endif
-
-template <int E>
-__device__ __forceinline__ bool nms_keep(const uint32_t (&c)[3][3]) {
-  // pixel E of the strip = byte 4+E of the 12-byte windows; strict maximum of its 8 neighbours
-  const int s = byte_of(c[1][1], E);
-  int m = 0;
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      if (dy == 1 && dx == 0) continue;
-      const int pos = 4 + E + dx;
-      m = max(m, byte_of(c[dy][pos >> 2], pos & 3));
-    }
-  return s > m;
-}
-
-#ifndef VUS_FAST_STRIP
-#define VUS_FAST_STRIP 1  // strip-level pre-test from per-dword extrema before the per-pixel one (see pass 1a)
-#endif
-#ifndef VUS_BLUR_MFMA
-#define VUS_BLUR_MFMA 1   // the 7x7 smoothing as two banded int8 GEMMs on the matrix cores (see blur_tile_mfma)
-#endif
-#ifndef VUS_FAST_LATE_BLUR
-#define VUS_FAST_LATE_BLUR 1
-#endif
 constexpr int VUS_CAND_REGIONS = 8;
-#ifndef VUS_FAST_SCORE_BYTES
-#define VUS_FAST_SCORE_BYTES 1   // exact score from 17 byte reads around the pixel (2.92 -> 2.89 ms per 1000 stereo frames)
-#endif
-#ifndef VUS_FAST_MM_BYTES
-#define VUS_FAST_MM_BYTES 1   // pass 1a reads the (min, max) pairs as bytes: 3.01 -> 2.96 ms per 1000 stereo frames
-#endif
-#ifndef VUS_FAST_DIAG
-#define VUS_FAST_DIAG 1   // pre-test also on the two diagonal opposite pairs: survivors 33 % -> 25 %, 6.32 -> 6.23 ms
-#endif
 // ---- the 7 x 7 smoothing of a staged tile on the matrix cores (round 4).  Both passes of the separable filter are
 // products with a banded (Toeplitz) weight matrix, and v_mfma_i32_16x16x32_i8 computes a 16 x 16 block of such a
 // product over a K window of 32 -- the 22 inputs a 16-wide block needs fit.  Exact integer arithmetic, same result as
-// the VALU form (u16 row sums, then sum w H + 32768 >> 16):
+// the definition (u16 row sums, then sum w H + 32768 >> 16):
 //   H pass   C[row][col] = sum_k img[row][k] T[k][col]      A = 8 consecutive image bytes of a row (one ds_read_b64),
 //            B = the weights, a per-lane constant.  The bytes are unsigned and the instruction is signed: a ^ 0x80 =
 //            a - 128, and 128 * sum(w) = 32768 goes into the accumulator's initial value.
@@ -211,7 +123,8 @@ constexpr int VUS_CAND_REGIONS = 8;
 //            H pass leaves in the registers: lane (col, g) holds rows 4g..4g+3 of both 16-row blocks = its 8 K slots;
 //            the weight operand is laid out to match.  No LDS round trip between the passes, and the result arrives as
 //            4 consecutive pixels of one row per lane = one dword store.
-// Cost per tile: 48 MFMAs and ~300 VALU wave-instructions against ~980 for the VALU form (two passes through LDS).
+// Cost per tile: 48 MFMAs and ~300 VALU wave-instructions against ~980 for the two-pass VALU form through
+// LDS that it replaced (v_dot4_u32_u8 on v_alignbyte windows).
 struct BlurMfmaTable {
   uint64_t h[64];      // H pass B operand: byte s of lane (g, n) = w[8 g + s - n - 5]
   uint64_t v[2][64];   // V pass B operand of output rows 16 nb + (lane & 15)
@@ -248,10 +161,7 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
   const long bv[2] = {(long)g_blur_mfma_table.v[0][l], (long)g_blur_mfma_table.v[1][l]};
   const uint8_t* img8 = reinterpret_cast<const uint8_t*>(s_img);
   constexpr unsigned long long SIGN = 0x8080808080808080ull;
-#ifndef VUS_BLUR_UNROLL
-#define VUS_BLUR_UNROLL 1
-#endif
-#pragma unroll VUS_BLUR_UNROLL
+#pragma unroll 1   // (measured, round 4: other unroll factors change nothing)
   for (int j = j_first; j < TW / 16; j += j_step) {
     v4i32_t ch[2];
 #pragma unroll
@@ -283,9 +193,6 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
       for (int r = 0; r < 4; ++r) q[r] = ((uint32_t)chi[r] << 8) + (uint32_t)clo[r];   // < 2^24: the pixel is byte 2
       const uint32_t v = __builtin_amdgcn_perm(q[1], q[0], 0x0c0c0602u) | __builtin_amdgcn_perm(q[3], q[2], 0x06020c0cu);
       const int ly = 16 * nb + m, gy = y0 + ly, gx = x0 + 16 * j + 4 * g;
-#ifdef VUS_BLUR_EXP_NOSTORE   // timing experiment: everything but the stores (a value nobody produces keeps the result live)
-      if (v != 0x12345678u) continue;
-#endif
       if (TILED) {
         if (ly < TH && gy < H && gx < W) __builtin_memcpy(blur_out + (size_t)n * H * W + vus_tiled_offset(gy, gx, W), &v, 4);
       } else if (ly < TH && gy < H) {
@@ -302,16 +209,14 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
   }
 }
 
-#ifdef VUS_FAST_DEBUG_COUNT   // counting build (tools/fast_counts.py): tiles, strips listed by pass 1a, pixels listed by pass 1b
-__device__ unsigned long long g_fast_dbg[4];
-extern "C" int vus_debug_fast_counters(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_dbg), sizeof(g_fast_dbg)) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[4] = {0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_fast_dbg), z, sizeof(z)) != hipSuccess) return -1; }
-  return 0;
-}
-#endif
-// One 128 x 24 tile of image n.  HIST (with DETECT): the non-max-suppression survivors of the tile are not listed but
-// counted by score into hist[256 n + score] (vus_fast_threshold_estimate's sample).
+// One 128 x 24 tile of image n, in phases:
+//   staging     the 144 x 32 window into s_img, and the (min, max) of every staged dword into s_mm;
+//   pass 1a     strip pre-test from the extrema: strips that may hold a corner are listed in s_strip;
+//   pass 1b     per-pixel pre-test of the listed strips: pixels that may be corners are listed in s_work;
+//   pass 2      exact score of the listed pixels into s_score (zeroed by pass 1a);
+//   then, as the instance asks: the score tile written out (WRITE_SCORE); non-max suppression over s_work, the
+//   survivors listed as keys and copied to the image's candidate list (DETECT) or counted by score into
+//   hist[256 n + score] (DETECT + HIST: vus_fast_threshold_estimate's sample); the smoothing (BLUR).
 // TILED (the late-smoothing detection launch only): blur_out is block-tiled (include/vus_tiled.h) and the tile's image
 // goes to raw_out, block-tiled as well -- from the staged tile, by the wave that waits for the candidate atomic.
 template <bool WRITE_SCORE, bool DETECT, bool BLUR, bool HIST = false, bool REGIONS = false, bool TILED = false>
@@ -320,30 +225,27 @@ __device__ __forceinline__ void fast_tile_body(
     uint8_t* __restrict__ score_out, uint8_t* __restrict__ blur_out,
     uint32_t* __restrict__ cand_keys, int cand_cap, int* __restrict__ cand_count, int* __restrict__ hist,
     int n, int tile, int tiles_x, uint8_t* __restrict__ raw_out = nullptr) {
-  __shared__ __attribute__((aligned(8))) uint32_t s_img[IMG_ROWS * IMG_DW];
-  __shared__ uint32_t s_score[(WRITE_SCORE || DETECT) ? SC_ROWS * SC_DW : 1];
-  // the strip pre-test's tables (s_mm, s_strip) share the horizontal-blur buffer of the VALU smoothing (not written
-  // before pass 2); the matrix-core smoothing has no such buffer
-  constexpr bool STRIP = VUS_FAST_STRIP && (WRITE_SCORE || DETECT);
-  constexpr bool MFMA_BLUR = VUS_BLUR_MFMA && BLUR && IMG_ROWS == 32;
-  constexpr int AUX_DW = STRIP ? (IMG_ROWS * IMG_DW + SC_ROWS * SC_DW + 1) / 2 : 2;
-  __shared__ uint32_t s_h[(BLUR && !MFMA_BLUR && H_ROWS * H_DW > AUX_DW) ? H_ROWS * H_DW : AUX_DW];
-  __shared__ uint16_t s_work[(WRITE_SCORE || DETECT) ? SC_ROWS * SC_DW * 4 : 2];   // pixels that pass the pre-test
-#if VUS_FAST_STRIP
-  uint16_t* const s_mm = reinterpret_cast<uint16_t*>(s_h);       // min | max << 8 of each staged dword
-  uint16_t* const s_strip = s_mm + IMG_ROWS * IMG_DW;            // strips that pass the strip test
-  __shared__ int s_nstrip;
-#endif
-  __shared__ int s_cnt, s_base, s_nwork;
+  static_assert(IMG_ROWS == 32, "the smoothing (blur_tile_mfma) takes the 32 staged rows as its K");
+  constexpr bool SCORES = WRITE_SCORE || DETECT;   // the pre-tests and the exact score run; the blur-only instance skips them
   // LATE_BLUR (the detection launch proper): the smoothing runs at the END of the tile, on three waves, while the fourth
   // waits for the returning atomic that reserves the tile's slots in the image's candidate list.  The staged image then
   // has to live to the end: the candidate list moves to the strip tables' buffer (dead after pass 1b).  Otherwise the
-  // list reuses the image tile, dead after the exact scores.
-  constexpr bool LATE_BLUR = MFMA_BLUR && DETECT && !HIST && STRIP && VUS_FAST_LATE_BLUR;
+  // smoothing runs after pass 1b on all four waves, and the list reuses the image tile, dead after the exact scores.
+  constexpr bool LATE_BLUR = BLUR && DETECT && !HIST;
+  static_assert(!TILED || LATE_BLUR, "the block-tiled planes are written by the late-smoothing detection launch");
+
+  __shared__ __attribute__((aligned(8))) uint32_t s_img[IMG_ROWS * IMG_DW];
+  __shared__ uint32_t s_score[SCORES ? SC_ROWS * SC_DW : 1];
+  constexpr int AUX_DW = SCORES ? (IMG_ROWS * IMG_DW + SC_ROWS * SC_DW + 1) / 2 : 2;
+  __shared__ uint32_t s_aux[AUX_DW];                               // the strip pre-test's two u16 tables:
+  uint16_t* const s_mm = reinterpret_cast<uint16_t*>(s_aux);       // min | max << 8 of each staged dword
+  uint16_t* const s_strip = s_mm + IMG_ROWS * IMG_DW;              // strips that pass the strip test
+  __shared__ uint16_t s_work[SCORES ? SC_ROWS * SC_DW * 4 : 2];    // pixels that pass the pre-test
+  __shared__ int s_nstrip;
+  __shared__ int s_cnt, s_base, s_nwork;
   static_assert(IMG_ROWS * IMG_DW >= TW * TH / 4, "candidate list must fit in the image tile");
   static_assert(!LATE_BLUR || AUX_DW >= TW * TH / 4, "candidate list must fit in the strip tables' buffer");
-  uint32_t* const s_keys = LATE_BLUR ? s_h : s_img;
-  static_assert(!TILED || LATE_BLUR, "the block-tiled planes are written by the late-smoothing detection launch");
+  uint32_t* const s_keys = LATE_BLUR ? s_aux : s_img;
 
   const int tid = threadIdx.x;
   const int x0 = (tile % tiles_x) * TW, y0 = (tile / tiles_x) * TH;
@@ -396,46 +298,34 @@ __device__ __forceinline__ void fast_tile_body(
         const int row = r0 + RPP * k;
         if (row < IMG_ROWS) {
           s_img[row * IMG_DW + col] = v[k];
-#if VUS_FAST_STRIP
-          if (WRITE_SCORE || DETECT) {
+          if (SCORES) {
             const int b0 = byte_of(v[k], 0), b1 = byte_of(v[k], 1), b2 = byte_of(v[k], 2), b3 = byte_of(v[k], 3);
             s_mm[row * IMG_DW + col] = (uint16_t)(min(min(b0, b1), min(b2, b3)) | (max(max(b0, b1), max(b2, b3)) << 8));
           }
-#endif
         }
       }
     }
   }
-  if (tid == 0) {
-    s_cnt = 0; s_nwork = 0;
-#if VUS_FAST_STRIP
-    s_nstrip = 0;
-#endif
-  }
+  if (tid == 0) { s_cnt = 0; s_nwork = 0; s_nstrip = 0; }
   __syncthreads();
-#ifdef VUS_FAST_EXIT_AFTER   // timing builds only (tools/ab): the kernel stops after phase N, results are wrong
-#define VUS_FAST_EXIT(N) do { if (VUS_FAST_EXIT_AFTER == (N)) return; } while (0)
-#else
-#define VUS_FAST_EXIT(N)
-#endif
   VUS_FAST_EXIT(1);   // staging (+ per-dword extrema)
 
-  if (WRITE_SCORE || DETECT) {
-    // Pass 1 -- cheap necessary test on every pixel of the tile plus a ring (the 3x3 non-max
-    // suppression needs 1 pixel), one strip of 4 per item.  A 9-long arc of the 16-circle always
-    // contains one pixel of every opposite pair, so a corner needs  min over the tested pairs of max(pair) > p + thr
-    // or  max over the pairs of min(pair) < p - thr  (pairs tested: N/S, E/W and the two diagonals).  Survivors are compacted into an LDS work list (wave prefix
-    // sum with DPP, one LDS atomic per wave) so that pass 2 runs the full score on dense lanes.
-#if VUS_FAST_STRIP
+  if (SCORES) {
+    // Pass 1 -- cheap necessary test on the pixels of the tile plus a ring (the 3x3 non-max suppression needs 1 pixel),
+    // one strip of 4 per item.  A 9-long arc of the 16-circle always contains one pixel of every opposite pair, so a
+    // corner needs  min over the tested pairs of max(pair) > p + thr  or  max over the pairs of min(pair) < p - thr
+    // (pairs tested: N/S, E/W and the two diagonals).  Survivors are compacted into an LDS work list (wave prefix sum
+    // with DPP, one LDS atomic per wave) so that pass 2 runs the full score on dense lanes.
+    //
     // Pass 1a (round 4) -- an even cheaper necessary test per STRIP, from the per-dword extrema recorded while staging:
     // a pixel of the strip can pass the N/S + E/W pair test only if
     //    max(max N dword, max S dword) > min(strip) + thr  and  max(max W dword, max E dword, b0, b3) > min(strip) + thr
     // (its N/S neighbours are bytes of the dwords above / below, its W/E neighbours lie in the dword to the left plus
     // the strip's first byte / the strip's last byte plus the dword to the right), or the mirrored condition on the
     // dark side.  Measured on the configs[1] frames: 9.0 % of the strips pass at the adaptive threshold where 8.2 % hold
-    // a pixel that passes the per-pixel test, 47 % against 45 % at fast_threshold 10 (single frames on the CPU; the counting
-    // build on the bench stream says 18.2 % of a tile's strips are listed and 3.9 % of its pixels pass pass 1b).  The per-pixel test then runs on
-    // the listed strips only.
+    // a pixel that passes the per-pixel test, 47 % against 45 % at fast_threshold 10 (single frames on the CPU; the
+    // counting build on the bench stream says 18.2 % of a tile's strips are listed and 3.9 % of its pixels pass pass 1b).
+    // The per-pixel test then runs on the listed strips only.
     // Thread = fixed strip column, S_RPP rows per pass (no per-item division; the LDS addresses of a pass differ from
     // the first one's by constants).  All passes are evaluated first and listed with ONE LDS atomic per wave.
     constexpr int S_RPP = NTHREADS / SC_DW;                       // 7 rows of 34 strips per pass
@@ -454,7 +344,8 @@ __device__ __forceinline__ void fast_tile_body(
         const int gy = y0 - 1 + sr;
         if (col_ok && gy >= 3 && gy < H - 3) {
           const int ci = ci0 + it * S_RPP * IMG_DW;
-#if VUS_FAST_MM_BYTES   // the (min, max) pairs read as the two bytes they are: ten ds_read_u8 instead of five ds_read_u16 + shifts / masks
+          // the (min, max) pairs read as the two bytes they are: ten ds_read_u8 instead of five ds_read_u16 + shifts /
+          // masks (3.01 -> 2.96 ms per 1000 stereo frames)
           const uint8_t* mm8 = reinterpret_cast<const uint8_t*>(s_mm) + 2 * ci;
           const int ma_lo = mm8[0], ma_hi = mm8[1], pmin = mm8[2], pmax = mm8[3], mc_lo = mm8[4], mc_hi = mm8[5];
           const int mn_lo = mm8[2 - 6 * IMG_DW], mn_hi = mm8[3 - 6 * IMG_DW], ms_lo = mm8[2 + 6 * IMG_DW], ms_hi = mm8[3 + 6 * IMG_DW];
@@ -463,16 +354,6 @@ __device__ __forceinline__ void fast_tile_body(
           const int hi = min(max(mn_hi, ms_hi), max3i(ma_hi, mc_hi, max(b0, b3)));
           const int lo = max(min(mn_lo, ms_lo), min3i(ma_lo, mc_lo, min(b0, b3)));
           pass[it] = hi > pmin + thr || lo < pmax - thr;
-#else
-          const int ma = s_mm[ci], mb = s_mm[ci + 1], mc = s_mm[ci + 2];
-          const int mn = s_mm[ci + 1 - 3 * IMG_DW], ms = s_mm[ci + 1 + 3 * IMG_DW];
-          const uint32_t b = s_img[ci + 1];
-          const int b0 = byte_of(b, 0), b3 = byte_of(b, 3);
-          const int pmin = mb & 0xFF, pmax = mb >> 8;
-          const int hi = min(max(mn >> 8, ms >> 8), max3i(ma >> 8, mc >> 8, max(b0, b3)));
-          const int lo = max(min(mn & 0xFF, ms & 0xFF), min3i(ma & 0xFF, mc & 0xFF, min(b0, b3)));
-          pass[it] = hi > pmin + thr || lo < pmax - thr;
-#endif
         }
         s_score[sr * SC_DW + ss] = 0u;
       }
@@ -499,6 +380,7 @@ __device__ __forceinline__ void fast_tile_body(
 #ifdef VUS_FAST_DEBUG_COUNT
     if (tid == 0 && BLUR) { atomicAdd(&g_fast_dbg[0], 1ull); atomicAdd(&g_fast_dbg[1], (unsigned long long)nstrip); }
 #endif
+    // Pass 1b -- the per-pixel test, one listed strip per lane.
     // (Measured and not kept, round 4: the same test with one PIXEL per lane -- nine byte reads, no v_alignbyte / v_bfe,
     // work spread over all four waves: bit-exact, 3.00 against 2.92 ms per 1000 stereo frames.  A tile lists 161 of its
     // 884 strips here and 138 of their pixels go on to the exact score, tools/fast_counts.py.)
@@ -509,49 +391,33 @@ __device__ __forceinline__ void fast_tile_body(
         idx = s_strip[j];
         const int sr = idx / SC_DW, ss = idx - sr * SC_DW;
         const int gx = x0 - 4 + 4 * ss;
-        {
-#else
-    for (int idx0 = 0; idx0 < SC_ROWS * SC_DW; idx0 += NTHREADS) {   // uniform trip count (wave scans inside)
-      const int idx = idx0 + tid;
-      int mask = 0;
-      if (idx < SC_ROWS * SC_DW) {
-        const int sr = idx / SC_DW, ss = idx - sr * SC_DW;
-        const int gy = y0 - 1 + sr, gx = x0 - 4 + 4 * ss;
-        if (gy >= 3 && gy < H - 3 && gx + 3 >= 3 && gx < W - 3) {
-#endif
-          const uint32_t* cp = &s_img[(sr + 3) * IMG_DW + ss];
-          const uint32_t a = cp[0], b = cp[1], c = cp[2];
-          const uint32_t nn = s_img[sr * IMG_DW + ss + 1], so = s_img[(sr + 6) * IMG_DW + ss + 1];
-          const uint32_t wv = __builtin_amdgcn_alignbyte(b, a, 1);   // bytes x-3 of the 4 pixels
-          const uint32_t ev = __builtin_amdgcn_alignbyte(c, b, 3);   // bytes x+3
-#if VUS_FAST_DIAG
-          // the diagonal opposite pairs of the circle, (x+2,y-2)/(x-2,y+2) and (x+2,y+2)/(x-2,y-2)
-          const uint32_t* up = &s_img[(sr + 1) * IMG_DW + ss];
-          const uint32_t* dn = &s_img[(sr + 5) * IMG_DW + ss];
-          const uint32_t nev = __builtin_amdgcn_alignbyte(up[2], up[1], 2), nwv = __builtin_amdgcn_alignbyte(up[1], up[0], 2);
-          const uint32_t sev = __builtin_amdgcn_alignbyte(dn[2], dn[1], 2), swv = __builtin_amdgcn_alignbyte(dn[1], dn[0], 2);
-#endif
+        const uint32_t* cp = &s_img[(sr + 3) * IMG_DW + ss];
+        const uint32_t a = cp[0], b = cp[1], c = cp[2];
+        const uint32_t nn = s_img[sr * IMG_DW + ss + 1], so = s_img[(sr + 6) * IMG_DW + ss + 1];
+        const uint32_t wv = __builtin_amdgcn_alignbyte(b, a, 1);   // bytes x-3 of the 4 pixels
+        const uint32_t ev = __builtin_amdgcn_alignbyte(c, b, 3);   // bytes x+3
+        // the diagonal opposite pairs of the circle, (x+2,y-2)/(x-2,y+2) and (x+2,y+2)/(x-2,y-2): with them 25 % of the
+        // pixels pass the pre-test instead of 33 %, fast_detect 6.32 -> 6.23 ms.  (Measured and not kept: all eight
+        // opposite pairs -- 22.7 % pass, the four more pairs cost more than the fewer exact scores save.)
+        const uint32_t* up = &s_img[(sr + 1) * IMG_DW + ss];
+        const uint32_t* dn = &s_img[(sr + 5) * IMG_DW + ss];
+        const uint32_t nev = __builtin_amdgcn_alignbyte(up[2], up[1], 2), nwv = __builtin_amdgcn_alignbyte(up[1], up[0], 2);
+        const uint32_t sev = __builtin_amdgcn_alignbyte(dn[2], dn[1], 2), swv = __builtin_amdgcn_alignbyte(dn[1], dn[0], 2);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int p = byte_of(b, e);
-            const int n_ = byte_of(nn, e), s_ = byte_of(so, e), w_ = byte_of(wv, e), e_ = byte_of(ev, e);
-            int hi = min(max(n_, s_), max(e_, w_)), lo = max(min(n_, s_), min(e_, w_));
-#if VUS_FAST_DIAG
-            const int ne = byte_of(nev, e), sw = byte_of(swv, e), se = byte_of(sev, e), nw = byte_of(nwv, e);
-            hi = min3i(hi, max(ne, sw), max(se, nw));
-            lo = max3i(lo, min(ne, sw), min(se, nw));
-#endif
-            mask |= (hi > p + thr || lo < p - thr) ? (1 << e) : 0;
-          }
-          if (gx < 3 || gx + 3 >= W - 3) {   // strips straddling the 3-pixel frame (edge tiles only)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (gx + e < 3 || gx + e >= W - 3) mask &= ~(1 << e);
-          }
+        for (int e = 0; e < 4; ++e) {
+          const int p = byte_of(b, e);
+          const int n_ = byte_of(nn, e), s_ = byte_of(so, e), w_ = byte_of(wv, e), e_ = byte_of(ev, e);
+          int hi = min(max(n_, s_), max(e_, w_)), lo = max(min(n_, s_), min(e_, w_));
+          const int ne = byte_of(nev, e), sw = byte_of(swv, e), se = byte_of(sev, e), nw = byte_of(nwv, e);
+          hi = min3i(hi, max(ne, sw), max(se, nw));
+          lo = max3i(lo, min(ne, sw), min(se, nw));
+          mask |= (hi > p + thr || lo < p - thr) ? (1 << e) : 0;
         }
-#if !VUS_FAST_STRIP
-        s_score[idx] = 0u;
-#endif
+        if (gx < 3 || gx + 3 >= W - 3) {   // strips straddling the 3-pixel frame (edge tiles only)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (gx + e < 3 || gx + e >= W - 3) mask &= ~(1 << e);
+        }
       }
       const int cnt = __popc(mask);
       int incl = cnt;   // inclusive wave scan (same DPP sequence as wave_sum_i32)
@@ -571,64 +437,24 @@ __device__ __forceinline__ void fast_tile_body(
         if (mask & (1 << e)) s_work[pos++] = (uint16_t)(idx * 4 + e);
     }
   }
-  auto blur_rows = [&]() {
-    // horizontal 7-tap pass: 4 outputs per item from 3 dwords, two v_dot4_u32_u8 per output
-    constexpr uint32_t W0123 = 18u | (33u << 8) | (49u << 16) | (56u << 24);
-    constexpr uint32_t W456 = 49u | (33u << 8) | (18u << 16);
-    for (int idx = tid; idx < H_ROWS * STRIPS; idx += NTHREADS) {
-      const int hr = idx / STRIPS, hs = idx - hr * STRIPS;
-      const uint32_t* rp = &s_img[(hr + 1) * IMG_DW + hs + 1];
-      const uint32_t a = rp[0], b = rp[1], c = rp[2];
-      // output e covers bytes (1+e)..(7+e) of the 12-byte window {a,b,c}
-      const uint32_t o0 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(b, a, 1), W0123, 0u, false) +
-                          __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(c, b, 1), W456, 0u, false);
-      const uint32_t o1 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(b, a, 2), W0123, 0u, false) +
-                          __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(c, b, 2), W456, 0u, false);
-      const uint32_t o2 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(b, a, 3), W0123, 0u, false) +
-                          __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(c, b, 3), W456, 0u, false);
-      const uint32_t o3 = __builtin_amdgcn_udot4(b, W0123, 0u, false) + __builtin_amdgcn_udot4(c, W456, 0u, false);
-      uint2 out = make_uint2(o0 | (o1 << 16), o2 | (o3 << 16));
-      *reinterpret_cast<uint2*>(&s_h[hr * H_DW + 2 * hs]) = out;
-    }
-  };
 #ifdef VUS_FAST_DEBUG_COUNT
   __syncthreads();
-  if (tid == 0 && BLUR && (WRITE_SCORE || DETECT)) atomicAdd(&g_fast_dbg[2], (unsigned long long)s_nwork);
+  if (tid == 0 && BLUR && SCORES) atomicAdd(&g_fast_dbg[2], (unsigned long long)s_nwork);
 #endif
   VUS_FAST_EXIT(3);   // + per-pixel pre-test of the listed strips
-  if (BLUR && !MFMA_BLUR && !STRIP) blur_rows();
-  if (MFMA_BLUR && !LATE_BLUR) blur_tile_mfma(s_img, blur_out, n, H, W, x0, y0, tid, tid >> 6, NTHREADS / 64);   // reads the staged tile only: no barrier of its own
+  if (BLUR && !LATE_BLUR) blur_tile_mfma(s_img, blur_out, n, H, W, x0, y0, tid, tid >> 6, NTHREADS / 64);   // reads the staged tile only: no barrier of its own
   __syncthreads();
   VUS_FAST_EXIT(4);   // + smoothing
 
-  if (BLUR && !MFMA_BLUR && STRIP) blur_rows();   // after the barrier: its buffer held the strip tables until here
-  if (WRITE_SCORE || DETECT) {
-    // Pass 2 -- exact FAST score of the survivors, one pixel per lane.  The 12-byte row windows are
-    // re-aligned with v_alignbyte so that the pixel sits at byte 4 and the strip code (E = 0) applies.
+  if (SCORES) {
+    // Pass 2 -- exact FAST score of the survivors, one pixel per lane, from the bytes around it in the staged tile.
     const int nwork = s_nwork;
     uint8_t* score8 = reinterpret_cast<uint8_t*>(s_score);
     for (int j = tid; j < nwork; j += NTHREADS) {
       const int ent = s_work[j];
       const int idx = ent >> 2, e = ent & 3;
       const int sr = idx / SC_DW, ss = idx - sr * SC_DW;
-#if VUS_FAST_SCORE_BYTES
       const int sc = fast_score_bytes(reinterpret_cast<const uint8_t*>(s_img) + (sr + 3) * (4 * IMG_DW) + 4 * (ss + 1) + e, 4 * IMG_DW);
-#else
-      uint32_t r[7][3];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const uint32_t* rp = &s_img[(sr + k) * IMG_DW + ss];
-        const uint32_t a = rp[0], b = rp[1], c = rp[2];
-        r[k][0] = __builtin_amdgcn_alignbyte(b, a, e);
-        r[k][1] = __builtin_amdgcn_alignbyte(c, b, e);
-        r[k][2] = c >> (8 * e);
-      }
-#if VUS_FAST_PK
-      const int sc = fast_score_pk(r);
-#else
-      const int sc = fast_score_strip<0>(r);
-#endif
-#endif
       if (sc >= thr) score8[ent] = (uint8_t)sc;
     }
     __syncthreads();
@@ -645,34 +471,6 @@ __device__ __forceinline__ void fast_tile_body(
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           if (gx + e < W) o[e] = (uint8_t)(v >> (8 * e));
-      }
-    }
-  }
-  if (BLUR && !MFMA_BLUR) {
-    constexpr int BW[7] = {18, 33, 49, 56, 49, 33, 18};
-    for (int idx = tid; idx < TH * STRIPS; idx += NTHREADS) {
-      const int ly = idx / STRIPS, ls = idx - ly * STRIPS;
-      const int gy = y0 + ly, gx = x0 + 4 * ls;
-      uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const uint2 h = *reinterpret_cast<const uint2*>(&s_h[(ly + k) * H_DW + 2 * ls]);
-        a0 += (uint32_t)BW[k] * (h.x & 0xFFFFu);
-        a1 += (uint32_t)BW[k] * (h.x >> 16);
-        a2 += (uint32_t)BW[k] * (h.y & 0xFFFFu);
-        a3 += (uint32_t)BW[k] * (h.y >> 16);
-      }
-      const uint32_t v = ((a0 + 32768u) >> 16) | (((a1 + 32768u) >> 16) << 8) | (((a2 + 32768u) >> 16) << 16) |
-                         (((a3 + 32768u) >> 16) << 24);
-      if (gy < H) {
-        uint8_t* o = blur_out + ((size_t)n * H + gy) * W + gx;
-        if (gx + 3 < W) {
-          __builtin_memcpy(o, &v, 4);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (gx + e < W) o[e] = (uint8_t)(v >> (8 * e));
-        }
       }
     }
   }
@@ -2470,9 +2268,6 @@ extern "C" int vus_fast_detect_adaptive(const uint8_t* img, int n_img, int H, in
   if (n_img == 0) return VUS_OK;
   hipStream_t st = vus::as_stream(stream);
   const TileGrid g = tile_grid(n_img, H, W);
-#ifndef VUS_FAST_LDS_PAD
-#define VUS_FAST_LDS_PAD 0   // occupancy experiment (tools/ab): dynamic LDS nobody uses = fewer workgroups per CU, same code
-#endif
   // with room for it, the list is filled as eight sub-lists and compacted afterwards (fast_tile_body, REGIONS)
   const bool regions = blur_out != nullptr && cand_cap >= 64 * VUS_CAND_REGIONS;
   if (regions) {
