@@ -28,11 +28,13 @@
 //    reserves the tile's slots in the candidate list;
 //  * the integer min/max/SDWA ops issue at ~0.57x the fp32 rate on gfx950 (tools/ubench): the
 //    kernel is VALU-issue bound, so the lever is instruction count, not bytes;
-//  * select_topk is an exact 4x8-bit MSB radix select + LDS bitonic sort, one workgroup per image;
+//  * select_topk is an exact MSB radix select (score byte, then the boundary bucket alone) + a bitonic sort held in
+//    registers, one workgroup per image;
 //  * orient_rbrief uses one 64-lane wave per keypoint: lane-strided disc moments, integer bin
 //    choice, and the descriptor words come straight out of __ballot (lane = test bit);
 //  * hamming_match keeps the train descriptors in LDS (broadcast reads) and one query per lane.
 #include "vus_common.h"
+#include <algorithm>
 #include <type_traits>
 #define VUS_TABLE_QUAL __device__ constexpr
 #include "../../include/vus_orb_tables.h"
@@ -708,96 +710,233 @@ __global__ __launch_bounds__(NTHREADS, VUS_FAST_WPE) void fast_retry_kernel(cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// Exact top-K: the max_kp smallest (unique) keys of one image, ascending.
-constexpr int SEL_THREADS = 1024;
+// Exact top-K: the max_kp smallest keys of one image, ascending.  One workgroup of sort_n / 8 threads per image
+// (sort_n = max_kp rounded up to a power of two, 2048 at least: 256 to 1024 threads).
+//  * The score byte (bits 24 .. 31) decides nearly everything: one histogram pass over it (a histogram per wave, summed
+//    and scanned by wave 0) finds the bucket b that holds the max_kp-th smallest key.  Keys of lower buckets are kept
+//    outright; only the keys of bucket b -- typically tens -- are looked at again.
+//  * Up to SEL_RANK_MAX boundary keys are ranked against each other in LDS.  A longer boundary bucket (an image with
+//    one score) takes three more 8-bit radix passes over the list in global memory, as every image did before.
+//  * The candidates are read from global memory once: a lane keeps its first SEL_CACHE in registers.  The tail of a
+//    longer list (more than SEL_CACHE * blockDim.x candidates) is streamed again in the second pass.
+//  * The kept keys (all below the threshold key T, so fewer than max_kp) are sorted by a bitonic network with SEL_E keys
+//    per lane in registers: partner distances below SEL_E are exchanges inside a lane, those below 64 * SEL_E are wave
+//    shuffles, and only the remaining ones (3 of the 66 stages at 2048 keys) go through LDS between two barriers.
+//    The output is those keys, then T as often as the list holds it up to max_kp (keys are unique except for
+//    VUS_KEY_INVALID entries of an overflowed list), then VUS_KEY_INVALID.
+constexpr int SEL_THREADS = 1024;   // select_grid_kernel; the largest workgroup of select_topk_kernel
+constexpr int SEL_E = 8;            // keys per lane in the register sort
+constexpr int SEL_CACHE = 16;       // candidates per lane kept in registers between the two passes
+constexpr int SEL_RANK_MAX = 256;   // boundary-bucket keys ranked directly in LDS
+
+// inclusive scan over the 64 lanes of a wave (DPP row shifts / broadcasts)
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xe, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xc, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
+  return v;
+}
+
+// Wave 0: sum the n_copies histograms of 256 bins, find the bin that holds the kk-th smallest key (kk >= 1, at most the
+// number of keys counted) and publish it: *s_thr |= bin << shift, *s_k = rank inside the bin, *s_nb = keys in the bin.
+__device__ __forceinline__ void sel_pick_bucket(const int* s_hist, int n_copies, int kk, int shift, uint32_t* s_thr, int* s_k,
+                                                int* s_nb) {
+  const int lane = threadIdx.x;   // callers pass threads 0 .. 63 only
+  int h[4], tot = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    int v = 0;
+    for (int w = 0; w < n_copies; ++w) v += s_hist[w * 256 + 4 * lane + q];
+    h[q] = v;
+    tot += v;
+  }
+  int excl = wave_incl_scan(tot) - tot;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (excl < kk && kk <= excl + h[q]) {   // exactly one (lane, q)
+      *s_thr |= (uint32_t)(4 * lane + q) << shift;
+      *s_k = kk - excl;
+      *s_nb = h[q];
+    }
+    excl += h[q];
+  }
+}
+
+// Append k to s_sort for the lanes with `take` set: one LDS atomic per wave.  Every lane of the wave calls it.
+__device__ __forceinline__ void sel_append(bool take, uint32_t k, uint32_t* s_sort, int sort_n, int* s_out) {
+  const uint64_t m = __ballot(take);
+  if (m == 0) return;
+  const int lane = threadIdx.x & 63;
+  const int leader = __ffsll((unsigned long long)m) - 1;
+  int base = 0;
+  if (lane == leader) base = atomicAdd(s_out, __popcll(m));
+  base = __shfl(base, leader);
+  const int p = base + __popcll(m & ((1ull << lane) - 1));
+  if (take && p < sort_n) s_sort[p] = k;
+}
 
 __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(
     const uint32_t* __restrict__ cand_keys, const int* __restrict__ cand_count, int cand_cap,
     int max_kp, int sort_n, uint32_t* __restrict__ kp_keys, int* __restrict__ kp_count) {
-  extern __shared__ uint32_t s_sort[];
-  __shared__ int s_hist[256];
-  __shared__ int s_scan[256];
-  __shared__ int s_wtot[4];
-  __shared__ uint32_t s_prefix;
-  __shared__ int s_k, s_out;
-  const int tid = threadIdx.x;
+  extern __shared__ uint32_t s_sort[];              // [sort_n] kept keys, then the exchange buffer of the sort
+  __shared__ uint32_t s_bnd[SEL_RANK_MAX];          // keys of the boundary bucket
+  __shared__ uint32_t s_thr;
+  __shared__ int s_k, s_nb, s_out, s_fill;
+  const int tid = threadIdx.x, NT = blockDim.x, n_waves = NT >> 6;   // the workgroup size NT == sort_n / SEL_E, a multiple of 64
+  int* s_hist = reinterpret_cast<int*>(s_sort + sort_n);            // [n_waves][256]
   const int n = blockIdx.x;
   const uint32_t* keys = cand_keys + (size_t)n * cand_cap;
   const int cnt = min(cand_count[n], cand_cap);
   const int K = min(cnt, max_kp);
 
-  uint32_t T = 0xFFFFFFFFu;  // keep everything
-  if (cnt > max_kp) {
-    // 4 passes of 8 bits, most significant first: afterwards prefix == the K-th smallest key
-    if (tid == 0) { s_prefix = 0; s_k = max_kp; }
-    uint32_t mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      for (int i = tid; i < 256; i += SEL_THREADS) s_hist[i] = 0;
-      __syncthreads();
-      const uint32_t prefix = s_prefix;
-      for (int i = tid; i < cnt; i += SEL_THREADS) {
-        uint32_t k = keys[i];
-        if ((k & mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255], 1);
-      }
-      __syncthreads();
-      // the bucket that holds the k-th smallest key: parallel inclusive scan of the 256 counts (a one-thread
-      // walk over the bins cost 10 us per pass)
-      const int kk = s_k;
-      __syncthreads();   // everybody has read s_k and s_prefix before they are rewritten
-      if (tid < 256) {
-        const int h = s_hist[tid];
-        int incl = h;   // inclusive scan inside the wave (DPP row shifts / broadcasts)
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true);
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true);
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xe, true);
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xc, true);
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, true);
-        incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, true);
-        if ((tid & 63) == 63) s_wtot[tid >> 6] = incl;
-        s_scan[tid] = incl;
-      }
-      __syncthreads();
-      if (tid < 256) {
-        int base = 0;
-        for (int w = 0; w < (tid >> 6); ++w) base += s_wtot[w];
-        const int incl = s_scan[tid] + base, excl = incl - s_hist[tid];
-        if (excl < kk && kk <= incl) {   // exactly one bucket
-          s_prefix = prefix | ((uint32_t)tid << shift);
-          s_k = kk - excl;
+  uint32_t r[SEL_CACHE];
+#pragma unroll
+  for (int u = 0; u < SEL_CACHE; ++u) r[u] = tid + u * NT < cnt ? keys[tid + u * NT] : VUS_KEY_INVALID;
+  for (int i = tid; i < sort_n; i += NT) s_sort[i] = VUS_KEY_INVALID;
+
+  uint32_t thr = VUS_KEY_INVALID;   // the K-th smallest key
+  int n_below = K;                  // how many keys of the output lie below thr
+  if (cnt <= max_kp) {              // keep everything: cnt <= max_kp <= sort_n
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < SEL_CACHE; ++u)
+      if (tid + u * NT < cnt) s_sort[tid + u * NT] = r[u];
+    for (int i = tid + SEL_CACHE * NT; i < cnt; i += NT) s_sort[i] = keys[i];
+  } else {
+    for (int i = tid; i < n_waves * 256; i += NT) s_hist[i] = 0;
+    if (tid == 0) { s_thr = 0; s_out = 0; s_fill = 0; }
+    __syncthreads();
+    int* my_hist = s_hist + (tid >> 6) * 256;
+#pragma unroll
+    for (int u = 0; u < SEL_CACHE; ++u)
+      if (tid + u * NT < cnt) atomicAdd(&my_hist[r[u] >> 24], 1);
+    for (int i = tid + SEL_CACHE * NT; i < cnt; i += NT) atomicAdd(&my_hist[keys[i] >> 24], 1);
+    __syncthreads();
+    if (tid < 64) sel_pick_bucket(s_hist, n_waves, max_kp, 24, &s_thr, &s_k, &s_nb);
+    __syncthreads();
+    const uint32_t bucket = s_thr >> 24;
+    const int kk = s_k, n_bnd = s_nb;
+    const bool ranked = n_bnd <= SEL_RANK_MAX;
+    // second pass: lower buckets are kept, the boundary bucket is set aside
+#pragma unroll
+    for (int u = 0; u < SEL_CACHE; ++u) {
+      const bool valid = tid + u * NT < cnt;
+      const uint32_t b = r[u] >> 24;
+      sel_append(valid && b < bucket, r[u], s_sort, sort_n, &s_out);
+      if (ranked && valid && b == bucket) s_bnd[atomicAdd(&s_fill, 1) & (SEL_RANK_MAX - 1)] = r[u];   // n_bnd of them
+    }
+    for (int i0 = SEL_CACHE * NT; i0 < cnt; i0 += NT) {
+      const bool valid = i0 + tid < cnt;
+      const uint32_t k = valid ? keys[i0 + tid] : VUS_KEY_INVALID;
+      sel_append(valid && (k >> 24) < bucket, k, s_sort, sort_n, &s_out);
+      if (ranked && valid && (k >> 24) == bucket) s_bnd[atomicAdd(&s_fill, 1) & (SEL_RANK_MAX - 1)] = k;
+    }
+    __syncthreads();
+    if (ranked) {
+      // x is the kk-th smallest of the bucket iff  #(y < x) < kk <= #(y <= x);  x lies below it iff #(y <= x) < kk
+      for (int t = tid; t < n_bnd; t += NT) {
+        const uint32_t x = s_bnd[t];
+        int less = 0, leq = 0;
+        for (int q = 0; q < n_bnd; ++q) {
+          const uint32_t y = s_bnd[q];
+          less += y < x;
+          leq += y <= x;
+        }
+        if (less < kk && kk <= leq) { s_thr = x; s_k = kk - less; }   // equal keys write equal values
+        if (leq < kk) {
+          const int p = atomicAdd(&s_out, 1);
+          if (p < sort_n) s_sort[p] = x;
         }
       }
-      mask |= 0xFFu << shift;
-      __syncthreads();
+    } else {
+      // three more radix passes over the keys that carry the prefix found so far
+      uint32_t mask = 0xFF000000u;
+      for (int shift = 16; shift >= 0; shift -= 8) {
+        for (int i = tid; i < 256; i += NT) s_hist[i] = 0;
+        __syncthreads();
+        const uint32_t prefix = s_thr;
+        const int kq = s_k;
+        for (int i = tid; i < cnt; i += NT) {
+          const uint32_t k = keys[i];
+          if ((k & mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (tid < 64) sel_pick_bucket(s_hist, 1, kq, shift, &s_thr, &s_k, &s_nb);
+        mask |= 0xFFu << shift;
+        __syncthreads();
+      }
+      const uint32_t t_key = s_thr;
+      for (int i0 = 0; i0 < cnt; i0 += NT) {
+        const bool valid = i0 + tid < cnt;
+        const uint32_t k = valid ? keys[i0 + tid] : VUS_KEY_INVALID;
+        sel_append(valid && (k >> 24) == bucket && k < t_key, k, s_sort, sort_n, &s_out);
+      }
     }
-    T = s_prefix;
-  }
-  for (int i = tid; i < sort_n; i += SEL_THREADS) s_sort[i] = VUS_KEY_INVALID;
-  if (tid == 0) s_out = 0;
-  __syncthreads();
-  for (int i = tid; i < cnt; i += SEL_THREADS) {
-    uint32_t k = keys[i];
-    if (k <= T) {
-      int p = atomicAdd(&s_out, 1);
-      if (p < sort_n) s_sort[p] = k;
-    }
+    __syncthreads();
+    thr = s_thr;
+    n_below = max_kp - s_k;   // == s_out
   }
   __syncthreads();
-  // bitonic sort, ascending
-  for (int k = 2; k <= sort_n; k <<= 1) {
+
+  // bitonic sort, ascending; lane tid holds elements tid * SEL_E .. tid * SEL_E + SEL_E - 1
+  uint32_t a[SEL_E];
+#pragma unroll
+  for (int e = 0; e < SEL_E; ++e) a[e] = s_sort[tid * SEL_E + e];
+#pragma unroll
+  for (int k = 2; k < SEL_E; k <<= 1) {
+#pragma unroll
     for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < sort_n; i += SEL_THREADS) {
-        int l = i ^ j;
-        if (l > i) {
-          uint32_t a = s_sort[i], b = s_sort[l];
-          bool up = (i & k) == 0;
-          if ((a > b) == up) { s_sort[i] = b; s_sort[l] = a; }
+#pragma unroll
+      for (int e = 0; e < SEL_E; ++e) {
+        if ((e ^ j) > e) {
+          const uint32_t lo = min(a[e], a[e ^ j]), hi = max(a[e], a[e ^ j]);
+          const bool up = (e & k) == 0;
+          a[e] = up ? lo : hi;
+          a[e ^ j] = up ? hi : lo;
         }
       }
-      __syncthreads();
     }
   }
-  for (int i = tid; i < max_kp; i += SEL_THREADS)
-    kp_keys[(size_t)n * max_kp + i] = i < K ? s_sort[i] : VUS_KEY_INVALID;
+  for (int k = SEL_E; k <= sort_n; k <<= 1) {
+    const bool up = ((tid * SEL_E) & k) == 0;   // k >= SEL_E: one direction for all of a lane's keys
+    for (int j = k >> 1; j >= SEL_E; j >>= 1) {
+      const int pj = j / SEL_E;                 // the partner is lane tid ^ pj
+      const bool keep_min = ((tid & pj) == 0) == up;
+      uint32_t b[SEL_E];
+      if (pj >= 64) {                           // another wave: through LDS, [e][tid] so that lanes hit distinct banks
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < SEL_E; ++e) s_sort[e * NT + tid] = a[e];
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < SEL_E; ++e) b[e] = s_sort[e * NT + (tid ^ pj)];
+      } else {
+#pragma unroll
+        for (int e = 0; e < SEL_E; ++e) b[e] = (uint32_t)__shfl_xor((int)a[e], pj);
+      }
+#pragma unroll
+      for (int e = 0; e < SEL_E; ++e) a[e] = keep_min ? min(a[e], b[e]) : max(a[e], b[e]);
+    }
+#pragma unroll
+    for (int j = SEL_E >> 1; j > 0; j >>= 1) {
+#pragma unroll
+      for (int e = 0; e < SEL_E; ++e) {
+        if ((e ^ j) > e) {
+          const uint32_t lo = min(a[e], a[e ^ j]), hi = max(a[e], a[e ^ j]);
+          a[e] = up ? lo : hi;
+          a[e ^ j] = up ? hi : lo;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < SEL_E; ++e) {
+    const int i = tid * SEL_E + e;
+    if (i < max_kp) kp_keys[(size_t)n * max_kp + i] = i < n_below ? a[e] : (i < K ? thr : VUS_KEY_INVALID);
+  }
   if (tid == 0) kp_count[n] = K;
 }
 
@@ -1417,7 +1556,7 @@ __global__ __launch_bounds__(256) void hamming_match_kernel(
   const int p = blockIdx.y;
   const int qi = q_index[p], ti = t_index[p];
   const int i = blockIdx.x * 256 + tid;
-  const int nq = kp_count[qi], nt = kp_count[ti];
+  const int nq = min(kp_count[qi], max_kp), nt = min(kp_count[ti], max_kp);   // a count above max_kp is clamped
   const bool active = i < nq;
   uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
   int yq = 0, xq = 0;
@@ -1468,7 +1607,9 @@ __global__ __launch_bounds__(256) void hamming_match_kernel(
 // train set is bucketed by image row in LDS (counting sort) and each query lane visits the ~30
 // keypoints of its 2*max_dy+1 rows instead of all 2000.  Ties are broken on the train index
 // explicitly, so the visiting order does not matter and the result equals the brute-force scan.
-__global__ __launch_bounds__(256) void hamming_match_rows_kernel(
+// This variant keeps only the index table in LDS and gathers the train descriptors from global memory, 256 queries
+// per workgroup: it serves the sizes whose train set does not fit into LDS whole (hamming_match_rows_kernel below).
+__global__ __launch_bounds__(256) void hamming_match_rows_gather_kernel(
     const uint64_t* __restrict__ desc, const uint32_t* __restrict__ kp_keys,
     const int* __restrict__ kp_count, int max_kp, int W, int Hrows, const int* __restrict__ q_index,
     const int* __restrict__ t_index, int max_dy, int min_disp, int max_disp, int max_dist,
@@ -1538,6 +1679,115 @@ __global__ __launch_bounds__(256) void hamming_match_rows_kernel(
     }
   }
   if (i < max_kp) {
+    if (bidx < 0) best = 512;
+    else if (best > max_dist) bidx = -1;
+    idx_out[(size_t)p * max_kp + i] = bidx;
+    dist_out[(size_t)p * max_kp + i] = best;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row-gated Hamming with the whole train set in LDS: ONE workgroup per pair buckets the train keypoints by row once
+// and stores them in row order -- descriptor (32 B), x and original index -- so a query lane walks one contiguous LDS
+// range, start[y - max_dy] .. start[y + max_dy + 1], tests the disparity on the LDS-resident x and only then reads the
+// descriptor, also from LDS.  At 2000 keypoints and 720 rows that is 78 KB: two workgroups per CU.
+// A thread stages at most HR_PER train keypoints (blockDim.x * HR_PER >= max_kp, the host's choice).
+constexpr int HR_THREADS = 1024;
+constexpr int HR_PER = 2;
+
+__host__ __device__ constexpr size_t hamming_rows_lds(int max_kp, int h_rows) {
+  return (size_t)max_kp * 32 + (size_t)max_kp * 4 + ((size_t)2 * h_rows + 1) * 4;
+}
+
+__global__ __launch_bounds__(HR_THREADS) void hamming_match_rows_kernel(
+    const uint64_t* __restrict__ desc, const uint32_t* __restrict__ kp_keys,
+    const int* __restrict__ kp_count, int max_kp, int W, int Hrows, const int* __restrict__ q_index,
+    const int* __restrict__ t_index, int max_dy, int min_disp, int max_disp, int max_dist,
+    int32_t* __restrict__ idx_out, int32_t* __restrict__ dist_out) {
+  extern __shared__ uint4 s_rows[];
+  uint4* s_desc = s_rows;                                               // [max_kp][2] descriptors in row order
+  uint32_t* s_xi = reinterpret_cast<uint32_t*>(s_desc + 2 * (size_t)max_kp);   // [max_kp] x | train index << 16
+  int* s_start = reinterpret_cast<int*>(s_xi + max_kp);                 // [Hrows + 1] first slot of every row
+  int* s_cursor = s_start + (Hrows + 1);                                // [Hrows]
+  __shared__ int s_wsum[HR_THREADS / 64];
+  const int tid = threadIdx.x, T = blockDim.x;
+  const int p = blockIdx.x;
+  const int qi = q_index[p], ti = t_index[p];
+  const int nq = min(kp_count[qi], max_kp), nt = min(kp_count[ti], max_kp);
+  const uint32_t* kt = kp_keys + (size_t)ti * max_kp;
+  const uint64_t* dt = desc + (size_t)ti * max_kp * 4;
+  for (int r = tid; r <= Hrows; r += T) s_start[r] = 0;
+  __syncthreads();
+  // this thread's train keypoints: row count, and the descriptor on its way while the rows are scanned
+  int t_yx[HR_PER];
+  uint64_t t_d[HR_PER][4];
+#pragma unroll
+  for (int u = 0; u < HR_PER; ++u) {
+    const int j = tid + u * T;
+    if (j < nt) {
+      const uint32_t pt = kt[j] & VUS_KEY_POS_MASK;
+      const uint32_t yt = pt / (uint32_t)W;
+      const int yc = min((int)yt, Hrows - 1);
+      t_yx[u] = (yc << 16) | (int)(pt - yt * (uint32_t)W);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) t_d[u][w] = dt[(size_t)j * 4 + w];
+      atomicAdd(&s_start[yc + 1], 1);
+    }
+  }
+  __syncthreads();
+  // inclusive scan of s_start[1 .. Hrows] (counts) -> row starts, chunked over the threads; the cursors start there
+  {
+    const int per = (Hrows + T - 1) / T;
+    const int b = min(Hrows + 1, 1 + tid * per), e = min(Hrows + 1, b + per);
+    int sum = 0;
+    for (int r = b; r < e; ++r) sum += s_start[r];
+    const int incl = wave_incl_scan(sum);
+    if ((tid & 63) == 63) s_wsum[tid >> 6] = incl;
+    __syncthreads();
+    int base = incl - sum;
+    for (int w = 0; w < (tid >> 6); ++w) base += s_wsum[w];
+    for (int r = b; r < e; ++r) {
+      base += s_start[r];
+      s_start[r] = base;
+      if (r < Hrows) s_cursor[r] = base;
+    }
+    if (tid == 0) s_cursor[0] = 0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < HR_PER; ++u) {
+    const int j = tid + u * T;
+    if (j < nt) {
+      const int c = atomicAdd(&s_cursor[t_yx[u] >> 16], 1);
+      s_xi[c] = (uint32_t)(t_yx[u] & 0xFFFF) | ((uint32_t)j << 16);
+      s_desc[2 * c] = make_uint4((uint32_t)t_d[u][0], (uint32_t)(t_d[u][0] >> 32), (uint32_t)t_d[u][1], (uint32_t)(t_d[u][1] >> 32));
+      s_desc[2 * c + 1] = make_uint4((uint32_t)t_d[u][2], (uint32_t)(t_d[u][2] >> 32), (uint32_t)t_d[u][3], (uint32_t)(t_d[u][3] >> 32));
+    }
+  }
+  __syncthreads();
+
+  for (int i = tid; i < max_kp; i += T) {
+    int best = 1 << 20, bidx = -1;
+    if (i < nq) {
+      const uint64_t* dq = desc + ((size_t)qi * max_kp + i) * 4;
+      const uint64_t q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3];
+      const uint32_t pq = kp_keys[(size_t)qi * max_kp + i] & VUS_KEY_POS_MASK;
+      const int yq = (int)(pq / (uint32_t)W), xq = (int)(pq - (uint32_t)yq * (uint32_t)W);
+      const int r0 = max(0, yq - max_dy), r1 = min(Hrows - 1, yq + max_dy);
+      if (r0 <= r1) {
+        const int c_end = s_start[r1 + 1];
+        for (int c = s_start[r0]; c < c_end; ++c) {
+          const uint32_t xi = s_xi[c];
+          const int dx = xq - (int)(xi & 0xFFFFu);
+          if (dx < min_disp || dx > max_disp) continue;
+          const uint4 d0 = s_desc[2 * c], d1 = s_desc[2 * c + 1];
+          const int dist = __popcll(q0 ^ (d0.x | ((uint64_t)d0.y << 32))) + __popcll(q1 ^ (d0.z | ((uint64_t)d0.w << 32))) +
+                           __popcll(q2 ^ (d1.x | ((uint64_t)d1.y << 32))) + __popcll(q3 ^ (d1.z | ((uint64_t)d1.w << 32)));
+          const int j = (int)(xi >> 16);
+          if (dist < best || (dist == best && j < bidx)) { best = dist; bidx = j; }
+        }
+      }
+    }
     if (bidx < 0) best = 512;
     else if (best > max_dist) bidx = -1;
     idx_out[(size_t)p * max_kp + i] = bidx;
@@ -2350,9 +2600,16 @@ extern "C" int vus_select_topk(const uint32_t* cand_keys, const int* cand_count,
   VUS_REQUIRE(cand_cap >= 1, "cand_cap=%d", cand_cap);
   VUS_REQUIRE(max_kp >= 1 && max_kp <= 8192, "max_kp=%d out of range [1, 8192]", max_kp);
   if (n_img == 0) return VUS_OK;
-  int sort_n = 64;
+  // at least four waves: a small max_kp (a pyramid level's quota) still meets lists of thousands of candidates, which
+  // one wave would stream and count alone; max_kp <= 8192 == SEL_THREADS * SEL_E
+  int sort_n = 256 * SEL_E;
   while (sort_n < max_kp) sort_n <<= 1;
-  select_topk_kernel<<<n_img, SEL_THREADS, sort_n * sizeof(uint32_t), vus::as_stream(stream)>>>(
+  const int threads = sort_n / SEL_E;
+  const size_t lds = sort_n * sizeof(uint32_t) + (size_t)(threads / 64) * 256 * sizeof(int);   // keys + a histogram per wave
+  if (lds > 48 * 1024)   // max_kp 8192: 48 KiB dynamic + 1 KiB static
+    VUS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_topk_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  select_topk_kernel<<<n_img, threads, lds, vus::as_stream(stream)>>>(
       cand_keys, cand_count, cand_cap, max_kp, sort_n, kp_keys, kp_count);
   VUS_CHECK_LAUNCH("select_topk");
   return VUS_OK;
@@ -2440,13 +2697,22 @@ extern "C" int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, 
   VUS_REQUIRE(n_pairs >= 0 && n_pairs <= 65535, "n_pairs=%d out of range [0, 65535]", n_pairs);
   if (n_pairs == 0) return VUS_OK;
   dim3 grid((max_kp + 255) / 256, n_pairs);
-  const int h_rows = H;   // the gated kernel buckets the train keypoints by image row
-  const size_t lds = sizeof(int) * ((size_t)2 * h_rows + 1 + 2 * (size_t)max_kp);
-  if (max_dy >= 0 && h_rows <= 16384 && lds <= 96 * 1024) {
-    if (lds > 48 * 1024)
+  const int h_rows = H;   // the gated kernels bucket the train keypoints by image row
+  const size_t lds_all = hamming_rows_lds(max_kp, h_rows);                                     // train set resident in LDS
+  const size_t lds = sizeof(int) * ((size_t)2 * h_rows + 1 + 2 * (size_t)max_kp);             // index table only
+  if (max_dy >= 0 && max_kp <= HR_THREADS * HR_PER && lds_all <= 96 * 1024) {
+    const int threads = std::min(HR_THREADS, (max_kp + 63) / 64 * 64);
+    if (lds_all > 48 * 1024)
       VUS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hamming_match_rows_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all));
+    hamming_match_rows_kernel<<<n_pairs, threads, lds_all, vus::as_stream(stream)>>>(
+        desc, kp_keys, kp_count, max_kp, W, h_rows, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out,
+        dist_out);
+  } else if (max_dy >= 0 && lds <= 96 * 1024) {
+    if (lds > 48 * 1024)
+      VUS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(hamming_match_rows_gather_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hamming_match_rows_kernel<<<grid, 256, lds, vus::as_stream(stream)>>>(
+    hamming_match_rows_gather_kernel<<<grid, 256, lds, vus::as_stream(stream)>>>(
         desc, kp_keys, kp_count, max_kp, W, h_rows, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out,
         dist_out);
   } else {
