@@ -941,45 +941,43 @@ __global__ __launch_bounds__(SEL_THREADS) void select_topk_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// One wave per keypoint: orientation bin + 256-bit rotated BRIEF.
-// Each wave stages the keypoint's two patches in LDS with row-contiguous dword loads (31 rows of the
-// image for the centroid disc, 37 rows of the smoothed image for the tests), then gathers from LDS.
+// Orientation bin + 256-bit rotated BRIEF: one wave serves eight keypoints of one image (orient_rbrief_kernel below).
+// Their 31-row centroid patches of the image are weighed in the registers they are loaded into; their 37-row patches of
+// the smoothed image pass through LDS one at a time for the 256 byte-pair tests.  The planes are row-major or
+// block-tiled (OrGeom).  The section's two build knobs, occupancy over identical code:
+#ifndef VUS_OR_WPE
+#define VUS_OR_WPE 4         // waves per SIMD asked of the compiler for the row-major instances
+#endif
+#ifndef VUS_OR_WPE_TILED
+#define VUS_OR_WPE_TILED 7   // ... for the tiled instances; tests/test_orient_resources.py holds what 7 takes
+#endif
 constexpr int OR_R = 15;                    // disc radius
 constexpr int OR_ROWS = 2 * OR_R + 1;       // 31
-#ifndef VUS_OR_VW
-#define VUS_OR_VW 2
-#endif
-constexpr int OR_VW = VUS_OR_VW;               // dwords per lane and load
-constexpr int OR_DW = OR_VW == 4 ? 12 : 10;    // 36 bytes cover x-15..x+15 from an aligned start; a multiple of OR_VW is loaded
+constexpr int OR_DW = 10;                   // 36 bytes cover x-15..x+15 from an aligned start; whole dwordx2 are loaded
 constexpr int BR_R = VUS_RBRIEF_REACH;      // 18
 constexpr int BR_ROWS = 2 * BR_R + 1;       // 37
-constexpr int BR_DW = OR_VW == 4 ? 12 : 10;    // 40 bytes cover x-18..x+18 from an aligned start
-#ifndef VUS_OR_KPW
-#define VUS_OR_KPW 8
-#endif
-constexpr int OR_KP_PER_WAVE = VUS_OR_KPW;  // keypoints handled sequentially by one wave
+constexpr int BR_DW = 10;                   // 40 bytes cover x-18..x+18 from an aligned start
+constexpr int BR_DW_TILED = 12;             // block-tiled planes: 44 of 48 bytes from an 8-byte aligned start (OrGeom)
+constexpr int OR_KP_PER_WAVE = 8;           // keypoints of one wave; the reduce-scatter and the one-store epilogue are written for 8
 
 // Load a (2*RADIUS+1) x (4*DW)-byte patch around (x, y) into registers: every lane issues all of
-// its dword loads back to back (one memory round trip), the caller stores them to LDS afterwards.
-// A lane moves VW dwords (dwordx2 / dwordx4 access at dword alignment): the texture path's cost is per
-// instruction, not per byte -- 11 dword loads per keypoint took 3.19 ms per 1000 frames, 6 dwordx2 2.82
-// (4 dwordx4 of 48-byte rows: 3.04).
-template <int VW> struct PatchVec;
-template <> struct PatchVec<2> { typedef uint32_t type __attribute__((ext_vector_type(2), aligned(1))); };
-template <> struct PatchVec<4> { typedef uint32_t type __attribute__((ext_vector_type(4), aligned(1))); };
+// its loads back to back (one memory round trip), the caller stores them to LDS afterwards.
+// A lane moves two dwords per load (dwordx2 at dword alignment): the texture path's cost is per instruction, not per
+// byte.  Measured and not kept, ms per 1000 frames against the 2.82 of 6 dwordx2 per keypoint: 11 dword loads: 3.19;
+// 4 dwordx4 of 48-byte rows: 3.04.
+typedef uint32_t PatchVec __attribute__((ext_vector_type(2), aligned(1)));
 
 // EXACT: the patch starts at column x - RADIUS whatever its alignment (images whose rows are not dword
 // aligned, e.g. odd-width pyramid levels); otherwise at the dword boundary below it (aligned loads are
 // ~7 % faster on the full-size image: 2.70 vs 2.90 ms per 1000 frames).
-template <int RADIUS, int DW, int VW, bool EXACT>
+template <int RADIUS, int DW, bool EXACT>
 struct PatchRegs {
-  static_assert(DW % VW == 0, "row width must be a multiple of the vector width");
-  typedef typename PatchVec<VW>::type vec_t;
+  static_assert(DW % 2 == 0, "row width must be a multiple of the vector width");
   static constexpr int ROWS = 2 * RADIUS + 1;
-  static constexpr int HW = DW / VW;            // vectors per row
+  static constexpr int HW = DW / 2;             // vectors per row
   static constexpr int N = ROWS * HW;
   static constexpr int ITERS = (N + 63) / 64;
-  vec_t v[ITERS];
+  PatchVec v[ITERS];
   uint32_t off[ITERS];   // byte offset of this lane's vectors inside an in-image patch (fixed per kernel); unsigned:
                          // scalar base + zero-extended 32-bit lane offset is an addressing mode of global_load
 
@@ -987,7 +985,7 @@ struct PatchRegs {
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) {
       const int t = min(lane + 64 * u, N - 1);
-      off[u] = (uint32_t)((t / HW) * pitch + 4 * VW * (t % HW));
+      off[u] = (uint32_t)((t / HW) * pitch + 8 * (t % HW));
     }
   }
   __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int pitch, int y, int x,
@@ -997,16 +995,16 @@ struct PatchRegs {
     if (inside) {   // wave-uniform
       const uint8_t* base = src + (size_t)(y - RADIUS) * pitch + xa;
 #pragma unroll
-      for (int u = 0; u < ITERS; ++u) v[u] = *reinterpret_cast<const vec_t*>(base + (size_t)off[u]);
+      for (int u = 0; u < ITERS; ++u) v[u] = *reinterpret_cast<const PatchVec*>(base + (size_t)off[u]);
     } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
 #pragma unroll
       for (int u = 0; u < ITERS; ++u) {
         const int t = min(lane + 64 * u, N - 1);
         const int r = t / HW, c = t - r * HW;
         const uint8_t* rp = src + (size_t)clampi(y - RADIUS + r, 0, H - 1) * pitch;
-        const int gx = xa + 4 * VW * c;
+        const int gx = xa + 8 * c;
 #pragma unroll
-        for (int k = 0; k < VW; ++k)
+        for (int k = 0; k < 2; ++k)
           v[u][k] = (uint32_t)rp[clampi(gx + 4 * k, 0, W - 1)] | ((uint32_t)rp[clampi(gx + 4 * k + 1, 0, W - 1)] << 8) |
                     ((uint32_t)rp[clampi(gx + 4 * k + 2, 0, W - 1)] << 16) |
                     ((uint32_t)rp[clampi(gx + 4 * k + 3, 0, W - 1)] << 24);
@@ -1016,17 +1014,13 @@ struct PatchRegs {
   __device__ __forceinline__ void store(uint32_t* __restrict__ dst, int lane) const {
 #pragma unroll
     for (int u = 0; u < ITERS; ++u)
-      if (lane + 64 * u < N) {
-        uint32_t* d = dst + VW * (lane + 64 * u);
-#pragma unroll
-        for (int k = 0; k < VW; k += 2) *reinterpret_cast<uint2*>(d + k) = make_uint2(v[u][k], v[u][k + 1]);
-      }
+      if (lane + 64 * u < N) *reinterpret_cast<uint2*>(dst + 2 * (lane + 64 * u)) = make_uint2(v[u][0], v[u][1]);
   }
 };
 
-// The same patch from a block-tiled plane (include/vus_tiled.h; W % 16 == 0, H % 8 == 0).  The patch starts at the
-// 8-byte boundary below x - RADIUS, so a lane's dwordx2 never leaves a 16-byte block row.  Pixel (y0 + r, xa + 8 c) of
-// vector (r, c) sits at
+// The same patch, and the same interface, from a block-tiled plane (include/vus_tiled.h; W % 16 == 0, H % 8 == 0, the
+// pitch is W and goes unused).  The patch starts at the 8-byte boundary below x - RADIUS, so a lane's dwordx2 never
+// leaves a 16-byte block row.  Pixel (y0 + r, xa + 8 c) of vector (r, c) sits at
 //   tiled(y0 & ~7, xa & ~15)  +  16 (y0 & 7) + 16 r + f(q)  +  (p >> 3) (8 W - 128),   p = (y0 & 7) + r,  q = (xa & 8) + 8 c,
 //   f(q) = 128 (q >> 4) + (q & 8)
 // -- the first two terms wave-uniform, 16 r + f(q) a per-lane constant for each of the two values of xa & 8: four
@@ -1035,16 +1029,15 @@ struct PatchRegs {
 template <int RADIUS, int DW>
 struct TiledPatchRegs {
   static_assert(DW % 2 == 0, "row width must be a multiple of the vector width");
-  typedef typename PatchVec<2>::type vec_t;
   static constexpr int ROWS = 2 * RADIUS + 1;
   static constexpr int HW = DW / 2;             // vectors per row
   static constexpr int N = ROWS * HW;
   static constexpr int ITERS = (N + 63) / 64;
   static_assert(ROWS + 7 < 64 && 16 * (ROWS - 1) + 128 * ((8 * HW) >> 4) + 8 < 1024, "pk fields: 6-bit row, 10-bit offsets");
-  vec_t v[ITERS];
+  PatchVec v[ITERS];
   uint32_t pk[ITERS];   // this lane's vectors: (patch row r) << 20 | (16 r + f(q), xa & 8 == 8) << 10 | (..., xa & 8 == 0)
 
-  __device__ __forceinline__ void init(int lane) {
+  __device__ __forceinline__ void init(int /*pitch*/, int lane) {
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) {
       const int t = min(lane + 64 * u, N - 1);
@@ -1053,7 +1046,8 @@ struct TiledPatchRegs {
       pk[u] = r << 20 | off8 << 10 | off0;
     }
   }
-  __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int y, int x, int lane) {
+  __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int /*pitch*/, int y, int x,
+                                       int lane) {
     const int xa = (x - RADIUS) & ~7, y0 = y - RADIUS;
     const bool inside = y0 >= 0 && y + RADIUS < H && xa >= 0 && xa + 4 * DW <= W;
     if (inside) {   // wave-uniform
@@ -1063,7 +1057,7 @@ struct TiledPatchRegs {
 #pragma unroll
       for (int u = 0; u < ITERS; ++u) {   // (ys + r) >> 3 == (pk + ys) >> 23: the row field has room for ys + r < 64
         const uint32_t off = ((pk[u] + ys) >> 23) * ystep + __builtin_amdgcn_ubfe(pk[u], sel, 10u);
-        v[u] = *reinterpret_cast<const vec_t*>(base + (size_t)off);
+        v[u] = *reinterpret_cast<const PatchVec*>(base + (size_t)off);
       }
     } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
 #pragma unroll
@@ -1088,7 +1082,7 @@ struct TiledPatchRegs {
   }
 };
 
-// Cross-lane helpers of orient_rbrief (round 4, second pass).  A wave works on EIGHT keypoints at once; the per-lane
+// Cross-lane helpers of orient_rbrief_kernel.  A wave works on EIGHT keypoints at once; the per-lane
 // partial sums of their centroid moments (16 values) are folded with a reduce-scatter instead of 16 full wave
 // reductions: v_permlane32_swap / v_permlane16_swap (gfx950) exchange half-waves / odd-even rows of TWO registers in one
 // instruction, so that one add folds two values at once; then one row_ror:8 and three 8-lane all-reduce steps.
@@ -1136,6 +1130,16 @@ __device__ __forceinline__ uint32_t writelane_u32(uint32_t reg, uint32_t value, 
   return reg;
 }
 
+// A lane ranks the four bins 4 (lane & 7) + q after phase A: their directions, from the two per-bin tables.
+__device__ __forceinline__ void load_bin_directions(const int (&cos_table)[VUS_N_ANGLE_BINS], const int (&sin_table)[VUS_N_ANGLE_BINS],
+                                                    int lane, int (&bin_cos)[4], int (&bin_sin)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int bq = min(4 * (lane & 7) + q, VUS_N_ANGLE_BINS - 1);
+    bin_cos[q] = cos_table[bq];
+    bin_sin[q] = sin_table[bq];
+  }
+}
 
 // Rotated test pattern re-laid for the kernel: [bin][lane][word] = the two patch byte offsets
 // (y * row bytes + x, int16 each) of test 64 * word + lane.  Derived from VUS_RBRIEF_ROT at COMPILE time, so
@@ -1154,48 +1158,11 @@ constexpr RotOffTable make_rot_off_table(int row_bytes) {
   return r;
 }
 __device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table = make_rot_off_table(4 * BR_DW);
+__device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table_tiled = make_rot_off_table(4 * BR_DW_TILED);
 
-#ifndef VUS_OR_WPE
-#define VUS_OR_WPE 4
-#endif
-#ifndef VUS_OR_WPE_TILED
-#define VUS_OR_WPE_TILED 7   // the tiled instances (OrGeom<true>)
-#endif
-#ifndef VUS_OR_GRP
-#define VUS_OR_GRP 4
-#endif
-#ifndef VUS_OR_GRP_TILED
-#define VUS_OR_GRP_TILED 2
-#endif
-constexpr int OR_GRP = VUS_OR_GRP;   // centroid patches of this many keypoints are in flight together (2, 4 or 8)
-static_assert(OR_VW == 2 && OR_KP_PER_WAVE == 8, "orient_rbrief_kernel is written for dwordx2 patch loads and 8 keypoints per wave");
-constexpr int OR_NV = OR_ROWS * (OR_DW / OR_VW);   // 155 dwordx2 vectors of a centroid patch
-constexpr int OR_WT = 192;                         // weight entries per byte alignment: one per vector, padded to 3 x 64 lanes
-
-// Patch geometry of orient_rbrief_kernel per plane layout.  Row-major planes: patch rows start on the dword boundary
-// below x - radius (4 alignments).  Block-tiled planes (TiledPatchRegs): on the 8-byte boundary below it (8 alignments),
-// so the descriptor patch needs 44 of 48 bytes (12 dwords) per row; the centroid patch's 38 still fit its 40.
-template <bool TILED> struct OrGeom {
-  static constexpr int ALIGN = 4, OR_DW = ::OR_DW, BR_DW = ::BR_DW;
-  static constexpr int WT_VEC4 = ALIGN * OR_WT;   // uint4 entries of s_w (DiscWeightTable<4>)
-  static constexpr int GRP = OR_GRP, BLUR_BUF = 2;   // BLUR_BUF: 1 or 2
-  typedef PatchRegs<OR_R, OR_DW, OR_VW, false> Disc;
-  typedef PatchRegs<BR_R, BR_DW, OR_VW, false> Brief;
-};
-constexpr int OR_WTD = 2 * OR_WT + 1;   // DiscWeightDwTable entries per byte alignment: a zero, then one per patch dword
-template <> struct OrGeom<true> {
-  static constexpr int ALIGN = 8, OR_DW = 10, BR_DW = 12;
-  static constexpr int WT_VEC4 = 4 * OR_WTD * 2 / 4;   // uint4 entries of s_w (DiscWeightDwTable)
-  // 7 waves per SIMD: <= 72 VGPRs (phase A keeps 2 centroid patches in flight, not 4) and <= 23,405 B of LDS (the weights
-  // per dword; ONE descriptor patch buffer per wave -- the ballots of keypoint k have consumed its patch bytes before
-  // the patch of k + 1 is stored).  tests/test_orient_resources.py holds these figures.
-  static constexpr int GRP = VUS_OR_GRP_TILED, BLUR_BUF = 1;
-  typedef TiledPatchRegs<OR_R, OR_DW> Disc;
-  typedef TiledPatchRegs<BR_R, BR_DW> Brief;
-};
-static_assert(OrGeom<true>::OR_DW == OR_DW && 2 * OR_R + 1 + 7 <= 4 * OrGeom<true>::OR_DW && 2 * BR_R + 1 + 7 <= 4 * OrGeom<true>::BR_DW,
-              "tiled patch rows: 8-byte aligned starts, same centroid vectors");
-__device__ __attribute__((aligned(16))) const RotOffTable g_rot_off_table_tiled = make_rot_off_table(4 * OrGeom<true>::BR_DW);
+constexpr int OR_NV = OR_ROWS * (OR_DW / 2);   // 155 dwordx2 vectors of a centroid patch
+constexpr int OR_WT = 192;                     // weight entries per byte alignment: one per vector, padded to 3 x 64 lanes
+constexpr int OR_WTD = 2 * OR_WT + 1;          // DiscWeightDwTable entries per byte alignment: a zero, then one per patch dword
 
 // The disc weights of orient_rbrief_kernel's s_w as a compile-time table: entry (sh, t) = weights of patch vector t (row
 // t / 5, dword pair t % 5) for a patch whose first column sits sh bytes into its first dword: .x/.y = (dx + 15) inside
@@ -1267,17 +1234,50 @@ constexpr bool disc_weight_dw_table_matches() {   // the same weights as the per
   return true;
 }
 static_assert(disc_weight_dw_table_matches(), "DiscWeightDwTable must weigh every vector as DiscWeightTable<8>");
+
+// What orient_rbrief_kernel takes from the plane layout.  Row-major planes: patch rows start on the dword boundary below
+// x - radius (4 alignments; EXACT: at x - radius itself).  Block-tiled planes: on the 8-byte boundary below it (8
+// alignments), so the descriptor patch needs 44 of 48 bytes (12 dwords) per row; the centroid patch's 38 still fit its 40.
+template <bool TILED, bool EXACT = false> struct OrGeom {
+  static constexpr int ALIGN = 4, BR_DW = ::BR_DW;
+  static constexpr int WT_VEC4 = ALIGN * OR_WT;   // uint4 entries of s_w (DiscWeightTable<4>)
+  // GRP: centroid patches of this many keypoints are in flight together.  BLUR_BUF: descriptor patch buffers per wave, 1 or 2.
+  static constexpr int GRP = 4, BLUR_BUF = 2;
+  static constexpr bool BINS_AFTER_PHASE_A = false;
+  typedef PatchRegs<OR_R, OR_DW, EXACT> Disc;
+  typedef PatchRegs<BR_R, BR_DW, EXACT> Brief;
+  static constexpr const uint32_t* WEIGHT_TABLE = g_disc_weight_table.v;   // s_w is a copy of it
+  static constexpr const uint32_t* ROT_TABLE = g_rot_off_table.v;
+  // the weights of the lane's vector lane + 64 u of a patch that starts sh bytes before its first column:
+  // .x/.y = (dx + 15) inside the disc else 0 (u8 x 4) of the two dwords, .z/.w = 1 inside the disc else 0
+  static __device__ __forceinline__ uint4 disc_weights(const uint4* s_w, int sh, int lane, int u) {
+    return s_w[sh * OR_WT + lane + 64 * u];
+  }
+};
+template <bool EXACT> struct OrGeom<true, EXACT> {
+  static_assert(!EXACT, "tiled planes are always read from aligned starts");
+  static constexpr int ALIGN = 8, BR_DW = BR_DW_TILED;
+  static constexpr int WT_VEC4 = 4 * OR_WTD * 2 / 4;   // uint4 entries of s_w (DiscWeightDwTable)
+  // 7 waves per SIMD: <= 72 VGPRs (phase A keeps 2 centroid patches in flight, not 4; the bin directions are loaded after
+  // phase A's patches, 8 registers fewer while they are in flight) and <= 23,405 B of LDS (the weights per dword; ONE
+  // descriptor patch buffer per wave -- the ballots of keypoint k have consumed its patch bytes before the patch of k + 1
+  // is stored).  tests/test_orient_resources.py holds these figures.
+  static constexpr int GRP = 2, BLUR_BUF = 1;
+  static constexpr bool BINS_AFTER_PHASE_A = true;
+  typedef TiledPatchRegs<OR_R, OR_DW> Disc;
+  typedef TiledPatchRegs<BR_R, BR_DW> Brief;
+  static constexpr const uint32_t* WEIGHT_TABLE = g_disc_weight_dw_table.v;   // s_w is a copy of it
+  static constexpr const uint32_t* ROT_TABLE = g_rot_off_table_tiled.v;
+  // the same uint4 from the per-dword table: {moment, count} of the vector's two dwords are entries 2t + 1 - s, 2t + 2 - s
+  static __device__ __forceinline__ uint4 disc_weights(const uint4* s_w, int sh, int lane, int u) {
+    const uint2* wd = reinterpret_cast<const uint2*>(s_w) + (sh & 3) * OR_WTD + 1 - (sh >> 2) + 2 * lane;
+    const uint2 w0 = wd[128 * u], w1 = wd[128 * u + 1];
+    return make_uint4(w0.x, w1.x, w0.y, w1.y);
+  }
+};
+static_assert(2 * OR_R + 1 + 7 <= 4 * OR_DW && 2 * BR_R + 1 + 7 <= 4 * BR_DW_TILED, "tiled patch rows: 8-byte aligned starts");
 static_assert(sizeof(DiscWeightDwTable) == 16 * OrGeom<true>::WT_VEC4, "LDS copy of the tiled weights: whole uint4");
 
-// One wave = eight consecutive keypoints of one image, in two phases.
-//  A. orientation of all eight: the 31-row image patches arrive in registers (3 dwordx2 per lane and keypoint, 3 GRP in
-//     flight) and are multiplied right there with the disc weights (v_dot4_u32_u8; the weights of a lane's two dwords
-//     are ONE LDS read): no LDS round trip for the patch.  Per-lane partial moments of the eight keypoints
-//     -> reduce-scatter (above) -> lane 8g + j holds m10 / m01 of keypoint g and ranks bins 4j .. 4j+3.
-//  B. descriptors, keypoint by keypoint: the 37-row patch of the smoothed image goes through LDS (BLUR_BUF buffers; the
-//     next keypoint's rows and its bin's test offsets are in flight meanwhile), 8 byte reads + 4 compares per lane; the
-//     ballots are written into lanes 4k + w of one register pair, so the eight descriptors leave in ONE 256-byte store.
-// Round 4 first pass: one keypoint at a time, 232 vector instructions per keypoint (2.67 ms per 1000 stereo frames).
 // One workgroup per image: the image's keypoints counting-sorted by 64 x 64-pixel cell (cells in raster order; inside a
 // cell as the atomics fall -- a schedule, not a result).  order [n_img][max_kp]; slots from the image's count on map to
 // themselves.
@@ -1329,22 +1329,28 @@ __global__ __launch_bounds__(256) void orient_order_kernel(const uint32_t* __res
   for (int j = cnt + tid; j < max_kp; j += 256) ord[j] = j;
 }
 
+// One wave = eight consecutive keypoints of one image, in two phases.
+//  A. orientation of all eight: the 31-row image patches arrive in registers (3 dwordx2 per lane and keypoint, those of
+//     GRP keypoints in flight) and are multiplied right there with the disc weights (v_dot4_u32_u8; the weights of a lane's two dwords
+//     are ONE LDS read): no LDS round trip for the patch.  Per-lane partial moments of the eight keypoints
+//     -> reduce-scatter (fold32 .. allsum8 above) -> lane 8g + j holds m10 / m01 of keypoint g and ranks bins 4j .. 4j+3.
+//  B. descriptors, keypoint by keypoint: the 37-row patch of the smoothed image goes through LDS (BLUR_BUF buffers; the
+//     next keypoint's rows and its bin's test offsets are in flight meanwhile), 8 byte reads + 4 compares per lane; the
+//     ballots are written into lanes 4k + w of one register pair, so the eight descriptors leave in ONE 256-byte store.
+// Its predecessor, one keypoint at a time: 232 vector instructions per keypoint (2.67 ms per 1000 stereo frames).
 // ORDERED: slot s of an image is served with keypoint order[s] (vus_orient_order: the image's keypoints grouped by 64 x 64
 // cell, the unused slots mapped to themselves), so that the eight keypoints of a wave and the 32 of a workgroup are
 // neighbours and their patch rows share lines in flight; the outputs go to the keypoint's own index.  A schedule only.
-// TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W): the patches arrive through TiledPatchRegs,
-// phase B's LDS patch stays row-major (48-byte rows), so the test offsets and ballots are those of the plain form.
-template <bool EXACT, bool ORDERED, bool TILED = false>
+// TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W).  OrGeom carries every difference: the
+// patch loaders, the weight and test-offset tables, the patches in flight.  Phase B's LDS patch stays row-major
+// (48-byte rows), so the ballots are those of the plain form.
+template <bool EXACT, bool ORDERED, bool TILED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS_OR_WPE_TILED : VUS_OR_WPE, 8))) void orient_rbrief_kernel(
     const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int H, int W, int pitch,
     const uint32_t* __restrict__ kp_keys, const int* __restrict__ kp_count, int max_kp, const int* __restrict__ order,
     uint64_t* __restrict__ desc_out, uint8_t* __restrict__ angle_out, int n_img, int chunks_per_img) {
-  // centroid weights per patch vector (two dwords), for the 4 possible byte alignments of the patch:
-  // .x/.y = (dx + 15) inside the disc else 0 (u8 x 4) of the two dwords, .z/.w = 1 inside the disc else 0
-  // (TILED: per dword, DiscWeightDwTable)
-  typedef OrGeom<TILED> G;
-  static_assert(!(TILED && EXACT), "tiled planes are always read from aligned starts");
-  __shared__ uint4 s_w[G::WT_VEC4];
+  typedef OrGeom<TILED, EXACT> G;
+  __shared__ uint4 s_w[G::WT_VEC4];   // the disc weights for every byte alignment of a centroid patch (G::disc_weights)
   __shared__ __attribute__((aligned(8))) uint32_t s_blur[4][G::BLUR_BUF][BR_ROWS * G::BR_DW];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1356,7 +1362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
   const int chunk = slot - (slot / chunks_per_img) * chunks_per_img;
   if (n >= n_img) return;
   {   // the disc weights: a compile-time table, copied (deriving them per workgroup cost ~19 vector instructions per keypoint)
-    const uint4* wt = reinterpret_cast<const uint4*>(TILED ? g_disc_weight_dw_table.v : g_disc_weight_table.v);
+    const uint4* wt = reinterpret_cast<const uint4*>(G::WEIGHT_TABLE);
 #pragma unroll
     for (int i = 0; i < (G::WT_VEC4 + 255) / 256; ++i)
       if (G::WT_VEC4 % 256 == 0 || threadIdx.x + 256 * i < G::WT_VEC4) s_w[threadIdx.x + 256 * i] = wt[threadIdx.x + 256 * i];
@@ -1373,29 +1379,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
     my_y = (int)(pos / (uint32_t)W);
     my_x = (int)(pos - (uint32_t)my_y * (uint32_t)W);
   }
-  // the bins this lane ranks in phase A: 4 (lane & 7) + q (TILED: loaded after phase A's patches, 8 registers fewer
-  // while they are in flight)
+  // the directions of the bins this lane ranks after phase A: 4 (lane & 7) + q.  Loaded here, or behind phase A's patches
+  // (G::BINS_AFTER_PHASE_A, a register-pressure decision)
   int bin_cos[4], bin_sin[4];
-  if constexpr (!TILED) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int bq = min(4 * (lane & 7) + q, VUS_N_ANGLE_BINS - 1);
-      bin_cos[q] = VUS_ANGLE_COS[bq];
-      bin_sin[q] = VUS_ANGLE_SIN[bq];
-    }
-  }
+  if constexpr (!G::BINS_AFTER_PHASE_A) load_bin_directions(VUS_ANGLE_COS, VUS_ANGLE_SIN, lane, bin_cos, bin_sin);
   constexpr int GRP = G::GRP;
-  typename std::conditional<TILED, typename G::Disc, PatchRegs<OR_R, OR_DW, OR_VW, EXACT>>::type pr[GRP];
-  typename std::conditional<TILED, typename G::Brief, PatchRegs<BR_R, BR_DW, OR_VW, EXACT>>::type pb;
-  if constexpr (TILED) {
+  typename G::Disc pr[GRP];
+  typename G::Brief pb;
 #pragma unroll
-    for (int kk = 0; kk < GRP; ++kk) pr[kk].init(lane);
-    pb.init(lane);
-  } else {
-#pragma unroll
-    for (int kk = 0; kk < GRP; ++kk) pr[kk].init(pitch, lane);
-    pb.init(W, lane);
-  }
+  for (int kk = 0; kk < GRP; ++kk) pr[kk].init(pitch, lane);
+  pb.init(W, lane);
   int mom_dy[3];
 #pragma unroll
   for (int u = 0; u < 3; ++u) mom_dy[u] = min(lane + 64 * u, OR_NV - 1) / (OR_DW / 2) - OR_R;
@@ -1413,19 +1406,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
 #pragma unroll
     for (int kk = 0; kk < GRP; ++kk) {
       const int k = GRP * g + kk;
-#ifndef VUS_OR_EXP_NORAW
-      if (k < n_live) {
-        if constexpr (TILED) pr[kk].load(im, H, W, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
-        else pr[kk].load(im, H, W, pitch, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
-      }
-#else
-      for (int u = 0; u < 3; ++u) pr[kk].v[u] = typename PatchVec<OR_VW>::type{(uint32_t)lane, (uint32_t)k};
-#endif
+      if (k < n_live) pr[kk].load(im, H, W, pitch, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
     }
-    if (g == 8 / GRP - 1) {   // the first descriptor patch joins the queue behind the last centroid patches
-      if constexpr (TILED) pb.load(bl, H, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
-      else pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
-    }
+    if (g == 8 / GRP - 1)   // the first descriptor patch joins the queue behind the last centroid patches
+      pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
 #pragma unroll
     for (int kk = 0; kk < GRP; ++kk) {
       const int k = GRP * g + kk;
@@ -1437,14 +1421,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
         int si = 0, sy = 0;
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-          uint4 w;
-          if constexpr (TILED) {   // {moment, count} of the vector's two dwords: entries 2t + 1 - s, 2t + 2 - s
-            const uint2* wd = reinterpret_cast<const uint2*>(s_w) + (sh & 3) * OR_WTD + 1 - (sh >> 2) + 2 * lane;
-            const uint2 w0 = wd[128 * u], w1 = wd[128 * u + 1];
-            w = make_uint4(w0.x, w1.x, w0.y, w1.y);
-          } else {
-            w = s_w[sh * OR_WT + lane + 64 * u];
-          }
+          const uint4 w = G::disc_weights(s_w, sh, lane, u);
           sx = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.x, sx, false);
           sx = __builtin_amdgcn_udot4(pr[kk].v[u][1], w.y, sx, false);
           uint32_t rs = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.z, 0u, false);
@@ -1457,14 +1434,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
       }
     }
   }
-  if constexpr (TILED) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int bq = min(4 * (lane & 7) + q, VUS_N_ANGLE_BINS - 1);
-      bin_cos[q] = VUS_ANGLE_COS[bq];
-      bin_sin[q] = VUS_ANGLE_SIN[bq];
-    }
-  }
+  if constexpr (G::BINS_AFTER_PHASE_A) load_bin_directions(VUS_ANGLE_COS, VUS_ANGLE_SIN, lane, bin_cos, bin_sin);
   // reduce-scatter: afterwards the lanes of group g = lane / 8 hold the moments of keypoint g
   int m10, m01;
   {
@@ -1503,7 +1473,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
 
   // ---- phase B: the descriptors
   uint32_t wlo = 0, whi = 0;   // lane 4k + w: word w of keypoint k
-  const uint4* rot = reinterpret_cast<const uint4*>(TILED ? g_rot_off_table_tiled.v : g_rot_off_table.v) + lane;
+  const uint4* rot = reinterpret_cast<const uint4*>(G::ROT_TABLE) + lane;
   uint4 to = rot[__builtin_amdgcn_readlane(my_bin, 0) * 64];
   for (int k = 0; k < n_live; ++k) {   // scalar loop
     uint32_t* patch = s_blur[wave][k & (G::BLUR_BUF - 1)];
@@ -1511,10 +1481,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
     const uint4 cto = to;
     const int cx = __builtin_amdgcn_readlane(my_x, k);
     if (k + 1 < n_live) {
-#ifndef VUS_OR_EXP_NOBLUR
-      if constexpr (TILED) pb.load(bl, H, W, __builtin_amdgcn_readlane(my_y, k + 1), __builtin_amdgcn_readlane(my_x, k + 1), lane);
-      else pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, k + 1), __builtin_amdgcn_readlane(my_x, k + 1), lane);
-#endif
+      pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, k + 1), __builtin_amdgcn_readlane(my_x, k + 1), lane);
       to = rot[__builtin_amdgcn_readlane(my_bin, 8 * (k + 1)) * 64];
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // this wave's LDS operations execute in order
@@ -2615,34 +2582,41 @@ extern "C" int vus_select_topk(const uint32_t* cand_keys, const int* cand_count,
   return VUS_OK;
 }
 
-static int orient_launch(const uint8_t* img, const uint8_t* blur, int n_img, int H, int W, int pitch, const uint32_t* kp_keys,
-                         const int* kp_count, int max_kp, const int* order, uint64_t* desc_out, uint8_t* angle_out, void* stream) {
+// The launch behind the three vus_orient_rbrief* entry points.  tiled: block-tiled planes, pitch == W.
+static int orient_launch(bool tiled, const uint8_t* img, const uint8_t* blur, int n_img, int H, int W, int pitch,
+                         const uint32_t* kp_keys, const int* kp_count, int max_kp, const int* order, uint64_t* desc_out,
+                         uint8_t* angle_out, void* stream) {
   if (int rc = check_image_args(img, n_img, H, W, pitch)) return rc;
+  if (tiled)
+    if (int rc = check_tiled_args(img, blur, H, W)) return rc;
   VUS_REQUIRE(blur && kp_keys && kp_count && desc_out && angle_out, "null buffer");
   VUS_REQUIRE(max_kp >= 1, "max_kp=%d", max_kp);
   if (n_img == 0) return VUS_OK;
   const int chunks = (max_kp + 4 * OR_KP_PER_WAVE - 1) / (4 * OR_KP_PER_WAVE);
   const long long blocks = (long long)((n_img + 7) / 8) * 8 * chunks;
   VUS_REQUIRE(blocks < (1ll << 31), "too many workgroups (%lld)", blocks);
-  // rows of both planes on dword boundaries -> aligned patch loads; otherwise exact-start (unaligned) loads
+  // rows of both planes on dword boundaries -> aligned patch loads; otherwise exact-start (unaligned) loads (row-major
+  // planes only: the tiled ones are 16-byte aligned throughout)
   const bool aligned = ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(blur) | (uintptr_t)pitch |
                          (uintptr_t)W | ((uintptr_t)H * (uintptr_t)pitch)) & 3u) == 0;
-#define VUS_OR_LAUNCH(EX, ORD)                                                                              \
-  orient_rbrief_kernel<EX, ORD><<<(unsigned)blocks, 256, 0, vus::as_stream(stream)>>>(                      \
-      img, blur, H, W, pitch, kp_keys, kp_count, max_kp, order, desc_out, angle_out, n_img, chunks)
-  if (aligned && order) VUS_OR_LAUNCH(false, true);
-  else if (aligned) VUS_OR_LAUNCH(false, false);
-  else if (order) VUS_OR_LAUNCH(true, true);
-  else VUS_OR_LAUNCH(true, false);
-#undef VUS_OR_LAUNCH
-  VUS_CHECK_LAUNCH("orient_rbrief");
+  auto launch = [&](auto exact, auto ordered, auto tiled_planes) {
+    orient_rbrief_kernel<decltype(exact)::value, decltype(ordered)::value, decltype(tiled_planes)::value>
+        <<<(unsigned)blocks, 256, 0, vus::as_stream(stream)>>>(img, blur, H, W, pitch, kp_keys, kp_count, max_kp, order, desc_out,
+                                                               angle_out, n_img, chunks);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (!tiled && aligned) order ? launch(no, yes, no) : launch(no, no, no);
+  else if (!tiled) order ? launch(yes, yes, no) : launch(yes, no, no);
+  else order ? launch(no, yes, yes) : launch(no, no, yes);
+  VUS_CHECK_LAUNCH(tiled ? "orient_rbrief_tiled" : "orient_rbrief");
   return VUS_OK;
 }
 
 extern "C" int vus_orient_rbrief(const uint8_t* img, const uint8_t* blur, int n_img, int H, int W, int pitch,
                                  const uint32_t* kp_keys, const int* kp_count, int max_kp,
                                  uint64_t* desc_out, uint8_t* angle_out, void* stream) {
-  return orient_launch(img, blur, n_img, H, W, pitch, kp_keys, kp_count, max_kp, nullptr, desc_out, angle_out, stream);
+  return orient_launch(false, img, blur, n_img, H, W, pitch, kp_keys, kp_count, max_kp, nullptr, desc_out, angle_out, stream);
 }
 
 extern "C" int vus_orient_order(const uint32_t* kp_keys, const int* kp_count, int n_img, int max_kp, int H, int W, int* order,
@@ -2664,28 +2638,13 @@ extern "C" int vus_orient_rbrief_ordered(const uint8_t* img, const uint8_t* blur
                                          const uint32_t* kp_keys, const int* kp_count, int max_kp, const int* order,
                                          uint64_t* desc_out, uint8_t* angle_out, void* stream) {
   VUS_REQUIRE(order != nullptr, "null buffer");
-  return orient_launch(img, blur, n_img, H, W, pitch, kp_keys, kp_count, max_kp, order, desc_out, angle_out, stream);
+  return orient_launch(false, img, blur, n_img, H, W, pitch, kp_keys, kp_count, max_kp, order, desc_out, angle_out, stream);
 }
 
 extern "C" int vus_orient_rbrief_tiled(const uint8_t* img_tiled, const uint8_t* blur_tiled, int n_img, int H, int W,
                                        const uint32_t* kp_keys, const int* kp_count, int max_kp, const int* order,
                                        uint64_t* desc_out, uint8_t* angle_out, void* stream) {
-  if (int rc = check_image_args(img_tiled, n_img, H, W, W)) return rc;
-  if (int rc = check_tiled_args(img_tiled, blur_tiled, H, W)) return rc;
-  VUS_REQUIRE(kp_keys && kp_count && desc_out && angle_out, "null buffer");
-  VUS_REQUIRE(max_kp >= 1, "max_kp=%d", max_kp);
-  if (n_img == 0) return VUS_OK;
-  const int chunks = (max_kp + 4 * OR_KP_PER_WAVE - 1) / (4 * OR_KP_PER_WAVE);
-  const long long blocks = (long long)((n_img + 7) / 8) * 8 * chunks;
-  VUS_REQUIRE(blocks < (1ll << 31), "too many workgroups (%lld)", blocks);
-  if (order)
-    orient_rbrief_kernel<false, true, true><<<(unsigned)blocks, 256, 0, vus::as_stream(stream)>>>(
-        img_tiled, blur_tiled, H, W, W, kp_keys, kp_count, max_kp, order, desc_out, angle_out, n_img, chunks);
-  else
-    orient_rbrief_kernel<false, false, true><<<(unsigned)blocks, 256, 0, vus::as_stream(stream)>>>(
-        img_tiled, blur_tiled, H, W, W, kp_keys, kp_count, max_kp, order, desc_out, angle_out, n_img, chunks);
-  VUS_CHECK_LAUNCH("orient_rbrief_tiled");
-  return VUS_OK;
+  return orient_launch(true, img_tiled, blur_tiled, n_img, H, W, W, kp_keys, kp_count, max_kp, order, desc_out, angle_out, stream);
 }
 
 extern "C" int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, const int* kp_count,
