@@ -529,4 +529,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* BetweenFactor<Pose3> (odometry, loop closures) added to the reduced camera system: vus_between_factors and
  * vus_between_check / _linearize / _assemble / _eval_step / _error. */
 #include "vus_between.h"
+
+/* Stereo factors with a camera-to-body extrinsic (GenericStereoFactor3D's body_P_sensor): vus_ba_sensor and the
+ * `_sensor` forms of the linearisation, step evaluation, error and robust weights. */
+#include "vus_sensor.h"
 #endif /* VUS_H */

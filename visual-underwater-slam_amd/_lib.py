@@ -49,6 +49,11 @@ SIGNATURES = {
     "vus_ba_eval_step_robust": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "vus_ba_error_robust": [_P, _P, _P, _P, _P, _P, _P],
     "vus_ba_stereo_weights": [_P, _P, _P, _P, _P, _P],
+    # stereo factors with a camera-to-body extrinsic (include/vus_sensor.h): the plain arguments, then loss and sensor
+    "vus_ba_linearize_sensor": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_eval_step_sensor": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_error_sensor": [_P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_stereo_weights_sensor": [_P, _P, _P, _P, _P, _P, _P],
     # graph packing (csrc/pack.hip)
     "vus_imu_preintegrate": [_P, _P, c_int, _P, _P, _P, _P],      # host pointers
     "vus_keys_to_indices": [_P, c_int, _P, _P, _P, _P, ctypes.c_longlong, _P],

@@ -56,6 +56,28 @@ def robust_loss(loss):
     return kind, k
 
 
+class _CSensor(ctypes.Structure):
+    _fields_ = [("T", c_double * 12)]
+
+
+def sensor_flat12(body_P_sensor):
+    """None, a 12-vector (R row-major, then t), a 4 x 4 matrix or an object with `.flat12()` (gtsam.Pose3) -> the 12
+    float64 values of include/vus_sensor.h, or None.  The library validates them (finite, orthonormal rotation)."""
+    if body_P_sensor is None:
+        return None
+    if hasattr(body_P_sensor, "flat12"):
+        return np.array(body_P_sensor.flat12(), dtype=np.float64).reshape(12)
+    a = body_P_sensor.detach().cpu().numpy() if torch.is_tensor(body_P_sensor) else np.asarray(body_P_sensor)
+    a = np.array(a, dtype=np.float64)
+    if a.shape == (4, 4):
+        if not np.array_equal(a[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("body_P_sensor: the last row of a 4 x 4 pose matrix must be 0 0 0 1")
+        return np.concatenate([a[:3, :3].reshape(9), a[:3, 3]])
+    if a.size == 12 and a.ndim == 1:
+        return a.copy()
+    raise ValueError(f"body_P_sensor: a 12-vector, a 4 x 4 matrix or a Pose3 is expected, not an array of shape {a.shape}")
+
+
 class _CTiles(ctypes.Structure):
     _fields_ = [("band", c_int), ("n_tiles", c_int), ("n_units", c_int), ("n_entries", c_int),
                 ("unit_ptr", c_void_p), ("entries", c_void_p), ("order", c_void_p)]
@@ -219,10 +241,14 @@ class StereoBAProblem:
     """Packed, device-resident stereo BA problem (vus_ba_problem + vus_ba_tiles).  `loss`: robust noise model of the
     stereo factors (robust_loss(): None = Gaussian, or e.g. ("cauchy", 2.0) with k in whitened units).  `between_span`: the
     widest pose distance of a BetweenFactorPose3 (BetweenFactors.span); the band in poses is the larger of it and the
-    landmark span, scaled by pose_stride, so the tiles, Sband and the band-solve mode all follow the wider of the two."""
+    landmark span, scaled by pose_stride, so the tiles, Sband and the band-solve mode all follow the wider of the two.
+    `body_P_sensor`: the camera-to-body extrinsic of every stereo factor (sensor_flat12(): a 12-vector, a 4 x 4 matrix or a
+    gtsam.Pose3) -- the poses are then BODY poses and the left camera sits at pose o body_P_sensor; None = the poses are
+    the camera's."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None,
-                 prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None, between_span=0):
+                 prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None, between_span=0,
+                 body_P_sensor=None):
         _lib.require_gpu()
         _lib.load()
         dev = torch.device(device)
@@ -260,6 +286,9 @@ class StereoBAProblem:
         self.loss = robust_loss(loss)
         self.robust = self.loss[0] != 0           # the Gaussian model keeps today's entry points
         self.c_loss = _CLoss(*self.loss)
+        self.body_P_sensor = sensor_flat12(body_P_sensor)
+        self.has_sensor = self.body_P_sensor is not None       # without one the entry points of today are called
+        self.c_sensor = _CSensor((c_double * 12)(*self.body_P_sensor)) if self.has_sensor else None
         if prior_pose is None or len(prior_pose) == 0:
             self.prior_pose = torch.zeros(0, dtype=torch.int32, device=dev)
             self.prior_T = torch.zeros((0, 12), dtype=torch.float64, device=dev)
@@ -429,7 +458,10 @@ class StereoBASolver:
         return ctypes.addressof(self.P.c_problem)
 
     def _loss_args(self, name):
-        """(entry point, trailing arguments): the `_robust` twin with the problem's vus_ba_loss for a robust model"""
+        """(entry point, trailing arguments): the `_robust` twin with the problem's vus_ba_loss for a robust model; with a
+        body_P_sensor the `_sensor` form, which takes the loss (Gaussian included) and the extrinsic"""
+        if self.P.has_sensor:
+            return name + "_sensor", (ctypes.addressof(self.P.c_loss), ctypes.addressof(self.P.c_sensor))
         return (name + "_robust", (ctypes.addressof(self.P.c_loss),)) if self.P.robust else (name, ())
 
     def error(self, poses, points) -> float:
@@ -450,8 +482,9 @@ class StereoBASolver:
         """Robust weight w(d) of every stereo observation at (poses, points), in the problem's INPUT row order (all ones
         under the Gaussian model): inliers near 1, gross outliers near 0."""
         w = torch.empty(self.P.n_obs, dtype=torch.float64, device=self.P.device)
-        _lib.call("vus_ba_stereo_weights", self._pp(), ctypes.addressof(self.P.c_loss), _lib.ptr(poses), _lib.ptr(points),
-                  _lib.ptr(w), _lib.current_stream_ptr())
+        fn, extra = ("vus_ba_stereo_weights", ()) if not self.P.has_sensor else self._loss_args("vus_ba_stereo_weights")
+        _lib.call(fn, self._pp(), ctypes.addressof(self.P.c_loss), _lib.ptr(poses), _lib.ptr(points),
+                  _lib.ptr(w), _lib.current_stream_ptr(), *extra[1:])
         out = torch.empty_like(w)
         out[self.P.pk["perm"].to(torch.int64)] = w               # perm: L-order row -> input row
         return out

@@ -31,10 +31,12 @@
 //   retract, eval_points, error_points, reduce_partials (the fixed-order sum, also behind nav.hip: vus::reduce_partials)
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include "vus_common.h"
 #include "band_index.h"
@@ -162,6 +164,68 @@ __device__ __forceinline__ double sym3(const double* v, int r, int c) {
   return v[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
 }
 
+// body_P_sensor (include/vus_sensor.h): S and Ad(S^-1), made once on the host (make_sensor) and passed BY VALUE in the
+// kernel arguments -- uniform across the launch, so scalar loads and no per-lane traffic.  The diagonal blocks of
+// Ad(S^-1) are Rs^T, read out of T transposed (sensor_A) instead of being carried twice: 42 scalar registers, not 60.
+// The instances without an extrinsic take the empty NoSensor in that place and are the kernels they were without it.
+struct SensorArg {
+  double T[12];     // S = (Rs row-major, ts)
+  double B[9];      // -Rs^T [ts]x: the lower-left block of Ad(S^-1)
+};
+__device__ __forceinline__ double sensor_A(const SensorArg& S, int r, int c) { return S.T[3 * c + r]; }     // Rs^T
+struct NoSensor {};
+template <bool SENSOR>
+using sensor_arg_t = std::conditional_t<SENSOR, SensorArg, NoSensor>;
+
+// the camera pose of a keyframe: its 12 doubles, or with an extrinsic C = X o S = (Rb Rs, tb + Rb ts)
+template <typename SA>
+__device__ __forceinline__ void load_camera(const double* __restrict__ src, const SA& S, double* T) {
+  if constexpr (std::is_same_v<SA, SensorArg>) {
+    double X[12];
+    load12(src, X);
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) T[3 * rr + c] = X[3 * rr] * S.T[c] + X[3 * rr + 1] * S.T[3 + c] + X[3 * rr + 2] * S.T[6 + c];
+      T[9 + rr] = X[9 + rr] + (X[3 * rr] * S.T[9] + X[3 * rr + 1] * S.T[10] + X[3 * rr + 2] * S.T[11]);
+    }
+  } else {
+    load12(src, T);
+  }
+}
+
+// H1 (3 x 6, camera tangent [omega, v]) <- H1 Ad(S^-1) = [Hw A + Hv B, Hv A]: the Jacobian in the body tangent
+template <typename SA>
+__device__ __forceinline__ void h1_to_body(const SA& S, double* H1) {
+  if constexpr (std::is_same_v<SA, SensorArg>) {
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+      const double w0 = H1[6 * rr], w1 = H1[6 * rr + 1], w2 = H1[6 * rr + 2];
+      const double v0 = H1[6 * rr + 3], v1 = H1[6 * rr + 4], v2 = H1[6 * rr + 5];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        H1[6 * rr + c] = (w0 * sensor_A(S, 0, c) + w1 * sensor_A(S, 1, c) + w2 * sensor_A(S, 2, c)) +
+                         (v0 * S.B[c] + v1 * S.B[3 + c] + v2 * S.B[6 + c]);
+        H1[6 * rr + 3 + c] = v0 * sensor_A(S, 0, c) + v1 * sensor_A(S, 1, c) + v2 * sensor_A(S, 2, c);
+      }
+    }
+  }
+}
+
+// a body-tangent step as the camera's: d <- Ad(S^-1) d = [A w, B w + A v]  (H1_cam (Ad d) = (H1_cam Ad) d)
+template <typename SA>
+__device__ __forceinline__ void step_to_camera(const SA& S, double* d) {
+  if constexpr (std::is_same_v<SA, SensorArg>) {
+    const double w0 = d[0], w1 = d[1], w2 = d[2], v0 = d[3], v1 = d[4], v2 = d[5];
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+      d[rr] = sensor_A(S, rr, 0) * w0 + sensor_A(S, rr, 1) * w1 + sensor_A(S, rr, 2) * w2;
+      d[3 + rr] = (S.B[3 * rr] * w0 + S.B[3 * rr + 1] * w1 + S.B[3 * rr + 2] * w2) +
+                  (sensor_A(S, rr, 0) * v0 + sensor_A(S, rr, 1) * v1 + sensor_A(S, rr, 2) * v2);
+    }
+  }
+}
+
 // IRLS (Block reweighting): scale a factor's whitened residual and Jacobian rows by sqrt(w), w from its own residual
 template <int LOSS, bool WITH_H1, bool WITH_H2>
 __device__ __forceinline__ void robust_reweight(double k, double* r, double* H1, double* H2) {
@@ -180,13 +244,14 @@ __device__ __forceinline__ void robust_reweight(double k, double* r, double* H1,
 
 // ---------------------------------------------------------------------------------------------
 // linearisation (LOSS = VUS_LOSS_*: the Gaussian instance is the plain statement, a robust one reweights every factor
-// before the products; loss_k = the mEstimator's parameter, unused by the Gaussian instance)
-template <int LOSS>
+// before the products; loss_k = the mEstimator's parameter, unused by the Gaussian instance.  SENSOR: the camera sits at
+// X o S and H1 is taken to the body tangent before W = H1^T H2)
+template <int LOSS, bool SENSOR = false>
 __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                          const double* __restrict__ points,
                                                          double* __restrict__ W, double* __restrict__ V,
                                                          double* __restrict__ gl, double* __restrict__ err_part,
-                                                         double loss_k) {
+                                                         double loss_k, sensor_arg_t<SENSOR> S) {
   const int lane = threadIdx.x & 63;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= P.n_points) return;
@@ -196,10 +261,11 @@ __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const
   double v[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, e = 0;
   for (int a = a0 + lane; a < a1; a += 64) {
     double T[12], r[3], H1[18], H2[9];
-    load12(poses + 12 * (size_t)P.obs_pose[a], T);
+    load_camera(poses + 12 * (size_t)P.obs_pose[a], S, T);
     const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
     stereo_factor<true, true>(T, p, m, K, r, H1, H2);
     if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, true>(loss_k, r, H1, H2);
+    h1_to_body(S, H1);
     e += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);      // robust: 0.5 w d^2, the linear error at delta = 0
     double* Wa = W + 18 * (size_t)a;
 #pragma unroll
@@ -228,17 +294,19 @@ __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const
   }
 }
 
-template <int LOSS>
+// SENSOR: Ad(S^-1) is the same for all of a pose's factors, so the sums are taken in the CAMERA tangent as without an
+// extrinsic and the epilogue applies Hpp = Ad^T (.) Ad, gp = Ad^T (.) once per workgroup
+template <int LOSS, bool SENSOR = false>
 __global__ __launch_bounds__(256) void lin_poses_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                         const double* __restrict__ points,
                                                         double* __restrict__ Hpp, double* __restrict__ gp,
-                                                        double loss_k) {
+                                                        double loss_k, sensor_arg_t<SENSOR> S) {
   __shared__ double s_part[4][27];
   const int i = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const Calib K = load_calib(P.K, P.inv_sigma);
   double T[12];
-  load12(poses + 12 * (size_t)i, T);
+  load_camera(poses + 12 * (size_t)i, S, T);
   double acc[27];
 #pragma unroll
   for (int k = 0; k < 27; ++k) acc[k] = 0;
@@ -265,14 +333,52 @@ __global__ __launch_bounds__(256) void lin_poses_kernel(vus_ba_problem P, const 
 #pragma unroll
     for (int k = 0; k < 27; ++k) s_part[wave][k] = acc[k];
   __syncthreads();
+  double sum = 0;
   if (threadIdx.x < 36) {
     const int rr = threadIdx.x / 6, c = threadIdx.x % 6;
     const int lo = rr < c ? rr : c, hi = rr < c ? c : rr;
     const int u = lo * 6 - lo * (lo - 1) / 2 + (hi - lo);  // index in the row-wise upper triangle
-    Hpp[36 * (size_t)i + threadIdx.x] = ((s_part[0][u] + s_part[1][u]) + s_part[2][u]) + s_part[3][u];
+    sum = ((s_part[0][u] + s_part[1][u]) + s_part[2][u]) + s_part[3][u];
+    if (!SENSOR) Hpp[36 * (size_t)i + threadIdx.x] = sum;
   } else if (threadIdx.x < 42) {
     const int u = 21 + threadIdx.x - 36;
-    gp[6 * (size_t)i + threadIdx.x - 36] = ((s_part[0][u] + s_part[1][u]) + s_part[2][u]) + s_part[3][u];
+    sum = ((s_part[0][u] + s_part[1][u]) + s_part[2][u]) + s_part[3][u];
+    if (!SENSOR) gp[6 * (size_t)i + threadIdx.x - 36] = sum;
+  }
+  if constexpr (SENSOR) {
+    // the camera-tangent sums expanded to the full 6 x 6 and the 6-vector, Ad(S^-1) beside them, then the congruence
+    __shared__ double s_hg[42], s_ad[36];
+    if (threadIdx.x < 42) s_hg[threadIdx.x] = sum;
+    if (threadIdx.x == 64) {      // lane 0 of a wave with nothing else to do here: constant indices into the arguments
+#pragma unroll
+      for (int rr = 0; rr < 3; ++rr)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          s_ad[6 * rr + c] = sensor_A(S, rr, c);
+          s_ad[6 * rr + 3 + c] = 0.0;
+          s_ad[6 * (rr + 3) + c] = S.B[3 * rr + c];
+          s_ad[6 * (rr + 3) + 3 + c] = sensor_A(S, rr, c);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 36) {
+      const int rr = threadIdx.x / 6, c = threadIdx.x % 6;
+      double out = 0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        double mk = 0;      // (H Ad)[k][c]
+#pragma unroll
+        for (int l = 0; l < 6; ++l) mk += s_hg[6 * k + l] * s_ad[6 * l + c];
+        out += s_ad[6 * k + rr] * mk;
+      }
+      Hpp[36 * (size_t)i + threadIdx.x] = out;
+    } else if (threadIdx.x < 42) {
+      const int rr = threadIdx.x - 36;
+      double out = 0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) out += s_ad[6 * k + rr] * s_hg[36 + k];
+      gp[6 * (size_t)i + rr] = out;
+    }
   }
 }
 
@@ -2455,14 +2561,15 @@ __global__ void retract_kernel(int n_poses, int n_points, int ps, const double* 
 // per point: part_lin[j] = 0.5 sum |r + H1 dp + H2 dl|^2 at the old values,
 //            part_new[j] = 0.5 sum |r|^2 at the new values
 // robust LOSS: r, H1, H2 at the old values reweighted by sqrt(w(old)) (the linearisation point), part_new = sum rho
-template <bool WITH_LIN, int LOSS = VUS_LOSS_GAUSSIAN>
+// SENSOR: both the old and the new poses are composed with S; dp is a body-tangent step, taken to the camera tangent
+template <bool WITH_LIN, int LOSS = VUS_LOSS_GAUSSIAN, bool SENSOR = false>
 __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                           const double* __restrict__ points,
                                                           const double* __restrict__ dp, const double* __restrict__ dl,
                                                           const double* __restrict__ new_poses,
                                                           const double* __restrict__ new_points,
                                                           double* __restrict__ part_lin, double* __restrict__ part_new,
-                                                          double loss_k) {
+                                                          double loss_k, sensor_arg_t<SENSOR> S) {
   const int lane = threadIdx.x & 63;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= P.n_points) return;
@@ -2481,7 +2588,7 @@ __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, cons
     const int i = P.obs_pose[a];
     const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
     double T[12], r[3];
-    load12(new_poses + 12 * (size_t)i, T);
+    load_camera(new_poses + 12 * (size_t)i, S, T);
     stereo_factor<false, false>(T, pn, m, K, r, nullptr, nullptr);
     if (LOSS == VUS_LOSS_GAUSSIAN) {
       e_new += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
@@ -2492,10 +2599,13 @@ __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, cons
     }
     if (WITH_LIN) {
       double H1[18], H2[9];
-      load12(poses + 12 * (size_t)i, T);
+      load_camera(poses + 12 * (size_t)i, S, T);
       stereo_factor<true, true>(T, po, m, K, r, H1, H2);
       if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, true>(loss_k, r, H1, H2);
-      const double* d = dp + 6 * (size_t)pose_stride(P) * i;
+      double d[6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) d[c] = dp[6 * (size_t)pose_stride(P) * i + c];
+      step_to_camera(S, d);
 #pragma unroll
       for (int rr = 0; rr < 3; ++rr) {
         double t = r[rr];
@@ -2532,10 +2642,10 @@ int check_problem(const vus_ba_problem* P) {
 }
 
 // w [n_obs] (L-order) of every stereo observation at (poses, points), thread / observation
-template <int LOSS>
+template <int LOSS, bool SENSOR = false>
 __global__ __launch_bounds__(256) void stereo_weights_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                              const double* __restrict__ points, double* __restrict__ w_out,
-                                                             double loss_k) {
+                                                             double loss_k, sensor_arg_t<SENSOR> S) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= P.n_obs) return;
   const Calib K = load_calib(P.K, P.inv_sigma);
@@ -2543,7 +2653,7 @@ __global__ __launch_bounds__(256) void stereo_weights_kernel(vus_ba_problem P, c
   const double p[3] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
   const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
   double T[12], r[3], w, rho;
-  load12(poses + 12 * (size_t)P.obs_pose[a], T);
+  load_camera(poses + 12 * (size_t)P.obs_pose[a], S, T);
   stereo_factor<false, false>(T, p, m, K, r, nullptr, nullptr);
   robust_weight<LOSS>(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], loss_k, w, rho);
   w_out[a] = w;
@@ -2554,6 +2664,30 @@ int check_loss(const vus_ba_loss* L) {
   VUS_REQUIRE(L->kind >= VUS_LOSS_GAUSSIAN && L->kind <= VUS_LOSS_WELSCH, "unknown loss kind %d", L->kind);
   VUS_REQUIRE(L->kind == VUS_LOSS_GAUSSIAN || (L->k > 0.0 && L->k <= 1.7976931348623157e308),
               "loss parameter k=%g must be finite and > 0", L->k);
+  return VUS_OK;
+}
+
+// vus_ba_sensor -> the kernels' SensorArg, validated on the host (include/vus_sensor.h)
+int make_sensor(const vus_ba_sensor* s, SensorArg& out) {
+  VUS_REQUIRE(s != nullptr, "sensor is null");
+  for (int k = 0; k < 12; ++k) VUS_REQUIRE(std::isfinite(s->T[k]), "sensor: T[%d]=%g is not finite", k, s->T[k]);
+  const double* R = s->T;
+  const double* t = s->T + 9;
+  double worst = 0;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double g = R[a] * R[b] + R[3 + a] * R[3 + b] + R[6 + a] * R[6 + b] - (a == b ? 1.0 : 0.0);
+      worst = std::fmax(worst, std::fabs(g));
+    }
+  VUS_REQUIRE(worst <= 1e-9, "sensor: the rotation is not orthonormal (max |R^T R - I| = %g)", worst);
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  VUS_REQUIRE(det > 0.0, "sensor: the rotation is a reflection (det = %g)", det);
+  for (int k = 0; k < 12; ++k) out.T[k] = s->T[k];
+  const double tx[9] = {0.0, -t[2], t[1], t[2], 0.0, -t[0], -t[1], t[0], 0.0};      // [ts]x
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      out.B[3 * a + b] = -(R[a] * tx[b] + R[3 + a] * tx[3 + b] + R[6 + a] * tx[6 + b]);
+    }
   return VUS_OK;
 }
 
@@ -2573,14 +2707,17 @@ int dispatch_loss(const vus_ba_loss* L, A... args) {
 template <int LOSS>
 struct ErrorOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* err,
-                 double* work, void* stream) {
+                 double* work, void* stream, const SensorArg* S) {
     if (int rc = check_problem(P)) return rc;
     VUS_REQUIRE(poses && (points || !P->n_points) && err && work, "null buffer");
     hipStream_t st = vus::as_stream(stream);
     const int nL = P->n_points;
-    if (nL > 0)
+    if (nL > 0 && S)
+      eval_points_kernel<false, LOSS, true><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
+                                                                        nullptr, work, k, *S);
+    else if (nL > 0)
       eval_points_kernel<false, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
-                                                                  nullptr, work, k);
+                                                                  nullptr, work, k, NoSensor{});
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, nullptr, nullptr, work + nL, 1);
     vus::reduce_partials(work, nL + 1, err, st);
     VUS_CHECK_LAUNCH("ba_error");
@@ -2591,7 +2728,7 @@ struct ErrorOp {
 template <int LOSS>
 struct LinearizeOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* W, double* V,
-                 double* gl, double* Hpp, double* gp, double* err, double* work, void* stream) {
+                 double* gl, double* Hpp, double* gp, double* err, double* work, void* stream, const SensorArg* S) {
     if (int rc = check_problem(P)) return rc;
     // a graph without landmarks (priors only) has empty per-landmark / per-observation arrays: those may be null
     VUS_REQUIRE(poses && Hpp && gp && err && work, "null buffer");
@@ -2599,8 +2736,13 @@ struct LinearizeOp {
     VUS_REQUIRE(W || !P->n_obs, "null observation buffer");
     hipStream_t st = vus::as_stream(stream);
     const int nL = P->n_points;
-    if (nL > 0) lin_points_kernel<LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k);
-    lin_poses_kernel<LOSS><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k);
+    if (S) {
+      if (nL > 0) lin_points_kernel<LOSS, true><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k, *S);
+      lin_poses_kernel<LOSS, true><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k, *S);
+    } else {
+      if (nL > 0) lin_points_kernel<LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k, NoSensor{});
+      lin_poses_kernel<LOSS><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k, NoSensor{});
+    }
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, Hpp, gp, work + nL, 0);
     vus::reduce_partials(work, nL + 1, err, st);
     VUS_CHECK_LAUNCH("ba_linearize");
@@ -2611,7 +2753,8 @@ struct LinearizeOp {
 template <int LOSS>
 struct EvalStepOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, const double* dp,
-                 const double* dl, double* new_poses, double* new_points, double* out, double* work, void* stream) {
+                 const double* dl, double* new_poses, double* new_points, double* out, double* work, void* stream,
+                 const SensorArg* S) {
     if (int rc = check_problem(P)) return rc;
     VUS_REQUIRE(poses && dp && new_poses && out && work, "null buffer");
     VUS_REQUIRE((points && dl && new_points) || !P->n_points, "null landmark buffer");
@@ -2621,9 +2764,12 @@ struct EvalStepOp {
                                                                                              dp, dl, new_poses, new_points);
     double* part_lin = work;
     double* part_new = work + (nL + 1);
-    if (nL > 0)
+    if (nL > 0 && S)
+      eval_points_kernel<true, LOSS, true><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, dp, dl, new_poses, new_points,
+                                                                       part_lin, part_new, k, *S);
+    else if (nL > 0)
       eval_points_kernel<true, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, dp, dl, new_poses, new_points, part_lin,
-                                                                 part_new, k);
+                                                                 part_new, k, NoSensor{});
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, dp, nullptr, nullptr, part_lin + nL, 2);
     priors_kernel<<<1, 64, 0, st>>>(*P, new_poses, nullptr, nullptr, nullptr, part_new + nL, 1);
     vus::reduce_partials(part_lin, nL + 1, out, st);
@@ -2635,11 +2781,15 @@ struct EvalStepOp {
 
 template <int LOSS>
 struct WeightsOp {
-  static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* w, void* stream) {
+  static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* w, void* stream,
+                 const SensorArg* S) {
     if (int rc = check_problem(P)) return rc;
     VUS_REQUIRE(poses && ((points && w) || !P->n_obs), "null buffer");
-    if (P->n_obs > 0)
-      stereo_weights_kernel<LOSS><<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k);
+    if (P->n_obs > 0 && S)
+      stereo_weights_kernel<LOSS, true><<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k, *S);
+    else if (P->n_obs > 0)
+      stereo_weights_kernel<LOSS><<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k,
+                                                                                          NoSensor{});
     VUS_CHECK_LAUNCH("ba_stereo_weights");
     return VUS_OK;
   }
@@ -2654,32 +2804,67 @@ extern "C" long long vus_ba_work_doubles(const vus_ba_problem* P) {
 
 extern "C" int vus_ba_error(const vus_ba_problem* P, const double* poses, const double* points, double* err,
                             double* work, void* stream) {
-  return ErrorOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, err, work, stream);
+  return ErrorOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, err, work, stream, nullptr);
 }
 
 extern "C" int vus_ba_error_robust(const vus_ba_problem* P, const double* poses, const double* points, double* err,
                                    double* work, void* stream, const vus_ba_loss* loss) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream);
+  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, (const SensorArg*)nullptr);
 }
 
 extern "C" int vus_ba_linearize(const vus_ba_problem* P, const double* poses, const double* points, double* W,
                                 double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
                                 void* stream) {
-  return LinearizeOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, W, V, gl, Hpp, gp, err, work, stream);
+  return LinearizeOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, nullptr);
 }
 
 extern "C" int vus_ba_linearize_robust(const vus_ba_problem* P, const double* poses, const double* points, double* W,
                                        double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
                                        void* stream, const vus_ba_loss* loss) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream);
+  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, (const SensorArg*)nullptr);
 }
 
 extern "C" int vus_ba_stereo_weights(const vus_ba_problem* P, const vus_ba_loss* loss, const double* poses,
                                      const double* points, double* w, void* stream) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream);
+  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, (const SensorArg*)nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// body_P_sensor (include/vus_sensor.h): one set of entry points for the Gaussian and the robust models
+namespace {
+const vus_ba_loss kGaussianLoss = {VUS_LOSS_GAUSSIAN, 0.0};
+
+// (loss or the Gaussian model for NULL, the kernels' form of the extrinsic), both validated
+int sensor_args(const vus_ba_loss*& loss, const vus_ba_sensor* sensor, SensorArg& S) {
+  if (!loss) loss = &kGaussianLoss;
+  if (int rc = check_loss(loss)) return rc;
+  return make_sensor(sensor, S);
+}
+}  // namespace
+
+extern "C" int vus_ba_error_sensor(const vus_ba_problem* P, const double* poses, const double* points, double* err,
+                                   double* work, void* stream, const vus_ba_loss* loss, const vus_ba_sensor* sensor) {
+  SensorArg S;
+  if (int rc = sensor_args(loss, sensor, S)) return rc;
+  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, (const SensorArg*)&S);
+}
+
+extern "C" int vus_ba_linearize_sensor(const vus_ba_problem* P, const double* poses, const double* points, double* W,
+                                       double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
+                                       void* stream, const vus_ba_loss* loss, const vus_ba_sensor* sensor) {
+  SensorArg S;
+  if (int rc = sensor_args(loss, sensor, S)) return rc;
+  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, (const SensorArg*)&S);
+}
+
+extern "C" int vus_ba_stereo_weights_sensor(const vus_ba_problem* P, const vus_ba_loss* loss, const double* poses,
+                                            const double* points, double* w, void* stream, const vus_ba_sensor* sensor) {
+  SensorArg S;
+  if (int rc = sensor_args(loss, sensor, S)) return rc;
+  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, (const SensorArg*)&S);
 }
 
 extern "C" int vus_ba_schur(const vus_ba_problem* P, const vus_ba_tiles* T, double lambda, const double* W, const double* V,
@@ -3359,14 +3544,25 @@ extern "C" int vus_ba_backsub(const vus_ba_problem* P, const double* W, const do
 extern "C" int vus_ba_eval_step(const vus_ba_problem* P, const double* poses, const double* points, const double* dp,
                                 const double* dl, double* new_poses, double* new_points, double* out, double* work,
                                 void* stream) {
-  return EvalStepOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, dp, dl, new_poses, new_points, out, work, stream);
+  return EvalStepOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, dp, dl, new_poses, new_points, out, work, stream, nullptr);
 }
 
 extern "C" int vus_ba_eval_step_robust(const vus_ba_problem* P, const double* poses, const double* points,
                                        const double* dp, const double* dl, double* new_poses, double* new_points,
                                        double* out, double* work, void* stream, const vus_ba_loss* loss) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream);
+  return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream,
+                                   (const SensorArg*)nullptr);
+}
+
+extern "C" int vus_ba_eval_step_sensor(const vus_ba_problem* P, const double* poses, const double* points,
+                                       const double* dp, const double* dl, double* new_poses, double* new_points,
+                                       double* out, double* work, void* stream, const vus_ba_loss* loss,
+                                       const vus_ba_sensor* sensor) {
+  SensorArg S;
+  if (int rc = sensor_args(loss, sensor, S)) return rc;
+  return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream,
+                                   (const SensorArg*)&S);
 }
 
 #ifdef VUS_TIMING

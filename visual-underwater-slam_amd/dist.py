@@ -189,11 +189,14 @@ class ShardedStereoBASolver:
     landmarks, band forced to the global band) and inserts the collectives."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
-                 prior_sigmas=None, device="cuda:0", loss=None, between=None):
+                 prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None):
         from .ba import StereoBAProblem, StereoBASolver
         if between is not None:
             raise NotImplementedError("BetweenFactorPose3 (ba.BetweenFactors) is not supported by the landmark-sharded solver: "
                                       "use StereoBASolver(problem, between) on one GPU")
+        if body_P_sensor is not None:
+            raise NotImplementedError("a camera-to-body extrinsic (body_P_sensor) is not supported by the landmark-sharded "
+                                      "solver: use StereoBASolver(StereoBAProblem(..., body_P_sensor=...)) on one GPU")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         obs_pose = torch.as_tensor(obs_pose).to(device)
@@ -267,4 +270,6 @@ def _make_shard_solver():
 
 
 def _ShardSolver(problem, world):
+    if getattr(problem, "has_sensor", False):
+        raise NotImplementedError("a camera-to-body extrinsic (body_P_sensor) is not supported by the landmark-sharded solver")
     return _make_shard_solver()(problem, world)

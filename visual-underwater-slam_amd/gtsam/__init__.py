@@ -510,15 +510,39 @@ class _Factor:
         return len(self._keys)
 
 
+def _sensor_pose(body_P_sensor):
+    """The stored form of a factor's body_P_sensor argument: None or an own Pose3."""
+    if body_P_sensor is None:
+        return None
+    if not isinstance(body_P_sensor, Pose3):
+        raise RuntimeError("body_P_sensor must be a Pose3 or None")
+    return Pose3(body_P_sensor)
+
+
+def _same_sensor(a, b):
+    """Two stored extrinsics agree: both None, or equal poses in gtsam's sense of Pose3::equals(tol = 1e-12), every
+    entry within the ABSOLUTE tolerance (Pose3.equals above also grants numpy's relative 1e-5)."""
+    if a is None or b is None:
+        return a is None and b is None
+    return a is b or bool(np.abs(a.flat12() - b.flat12()).max() <= 1e-12)
+
+
 class GenericStereoFactor3D(_Factor):
-    """GenericStereoFactor<Pose3, Point3>(measured, model, poseKey, landmarkKey, K)  (batch.py:300-304)."""
+    """GenericStereoFactor<Pose3, Point3>(measured, model, poseKey, landmarkKey, K, body_P_sensor=None)
+    (batch.py:300-304).  With a body_P_sensor the pose variable is the vehicle body and the left camera sits at
+    pose o body_P_sensor; one graph holds one extrinsic (or none)."""
 
     def __init__(self, measured: StereoPoint2, model: _NoiseModel, poseKey: int, landmarkKey: int,
-                 K: Cal3_S2Stereo):
+                 K: Cal3_S2Stereo, body_P_sensor: Optional[Pose3] = None):
         super().__init__([poseKey, landmarkKey])
         if model.dim() != 3:
             raise RuntimeError("GenericStereoFactor3D needs a 3-dimensional noise model")
         self._measured, self._model, self._K = measured, model, K
+        self._sensor = _sensor_pose(body_P_sensor)
+
+    def body_P_sensor(self):
+        """A copy of the camera-to-body extrinsic, or None."""
+        return None if self._sensor is None else Pose3(self._sensor)
 
     def measured(self):
         return self._measured
@@ -535,7 +559,8 @@ class StereoFactorBlock(_Factor):
     calibration, held as arrays.  It is the vectorised form of the emission loop batch.py:296-305 for
     graphs with millions of observations, where one Python object per factor is the bottleneck."""
 
-    def __init__(self, measured, model: _NoiseModel, poseKeys, landmarkKeys, K: Cal3_S2Stereo):
+    def __init__(self, measured, model: _NoiseModel, poseKeys, landmarkKeys, K: Cal3_S2Stereo,
+                 body_P_sensor: Optional[Pose3] = None):
         self.meas = np.ascontiguousarray(measured, dtype=float).reshape(-1, 3)
         self.pose_keys = np.ascontiguousarray(poseKeys, dtype=np.int64).reshape(-1)
         self.landmark_keys = np.ascontiguousarray(landmarkKeys, dtype=np.int64).reshape(-1)
@@ -544,7 +569,12 @@ class StereoFactorBlock(_Factor):
         if model.dim() != 3:
             raise RuntimeError("StereoFactorBlock needs a 3-dimensional noise model")
         self._model, self._K = model, K
+        self._sensor = _sensor_pose(body_P_sensor)
         self._keys = None
+
+    def body_P_sensor(self):
+        """A copy of the camera-to-body extrinsic of every factor of the block, or None."""
+        return None if self._sensor is None else Pose3(self._sensor)
 
     def keys(self):
         return np.unique(np.concatenate([self.pose_keys, self.landmark_keys])).tolist()
@@ -1094,17 +1124,18 @@ class NonlinearFactorGraph:
         self._factors: List[_Factor] = []
         self._other: List[_Factor] = []          # everything that is not a single GenericStereoFactor3D
         self._st_meas, self._st_pk, self._st_lk = array("d"), array("q"), array("q")
-        self._st_model = self._st_K = None       # the one noise model / calibration the stereo factors share ...
+        self._st_model = self._st_K = self._st_sensor = None     # the one noise model / calibration / extrinsic the stereo factors share ...
         self._st_mixed = False                   # ... or the fact that they do not (refused at optimize())
 
     def _record(self, factor):
         self._factors.append(factor)
         if type(factor) is GenericStereoFactor3D:
-            m, K = factor._model, factor._K
+            m, K, S = factor._model, factor._K, factor._sensor
             if self._st_model is None:
-                self._st_model, self._st_K = m, K
+                self._st_model, self._st_K, self._st_sensor = m, K, S
             elif (m is not self._st_model and _stereo_model_key(m) != _stereo_model_key(self._st_model)) or \
-                    (K is not self._st_K and not K.equals(self._st_K)):
+                    (K is not self._st_K and not K.equals(self._st_K)) or \
+                    (S is not self._st_sensor and not _same_sensor(S, self._st_sensor)):
                 self._st_mixed = True
             self._st_meas.extend(factor._measured._m)
             self._st_pk.append(factor._keys[0])

@@ -148,12 +148,13 @@ def _pack_graph(graph, values, device=None):
     between_f = []
     imu_f, dvl_f, bias_f = [], [], []
     from . import _Robust
-    model_sigma, calib, loss = None, None, None
+    from . import _same_sensor
+    model_sigma, calib, loss, sensor = None, None, None, None
     prior_pose, prior_vec = [], []
     single_m, single_p, single_l = [], [], []
 
-    def check_model(model, K):
-        nonlocal model_sigma, calib, loss
+    def check_model(model, K, body_P_sensor):
+        nonlocal model_sigma, calib, loss, sensor
         if not model.is_isotropic():
             raise NotImplementedError("stereo factors need an isotropic noise model (batch.py:118 uses Isotropic.Sigma(3, 10)), "
                                       "optionally wrapped in noiseModel.Robust")
@@ -161,18 +162,20 @@ def _pack_graph(graph, values, device=None):
         rob = model.robust() if isinstance(model, _Robust) else None
         lo = (rob.kind, rob.k) if rob is not None else None          # (VUS_LOSS_* kind, k) of a robust model
         if model_sigma is None:
-            model_sigma, calib, loss = s, K, lo
+            model_sigma, calib, loss, sensor = s, K, lo, body_P_sensor
         elif s != model_sigma or lo != loss or not K.equals(calib):
             raise NotImplementedError("all stereo factors of one graph must share one noise model and one Cal3_S2Stereo")
+        elif not _same_sensor(body_P_sensor, sensor):
+            raise NotImplementedError("all stereo factors of one graph must share one body_P_sensor (or all have none)")
 
     # single GenericStereoFactor3D objects were recorded column-wise when they were added (NonlinearFactorGraph._record):
     # only the O(#keyframes) other factors are visited here
     for f in graph._other:
         if isinstance(f, StereoFactorBlock):
-            check_model(f._model, f._K)
+            check_model(f._model, f._K, f._sensor)
             meas.append(f.meas); pkeys.append(f.pose_keys); lkeys.append(f.landmark_keys)
         elif isinstance(f, GenericStereoFactor3D):       # a subclass instance: not recorded column-wise
-            check_model(f._model, f._K)
+            check_model(f._model, f._K, f._sensor)
             single_m.append(f._measured._m); single_p.append(f._keys[0]); single_l.append(f._keys[1])
         elif isinstance(f, PriorFactorPose3):
             prior_pose.append(f)
@@ -205,8 +208,9 @@ def _pack_graph(graph, values, device=None):
     c_meas, c_pk, c_lk, c_model, c_K, c_mixed = graph._stereo_columns()
     if len(c_pk):
         if c_mixed:
-            raise NotImplementedError("all stereo factors of one graph must share one noise model and one Cal3_S2Stereo")
-        check_model(c_model, c_K)
+            raise NotImplementedError("all stereo factors of one graph must share one noise model, one Cal3_S2Stereo and one "
+                                      "body_P_sensor (or have none)")
+        check_model(c_model, c_K, graph._st_sensor)
         meas.append(c_meas); pkeys.append(c_pk); lkeys.append(c_lk)
     if single_m:
         meas.append(np.asarray(single_m, dtype=float).reshape(-1, 3))
@@ -278,6 +282,7 @@ def _pack_graph(graph, values, device=None):
         raise NotImplementedError("several prior factors on one vector variable are not supported")
     return dict(meas=meas, pose_idx=pose_idx, lm_idx=lm_idx, pose_keys=pose_keys, lm_keys=lm_keys, poses=poses,
                 points=points, sigma=model_sigma if model_sigma is not None else 1.0, loss=loss,
+                body_P_sensor=sensor.flat12() if sensor is not None else None,
                 K=calib.vector6() if calib is not None else np.array([1.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
                 prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between)
@@ -431,7 +436,8 @@ def _build_solver(pg, device="cuda:0"):
     prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
                            prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
-                           loss=pg.get("loss"), between_span=btw["span"] if btw else 0)
+                           loss=pg.get("loss"), between_span=btw["span"] if btw else 0,
+                           body_P_sensor=pg.get("body_P_sensor"))
     bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
                         loss=list(btw["losses"]), device=device) if btw else None
     if walk:

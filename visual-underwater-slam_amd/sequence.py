@@ -46,8 +46,12 @@ def depth_from_pressure(press_abs):
 class BatchSequence:
     """AUV_ISAM's batch accumulators and graph construction (batch.py:74-118, 144-176, 253-305)."""
 
-    def __init__(self, disparity_sign: int = -1, device: str = "cuda:0"):
+    def __init__(self, disparity_sign: int = -1, device: str = "cuda:0", body_P_sensor: Optional["gtsam.Pose3"] = None):
+        """body_P_sensor: the camera-to-body extrinsic put on every stereo factor (the reference builds it as DELTA,
+        batch.py:190-193, and never passes it on); X(i) is then the body pose.  Landmarks are initialised from
+        zed_world_transform -- the CAMERA in the world -- as in the reference (batch.py:166)."""
         assert disparity_sign in (-1, 1)
+        self.body_P_sensor = None if body_P_sensor is None else gtsam.Pose3(body_P_sensor)
         self.device = torch.device(device)
         self.graph = gtsam.NonlinearFactorGraph()                                    # batch.py:80
         self.initial_estimate = gtsam.Values()                                       # :81
@@ -153,7 +157,7 @@ class BatchSequence:
                         self.initial_estimate.insert(L(landmark['id']), landmark['pose'])
                     self.graph.push_back(gtsam.GenericStereoFactor3D(
                         gtsam.StereoPoint2(landmark['uL'], landmark['uR'], landmark['v']), self.landmark_noise,
-                        X(i), L(landmark['id']), self.K))                            # :300-305
+                        X(i), L(landmark['id']), self.K, self.body_P_sensor))        # :300-305
 
     def gate_factors(self, factors, Rt: torch.Tensor, gate_px: float):
         """EXTENSION (no counterpart in batch.py, whose input has been through the nodelet's RANSAC): drop every
@@ -193,7 +197,7 @@ class BatchSequence:
             kx += X(0)
             kl = oi.astype(np.int64)
             kl += L(0)
-            self.graph.push_back(gtsam.StereoFactorBlock(om, self.landmark_noise, kx, kl, self.K))
+            self.graph.push_back(gtsam.StereoFactorBlock(om, self.landmark_noise, kx, kl, self.K, self.body_P_sensor))
         first = factors["lm_first"].cpu().numpy()
         seen = np.nonzero(first >= 0)[0]
         if len(seen):
@@ -223,26 +227,29 @@ GATE_PX = 60.0        # 6 sigma of the stereo noise model (batch.py:118: sigma =
 
 def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, disparity_sign: int = 1,
                  params: Optional[ImageProcessorParams] = None, bulk: bool = True, frontend: Optional[StereoOrbFrontend] = None,
-                 gate_px: float = GATE_PX):
+                 gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None):
     """Images to optimised trajectory: frames uint8 [F,2,H,W] on the GPU (one stereo pair per keyframe), odom_poses
     [F,12] (the odometry estimate of every keyframe = initial value of X(i) AND the camera transform get_landmarks
     uses), imu [F-1][n,>=6] samples between keyframes, dvl [F,3].  gate_px > 0 applies BatchSequence.gate_factors (bulk
-    path only).  Returns (results Values, BatchSequence, stages dict)."""
+    path only).  body_P_sensor: odom_poses are BODY poses, every stereo factor carries the extrinsic, and the camera
+    transform of get_landmarks and of the gate is odom_pose o body_P_sensor.  Returns (results Values, BatchSequence,
+    stages dict)."""
     if params is None:
         params = ImageProcessorParams(**SEQUENCE_PARAMS)
     F, _, H, W = frames.shape
     fe = frontend or StereoOrbFrontend(H, W, max_frames=F, params=params)
     res = fe.process(frames)
     ids, feats, n_ids = fe.feature_tracks(res)
-    seq = BatchSequence(disparity_sign=disparity_sign, device=str(frames.device))
+    seq = BatchSequence(disparity_sign=disparity_sign, device=str(frames.device), body_P_sensor=body_P_sensor)
     Rt = keyframe_transforms(odom_poses)
+    Rt_cam = Rt if body_P_sensor is None else np.stack([gtsam.Pose3.from_flat12(r).compose(body_P_sensor).flat12() for r in Rt])
     stages = {"frontend": res, "ids": ids, "feats": feats, "n_ids": n_ids}
     if bulk:
         for i in range(F):
             seq.odom_accum.append(gtsam.Pose3.from_flat12(Rt[i]))
             seq.dvl_accum.append(np.asarray(dvl[i], float))
             seq.imu_accum.append([np.asarray(s, float)[:6] for s in imu[i - 1]] if i > 0 else [])
-        Rt_d = torch.from_numpy(Rt).to(frames.device)
+        Rt_d = torch.from_numpy(Rt_cam).to(frames.device)
         factors = fe.stereo_factors(ids, feats, n_ids, Rt_d, seq.cam_array())
         stages["factors_ungated"] = factors
         if gate_px > 0:
@@ -253,7 +260,7 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
         msgs = fe.camera_measurements(res)
         for i in range(F):
             pose = gtsam.Pose3.from_flat12(Rt[i])
-            seq.set_zed_world_transform(pose.rotation(), Rt[i, 9:])
+            seq.set_zed_world_transform(gtsam.Pose3.from_flat12(Rt_cam[i]).rotation(), Rt_cam[i, 9:])
             if i > 0:
                 for s in imu[i - 1]:
                     seq.update_imu(s[:3], s[3:6])
