@@ -197,7 +197,11 @@ int vus_cross_check(const int32_t* idx_fwd, const int32_t* idx_bwd, int n_pairs,
  *   ids_out  int64 [n_frames, max_kp]   id of every PUBLISHED feature, -1 otherwise
  *   feat_out f64   [n_frames, max_kp, 4] (u0, v0, u1, v1) = 2*x/W - 1, 2*y/H - 1 for both cameras
  *                  (zeros where not published)
- *   n_ids_out int64 [1]                 number of ids issued */
+ *   n_ids_out int64 [1]                 number of ids issued
+ * kp_count is clamped to max_kp (a negative count: an empty list); a track index outside [0, count of the next left
+ * image) and a stereo index outside [0, count of the right image) are no match; every slot of ids_out / feat_out is
+ * written.  1 <= max_kp <= 8192: one workgroup keeps two int64 per keypoint in LDS next to 4104 B of its own,
+ * 135,176 B at 8192 of the 160 KiB a gfx950 workgroup can have. */
 int vus_track_ids(const int32_t* stereo_idx, const int32_t* track_idx, const uint32_t* kp_keys,
                   const int* kp_count, int n_frames, int max_kp, int H, int W, int64_t* ids_out,
                   double* feat_out, int64_t* n_ids_out, void* stream);

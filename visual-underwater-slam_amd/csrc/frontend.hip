@@ -1767,15 +1767,20 @@ __global__ __launch_bounds__(HR_THREADS) void hamming_match_rows_kernel(
 // sequential (ids of frame f depend on frame f-1), so ONE workgroup walks the frames; inside a frame
 // everything is parallel over keypoints (LDS atomicMin picks the lowest-index predecessor, a block
 // scan numbers the fresh ids in index order).
+// LDS: two int64 per keypoint (dynamic) + s_part and s_next (static, 4104 B): 16 B x 8192 + 4104 B = 135,176 B at the
+// largest max_kp, of the 160 KiB a workgroup can have.  The predecessor choice lives in s_nxt itself: -1 read as
+// unsigned is the largest value, so an unsigned atomicMin of the predecessor's index needs no array of its own.
 constexpr int TRK_THREADS = 1024;
+constexpr int TRK_MAX_KP = 8192;
+constexpr size_t TRK_LDS_PER_KP = 2 * sizeof(long long);
+constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 __global__ __launch_bounds__(TRK_THREADS) void track_ids_kernel(
     const int32_t* __restrict__ stereo_idx, const int32_t* __restrict__ track_idx,
     const uint32_t* __restrict__ kp_keys, const int* __restrict__ kp_count, int n_frames, int max_kp, int H, int W,
     long long* __restrict__ ids_out, double* __restrict__ feat_out, long long* __restrict__ n_ids_out) {
   extern __shared__ long long s_trk[];
   long long* s_cur = s_trk;                    // [max_kp] ids carried by the previous frame's keypoints
-  long long* s_nxt = s_trk + max_kp;           // [max_kp]
-  int* s_src = reinterpret_cast<int*>(s_trk + 2 * max_kp);   // [max_kp] lowest predecessor index
+  long long* s_nxt = s_trk + max_kp;           // [max_kp] first the lowest id-carrying predecessor's index, then its id
   __shared__ int s_part[TRK_THREADS];
   __shared__ long long s_next;
   const int tid = threadIdx.x;
@@ -1784,16 +1789,19 @@ __global__ __launch_bounds__(TRK_THREADS) void track_ids_kernel(
   int n_prev = 0;
   for (int f = 0; f < n_frames; ++f) {
     const int nl = min(kp_count[2 * f], max_kp), nr = min(kp_count[2 * f + 1], max_kp);
-    for (int i = tid; i < max_kp; i += TRK_THREADS) { s_nxt[i] = -1; s_src[i] = 0x7FFFFFFF; }
+    for (int i = tid; i < max_kp; i += TRK_THREADS) s_nxt[i] = -1;
     __syncthreads();
     if (f > 0)
       for (int ip = tid; ip < n_prev; ip += TRK_THREADS) {
         const int j = track_idx[(size_t)(f - 1) * max_kp + ip];
-        if (j >= 0 && j < nl && s_cur[ip] >= 0) atomicMin(&s_src[j], ip);
+        if (j >= 0 && j < nl && s_cur[ip] >= 0)
+          atomicMin(reinterpret_cast<unsigned long long*>(&s_nxt[j]), (unsigned long long)ip);
       }
     __syncthreads();
-    for (int j = tid; j < nl; j += TRK_THREADS)
-      if (s_src[j] != 0x7FFFFFFF) s_nxt[j] = s_cur[s_src[j]];
+    for (int j = tid; j < nl; j += TRK_THREADS) {
+      const long long src = s_nxt[j];
+      if (src >= 0) s_nxt[j] = s_cur[src];
+    }
     __syncthreads();
     // fresh ids in index order: thread t owns keypoints [t*per, (t+1)*per)
     int local = 0;
@@ -2693,13 +2701,20 @@ extern "C" int vus_track_ids(const int32_t* stereo_idx, const int32_t* track_idx
                              const int* kp_count, int n_frames, int max_kp, int H, int W, int64_t* ids_out,
                              double* feat_out, int64_t* n_ids_out, void* stream) {
   VUS_REQUIRE(stereo_idx && kp_keys && kp_count && ids_out && feat_out && n_ids_out, "null buffer");
-  VUS_REQUIRE(n_frames >= 0 && max_kp >= 1 && max_kp <= 8192 && H >= 1 && W >= 1, "n_frames=%d max_kp=%d H=%d W=%d",
+  // max_kp <= 8192: the kernel keeps 16 B of LDS per keypoint next to 4104 B of static LDS, 135,176 B of 163,840 B
+  VUS_REQUIRE(n_frames >= 0 && max_kp >= 1 && max_kp <= TRK_MAX_KP && H >= 1 && W >= 1, "n_frames=%d max_kp=%d H=%d W=%d",
               n_frames, max_kp, H, W);
   VUS_REQUIRE(n_frames <= 1 || track_idx != nullptr, "track_idx is null");
-  const size_t lds = (size_t)max_kp * (2 * sizeof(long long) + sizeof(int));
-  if (lds > 48 * 1024)
+  const size_t lds = (size_t)max_kp * TRK_LDS_PER_KP;
+  if (lds > 48 * 1024) {
+    hipFuncAttributes attr;
+    VUS_CHECK_HIP(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(track_ids_kernel)));
+    VUS_REQUIRE(lds + attr.sharedSizeBytes <= LDS_PER_WORKGROUP,
+                "track_ids: max_kp=%d needs %zu B of dynamic LDS next to %zu B of static LDS, more than the %zu B of a "
+                "workgroup", max_kp, lds, (size_t)attr.sharedSizeBytes, LDS_PER_WORKGROUP);
     VUS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(track_ids_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
   track_ids_kernel<<<1, TRK_THREADS, lds, vus::as_stream(stream)>>>(
       stereo_idx, track_idx, kp_keys, kp_count, n_frames, max_kp, H, W, reinterpret_cast<long long*>(ids_out), feat_out,
       reinterpret_cast<long long*>(n_ids_out));
