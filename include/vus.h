@@ -193,7 +193,8 @@ int vus_cross_check(const int32_t* idx_fwd, const int32_t* idx_bwd, int n_pairs,
  * A left keypoint j of frame f inherits the id of the lowest-index keypoint of frame f-1 whose track
  * match is j (if that keypoint carries an id); stereo-matched keypoints without an id get fresh ids
  * in index order.  Keypoints without a stereo match keep an inherited id for later frames but are
- * not published.
+ * not published.  Wrong temporal matches are the caller's to remove BEFORE this call: vus_cross_check above, and the
+ * nodelet's two-point RANSAC, vus_two_point_ransac of vus_ransac.h (rejected matches become -1 in track_idx).
  *   ids_out  int64 [n_frames, max_kp]   id of every PUBLISHED feature, -1 otherwise
  *   feat_out f64   [n_frames, max_kp, 4] (u0, v0, u1, v1) = 2*x/W - 1, 2*y/H - 1 for both cameras
  *                  (zeros where not published)
@@ -229,8 +230,9 @@ int vus_emit_stereo_factors(const int64_t* ids, const double* feat, const double
 /* Unwhitened residual of every emitted stereo factor at the INITIAL estimate -- GenericStereoFactor3D's
  * h(X(f), L(id)) - measurement with X(f) = Rt[obs_frame], L(id) = lm_point[obs_id], K = (fx, fy, skew, cx, cy, b):
  *   resid f64 [n,3];  a point at or behind the camera (z <= 0, gtsam's cheirality case) gives +infinity in all three.
- * EXTENSION (not in the reference, which has no outlier handling of its own: the nodelet's RANSAC precedes it): lets the
- * caller gate gross mismatches of the brute-force matcher before they enter the graph (sequence.py, gate_px). */
+ * EXTENSION (not in the reference, which has no outlier handling of its own: the nodelet's RANSAC precedes it -- here
+ * vus_two_point_ransac of vus_ransac.h, off by default): lets the caller gate gross mismatches of the brute-force matcher
+ * before they enter the graph (sequence.py, gate_px). */
 int vus_stereo_initial_residuals(const double* Rt, const double* K, const double* lm_point, const int* obs_frame,
                                  const int64_t* obs_id, const double* obs_meas, int n, double* resid, void* stream);
 
@@ -537,4 +539,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Stereo factors with a camera-to-body extrinsic (GenericStereoFactor3D's body_P_sensor): vus_ba_sensor and the
  * `_sensor` forms of the linearisation, step evaluation, error and robust weights. */
 #include "vus_sensor.h"
+
+/* Two-point RANSAC with a known inter-frame rotation on the temporal matches (the nodelet's ransac_threshold,
+ * launch/stereo.launch:46), between the track matcher and the id emitter above: vus_two_point_ransac. */
+#include "vus_ransac.h"
 #endif /* VUS_H */

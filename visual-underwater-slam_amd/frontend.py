@@ -13,9 +13,10 @@ Python here only owns buffers and launches: every number is produced by libvus_h
 from dataclasses import dataclass, field
 from typing import List, Optional
 
+import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, synth
 
 
 TILE_BW, TILE_BH = 16, 8   # block-tiled planes (include/vus_tiled.h): 16 x 8-pixel blocks of 128 bytes, raster order
@@ -65,6 +66,11 @@ class ImageProcessorParams:
                                    # max_features keypoints as detection at fast_threshold, bit for bit, at a fraction
                                    # of the exact-score work.  Applies wherever a global top-K follows (single level, or
                                    # every pyramid level with its quota); grid bucketing needs every candidate: off there
+    ransac_threshold: float = 0.0  # stereo.launch:46 (the nodelet's value: 3) -- two-point RANSAC with the inter-frame
+                                   # rotation on the temporal matches, inlier distance in pixels
+                                   # (StereoOrbFrontend.reject_track_outliers, include/vus_ransac.h); 0 = off
+    ransac_hypotheses: int = 256   # models tried per frame pair
+    ransac_seed: int = synth.SEED  # seed of their two-match samples
     fast_sample_stride: int = 32   # every 32nd 128 x 24 tile is sampled (3 % of the image: ~90 survivors decide, 3.9 sigma
                                    # from a wrong answer at the 1.75x margin -- and a wrong answer only costs that image a retry)
 
@@ -85,6 +91,14 @@ def pyramid_layout(H: int, W: int, max_features: int, n_levels: int, scale_facto
         nd *= f
     quotas.append(max(max_features - total, 0))
     return sizes, quotas
+
+
+def default_camera(H: int, W: int) -> np.ndarray:
+    """(fx, fy, cx, cy) of batch.py:111's calibration -- given for the 1920 x 1080 frame -- in pixels of an H x W image:
+    pixel x is the ray through u = x * 1920 / W, the mapping synth.scene_sequence and BatchSequence.cam_array assume."""
+    fx, fy, cx, cy = synth.INTRINSIC
+    sx, sy = W / float(synth.RES_X), H / float(synth.RES_Y)
+    return np.array([fx * sx, fy * sy, cx * sx, cy * sy], dtype=np.float64)
 
 
 @dataclass
@@ -384,6 +398,32 @@ class StereoOrbFrontend:
                   ptr(res.kp_count), F, K, self.H, self.W, ptr(ids), ptr(feats), ptr(n_ids),
                   _lib.current_stream_ptr())
         return ids, feats, int(n_ids.item())
+
+    def reject_track_outliers(self, res: FrontendResult, rot: torch.Tensor, cam=None, threshold_px: Optional[float] = None):
+        """The nodelet's two-point RANSAC (stereo.launch:46; vus_two_point_ransac) on the temporal matches of `res`, IN
+        PLACE: a left(t) -> left(t+1) match off the epipolar line that the known rotation and the best two-match model
+        give becomes -1 in res.track_idx, so feature_tracks() / camera_measurements() called afterwards never join
+        the two keypoints under one id.  rot: f64 [F-1, 9] device tensor, row-major R_cur_prev of every frame pair
+        (a ray of camera t into camera t+1: R_{t+1}^T R_t of the world-from-camera rotations, e.g. the transpose of
+        PreintegratedImuMeasurements.deltaRij()).  cam: (fx, fy, cx, cy) in pixels of this H x W image, default
+        default_camera(H, W).  The inlier distance is threshold_px, default ImageProcessorParams.ransac_threshold;
+        hypotheses and seed come from the parameters.  Returns info int32 [F-1, 4] on the device: (matches, survivors,
+        winning hypothesis or -1, matches explained by the rotation alone) per pair.  A no-op for one frame."""
+        F, K = res.n_frames, self.p.max_features
+        if F < 2:
+            return torch.zeros((0, 4), dtype=torch.int32, device=self.device)
+        thr = float(self.p.ransac_threshold if threshold_px is None else threshold_px)
+        assert rot.dtype == torch.float64 and rot.is_cuda and rot.is_contiguous() and tuple(rot.shape) == (F - 1, 9), \
+            "rot: f64 [F-1, 9] on the device"
+        cam_h = np.ascontiguousarray(default_camera(self.H, self.W) if cam is None else
+                                     (cam.detach().cpu().numpy() if isinstance(cam, torch.Tensor) else cam), dtype=np.float64)
+        assert cam_h.size >= 4
+        info = torch.empty((F - 1, 4), dtype=torch.int32, device=self.device)
+        ptr = _lib.ptr
+        _lib.call("vus_two_point_ransac", ptr(res.track_idx), ptr(res.kp_keys), ptr(res.kp_count), F, K, self.H, self.W,
+                  ptr(rot), cam_h.ctypes.data, thr, int(self.p.ransac_hypotheses), int(self.p.ransac_seed) & 0xFFFFFFFF,
+                  ptr(res.track_idx), ptr(info), _lib.current_stream_ptr())
+        return info
 
     def stereo_factors(self, ids: torch.Tensor, feats: torch.Tensor, n_ids: int, Rt: torch.Tensor, cam: torch.Tensor,
                        first_frame: int = 1):

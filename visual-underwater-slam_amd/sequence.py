@@ -160,7 +160,8 @@ class BatchSequence:
                         X(i), L(landmark['id']), self.K, self.body_P_sensor))        # :300-305
 
     def gate_factors(self, factors, Rt: torch.Tensor, gate_px: float):
-        """EXTENSION (no counterpart in batch.py, whose input has been through the nodelet's RANSAC): drop every
+        """EXTENSION (no counterpart in batch.py, whose input has been through the nodelet's RANSAC -- here
+        StereoOrbFrontend.reject_track_outliers, include/vus_ransac.h, run_sequence's ransac_px): drop every
         emitted factor whose residual AT THE INITIAL ESTIMATE -- keyframe transform Rt[f], first-sighting landmark --
         exceeds gate_px in any of (uL, uR, v) or whose landmark lies behind the camera (vus_stereo_initial_residuals).
         A brute-force Hamming mismatch is a residual of hundreds of pixels; without a robust kernel (gtsam's default,
@@ -225,25 +226,63 @@ SEQUENCE_PARAMS = dict(track_max_distance=30, cross_check=True)
 GATE_PX = 60.0        # 6 sigma of the stereo noise model (batch.py:118: sigma = 10 px)
 
 
+def ransac_rotations(delta_body: np.ndarray, body_P_sensor: Optional["gtsam.Pose3"] = None) -> np.ndarray:
+    """[P,9] R_cur_prev of vus_two_point_ransac from the BODY rotation increments delta_body [P,3,3] (R_{p+1} = R_p dR:
+    what PreintegratedImuMeasurements.deltaRij() integrates from the gyro).  The camera sits at X o body_P_sensor, so
+    its increment is the conjugate Rs^T dR Rs, and the map of a ray of camera p into camera p+1 its transpose."""
+    Rs = np.eye(3) if body_P_sensor is None else gtsam.Pose3(body_P_sensor).rotation().matrix()
+    out = [((Rs.T @ dR) @ Rs).T.reshape(-1) for dR in np.asarray(delta_body, dtype=np.float64).reshape(-1, 3, 3)]
+    return np.ascontiguousarray(np.array(out, dtype=np.float64).reshape(-1, 9))
+
+
+def imu_delta_rotations(imu, params: "gtsam.PreintegrationParams") -> np.ndarray:
+    """[F-1,3,3] deltaRij() of every keyframe interval: the gyro samples integrated with zero bias at batch.py:290's dt."""
+    pim = gtsam.PreintegratedImuMeasurements(params)
+    out = []
+    for smp in imu:
+        pim.resetIntegration()
+        for s in smp:
+            s = np.asarray(s, float)
+            pim.integrateMeasurement(s[:3], s[3:6], 0.005)
+        out.append(pim.deltaRij().matrix())
+    return np.array(out, dtype=np.float64).reshape(-1, 3, 3)
+
+
 def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, disparity_sign: int = 1,
                  params: Optional[ImageProcessorParams] = None, bulk: bool = True, frontend: Optional[StereoOrbFrontend] = None,
-                 gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None):
+                 gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None, ransac_px: float = 0.0,
+                 ransac_rotation: str = "imu"):
     """Images to optimised trajectory: frames uint8 [F,2,H,W] on the GPU (one stereo pair per keyframe), odom_poses
     [F,12] (the odometry estimate of every keyframe = initial value of X(i) AND the camera transform get_landmarks
     uses), imu [F-1][n,>=6] samples between keyframes, dvl [F,3].  gate_px > 0 applies BatchSequence.gate_factors (bulk
     path only).  body_P_sensor: odom_poses are BODY poses, every stereo factor carries the extrinsic, and the camera
-    transform of get_landmarks and of the gate is odom_pose o body_P_sensor.  Returns (results Values, BatchSequence,
-    stages dict)."""
+    transform of get_landmarks and of the gate is odom_pose o body_P_sensor.  ransac_px > 0 (the nodelet's
+    ransac_threshold, stereo.launch:46: 3) runs StereoOrbFrontend.reject_track_outliers on the temporal matches before
+    the ids are issued, with the inter-frame rotation from the gyro samples (ransac_rotation="imu": deltaRij() of every
+    interval, zero bias) or from odom_poses ("odom"); stages then holds "ransac_info".  Returns (results Values,
+    BatchSequence, stages dict)."""
+    assert ransac_rotation in ("imu", "odom")
     if params is None:
         params = ImageProcessorParams(**SEQUENCE_PARAMS)
     F, _, H, W = frames.shape
     fe = frontend or StereoOrbFrontend(H, W, max_frames=F, params=params)
     res = fe.process(frames)
-    ids, feats, n_ids = fe.feature_tracks(res)
     seq = BatchSequence(disparity_sign=disparity_sign, device=str(frames.device), body_P_sensor=body_P_sensor)
     Rt = keyframe_transforms(odom_poses)
+    ransac_info = None
+    if ransac_px > 0 and F > 1:
+        if ransac_rotation == "imu":
+            dR = imu_delta_rotations(imu[:F - 1], seq.PARAMS)
+        else:
+            Rb = Rt[:, :9].reshape(-1, 3, 3)
+            dR = np.einsum("pji,pjk->pik", Rb[:-1], Rb[1:])                             # R_p^T R_{p+1}
+        rot = torch.from_numpy(ransac_rotations(dR, body_P_sensor)).to(frames.device)
+        ransac_info = fe.reject_track_outliers(res, rot, threshold_px=ransac_px)
+    ids, feats, n_ids = fe.feature_tracks(res)
     Rt_cam = Rt if body_P_sensor is None else np.stack([gtsam.Pose3.from_flat12(r).compose(body_P_sensor).flat12() for r in Rt])
     stages = {"frontend": res, "ids": ids, "feats": feats, "n_ids": n_ids}
+    if ransac_info is not None:
+        stages["ransac_info"] = ransac_info
     if bulk:
         for i in range(F):
             seq.odom_accum.append(gtsam.Pose3.from_flat12(Rt[i]))
