@@ -162,7 +162,8 @@ def _pipeline_oracle(oracle, img, max_kp):
 @pytest.mark.parametrize("shape,max_kp", [((160, 224), 300), ((720, 1280), 2000), ((100, 236), 150), ((97, 203), 120)])
 def test_orient_rbrief_bit_exact(gpu, oracle, shape, max_kp):
     """(97, 203): rows not dword aligned (exact-start patch loads); max_kp values that leave the last wave's batch of
-    eight keypoints partly empty."""
+    eight keypoints partly empty.  Bin ties, the patch loaders' fast-path boundary, pitches, counts and image counts:
+    tests/test_orient_adversarial_gpu.py."""
     import visual_underwater_slam_amd._lib as L
     H, W = shape
     img = synth.stereo_frames(20, 1, H=H, W=W).reshape(2, H, W)
@@ -183,7 +184,8 @@ def test_orient_rbrief_bit_exact(gpu, oracle, shape, max_kp):
 @pytest.mark.parametrize("shape,max_kp", [((160, 224), 300), ((720, 1280), 2000), ((97, 203), 120)])
 def test_orient_rbrief_in_cell_order_is_the_same_result(gpu, oracle, shape, max_kp):
     """vus_orient_order groups an image's keypoints by 64 x 64 cell (a permutation that fixes the unused slots);
-    vus_orient_rbrief_ordered serves the slots in that order -- and in ANY such order -- with bit-identical outputs."""
+    vus_orient_rbrief_ordered serves the slots in that order -- and in ANY such order -- with bit-identical outputs.
+    vus_orient_order on its own edge cases (cells, counts, the refused size): tests/test_orient_adversarial_gpu.py."""
     import visual_underwater_slam_amd._lib as L
     H, W = shape
     img = synth.stereo_frames(21, 1, H=H, W=W).reshape(2, H, W)

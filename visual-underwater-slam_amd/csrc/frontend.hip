@@ -1287,7 +1287,7 @@ __global__ __launch_bounds__(256) void orient_order_kernel(const uint32_t* __res
   __shared__ int s_cnt[OO_MAX_CELLS];
   __shared__ int s_wave[4];
   const int n = blockIdx.x, tid = threadIdx.x;
-  const int cnt = min(kp_count[n], max_kp);
+  const int cnt = clampi(kp_count[n], 0, max_kp);   // a negative count is an empty list: the identity starts at slot 0
   const uint32_t* keys = kp_keys + (size_t)n * max_kp;
   int* ord = order + (size_t)n * max_kp;
   for (int r = tid; r < n_cells; r += 256) s_cnt[r] = 0;
@@ -2632,8 +2632,8 @@ extern "C" int vus_orient_order(const uint32_t* kp_keys, const int* kp_count, in
   VUS_REQUIRE(kp_keys && kp_count && order, "null buffer");
   VUS_REQUIRE(n_img >= 0 && max_kp >= 1 && H >= 1 && W >= 1, "n_img=%d max_kp=%d H=%d W=%d", n_img, max_kp, H, W);
   if (n_img == 0) return VUS_OK;
-  // cells of 64 x 64 pixels; an image with more than 1024 of them gets coarser cells (the order is a schedule: any
-  // grouping is valid)
+  // cells of 64 x 64 pixels; an image with more than 1024 of them is refused (include/vus.h: the caller then uses
+  // vus_orient_rbrief, which needs no order)
   int cw = (W + OO_CELL - 1) / OO_CELL, ch = (H + OO_CELL - 1) / OO_CELL;
   VUS_REQUIRE((long long)cw * ch <= OO_MAX_CELLS, "image of %d x %d pixels has more than %d cells of %d x %d", W, H, OO_MAX_CELLS,
               OO_CELL, OO_CELL);
