@@ -1,6 +1,6 @@
 // CPU sweep of visual-underwater-slam_amd/csrc/band_index.h: the address arithmetic of the band-solve kernels, run for
 // every (panel, thread) of a system of n poses and half-bandwidth `band` exactly as factor_launches() / backsolve_launch()
-// of ba.hip launch them, against a REAL buffer of the band's size (built with -fsanitize=address,undefined by
+// of band_solve.hip launch them, against a REAL buffer of the band's size (built with -fsanitize=address,undefined by
 // tests/test_band_index.py: an offset outside the buffer is an ASan report, not only a failed comparison).
 // Test infrastructure; not part of the product.
 #include <cstdio>

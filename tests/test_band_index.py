@@ -2,7 +2,7 @@
 of cb_load_inv once pointed 2 KB in front of the band, and only a fault on the GPU box showed it).
 
 visual-underwater-slam_amd/csrc/band_index.h holds that arithmetic as __host__ __device__ functions; the kernels of
-ba.hip call them, and tests/native/band_index_check.cpp replays them here for every (panel, thread) the launches of
+band_solve.hip call them, and tests/native/band_index_check.cpp replays them here for every (panel, thread) the launches of
 factor_launches() / backsolve_launch() create -- built with AddressSanitizer + UBSan, reading a real buffer of the
 band's size, so an out-of-range offset is a sanitizer report as well as a failed count."""
 import ctypes

@@ -1,4 +1,4 @@
-// band_index.h -- every address the band-solve kernels of ba.hip form inside the block band `Sband`, as plain
+// band_index.h -- every address the band-solve kernels of band_solve.hip form inside the block band `Sband`, as plain
 // __host__ __device__ functions of (geometry, thread), so that the SAME arithmetic the kernels run can be swept on the
 // CPU over every (n, band, panel, thread) and checked against the buffer's bounds (tests/test_band_index.py compiles
 // this header with g++ under AddressSanitizer/UBSan; the GPU pool offers no device sanitizer).

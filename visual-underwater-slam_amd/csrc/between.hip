@@ -1,12 +1,12 @@
 // between.hip -- BetweenFactor<Pose3> kernels for gfx950 (MI355X), fp64 (include/vus_between.h).
 //
 // Odometry and loop-closure factors between two keyframe poses.  Their blocks are added into the reduced camera system
-// after the landmark Schur step, so the band solve, back-substitution and retraction are those of ba.hip unchanged.
+// after the landmark Schur step, so the band solve, back-substitution and retraction are those of band_solve.hip and ba.hip unchanged.
 //   linearize   thread / factor   hx = T1^-1 T2, r = Log(meas^-1 hx), H1 = -Ad(hx^-1), H2 = I, whitened and reweighted:
 //                                 the five products of the factor to `lin`, its error to a partial
 //   assemble    thread / element of a target block: the fixed-order sum over the block's CSR list, added to Sband (and gs)
 //   eval        thread / factor   linearised error at the step (old poses) and error at the new poses
-// Errors are summed by the fixed-order reduce of ba.hip (vus::reduce_partials).
+// Errors are summed by the fixed-order reduce of vus_common.hip (vus::reduce_partials).
 #include <cmath>
 #include <vector>
 #include "vus_common.h"

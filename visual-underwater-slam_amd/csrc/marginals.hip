@@ -1,5 +1,6 @@
 // marginals.hip -- marginal covariances of the bundle adjustment on gfx950 (MI355X), fp64: what
-// gtsam.Marginals(graph, values).marginalCovariance(key) computes, from the reduced camera system S of ba.hip.
+// gtsam.Marginals(graph, values).marginalCovariance(key) computes, from the reduced camera system S of ba.hip
+// as band_solve.hip has factored it.
 //
 //   selinv_prep     block / panel      dense L_PP^-1 of every 8-node diagonal panel (read from the inverted panel the band
 //                                      solve leaves for bands >= 7 nodes, inverted here by substitution for narrower ones)
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(64) void selinv_prep_kernel(const double* __restric
   if (inverted) {
     for (int t = lane; t < NB * LDA; t += 64) sI[t] = sL[t];
   } else if (lane < nb) {
-    // column `lane` of the inverse by forward substitution (as diag_invert_kernel of ba.hip)
+    // column `lane` of the inverse by forward substitution (as diag_invert_kernel of band_solve.hip)
     double x[NB];
 #pragma unroll
     for (int r = 0; r < NB; ++r) {

@@ -13,7 +13,7 @@ int fail(int code, const char* fmt, ...);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// out[0] = sum of part[0..n) in a fixed order: one workgroup of reduce_partials_kernel (ba.hip), launched on st
+// out[0] = sum of part[0..n) in a fixed order: one workgroup of reduce_partials_kernel (vus_common.hip), launched on st
 void reduce_partials(const double* part, int n, double* out, hipStream_t st);
 
 }  // namespace vus
