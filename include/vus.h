@@ -540,6 +540,10 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * `_sensor` forms of the linearisation, step evaluation, error and robust weights. */
 #include "vus_sensor.h"
 
+/* Monocular projection factors (GenericProjectionFactor<Pose3, Point3, Cal3_S2>) in the same observation list as the
+ * stereo factors: vus_ba_mono and the `_mixed` forms of the linearisation, step evaluation, error and robust weights. */
+#include "vus_mono.h"
+
 /* Two-point RANSAC with a known inter-frame rotation on the temporal matches (the nodelet's ransac_threshold,
  * launch/stereo.launch:46), between the track matcher and the id emitter above: vus_two_point_ransac. */
 #include "vus_ransac.h"

@@ -56,6 +56,11 @@ SIGNATURES = {
     "vus_ba_eval_step_sensor": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "vus_ba_error_sensor": [_P, _P, _P, _P, _P, _P, _P, _P],
     "vus_ba_stereo_weights_sensor": [_P, _P, _P, _P, _P, _P, _P],
+    # monocular projection factors next to the stereo ones (include/vus_mono.h): the `_sensor` arguments, then mono
+    "vus_ba_linearize_mixed": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_eval_step_mixed": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_error_mixed": [_P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vus_ba_stereo_weights_mixed": [_P, _P, _P, _P, _P, _P, _P, _P],
     # graph packing (csrc/pack.hip)
     "vus_imu_preintegrate": [_P, _P, c_int, _P, _P, _P, _P],      # host pointers
     "vus_keys_to_indices": [_P, c_int, _P, _P, _P, _P, ctypes.c_longlong, _P],

@@ -78,6 +78,10 @@ def sensor_flat12(body_P_sensor):
     raise ValueError(f"body_P_sensor: a 12-vector, a 4 x 4 matrix or a Pose3 is expected, not an array of shape {a.shape}")
 
 
+class _CMono(ctypes.Structure):
+    _fields_ = [("is_mono", c_void_p), ("K", c_double * 5), ("inv_sigma", c_double)]
+
+
 class _CTiles(ctypes.Structure):
     _fields_ = [("band", c_int), ("n_tiles", c_int), ("n_units", c_int), ("n_entries", c_int),
                 ("unit_ptr", c_void_p), ("entries", c_void_p), ("order", c_void_p)]
@@ -244,11 +248,15 @@ class StereoBAProblem:
     landmark span, scaled by pose_stride, so the tiles, Sband and the band-solve mode all follow the wider of the two.
     `body_P_sensor`: the camera-to-body extrinsic of every stereo factor (sensor_flat12(): a 12-vector, a 4 x 4 matrix or a
     gtsam.Pose3) -- the poses are then BODY poses and the left camera sits at pose o body_P_sensor; None = the poses are
-    the camera's."""
+    the camera's.
+    `mono`: a bool / uint8 array per INPUT observation, nonzero = a monocular GenericProjectionFactor (include/vus_mono.h)
+    whose `meas` row is (u, ignored, v) -- the middle slot is never used -- with the calibration `mono_K` = (fx, fy, skew,
+    cx, cy) and the sigma `mono_sigma` of all of them.  K and sigma keep serving the stereo rows and are required even when
+    every observation is mono.  None or all zero = a stereo-only problem, which calls the entry points it called before."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None,
                  prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None, between_span=0,
-                 body_P_sensor=None):
+                 body_P_sensor=None, mono=None, mono_K=None, mono_sigma=None):
         _lib.require_gpu()
         _lib.load()
         dev = torch.device(device)
@@ -289,6 +297,7 @@ class StereoBAProblem:
         self.body_P_sensor = sensor_flat12(body_P_sensor)
         self.has_sensor = self.body_P_sensor is not None       # without one the entry points of today are called
         self.c_sensor = _CSensor((c_double * 12)(*self.body_P_sensor)) if self.has_sensor else None
+        self._set_mono(mono, mono_K, mono_sigma)
         if prior_pose is None or len(prior_pose) == 0:
             self.prior_pose = torch.zeros(0, dtype=torch.int32, device=dev)
             self.prior_T = torch.zeros((0, 12), dtype=torch.float64, device=dev)
@@ -313,6 +322,31 @@ class StereoBAProblem:
                                p(tl["entries"]), p(tl["order"]))
         torch.cuda.synchronize(dev)
         self.setup_seconds = time.perf_counter() - t0
+
+
+    def _set_mono(self, mono, mono_K, mono_sigma):
+        """has_mono, is_mono_L (uint8 [n_obs], L-order: the input flags through the pack's `perm`) and the vus_ba_mono"""
+        flags = None if mono is None else np.asarray(
+            mono.detach().cpu().numpy() if torch.is_tensor(mono) else mono).reshape(-1) != 0
+        self.has_mono = flags is not None and bool(flags.any())
+        self.is_mono_L, self.c_mono, self.mono_K, self.mono_sigma = None, None, None, None
+        if flags is not None and len(flags) != self.n_obs:
+            raise ValueError(f"mono: {len(flags)} flags for {self.n_obs} observations")
+        if not self.has_mono:
+            return
+        if mono_K is None or mono_sigma is None:
+            raise ValueError("mono observations need mono_K = (fx, fy, skew, cx, cy) and mono_sigma")
+        mk = np.array(mono_K.detach().cpu().numpy() if torch.is_tensor(mono_K) else mono_K, dtype=np.float64).reshape(-1)
+        if mk.size != 5:
+            raise ValueError(f"mono_K: (fx, fy, skew, cx, cy) is expected, not {mk.size} values")
+        self.mono_K, self.mono_sigma = mk, float(mono_sigma)
+        if not (np.isfinite(mk).all() and mk[0] > 0 and mk[1] > 0):
+            raise ValueError(f"mono_K={mk.tolist()}: finite values with fx, fy > 0 are expected")
+        if not (math.isfinite(self.mono_sigma) and self.mono_sigma > 0):
+            raise ValueError(f"mono_sigma={self.mono_sigma} must be finite and > 0")
+        perm = self.pk["perm"].cpu().numpy().astype(np.int64)
+        self.is_mono_L = torch.from_numpy(flags[perm].astype(np.uint8)).to(self.device)
+        self.c_mono = _CMono(_lib.ptr(self.is_mono_L), (c_double * 5)(*mk), 1.0 / self.mono_sigma)
 
 
 class IndeterminantSystem(RuntimeError):
@@ -459,7 +493,12 @@ class StereoBASolver:
 
     def _loss_args(self, name):
         """(entry point, trailing arguments): the `_robust` twin with the problem's vus_ba_loss for a robust model; with a
-        body_P_sensor the `_sensor` form, which takes the loss (Gaussian included) and the extrinsic"""
+        body_P_sensor the `_sensor` form, which takes the loss (Gaussian included) and the extrinsic; with monocular
+        observations the `_mixed` form, which takes the loss, the extrinsic or NULL, and the vus_ba_mono"""
+        if self.P.has_mono:
+            return name + "_mixed", (ctypes.addressof(self.P.c_loss),
+                                     ctypes.addressof(self.P.c_sensor) if self.P.has_sensor else None,
+                                     ctypes.addressof(self.P.c_mono))
         if self.P.has_sensor:
             return name + "_sensor", (ctypes.addressof(self.P.c_loss), ctypes.addressof(self.P.c_sensor))
         return (name + "_robust", (ctypes.addressof(self.P.c_loss),)) if self.P.robust else (name, ())
@@ -479,10 +518,11 @@ class StereoBASolver:
                   p(self.Hpp), p(self.gp), p(self.scal), p(self.work), _lib.current_stream_ptr(), *extra)
 
     def stereo_weights(self, poses, points) -> torch.Tensor:
-        """Robust weight w(d) of every stereo observation at (poses, points), in the problem's INPUT row order (all ones
-        under the Gaussian model): inliers near 1, gross outliers near 0."""
+        """Robust weight w(d) of every observation, stereo or mono, at (poses, points), in the problem's INPUT row order
+        (all ones under the Gaussian model): inliers near 1, gross outliers near 0."""
         w = torch.empty(self.P.n_obs, dtype=torch.float64, device=self.P.device)
-        fn, extra = ("vus_ba_stereo_weights", ()) if not self.P.has_sensor else self._loss_args("vus_ba_stereo_weights")
+        plain = not (self.P.has_sensor or self.P.has_mono)
+        fn, extra = ("vus_ba_stereo_weights", ()) if plain else self._loss_args("vus_ba_stereo_weights")
         _lib.call(fn, self._pp(), ctypes.addressof(self.P.c_loss), _lib.ptr(poses), _lib.ptr(points),
                   _lib.ptr(w), _lib.current_stream_ptr(), *extra[1:])
         out = torch.empty_like(w)

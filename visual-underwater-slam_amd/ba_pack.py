@@ -9,6 +9,10 @@ the GPU for the 2M-observation problems and on the CPU for tests.  No BA arithme
 """
 import torch
 
+# one observation list holds the stereo and the monocular factors: a pose-landmark pair may carry one factor of either kind
+DUPLICATE_MESSAGE = ("two stereo factors between the same pose and landmark are not supported (nor two monocular "
+                     "projection factors, nor a stereo and a monocular one on the same pair)")
+
 
 def pack_observations(obs_pose, obs_point, meas, n_poses, n_points):
     """obs_* : 1-D integer tensors, meas [n_obs,3] float64, any order.  Returns a dict of tensors:
@@ -23,7 +27,7 @@ def pack_observations(obs_pose, obs_point, meas, n_poses, n_points):
         key = key.to(torch.int32)
     key_sorted, perm = torch.sort(key, stable=True)
     if n_obs > 1 and bool((key_sorted[1:] == key_sorted[:-1]).any()):
-        raise NotImplementedError("two stereo factors between the same pose and landmark are not supported")
+        raise NotImplementedError(DUPLICATE_MESSAGE)
     op = obs_pose[perm]
     ol = obs_point[perm]
     m = meas[perm].contiguous()
@@ -72,7 +76,7 @@ def pack_observations_device(obs_pose, obs_point, meas, n_poses, n_points):
     if f & 2:
         raise IndexError("a stereo factor refers to a pose or landmark index outside the problem")
     if f & 1:
-        raise NotImplementedError("two stereo factors between the same pose and landmark are not supported")
+        raise NotImplementedError(DUPLICATE_MESSAGE)
     return out
 
 

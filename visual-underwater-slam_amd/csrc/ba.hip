@@ -84,6 +84,90 @@ __device__ __forceinline__ void stereo_factor(const double* __restrict__ T, cons
   }
 }
 
+// Stereo and monocular projection factors side by side (include/vus_mono.h).  gtsam GenericProjectionFactor<Pose3,
+// Point3, Cal3_S2>: q = R^T (p - t), u = cx + fx x/z + s y/z, v = cy + fy y/z, residual (u - m_u, v - m_v) / sigma; z <= 0 ->
+// cheirality: residual 2 fx / sigma on both rows, zero Jacobians.  With d = 1/z the rows of d(u, v)/dq are
+//   (fx d, s d, -d^2 (fx x + s y))   and   (0, fy d, -d^2 fy y),
+// i.e. the stereo factor's uL and v rows with a skew term, and then H2 = J R^T, H1 = [J [q]x, -J] as there.  So ONE body
+// serves both kinds per lane: the calibration (fx, fy, s, cx, cy, b, w) is selected by the observation's flag (s = b = 0
+// for a stereo lane, whose terms in s are then exact zeros and change no bit), the three rows are formed once, and the uR
+// row (slot 1) of a mono lane is zero in r, H1 and H2 -- it adds nothing to any product, d^2 or error.  A wave holding
+// both kinds runs this body once, not a stereo and a mono body in turn; a mono lane pays for a row of zeros.
+struct MixedCalib {
+  double fx, fy, s, cx, cy, b, w;
+};
+struct MonoArg {
+  const unsigned char* is_mono;      // [n_obs] L-order
+  double fx, fy, s, cx, cy, w;
+};
+struct NoMono {};
+template <bool MIXED>
+using mono_arg_t = std::conditional_t<MIXED, MonoArg, NoMono>;
+
+template <bool WITH_H1, bool WITH_H2>
+__device__ __forceinline__ void mixed_factor(const double* __restrict__ T, const double* __restrict__ p,
+                                             const double* __restrict__ m, const MixedCalib& K, bool mono, double* r,
+                                             double* H1, double* H2) {
+  const double d0 = p[0] - T[9], d1 = p[1] - T[10], d2 = p[2] - T[11];
+  const double x = T[0] * d0 + T[3] * d1 + T[6] * d2;
+  const double y = T[1] * d0 + T[4] * d1 + T[7] * d2;
+  const double z = T[2] * d0 + T[5] * d1 + T[8] * d2;
+  if (z <= 0.0) {
+    r[0] = r[2] = 2.0 * K.fx * K.w;
+    r[1] = mono ? 0.0 : r[0];
+    if (WITH_H1)
+#pragma unroll
+      for (int k = 0; k < 18; ++k) H1[k] = 0.0;
+    if (WITH_H2)
+#pragma unroll
+      for (int k = 0; k < 9; ++k) H2[k] = 0.0;
+    return;
+  }
+  const double d = 1.0 / z;
+  r[0] = (K.cx + d * K.fx * x + d * K.s * y - m[0]) * K.w;
+  r[1] = mono ? 0.0 : (K.cx + d * K.fx * (x - K.b) - m[1]) * K.w;
+  r[2] = (K.cy + d * K.fy * y - m[2]) * K.w;
+  if (!WITH_H1 && !WITH_H2) return;
+  const double J[9] = {K.w * d * K.fx, K.w * d * K.s, -K.w * d * d * K.fx * x - K.w * d * d * K.s * y,
+                       mono ? 0.0 : K.w * d * K.fx, 0.0, mono ? 0.0 : -K.w * d * d * K.fx * (x - K.b),
+                       0.0, K.w * d * K.fy, -K.w * d * d * K.fy * y};
+  if (WITH_H2)
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        H2[3 * rr + c] = J[3 * rr] * T[3 * c] + J[3 * rr + 1] * T[3 * c + 1] + J[3 * rr + 2] * T[3 * c + 2];
+  if (WITH_H1) {
+    const double Q[9] = {0, -z, y, z, 0, -x, -y, x, 0};
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        H1[6 * rr + c] = J[3 * rr] * Q[c] + J[3 * rr + 1] * Q[3 + c] + J[3 * rr + 2] * Q[6 + c];
+        H1[6 * rr + 3 + c] = -J[3 * rr + c];
+      }
+  }
+}
+
+// observation a (L-order) at camera pose T and point p: the stereo factor, or in a mixed instance the form its flag names.
+// The middle slot of a mono observation's measurement is not used (it may hold anything, NaN included).
+template <bool WITH_H1, bool WITH_H2, typename MA>
+__device__ __forceinline__ void obs_factor(const vus_ba_problem& P, const Calib& K, const MA& M, int a,
+                                           const double* __restrict__ T, const double* __restrict__ p, double* r,
+                                           double* H1, double* H2) {
+  if constexpr (std::is_same_v<MA, MonoArg>) {
+    const bool mono = M.is_mono[a] != 0;
+    const double m1 = P.meas[3 * (size_t)a + 1];
+    const double m[3] = {P.meas[3 * (size_t)a], mono ? 0.0 : m1, P.meas[3 * (size_t)a + 2]};
+    const MixedCalib C = {mono ? M.fx : K.fx, mono ? M.fy : K.fy, mono ? M.s : 0.0, mono ? M.cx : K.cx,
+                          mono ? M.cy : K.cy, mono ? 0.0 : K.b, mono ? M.w : K.w};
+    mixed_factor<WITH_H1, WITH_H2>(T, p, m, C, mono, r, H1, H2);
+  } else {
+    const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
+    stereo_factor<WITH_H1, WITH_H2>(T, p, m, K, r, H1, H2);
+  }
+}
+
 __host__ __device__ __forceinline__ int pose_stride(const vus_ba_problem& P) { return P.pose_stride > 1 ? P.pose_stride : 1; }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -185,12 +269,12 @@ __device__ __forceinline__ void robust_reweight(double k, double* r, double* H1,
 // linearisation (LOSS = VUS_LOSS_*: the Gaussian instance is the plain statement, a robust one reweights every factor
 // before the products; loss_k = the mEstimator's parameter, unused by the Gaussian instance.  SENSOR: the camera sits at
 // X o S and H1 is taken to the body tangent before W = H1^T H2)
-template <int LOSS, bool SENSOR = false>
+template <int LOSS, bool SENSOR = false, bool MIXED = false>
 __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                          const double* __restrict__ points,
                                                          double* __restrict__ W, double* __restrict__ V,
                                                          double* __restrict__ gl, double* __restrict__ err_part,
-                                                         double loss_k, sensor_arg_t<SENSOR> S) {
+                                                         double loss_k, sensor_arg_t<SENSOR> S, mono_arg_t<MIXED> M) {
   const int lane = threadIdx.x & 63;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= P.n_points) return;
@@ -201,8 +285,7 @@ __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const
   for (int a = a0 + lane; a < a1; a += 64) {
     double T[12], r[3], H1[18], H2[9];
     load_camera(poses + 12 * (size_t)P.obs_pose[a], S, T);
-    const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
-    stereo_factor<true, true>(T, p, m, K, r, H1, H2);
+    obs_factor<true, true>(P, K, M, a, T, p, r, H1, H2);
     if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, true>(loss_k, r, H1, H2);
     h1_to_body(S, H1);
     e += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);      // robust: 0.5 w d^2, the linear error at delta = 0
@@ -235,11 +318,11 @@ __global__ __launch_bounds__(256) void lin_points_kernel(vus_ba_problem P, const
 
 // SENSOR: Ad(S^-1) is the same for all of a pose's factors, so the sums are taken in the CAMERA tangent as without an
 // extrinsic and the epilogue applies Hpp = Ad^T (.) Ad, gp = Ad^T (.) once per workgroup
-template <int LOSS, bool SENSOR = false>
+template <int LOSS, bool SENSOR = false, bool MIXED = false>
 __global__ __launch_bounds__(256) void lin_poses_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                         const double* __restrict__ points,
                                                         double* __restrict__ Hpp, double* __restrict__ gp,
-                                                        double loss_k, sensor_arg_t<SENSOR> S) {
+                                                        double loss_k, sensor_arg_t<SENSOR> S, mono_arg_t<MIXED> M) {
   __shared__ double s_part[4][27];
   const int i = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -254,9 +337,8 @@ __global__ __launch_bounds__(256) void lin_poses_kernel(vus_ba_problem P, const 
     const int a = P.pobs_lidx[s];
     const int j = P.obs_point[a];
     const double p[3] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
-    const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
     double r[3], H1[18];
-    stereo_factor<true, false>(T, p, m, K, r, H1, nullptr);
+    obs_factor<true, false>(P, K, M, a, T, p, r, H1, nullptr);
     if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, false>(loss_k, r, H1, nullptr);
     int u = 0;
 #pragma unroll
@@ -659,14 +741,14 @@ __global__ void retract_kernel(int n_poses, int n_points, int ps, const double* 
 //            part_new[j] = 0.5 sum |r|^2 at the new values
 // robust LOSS: r, H1, H2 at the old values reweighted by sqrt(w(old)) (the linearisation point), part_new = sum rho
 // SENSOR: both the old and the new poses are composed with S; dp is a body-tangent step, taken to the camera tangent
-template <bool WITH_LIN, int LOSS = VUS_LOSS_GAUSSIAN, bool SENSOR = false>
+template <bool WITH_LIN, int LOSS = VUS_LOSS_GAUSSIAN, bool SENSOR = false, bool MIXED = false>
 __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                           const double* __restrict__ points,
                                                           const double* __restrict__ dp, const double* __restrict__ dl,
                                                           const double* __restrict__ new_poses,
                                                           const double* __restrict__ new_points,
                                                           double* __restrict__ part_lin, double* __restrict__ part_new,
-                                                          double loss_k, sensor_arg_t<SENSOR> S) {
+                                                          double loss_k, sensor_arg_t<SENSOR> S, mono_arg_t<MIXED> M) {
   const int lane = threadIdx.x & 63;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= P.n_points) return;
@@ -683,10 +765,9 @@ __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, cons
   double e_lin = 0, e_new = 0;
   for (int a = P.point_ptr[j] + lane; a < P.point_ptr[j + 1]; a += 64) {
     const int i = P.obs_pose[a];
-    const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
     double T[12], r[3];
     load_camera(new_poses + 12 * (size_t)i, S, T);
-    stereo_factor<false, false>(T, pn, m, K, r, nullptr, nullptr);
+    obs_factor<false, false>(P, K, M, a, T, pn, r, nullptr, nullptr);
     if (LOSS == VUS_LOSS_GAUSSIAN) {
       e_new += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
     } else {
@@ -697,7 +778,7 @@ __global__ __launch_bounds__(256) void eval_points_kernel(vus_ba_problem P, cons
     if (WITH_LIN) {
       double H1[18], H2[9];
       load_camera(poses + 12 * (size_t)i, S, T);
-      stereo_factor<true, true>(T, po, m, K, r, H1, H2);
+      obs_factor<true, true>(P, K, M, a, T, po, r, H1, H2);
       if (LOSS != VUS_LOSS_GAUSSIAN) robust_reweight<LOSS, true, true>(loss_k, r, H1, H2);
       double d[6];
 #pragma unroll
@@ -739,19 +820,18 @@ int check_problem(const vus_ba_problem* P) {
 }
 
 // w [n_obs] (L-order) of every stereo observation at (poses, points), thread / observation
-template <int LOSS, bool SENSOR = false>
+template <int LOSS, bool SENSOR = false, bool MIXED = false>
 __global__ __launch_bounds__(256) void stereo_weights_kernel(vus_ba_problem P, const double* __restrict__ poses,
                                                              const double* __restrict__ points, double* __restrict__ w_out,
-                                                             double loss_k, sensor_arg_t<SENSOR> S) {
+                                                             double loss_k, sensor_arg_t<SENSOR> S, mono_arg_t<MIXED> M) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= P.n_obs) return;
   const Calib K = load_calib(P.K, P.inv_sigma);
   const int j = P.obs_point[a];
   const double p[3] = {points[3 * (size_t)j], points[3 * (size_t)j + 1], points[3 * (size_t)j + 2]};
-  const double m[3] = {P.meas[3 * (size_t)a], P.meas[3 * (size_t)a + 1], P.meas[3 * (size_t)a + 2]};
   double T[12], r[3], w, rho;
   load_camera(poses + 12 * (size_t)P.obs_pose[a], S, T);
-  stereo_factor<false, false>(T, p, m, K, r, nullptr, nullptr);
+  obs_factor<false, false>(P, K, M, a, T, p, r, nullptr, nullptr);
   robust_weight<LOSS>(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], loss_k, w, rho);
   w_out[a] = w;
 }
@@ -788,6 +868,30 @@ int make_sensor(const vus_ba_sensor* s, SensorArg& out) {
   return VUS_OK;
 }
 
+// vus_ba_mono -> the kernels' MonoArg, validated on the host (include/vus_mono.h)
+int make_mono(const vus_ba_problem* P, const vus_ba_mono* m, MonoArg& out) {
+  VUS_REQUIRE(m != nullptr, "mono is null");
+  for (int k = 0; k < 5; ++k) VUS_REQUIRE(std::isfinite(m->K[k]), "mono: K[%d]=%g is not finite", k, m->K[k]);
+  VUS_REQUIRE(m->K[0] > 0.0 && m->K[1] > 0.0, "mono: fx=%g fy=%g must be > 0", m->K[0], m->K[1]);
+  VUS_REQUIRE(std::isfinite(m->inv_sigma) && m->inv_sigma > 0.0, "mono: inv_sigma=%g must be finite and > 0", m->inv_sigma);
+  VUS_REQUIRE(m->is_mono != nullptr || !P || P->n_obs <= 0, "mono: is_mono is null");
+  out = MonoArg{m->is_mono, m->K[0], m->K[1], m->K[2], m->K[3], m->K[4], m->inv_sigma};
+  return VUS_OK;
+}
+
+// f(sensor argument, mono argument) with the kernels' argument types of the (SENSOR, MIXED) instance a call takes
+template <typename F>
+void with_variant(const SensorArg* S, const MonoArg* M, F f) {
+  if (S && M) f(*S, *M);
+  else if (S) f(*S, NoMono{});
+  else if (M) f(NoSensor{}, *M);
+  else f(NoSensor{}, NoMono{});
+}
+template <typename SA>
+constexpr bool is_sensor_v = std::is_same_v<SA, SensorArg>;
+template <typename MA>
+constexpr bool is_mono_v = std::is_same_v<MA, MonoArg>;
+
 // one instance of F<LOSS> per kind, chosen at run time (the loss was validated by check_loss)
 template <template <int> class F, typename... A>
 int dispatch_loss(const vus_ba_loss* L, A... args) {
@@ -804,17 +908,16 @@ int dispatch_loss(const vus_ba_loss* L, A... args) {
 template <int LOSS>
 struct ErrorOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* err,
-                 double* work, void* stream, const SensorArg* S) {
+                 double* work, void* stream, const SensorArg* S, const MonoArg* M) {
     if (int rc = check_problem(P)) return rc;
     VUS_REQUIRE(poses && (points || !P->n_points) && err && work, "null buffer");
     hipStream_t st = vus::as_stream(stream);
     const int nL = P->n_points;
-    if (nL > 0 && S)
-      eval_points_kernel<false, LOSS, true><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
-                                                                        nullptr, work, k, *S);
-    else if (nL > 0)
-      eval_points_kernel<false, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, nullptr, nullptr, nullptr, nullptr, poses, points,
-                                                                  nullptr, work, k, NoSensor{});
+    if (nL > 0)
+      with_variant(S, M, [&](auto s, auto m) {
+        eval_points_kernel<false, LOSS, is_sensor_v<decltype(s)>, is_mono_v<decltype(m)>><<<cdiv(nL, 4), 256, 0, st>>>(
+            *P, nullptr, nullptr, nullptr, nullptr, poses, points, nullptr, work, k, s, m);
+      });
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, nullptr, nullptr, work + nL, 1);
     vus::reduce_partials(work, nL + 1, err, st);
     VUS_CHECK_LAUNCH("ba_error");
@@ -825,7 +928,8 @@ struct ErrorOp {
 template <int LOSS>
 struct LinearizeOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* W, double* V,
-                 double* gl, double* Hpp, double* gp, double* err, double* work, void* stream, const SensorArg* S) {
+                 double* gl, double* Hpp, double* gp, double* err, double* work, void* stream, const SensorArg* S,
+                 const MonoArg* M) {
     if (int rc = check_problem(P)) return rc;
     // a graph without landmarks (priors only) has empty per-landmark / per-observation arrays: those may be null
     VUS_REQUIRE(poses && Hpp && gp && err && work, "null buffer");
@@ -833,13 +937,11 @@ struct LinearizeOp {
     VUS_REQUIRE(W || !P->n_obs, "null observation buffer");
     hipStream_t st = vus::as_stream(stream);
     const int nL = P->n_points;
-    if (S) {
-      if (nL > 0) lin_points_kernel<LOSS, true><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k, *S);
-      lin_poses_kernel<LOSS, true><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k, *S);
-    } else {
-      if (nL > 0) lin_points_kernel<LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k, NoSensor{});
-      lin_poses_kernel<LOSS><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k, NoSensor{});
-    }
+    with_variant(S, M, [&](auto s, auto m) {
+      constexpr bool SE = is_sensor_v<decltype(s)>, MI = is_mono_v<decltype(m)>;
+      if (nL > 0) lin_points_kernel<LOSS, SE, MI><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, W, V, gl, work, k, s, m);
+      lin_poses_kernel<LOSS, SE, MI><<<P->n_poses, 256, 0, st>>>(*P, poses, points, Hpp, gp, k, s, m);
+    });
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, nullptr, Hpp, gp, work + nL, 0);
     vus::reduce_partials(work, nL + 1, err, st);
     VUS_CHECK_LAUNCH("ba_linearize");
@@ -851,7 +953,7 @@ template <int LOSS>
 struct EvalStepOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, const double* dp,
                  const double* dl, double* new_poses, double* new_points, double* out, double* work, void* stream,
-                 const SensorArg* S) {
+                 const SensorArg* S, const MonoArg* M) {
     if (int rc = check_problem(P)) return rc;
     VUS_REQUIRE(poses && dp && new_poses && out && work, "null buffer");
     VUS_REQUIRE((points && dl && new_points) || !P->n_points, "null landmark buffer");
@@ -861,12 +963,11 @@ struct EvalStepOp {
                                                                                              dp, dl, new_poses, new_points);
     double* part_lin = work;
     double* part_new = work + (nL + 1);
-    if (nL > 0 && S)
-      eval_points_kernel<true, LOSS, true><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, dp, dl, new_poses, new_points,
-                                                                       part_lin, part_new, k, *S);
-    else if (nL > 0)
-      eval_points_kernel<true, LOSS><<<cdiv(nL, 4), 256, 0, st>>>(*P, poses, points, dp, dl, new_poses, new_points, part_lin,
-                                                                 part_new, k, NoSensor{});
+    if (nL > 0)
+      with_variant(S, M, [&](auto s, auto m) {
+        eval_points_kernel<true, LOSS, is_sensor_v<decltype(s)>, is_mono_v<decltype(m)>><<<cdiv(nL, 4), 256, 0, st>>>(
+            *P, poses, points, dp, dl, new_poses, new_points, part_lin, part_new, k, s, m);
+      });
     priors_kernel<<<1, 64, 0, st>>>(*P, poses, dp, nullptr, nullptr, part_lin + nL, 2);
     priors_kernel<<<1, 64, 0, st>>>(*P, new_poses, nullptr, nullptr, nullptr, part_new + nL, 1);
     vus::reduce_partials(part_lin, nL + 1, out, st);
@@ -879,14 +980,14 @@ struct EvalStepOp {
 template <int LOSS>
 struct WeightsOp {
   static int run(double k, const vus_ba_problem* P, const double* poses, const double* points, double* w, void* stream,
-                 const SensorArg* S) {
+                 const SensorArg* S, const MonoArg* M) {
     if (int rc = check_problem(P)) return rc;
     VUS_REQUIRE(poses && ((points && w) || !P->n_obs), "null buffer");
-    if (P->n_obs > 0 && S)
-      stereo_weights_kernel<LOSS, true><<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k, *S);
-    else if (P->n_obs > 0)
-      stereo_weights_kernel<LOSS><<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k,
-                                                                                          NoSensor{});
+    if (P->n_obs > 0)
+      with_variant(S, M, [&](auto s, auto m) {
+        stereo_weights_kernel<LOSS, is_sensor_v<decltype(s)>, is_mono_v<decltype(m)>>
+            <<<cdiv(P->n_obs, 256), 256, 0, vus::as_stream(stream)>>>(*P, poses, points, w, k, s, m);
+      });
     VUS_CHECK_LAUNCH("ba_stereo_weights");
     return VUS_OK;
   }
@@ -901,32 +1002,32 @@ extern "C" long long vus_ba_work_doubles(const vus_ba_problem* P) {
 
 extern "C" int vus_ba_error(const vus_ba_problem* P, const double* poses, const double* points, double* err,
                             double* work, void* stream) {
-  return ErrorOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, err, work, stream, nullptr);
+  return ErrorOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, err, work, stream, nullptr, nullptr);
 }
 
 extern "C" int vus_ba_error_robust(const vus_ba_problem* P, const double* poses, const double* points, double* err,
                                    double* work, void* stream, const vus_ba_loss* loss) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, (const SensorArg*)nullptr);
+  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, (const SensorArg*)nullptr, (const MonoArg*)nullptr);
 }
 
 extern "C" int vus_ba_linearize(const vus_ba_problem* P, const double* poses, const double* points, double* W,
                                 double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
                                 void* stream) {
-  return LinearizeOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, nullptr);
+  return LinearizeOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, nullptr, nullptr);
 }
 
 extern "C" int vus_ba_linearize_robust(const vus_ba_problem* P, const double* poses, const double* points, double* W,
                                        double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
                                        void* stream, const vus_ba_loss* loss) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, (const SensorArg*)nullptr);
+  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, (const SensorArg*)nullptr, (const MonoArg*)nullptr);
 }
 
 extern "C" int vus_ba_stereo_weights(const vus_ba_problem* P, const vus_ba_loss* loss, const double* poses,
                                      const double* points, double* w, void* stream) {
   if (int rc = check_loss(loss)) return rc;
-  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, (const SensorArg*)nullptr);
+  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, (const SensorArg*)nullptr, (const MonoArg*)nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -946,7 +1047,7 @@ extern "C" int vus_ba_error_sensor(const vus_ba_problem* P, const double* poses,
                                    double* work, void* stream, const vus_ba_loss* loss, const vus_ba_sensor* sensor) {
   SensorArg S;
   if (int rc = sensor_args(loss, sensor, S)) return rc;
-  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, (const SensorArg*)&S);
+  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, (const SensorArg*)&S, (const MonoArg*)nullptr);
 }
 
 extern "C" int vus_ba_linearize_sensor(const vus_ba_problem* P, const double* poses, const double* points, double* W,
@@ -954,14 +1055,14 @@ extern "C" int vus_ba_linearize_sensor(const vus_ba_problem* P, const double* po
                                        void* stream, const vus_ba_loss* loss, const vus_ba_sensor* sensor) {
   SensorArg S;
   if (int rc = sensor_args(loss, sensor, S)) return rc;
-  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, (const SensorArg*)&S);
+  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, (const SensorArg*)&S, (const MonoArg*)nullptr);
 }
 
 extern "C" int vus_ba_stereo_weights_sensor(const vus_ba_problem* P, const vus_ba_loss* loss, const double* poses,
                                             const double* points, double* w, void* stream, const vus_ba_sensor* sensor) {
   SensorArg S;
   if (int rc = sensor_args(loss, sensor, S)) return rc;
-  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, (const SensorArg*)&S);
+  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, (const SensorArg*)&S, (const MonoArg*)nullptr);
 }
 
 extern "C" int vus_ba_schur(const vus_ba_problem* P, const vus_ba_tiles* T, double lambda, const double* W, const double* V,
@@ -1032,7 +1133,7 @@ extern "C" int vus_ba_backsub(const vus_ba_problem* P, const double* W, const do
 extern "C" int vus_ba_eval_step(const vus_ba_problem* P, const double* poses, const double* points, const double* dp,
                                 const double* dl, double* new_poses, double* new_points, double* out, double* work,
                                 void* stream) {
-  return EvalStepOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, dp, dl, new_poses, new_points, out, work, stream, nullptr);
+  return EvalStepOp<VUS_LOSS_GAUSSIAN>::run(0.0, P, poses, points, dp, dl, new_poses, new_points, out, work, stream, nullptr, nullptr);
 }
 
 extern "C" int vus_ba_eval_step_robust(const vus_ba_problem* P, const double* poses, const double* points,
@@ -1040,7 +1141,7 @@ extern "C" int vus_ba_eval_step_robust(const vus_ba_problem* P, const double* po
                                        double* out, double* work, void* stream, const vus_ba_loss* loss) {
   if (int rc = check_loss(loss)) return rc;
   return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream,
-                                   (const SensorArg*)nullptr);
+                                   (const SensorArg*)nullptr, (const MonoArg*)nullptr);
 }
 
 extern "C" int vus_ba_eval_step_sensor(const vus_ba_problem* P, const double* poses, const double* points,
@@ -1050,5 +1151,66 @@ extern "C" int vus_ba_eval_step_sensor(const vus_ba_problem* P, const double* po
   SensorArg S;
   if (int rc = sensor_args(loss, sensor, S)) return rc;
   return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream,
-                                   (const SensorArg*)&S);
+                                   (const SensorArg*)&S, (const MonoArg*)nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// monocular projection factors next to the stereo ones (include/vus_mono.h): the arguments of the `_sensor` forms, the
+// extrinsic optional, and the descriptor of the mono observations
+namespace {
+// (loss or Gaussian for NULL, the extrinsic or none for NULL, the mono descriptor), all validated; Sp = &S or nullptr
+int mixed_args(const vus_ba_problem* P, const vus_ba_loss*& loss, const vus_ba_sensor* sensor, const vus_ba_mono* mono,
+               SensorArg& S, const SensorArg*& Sp, MonoArg& M) {
+  if (!loss) loss = &kGaussianLoss;
+  if (int rc = check_loss(loss)) return rc;
+  Sp = nullptr;
+  if (sensor) {
+    if (int rc = make_sensor(sensor, S)) return rc;
+    Sp = &S;
+  }
+  return make_mono(P, mono, M);
+}
+}  // namespace
+
+extern "C" int vus_ba_error_mixed(const vus_ba_problem* P, const double* poses, const double* points, double* err,
+                                  double* work, void* stream, const vus_ba_loss* loss, const vus_ba_sensor* sensor,
+                                  const vus_ba_mono* mono) {
+  SensorArg S;
+  const SensorArg* Sp;
+  MonoArg M;
+  if (int rc = mixed_args(P, loss, sensor, mono, S, Sp, M)) return rc;
+  return dispatch_loss<ErrorOp>(loss, P, poses, points, err, work, stream, Sp, (const MonoArg*)&M);
+}
+
+extern "C" int vus_ba_linearize_mixed(const vus_ba_problem* P, const double* poses, const double* points, double* W,
+                                      double* V, double* gl, double* Hpp, double* gp, double* err, double* work,
+                                      void* stream, const vus_ba_loss* loss, const vus_ba_sensor* sensor,
+                                      const vus_ba_mono* mono) {
+  SensorArg S;
+  const SensorArg* Sp;
+  MonoArg M;
+  if (int rc = mixed_args(P, loss, sensor, mono, S, Sp, M)) return rc;
+  return dispatch_loss<LinearizeOp>(loss, P, poses, points, W, V, gl, Hpp, gp, err, work, stream, Sp, (const MonoArg*)&M);
+}
+
+extern "C" int vus_ba_eval_step_mixed(const vus_ba_problem* P, const double* poses, const double* points,
+                                      const double* dp, const double* dl, double* new_poses, double* new_points,
+                                      double* out, double* work, void* stream, const vus_ba_loss* loss,
+                                      const vus_ba_sensor* sensor, const vus_ba_mono* mono) {
+  SensorArg S;
+  const SensorArg* Sp;
+  MonoArg M;
+  if (int rc = mixed_args(P, loss, sensor, mono, S, Sp, M)) return rc;
+  return dispatch_loss<EvalStepOp>(loss, P, poses, points, dp, dl, new_poses, new_points, out, work, stream, Sp,
+                                   (const MonoArg*)&M);
+}
+
+extern "C" int vus_ba_stereo_weights_mixed(const vus_ba_problem* P, const vus_ba_loss* loss, const double* poses,
+                                           const double* points, double* w, void* stream, const vus_ba_sensor* sensor,
+                                           const vus_ba_mono* mono) {
+  SensorArg S;
+  const SensorArg* Sp;
+  MonoArg M;
+  if (int rc = mixed_args(P, loss, sensor, mono, S, Sp, M)) return rc;
+  return dispatch_loss<WeightsOp>(loss, P, poses, points, w, stream, Sp, (const MonoArg*)&M);
 }

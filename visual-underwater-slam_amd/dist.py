@@ -189,7 +189,7 @@ class ShardedStereoBASolver:
     landmarks, band forced to the global band) and inserts the collectives."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
-                 prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None):
+                 prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None, mono=None):
         from .ba import StereoBAProblem, StereoBASolver
         if between is not None:
             raise NotImplementedError("BetweenFactorPose3 (ba.BetweenFactors) is not supported by the landmark-sharded solver: "
@@ -197,6 +197,9 @@ class ShardedStereoBASolver:
         if body_P_sensor is not None:
             raise NotImplementedError("a camera-to-body extrinsic (body_P_sensor) is not supported by the landmark-sharded "
                                       "solver: use StereoBASolver(StereoBAProblem(..., body_P_sensor=...)) on one GPU")
+        if mono is not None and bool(torch.as_tensor(mono).any()):
+            raise NotImplementedError("monocular projection factors (mono) are not supported by the landmark-sharded "
+                                      "solver: use StereoBASolver(StereoBAProblem(..., mono=...)) on one GPU")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         obs_pose = torch.as_tensor(obs_pose).to(device)
@@ -272,4 +275,6 @@ def _make_shard_solver():
 def _ShardSolver(problem, world):
     if getattr(problem, "has_sensor", False):
         raise NotImplementedError("a camera-to-body extrinsic (body_P_sensor) is not supported by the landmark-sharded solver")
+    if getattr(problem, "has_mono", False):
+        raise NotImplementedError("monocular projection factors (mono) are not supported by the landmark-sharded solver")
     return _make_shard_solver()(problem, world)

@@ -10,7 +10,7 @@ module exposes the same names with the same argument meaning, so that
 is the only change batch.py needs for the stereo path; `LevenbergMarquardtOptimizer.optimize()` then
 runs on the MI355X kernels (ba.py / csrc/ba.hip).
 
-Scope: GenericStereoFactor3D, PriorFactorPose3, PriorFactorVector, ImuFactor (with
+Scope: GenericStereoFactor3D, GenericProjectionFactorCal3_S2, PriorFactorPose3, PriorFactorVector, ImuFactor (with
 PreintegratedImuMeasurements) and the DVL velocity factor (DvlVelocityFactor, the well-formed
 replacement of the reference's CustomFactor) are solved on the GPU.  A generic gtsam.CustomFactor
 (arbitrary Python callback) can be constructed and added, but optimize() refuses it, loudly.
@@ -36,6 +36,7 @@ __all__ = [
     "PinholeCameraCal3_S2",
     "NonlinearFactorGraph", "Values", "LevenbergMarquardtParams", "LevenbergMarquardtOptimizer",
     "StereoFactorBlock", "symbol_shorthand", "symbol",
+    "Point2", "GenericProjectionFactorCal3_S2", "ProjectionFactorBlock",
 ]
 
 
@@ -46,6 +47,13 @@ def Point3(x=0.0, y=0.0, z=0.0):
     if isinstance(x, (list, tuple, np.ndarray)):
         return np.asarray(x, dtype=float).reshape(3).copy()
     return np.array([x, y, z], dtype=float)
+
+
+def Point2(x=0.0, y=0.0):
+    """gtsam.Point2 is a numpy 2-vector in the Python wrapper."""
+    if isinstance(x, (list, tuple, np.ndarray)):
+        return np.asarray(x, dtype=float).reshape(2).copy()
+    return np.array([x, y], dtype=float)
 
 
 def _skew(w):
@@ -269,8 +277,39 @@ class Cal3_S2Stereo:
 
 
 class Cal3_S2:
+    """gtsam.Cal3_S2(fx, fy, s, u0, v0): the five-parameter pinhole calibration.  Its skew IS used by the projection."""
+
     def __init__(self, fx=1.0, fy=1.0, s=0.0, u0=0.0, v0=0.0):
         self._v = (float(fx), float(fy), float(s), float(u0), float(v0))
+
+    def fx(self):
+        return self._v[0]
+
+    def fy(self):
+        return self._v[1]
+
+    def skew(self):
+        return self._v[2]
+
+    def px(self):
+        return self._v[3]
+
+    def py(self):
+        return self._v[4]
+
+    def vector(self):
+        """(fx, fy, s, u0, v0)"""
+        return np.array(self._v)
+
+    def K(self):
+        fx, fy, s, u0, v0 = self._v
+        return np.array([[fx, s, u0], [0.0, fy, v0], [0.0, 0.0, 1.0]])
+
+    def equals(self, other, tol=1e-9):
+        return bool(np.allclose(self._v, other._v, atol=tol))
+
+    def __repr__(self):
+        return "Cal3_S2(fx={}, fy={}, s={}, u0={}, v0={})".format(*self._v)
 
 
 class StereoPoint2:
@@ -554,6 +593,79 @@ class GenericStereoFactor3D(_Factor):
         return self._model
 
 
+class GenericProjectionFactorCal3_S2(_Factor):
+    """GenericProjectionFactor<Pose3, Point3, Cal3_S2>(measured, model, poseKey, pointKey, K, body_P_sensor=None): a
+    landmark seen in one image, residual project(pose o body_P_sensor, point) - measured under a 2-dimensional model.
+    It shares the graph with GenericStereoFactor3D factors (include/vus_mono.h): one Cal3_S2, one isotropic model and one
+    extrinsic for all mono factors of a graph; the extrinsic and, for robust models, the mEstimator are those of the
+    stereo factors too (the sigmas may differ).
+    There is no observability check: a landmark held by a single monocular sighting has a rank-2 information block and is
+    kept finite by the Levenberg-Marquardt damping alone -- as in GTSAM, until its linear solver throws."""
+
+    def __init__(self, measured, model: _NoiseModel, poseKey: int, pointKey: int, K: Cal3_S2,
+                 body_P_sensor: Optional[Pose3] = None):
+        super().__init__([poseKey, pointKey])
+        if model.dim() != 2:
+            raise RuntimeError("GenericProjectionFactorCal3_S2 needs a 2-dimensional noise model")
+        if not isinstance(K, Cal3_S2):
+            raise RuntimeError("GenericProjectionFactorCal3_S2 needs a Cal3_S2 calibration")
+        self._measured = Point2(np.asarray(measured, dtype=float).reshape(2))
+        self._model, self._K = model, K
+        self._sensor = _sensor_pose(body_P_sensor)
+
+    def body_P_sensor(self):
+        """A copy of the camera-to-body extrinsic, or None."""
+        return None if self._sensor is None else Pose3(self._sensor)
+
+    def measured(self):
+        return self._measured.copy()
+
+    def calibration(self):
+        return self._K
+
+    def noiseModel(self):
+        return self._model
+
+
+class ProjectionFactorBlock(_Factor):
+    """EXTENSION (not in gtsam): many GenericProjectionFactorCal3_S2 factors sharing one noise model, one calibration
+    and one extrinsic, held as arrays -- what StereoFactorBlock is to GenericStereoFactor3D.  measured: [n, 2] (u, v)."""
+
+    def __init__(self, measured, model: _NoiseModel, poseKeys, pointKeys, K: Cal3_S2,
+                 body_P_sensor: Optional[Pose3] = None):
+        self.meas = np.ascontiguousarray(measured, dtype=float).reshape(-1, 2)
+        self.pose_keys = np.ascontiguousarray(poseKeys, dtype=np.int64).reshape(-1)
+        self.landmark_keys = np.ascontiguousarray(pointKeys, dtype=np.int64).reshape(-1)
+        if not (len(self.meas) == len(self.pose_keys) == len(self.landmark_keys)):
+            raise RuntimeError("ProjectionFactorBlock: arrays differ in length")
+        if model.dim() != 2:
+            raise RuntimeError("ProjectionFactorBlock needs a 2-dimensional noise model")
+        if not isinstance(K, Cal3_S2):
+            raise RuntimeError("ProjectionFactorBlock needs a Cal3_S2 calibration")
+        self._model, self._K = model, K
+        self._sensor = _sensor_pose(body_P_sensor)
+        self._keys = None
+
+    def body_P_sensor(self):
+        """A copy of the camera-to-body extrinsic of every factor of the block, or None."""
+        return None if self._sensor is None else Pose3(self._sensor)
+
+    def calibration(self):
+        return self._K
+
+    def noiseModel(self):
+        return self._model
+
+    def keys(self):
+        return np.unique(np.concatenate([self.pose_keys, self.landmark_keys])).tolist()
+
+    def size(self):
+        return len(self.meas)
+
+    def __len__(self):
+        return len(self.meas)
+
+
 class StereoFactorBlock(_Factor):
     """EXTENSION (not in gtsam): many GenericStereoFactor3D factors sharing one noise model and one
     calibration, held as arrays.  It is the vectorised form of the emission loop batch.py:296-305 for
@@ -768,10 +880,37 @@ class ConstantTwistScenario:
 
 
 class PinholeCameraCal3_S2:
-    """Imported by batch.py:19-25 and never used; only the name has to exist for the import line."""
+    """gtsam.PinholeCameraCal3_S2(pose, K), host-only: for initialising landmarks (backproject) and synthesising
+    measurements (project); the factors' arithmetic runs on the GPU.  project() is the prediction of
+    GenericProjectionFactorCal3_S2 for the camera pose (pose o body_P_sensor of the factor)."""
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("PinholeCameraCal3_S2 is imported but unused by batch.py; not part of the hot path")
+    def __init__(self, pose: Optional[Pose3] = None, K: Optional[Cal3_S2] = None):
+        self._pose = Pose3() if pose is None else Pose3(pose)
+        self._K = Cal3_S2() if K is None else K
+        if not isinstance(self._K, Cal3_S2):
+            raise RuntimeError("PinholeCameraCal3_S2 needs a Cal3_S2 calibration")
+
+    def pose(self):
+        return Pose3(self._pose)
+
+    def calibration(self):
+        return self._K
+
+    def project(self, point):
+        """Point2 (u, v) of a world point; RuntimeError (gtsam's CheiralityException) at or behind the camera."""
+        q = self._pose.transformTo(np.asarray(point, dtype=float).reshape(3))
+        if q[2] <= 0.0:
+            raise RuntimeError("CheiralityException: the point is behind the camera")
+        fx, fy, s, u0, v0 = self._K._v
+        return np.array([u0 + fx * q[0] / q[2] + s * q[1] / q[2], v0 + fy * q[1] / q[2]])
+
+    def backproject(self, p, depth):
+        """The world point at `depth` along the ray of pixel p."""
+        fx, fy, s, u0, v0 = self._K._v
+        p = np.asarray(p, dtype=float).reshape(2)
+        yn = (p[1] - v0) / fy
+        xn = (p[0] - u0 - s * yn) / fx
+        return self._pose.transformFrom(float(depth) * np.array([xn, yn, 1.0]))
 
 
 class ISAM2:
@@ -1126,6 +1265,10 @@ class NonlinearFactorGraph:
         self._st_meas, self._st_pk, self._st_lk = array("d"), array("q"), array("q")
         self._st_model = self._st_K = self._st_sensor = None     # the one noise model / calibration / extrinsic the stereo factors share ...
         self._st_mixed = False                   # ... or the fact that they do not (refused at optimize())
+        # single GenericProjectionFactorCal3_S2 factors, column-wise in the same way: (u, v), pose key, point key
+        self._mo_meas, self._mo_pk, self._mo_lk = array("d"), array("q"), array("q")
+        self._mo_model = self._mo_K = self._mo_sensor = None
+        self._mo_mixed = False
 
     def _record(self, factor):
         self._factors.append(factor)
@@ -1140,6 +1283,17 @@ class NonlinearFactorGraph:
             self._st_meas.extend(factor._measured._m)
             self._st_pk.append(factor._keys[0])
             self._st_lk.append(factor._keys[1])
+        elif type(factor) is GenericProjectionFactorCal3_S2:
+            m, K, S = factor._model, factor._K, factor._sensor
+            if self._mo_model is None:
+                self._mo_model, self._mo_K, self._mo_sensor = m, K, S
+            elif (m is not self._mo_model and _stereo_model_key(m) != _stereo_model_key(self._mo_model)) or \
+                    (K is not self._mo_K and not K.equals(self._mo_K)) or \
+                    (S is not self._mo_sensor and not _same_sensor(S, self._mo_sensor)):
+                self._mo_mixed = True
+            self._mo_meas.extend(factor._measured)
+            self._mo_pk.append(factor._keys[0])
+            self._mo_lk.append(factor._keys[1])
         else:
             self._other.append(factor)
 
@@ -1160,11 +1314,21 @@ class NonlinearFactorGraph:
                 np.frombuffer(self._st_pk, dtype=np.int64).copy(), np.frombuffer(self._st_lk, dtype=np.int64).copy(),
                 self._st_model, self._st_K, self._st_mixed)
 
+    def _mono_columns(self):
+        """(meas [n,2], pose keys [n], point keys [n], model, K, mixed) of the single projection factors, in graph order."""
+        n = len(self._mo_pk)
+        if n == 0:
+            return np.zeros((0, 2)), np.zeros(0, np.int64), np.zeros(0, np.int64), None, None, False
+        return (np.frombuffer(self._mo_meas, dtype=np.float64).reshape(n, 2).copy(),
+                np.frombuffer(self._mo_pk, dtype=np.int64).copy(), np.frombuffer(self._mo_lk, dtype=np.int64).copy(),
+                self._mo_model, self._mo_K, self._mo_mixed)
+
     def size(self):
         return len(self._factors)
 
     def nrFactors(self):
-        return sum(f.size() if isinstance(f, StereoFactorBlock) else 1 for f in self._other) + len(self._st_pk)
+        blocks = (StereoFactorBlock, ProjectionFactorBlock)
+        return sum(f.size() if isinstance(f, blocks) else 1 for f in self._other) + len(self._st_pk) + len(self._mo_pk)
 
     def at(self, i):
         return self._factors[i]
@@ -1175,6 +1339,8 @@ class NonlinearFactorGraph:
             out.update(f.keys())
         out.update(self._st_pk.tolist())
         out.update(self._st_lk.tolist())
+        out.update(self._mo_pk.tolist())
+        out.update(self._mo_lk.tolist())
         return sorted(out)
 
     def error(self, values: Values) -> float:
@@ -1193,7 +1359,7 @@ class NonlinearFactorGraph:
             f.write("\n")
             n = 0
             for fac in self._factors:
-                if isinstance(fac, StereoFactorBlock):
+                if isinstance(fac, (StereoFactorBlock, ProjectionFactorBlock)):
                     for pk, lk in zip(fac.pose_keys.tolist(), fac.landmark_keys.tolist()):
                         f.write(f"  factor{n}[label=\"\", shape=point];\n  var{pk}--factor{n};\n  var{lk}--factor{n};\n")
                         n += 1

@@ -143,8 +143,10 @@ def _pack_graph(graph, values, device=None):
     is given (2 M observations: ~3 ms on the GPU against ~0.3 s in numpy), else in numpy (CPU tests)."""
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
                    ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias, PriorFactorConstantBias,
-                   BetweenFactorConstantBias, BetweenFactorPose3)
+                   BetweenFactorConstantBias, BetweenFactorPose3, GenericProjectionFactorCal3_S2, ProjectionFactorBlock)
     meas, pkeys, lkeys = [], [], []
+    mono_n = []                     # per part of meas / pkeys / lkeys: 0 for a stereo part, its length for a mono part
+    mono = dict(sigma=None, calib=None, loss=None, sensor=None)
     between_f = []
     imu_f, dvl_f, bias_f = [], [], []
     from . import _Robust
@@ -168,12 +170,42 @@ def _pack_graph(graph, values, device=None):
         elif not _same_sensor(body_P_sensor, sensor):
             raise NotImplementedError("all stereo factors of one graph must share one body_P_sensor (or all have none)")
 
+    def check_mono_model(model, K, body_P_sensor):
+        if model.dim() != 2 or not model.is_isotropic():
+            raise NotImplementedError("monocular projection factors need an isotropic 2-dimensional noise model "
+                                      "(Isotropic.Sigma(2, sigma)), optionally wrapped in noiseModel.Robust")
+        s = float(model.sigmas()[0])
+        rob = model.robust() if isinstance(model, _Robust) else None
+        lo = (rob.kind, rob.k) if rob is not None else None
+        if mono["sigma"] is None:
+            mono.update(sigma=s, calib=K, loss=lo, sensor=body_P_sensor)
+        elif s != mono["sigma"] or lo != mono["loss"] or not K.equals(mono["calib"]):
+            raise NotImplementedError("all monocular projection factors of one graph must share one noise model and one Cal3_S2")
+        elif not _same_sensor(body_P_sensor, mono["sensor"]):
+            raise NotImplementedError("all monocular projection factors of one graph must share one body_P_sensor (or all "
+                                      "have none)")
+
+    def add_mono(m2, pk, lk):
+        """(u, v) rows -> (u, unused, v) rows of the one observation list"""
+        m2 = np.asarray(m2, dtype=float).reshape(-1, 2)
+        m3 = np.zeros((len(m2), 3))
+        m3[:, 0], m3[:, 2] = m2[:, 0], m2[:, 1]
+        meas.append(m3); pkeys.append(np.asarray(pk, dtype=np.int64)); lkeys.append(np.asarray(lk, dtype=np.int64))
+        mono_n.append(len(m3))
+
+    mono_single = ([], [], [])
     # single GenericStereoFactor3D objects were recorded column-wise when they were added (NonlinearFactorGraph._record):
     # only the O(#keyframes) other factors are visited here
     for f in graph._other:
         if isinstance(f, StereoFactorBlock):
             check_model(f._model, f._K, f._sensor)
-            meas.append(f.meas); pkeys.append(f.pose_keys); lkeys.append(f.landmark_keys)
+            meas.append(f.meas); pkeys.append(f.pose_keys); lkeys.append(f.landmark_keys); mono_n.append(0)
+        elif isinstance(f, ProjectionFactorBlock):
+            check_mono_model(f._model, f._K, f._sensor)
+            add_mono(f.meas, f.pose_keys, f.landmark_keys)
+        elif isinstance(f, GenericProjectionFactorCal3_S2):       # a subclass instance: not recorded column-wise
+            check_mono_model(f._model, f._K, f._sensor)
+            mono_single[0].append(f._measured); mono_single[1].append(f._keys[0]); mono_single[2].append(f._keys[1])
         elif isinstance(f, GenericStereoFactor3D):       # a subclass instance: not recorded column-wise
             check_model(f._model, f._K, f._sensor)
             single_m.append(f._measured._m); single_p.append(f._keys[0]); single_l.append(f._keys[1])
@@ -211,10 +243,31 @@ def _pack_graph(graph, values, device=None):
             raise NotImplementedError("all stereo factors of one graph must share one noise model, one Cal3_S2Stereo and one "
                                       "body_P_sensor (or have none)")
         check_model(c_model, c_K, graph._st_sensor)
-        meas.append(c_meas); pkeys.append(c_pk); lkeys.append(c_lk)
+        meas.append(c_meas); pkeys.append(c_pk); lkeys.append(c_lk); mono_n.append(0)
     if single_m:
         meas.append(np.asarray(single_m, dtype=float).reshape(-1, 3))
-        pkeys.append(np.asarray(single_p, dtype=np.int64)); lkeys.append(np.asarray(single_l, dtype=np.int64))
+        pkeys.append(np.asarray(single_p, dtype=np.int64)); lkeys.append(np.asarray(single_l, dtype=np.int64)); mono_n.append(0)
+    m_meas, m_pk, m_lk, m_model, m_K, m_mixed = graph._mono_columns()
+    if len(m_pk):
+        if m_mixed:
+            raise NotImplementedError("all monocular projection factors of one graph must share one noise model, one Cal3_S2 "
+                                      "and one body_P_sensor (or have none)")
+        check_mono_model(m_model, m_K, graph._mo_sensor)
+        add_mono(m_meas, m_pk, m_lk)
+    if mono_single[0]:
+        add_mono(*mono_single)
+    has_mono = mono["sigma"] is not None
+    if has_mono and model_sigma is not None:
+        # one graph, one extrinsic and one mEstimator: the kernels take a single vus_ba_sensor and a single vus_ba_loss
+        if not _same_sensor(mono["sensor"], sensor):
+            raise NotImplementedError("the monocular projection factors and the stereo factors of one graph must share one "
+                                      "body_P_sensor (or all have none)")
+        if mono["loss"] != loss:
+            raise NotImplementedError("the monocular projection factors and the stereo factors of one graph must share one "
+                                      "robust mEstimator and parameter (or all be Gaussian); their sigmas may differ")
+    elif has_mono:                  # a graph of mono factors only: their extrinsic and loss are the graph's
+        loss, sensor = mono["loss"], mono["sensor"]
+    mono_flags = np.concatenate([np.full(len(m), bool(k)) for m, k in zip(meas, mono_n)]) if has_mono else None
     cat = lambda parts, empty: parts[0] if len(parts) == 1 else (np.concatenate(parts) if parts else empty)
     meas = cat(meas, np.zeros((0, 3)))
     pkeys = cat(pkeys, np.zeros(0, np.int64))
@@ -284,6 +337,7 @@ def _pack_graph(graph, values, device=None):
                 points=points, sigma=model_sigma if model_sigma is not None else 1.0, loss=loss,
                 body_P_sensor=sensor.flat12() if sensor is not None else None,
                 K=calib.vector6() if calib is not None else np.array([1.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
+                mono=mono_flags, mono_K=mono["calib"].vector() if has_mono else None, mono_sigma=mono["sigma"],
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
                 prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between)
 
@@ -437,7 +491,8 @@ def _build_solver(pg, device="cuda:0"):
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
                            prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
                            loss=pg.get("loss"), between_span=btw["span"] if btw else 0,
-                           body_P_sensor=pg.get("body_P_sensor"))
+                           body_P_sensor=pg.get("body_P_sensor"), mono=pg.get("mono"), mono_K=pg.get("mono_K"),
+                           mono_sigma=pg.get("mono_sigma"))
     bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
                         loss=list(btw["losses"]), device=device) if btw else None
     if walk:
