@@ -544,6 +544,10 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * stereo factors: vus_ba_mono and the `_mixed` forms of the linearisation, step evaluation, error and robust weights. */
 #include "vus_mono.h"
 
+/* PriorFactor<Point3> on landmarks that stereo or monocular factors observe, added to V / gl before the Schur step:
+ * vus_point_priors and vus_point_prior_check / _linearize / _eval_step / _error. */
+#include "vus_point_prior.h"
+
 /* Two-point RANSAC with a known inter-frame rotation on the temporal matches (the nodelet's ransac_threshold,
  * launch/stereo.launch:46), between the track matcher and the id emitter above: vus_two_point_ransac. */
 #include "vus_ransac.h"

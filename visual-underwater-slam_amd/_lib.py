@@ -92,6 +92,11 @@ SIGNATURES = {
     "vus_between_assemble": [_P, _P, c_int, _P, _P, _P],
     "vus_between_eval_step": [_P, _P, _P, _P, _P, _P, _P],
     "vus_between_error": [_P, _P, _P, _P, _P],
+    # PriorFactor<Point3> on observed landmarks (include/vus_point_prior.h)
+    "vus_point_prior_check": [_P, _P],
+    "vus_point_prior_linearize": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_point_prior_eval_step": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_point_prior_error": [_P, _P, _P, _P, _P],
     # host-only tuning knobs of the band solve (tests, A/B timing)
     "vus_ba_set_tuning": [c_int, c_int],
 }
@@ -143,6 +148,8 @@ def load():
     lib.vus_navb_work_doubles.restype = ctypes.c_longlong
     lib.vus_between_work_doubles.argtypes = [_P]
     lib.vus_between_work_doubles.restype = ctypes.c_longlong
+    lib.vus_point_prior_work_doubles.argtypes = [_P]
+    lib.vus_point_prior_work_doubles.restype = ctypes.c_longlong
     lib.vus_ba_band_selinv_work_doubles.argtypes = [c_int, c_int]
     lib.vus_ba_band_selinv_work_doubles.restype = ctypes.c_longlong
     _lib = lib

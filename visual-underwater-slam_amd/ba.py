@@ -159,6 +159,55 @@ class BetweenFactors:
         return ctypes.addressof(self.c)
 
 
+class _CPointPriors(ctypes.Structure):
+    _fields_ = [("n", c_int), ("n_points", c_int), ("n_rows", c_int), ("row_point", c_void_p), ("row_ptr", c_void_p),
+                ("mean", c_void_p), ("w", c_void_p)]
+
+
+def point_prior_rows(point_idx):
+    """The CSR of include/vus_point_prior.h on the host: (order, row_point, row_ptr) -- `order` sorts the factors stably by
+    landmark (graph order within one landmark), row_point lists the distinct landmarks ascending, row_ptr [n_rows + 1]
+    points into the sorted factors."""
+    idx = np.asarray(point_idx, np.int64).reshape(-1)
+    order = np.argsort(idx, kind="stable")
+    row_point, first = np.unique(idx[order], return_index=True)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return order, i32(row_point), i32(np.append(first, len(idx)))
+
+
+class PointPriors:
+    """Device-resident vus_point_priors: PriorFactorPoint3(L(j), mean, model) for j = `point_idx` on landmarks of a
+    StereoBAProblem with `n_points` landmarks; mean [n, 3], sigmas [n, 3] (a diagonal model; several priors on one landmark
+    are summed).  The factors are sorted stably by landmark into the CSR on the host; `host` keeps them in that order.
+    n = 0 is allowed and is the same as no PointPriors at all."""
+
+    def __init__(self, point_idx, mean, sigmas, n_points, device="cuda:0"):
+        idx = np.asarray(point_idx, np.int64).reshape(-1)
+        mean = np.asarray(mean, np.float64).reshape(-1, 3)
+        sig = np.asarray(sigmas, np.float64).reshape(-1, 3)
+        n = len(idx)
+        if not (len(mean) == len(sig) == n):
+            raise ValueError(f"point priors: {n} landmark indices, {len(mean)} means, {len(sig)} sigmas")
+        if ((idx < 0) | (idx >= n_points)).any():
+            raise ValueError(f"point priors: a landmark index outside [0, {int(n_points)})")
+        if not (np.isfinite(sig).all() and (sig > 0).all()):
+            raise ValueError("point priors: sigmas must be finite and > 0")
+        if not np.isfinite(mean).all():
+            raise ValueError("point priors: means must be finite")
+        order, row_point, row_ptr = point_prior_rows(idx)
+        self.n, self.n_points, self.n_rows = n, int(n_points), len(row_point)
+        self.host = dict(idx=idx[order], mean=mean[order], sigmas=sig[order], row_point=row_point, row_ptr=row_ptr)
+        dev = torch.device(device)
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        self.row_point, self.row_ptr = t(row_point, torch.int32), t(row_ptr, torch.int32)
+        self.mean, self.w = t(mean[order], torch.float64), t(1.0 / sig[order], torch.float64)
+        p = (lambda x: _lib.ptr(x)) if n else (lambda x: None)
+        self.c = _CPointPriors(n, self.n_points, self.n_rows, p(self.row_point), p(self.row_ptr), p(self.mean), p(self.w))
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+
 @dataclass
 class LMParams:
     """gtsam.LevenbergMarquardtParams() defaults."""
@@ -437,7 +486,8 @@ class BAMarginals:
 class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
 
-    def __init__(self, problem: StereoBAProblem, between: Optional[BetweenFactors] = None):
+    def __init__(self, problem: StereoBAProblem, between: Optional[BetweenFactors] = None,
+                 point_priors: Optional[PointPriors] = None):
         self.P = problem
         dev, nP, nL, nO, B = problem.device, problem.n_poses, problem.n_points, problem.n_obs, problem.band
         nN = problem.n_nodes                       # camera-side nodes (= poses unless velocity nodes are interleaved)
@@ -457,8 +507,9 @@ class StereoBASolver:
         self.work = torch.empty((2 * (nL + 1) + 8,), **f64)
         # one 40-byte record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised
         # error at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word; with between
-        # factors [5..7] their three errors in the same order, [8] spare
-        self._trial = torch.zeros((5 if between is None else 9,), **f64)
+        # factors [5..7] their three errors in the same order, [8] spare; with landmark priors [9..11] theirs
+        self.Q = point_priors if point_priors is not None and point_priors.n else None      # no factors: no hooks
+        self._trial = torch.zeros((12 if self.Q is not None else 5 if between is None else 9,), **f64)
         self.scal = self._trial[:4]
         self.status = self._trial[4:].view(torch.int32)[:1]
         self.B = between
@@ -473,6 +524,13 @@ class StereoBASolver:
             self.btw_err = torch.empty((1,), **f64)
             self.btw_work = torch.empty((int(_lib.load().vus_between_work_doubles(between.addr())),), **f64)
             _lib.call("vus_between_check", between.addr(), B, _lib.current_stream_ptr())
+        if self.Q is not None:
+            if self.Q.n_points != nL:
+                raise ValueError(f"PointPriors built for {self.Q.n_points} landmarks, the problem has {nL}")
+            self.pp_scal = self._trial[9:12]
+            self.pp_err = torch.empty((1,), **f64)
+            self.pp_work = torch.empty((int(_lib.load().vus_point_prior_work_doubles(self.Q.addr())),), **f64)
+            _lib.call("vus_point_prior_check", self.Q.addr(), _lib.current_stream_ptr())
         # two-sided band solve (vus_ba_band_solve_split): worth it once the chain of panel steps is much longer than
         # the band; its workspace (pose-reversed copy of the lower half + the middle system) is allocated once
         self.band_rhs = 1
@@ -601,12 +659,35 @@ class StereoBASolver:
             _lib.call("vus_between_eval_step", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.dp), _lib.ptr(self.new_poses),
                       _lib.ptr(self.btw_scal[1:]), _lib.ptr(self.btw_work), _lib.current_stream_ptr())
 
+    # -- priors on observed landmarks (include/vus_point_prior.h); every hook is a no-op without them -----------------
+    def point_prior_error(self, points) -> float:
+        """Error of the landmark priors at points; 0.0 without them."""
+        if self.Q is None:
+            return 0.0
+        _lib.call("vus_point_prior_error", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.pp_err), _lib.ptr(self.pp_work),
+                  _lib.current_stream_ptr())
+        return float(self.pp_err[0].item())
+
+    def point_prior_linearize(self, points):
+        """V, gl += the landmark priors at points, pp_scal[0] = their error: after linearize(), before schur()."""
+        if self.Q is not None:
+            _lib.call("vus_point_prior_linearize", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.V), _lib.ptr(self.gl),
+                      _lib.ptr(self.pp_scal), _lib.ptr(self.pp_work), _lib.current_stream_ptr())
+
+    def point_prior_eval_step(self, points):
+        """pp_scal[1] = the priors' error at points + dl, pp_scal[2] = at new_points (after eval_step)."""
+        if self.Q is not None:
+            _lib.call("vus_point_prior_eval_step", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.dl),
+                      _lib.ptr(self.new_points), _lib.ptr(self.pp_scal[1:]), _lib.ptr(self.pp_work),
+                      _lib.current_stream_ptr())
+
     def _trial_errors(self, rec):
-        """[linearise error, linearised error at the step, new error] of the stereo factors, priors and between factors
-        from one trial record"""
-        if self.B is None:
+        """[linearise error, linearised error at the step, new error] of the stereo factors, priors, between factors and
+        landmark priors from one trial record"""
+        if self.B is None and self.Q is None:
             return [float(x) for x in rec[:3]]
-        return [float(rec[k]) + float(rec[5 + k]) for k in range(3)]
+        return [float(rec[k]) + (float(rec[5 + k]) if self.B is not None else 0.0) +
+                (float(rec[9 + k]) if self.Q is not None else 0.0) for k in range(3)]
 
     # -- marginal covariances (gtsam.Marginals) ---------------------------------------------------------------------
     def _check_points(self):
@@ -657,8 +738,9 @@ class StereoBASolver:
 
     def _point_rows(self, values, points):
         """Per landmark j of `points`: (Y rows [m, 6, 3] = W V^-1 at lambda = 0, the camera-side nodes of its observations,
-        V_j^-1) at `values`, from a fresh stereo linearisation (robust weights included)."""
+        V_j^-1) at `values`, from a fresh stereo linearisation (robust weights and landmark priors included)."""
         self.linearize(values[0], values[-1])
+        self.point_prior_linearize(values[-1])
         ptr = self.P.pk["point_ptr"].cpu().numpy()
         obs_pose = self.P.pk["obs_pose"]
         out = []
@@ -723,6 +805,7 @@ class StereoBASolver:
     def _linearize_all(self, values):
         poses, points = values
         self.linearize(poses, points)
+        self.point_prior_linearize(points)          # before the check: a prior can make a landmark determinate
         self._check_points()
         self.between_linearize(poses)
 
@@ -735,10 +818,11 @@ class StereoBASolver:
     _NEW_STATE = ("new_poses", "new_points")      # the buffers a trial writes, one per state tensor
 
     def _lm_error(self, state) -> float:
-        return self.error(*state) + self.between_error(state[0])
+        return self.error(*state) + self.between_error(state[0]) + self.point_prior_error(state[1])
 
     def _lm_linearize(self, state):
         self.linearize(*state)
+        self.point_prior_linearize(state[1])
         self.between_linearize(state[0])
 
     def _lm_solve(self, lam):
@@ -751,6 +835,7 @@ class StereoBASolver:
         """Evaluate the trial step; (status, [linearised error at 0, at the step, new error]) from ONE blocking read."""
         self.eval_step(*state)
         self.between_eval_step(state[0])
+        self.point_prior_eval_step(state[1])
         rec = self._trial.cpu()
         return int(rec[4:].view(torch.int32)[0]), self._trial_errors(rec)
 
@@ -951,10 +1036,10 @@ class _InertialBASolver(StereoBASolver):
     _ABI = None
     _NEW_STATE = ("new_poses", "new_vels", "new_bias", "new_points")     # state = (poses, vels, bias, points)
 
-    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None):
+    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None):
         if problem.pose_stride != self.POSE_STRIDE:
             raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
-        super().__init__(problem, between)
+        super().__init__(problem, between, point_priors)
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
         f64 = dict(dtype=torch.float64, device=dev)
@@ -974,6 +1059,7 @@ class _InertialBASolver(StereoBASolver):
     def _linearize_all(self, values):
         poses, vels, bias, points = values
         self.linearize(poses, points)
+        self.point_prior_linearize(points)
         self._check_points()
         self.nav_linearize(poses, vels, bias)
         self.between_linearize(poses)
@@ -985,11 +1071,13 @@ class _InertialBASolver(StereoBASolver):
 
     def _lm_error(self, state):
         poses, vels, bias, points = state
-        return self.error(poses, points) + self.nav_error(poses, vels, bias) + self.between_error(poses)
+        return (self.error(poses, points) + self.nav_error(poses, vels, bias) + self.between_error(poses) +
+                self.point_prior_error(points))
 
     def _lm_linearize(self, state):
         poses, vels, bias, points = state
         self.linearize(poses, points)
+        self.point_prior_linearize(points)
         self.nav_linearize(poses, vels, bias)
         self.between_linearize(poses)
 
@@ -1005,6 +1093,7 @@ class _InertialBASolver(StereoBASolver):
         self.eval_step(poses, points)
         self.nav_eval_step(poses, vels, bias)
         self.between_eval_step(poses)
+        self.point_prior_eval_step(points)
         rec, nsc = self._trial.cpu(), self.nav_scal.cpu()         # stereo (+ between) scalars + status, then the inertial scalars
         sc = self._trial_errors(rec)
         return int(rec[4:].view(torch.int32)[0]), [sc[k] + float(nsc[k]) for k in range(3)]
@@ -1024,8 +1113,9 @@ class NavBASolver(_InertialBASolver):
     7-right-hand-side band solve."""
     POSE_STRIDE, SDIAG, _ABI = 2, 4, "vus_nav"
 
-    def __init__(self, problem: StereoBAProblem, nav: NavFactors, between: Optional[BetweenFactors] = None):
-        super().__init__(problem, nav, None, between)
+    def __init__(self, problem: StereoBAProblem, nav: NavFactors, between: Optional[BetweenFactors] = None,
+                 point_priors: Optional[PointPriors] = None):
+        super().__init__(problem, nav, None, between, point_priors)
         self.band_rhs = 7
         self._alloc_band_work()
         nN = problem.n_nodes
@@ -1100,8 +1190,9 @@ class NavBiasBASolver(_InertialBASolver):
     common inertial loop, with `bias` the [n_poses, 6] per-keyframe biases."""
     POSE_STRIDE, SDIAG, _ABI = 3, 5, "vus_navb"
 
-    def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors, between: Optional[BetweenFactors] = None):
-        super().__init__(problem, nav, problem.n_poses, between)
+    def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors, between: Optional[BetweenFactors] = None,
+                 point_priors: Optional[PointPriors] = None):
+        super().__init__(problem, nav, problem.n_poses, between, point_priors)
 
     def nav_linearize(self, poses, vels, biases):
         p = _lib.ptr

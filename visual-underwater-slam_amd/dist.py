@@ -189,7 +189,8 @@ class ShardedStereoBASolver:
     landmarks, band forced to the global band) and inserts the collectives."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
-                 prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None, mono=None):
+                 prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None, mono=None,
+                 point_priors=None):
         from .ba import StereoBAProblem, StereoBASolver
         if between is not None:
             raise NotImplementedError("BetweenFactorPose3 (ba.BetweenFactors) is not supported by the landmark-sharded solver: "
@@ -200,6 +201,9 @@ class ShardedStereoBASolver:
         if mono is not None and bool(torch.as_tensor(mono).any()):
             raise NotImplementedError("monocular projection factors (mono) are not supported by the landmark-sharded "
                                       "solver: use StereoBASolver(StereoBAProblem(..., mono=...)) on one GPU")
+        if point_priors is not None:
+            raise NotImplementedError("priors on observed landmarks (ba.PointPriors) are not supported by the landmark-sharded "
+                                      "solver: use StereoBASolver(problem, point_priors=...) on one GPU")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         obs_pose = torch.as_tensor(obs_pose).to(device)

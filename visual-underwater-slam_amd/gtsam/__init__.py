@@ -600,7 +600,9 @@ class GenericProjectionFactorCal3_S2(_Factor):
     extrinsic for all mono factors of a graph; the extrinsic and, for robust models, the mEstimator are those of the
     stereo factors too (the sigmas may differ).
     There is no observability check: a landmark held by a single monocular sighting has a rank-2 information block and is
-    kept finite by the Levenberg-Marquardt damping alone -- as in GTSAM, until its linear solver throws."""
+    kept finite by the Levenberg-Marquardt damping alone -- as in GTSAM, until its linear solver throws.  A
+    PriorFactorPoint3 on such a landmark makes it determinate (and, with a PriorFactorPose3, fixes the scale of a graph of
+    monocular factors only)."""
 
     def __init__(self, measured, model: _NoiseModel, poseKey: int, pointKey: int, K: Cal3_S2,
                  body_P_sensor: Optional[Pose3] = None):
@@ -728,7 +730,17 @@ class PriorFactorVector(_PriorFactor):
 
 
 class PriorFactorPoint3(PriorFactorVector):
-    pass
+    """gtsam.PriorFactorPoint3(key, prior, model): error 0.5 |(p - prior) / sigma|^2 under a 3-dimensional Diagonal /
+    Isotropic / Unit model.  On a landmark that stereo or monocular factors observe it is solved on the GPU with them
+    (include/vus_point_prior.h; several priors on one landmark are summed); on a landmark nothing observes it decouples
+    and stays on the host."""
+
+    def __init__(self, key, prior, model: _NoiseModel):
+        if np.asarray(prior, dtype=float).size != 3:
+            raise RuntimeError("PriorFactorPoint3 needs a 3-vector prior")
+        if model.dim() != 3:
+            raise RuntimeError("PriorFactorPoint3 needs a 3-dimensional noise model")
+        super().__init__(key, prior, model)
 
 
 class PriorFactorConstantBias(_PriorFactor):

@@ -323,11 +323,16 @@ def _pack_graph(graph, values, device=None):
     if imu_f or dvl_f or bias_f:
         nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f)
     aux = _AuxPriors()
+    pp_idx, pp_mean, pp_sig = [], [], []
     for f in prior_vec:
         k = f._keys[0]
         j = int(np.searchsorted(lm_keys, k))
-        if j < len(lm_keys) and lm_keys[j] == k:      # lm_keys ascend (unique)
-            raise NotImplementedError("a prior factor on a landmark observed by stereo factors is not supported yet")
+        if j < len(lm_keys) and lm_keys[j] == k:      # lm_keys ascend (unique): a prior on an observed landmark
+            if f._prior.size != 3:
+                raise RuntimeError(f"a prior factor on the landmark {_sym.key_string(k)} needs a 3-vector, not "
+                                   f"{f._prior.size} values")
+            pp_idx.append(j); pp_mean.append(f._prior); pp_sig.append(f._model.sigmas())
+            continue
         if not values.exists(k):
             raise RuntimeError(f"Attempting to at the key \"{_sym.key_string(k)}\", which does not exist in the Values.")
         aux.add(k, values.atVector(k), f._prior, f._model.sigmas())
@@ -339,7 +344,9 @@ def _pack_graph(graph, values, device=None):
                 K=calib.vector6() if calib is not None else np.array([1.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
                 mono=mono_flags, mono_K=mono["calib"].vector() if has_mono else None, mono_sigma=mono["sigma"],
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
-                prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between)
+                prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between,
+                point_priors=dict(idx=np.asarray(pp_idx, np.int32), mean=np.asarray(pp_mean, float).reshape(-1, 3),
+                                  sigmas=np.asarray(pp_sig, float).reshape(-1, 3)) if pp_idx else None)
 
 
 def _pack_between(pose_keys, between_f):
@@ -481,7 +488,7 @@ def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
 
 def _build_solver(pg, device="cuda:0"):
     from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
-                      BetweenFactors)
+                      BetweenFactors, PointPriors)
     nav = pg.get("nav")
     btw = pg.get("between")
     walk = bool(nav) and nav.get("per_keyframe", False)
@@ -495,14 +502,16 @@ def _build_solver(pg, device="cuda:0"):
                            mono_sigma=pg.get("mono_sigma"))
     bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
                         loss=list(btw["losses"]), device=device) if btw else None
+    pp = pg.get("point_priors")
+    pf = PointPriors(pp["idx"], pp["mean"], pp["sigmas"], len(pg["lm_keys"]), device=device) if pp else None
     if walk:
         nf = NavBiasFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], bbetween=nav["bbetween"],
                             bprior=nav["bprior"], device=device)
-        return prob, NavBiasBASolver(prob, nf, bf)
+        return prob, NavBiasBASolver(prob, nf, bf, pf)
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
-        return prob, NavBASolver(prob, nf, bf)
-    return prob, StereoBASolver(prob, bf)
+        return prob, NavBASolver(prob, nf, bf, pf)
+    return prob, StereoBASolver(prob, bf, pf)
 
 
 def graph_error(graph, values) -> float:
@@ -512,7 +521,8 @@ def graph_error(graph, values) -> float:
     prob, sv = _build_solver(pg)
     dev = prob.device
     poses = torch.from_numpy(pg["poses"]).to(dev)
-    e = sv.error(poses, torch.from_numpy(pg["points"]).to(dev)) + sv.between_error(poses)
+    points = torch.from_numpy(pg["points"]).to(dev)
+    e = sv.error(poses, points) + sv.between_error(poses) + sv.point_prior_error(points)
     if pg.get("nav"):
         e += sv.nav_error(poses, torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev))
     return e + pg["aux"].error()
