@@ -11,6 +11,7 @@ import ctypes
 import math
 import time
 from ctypes import c_double, c_int, c_void_p
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -78,6 +79,14 @@ def sensor_flat12(body_P_sensor):
     raise ValueError(f"body_P_sensor: a 12-vector, a 4 x 4 matrix or a Pose3 is expected, not an array of shape {a.shape}")
 
 
+def _upload(a, device, dtype, shape=None):
+    """A host array (numpy, list or tensor) as a contiguous device tensor of `dtype`, reshaped to `shape` if given."""
+    if isinstance(a, np.ndarray):
+        a = np.ascontiguousarray(a)             # torch refuses negative strides
+    t = torch.as_tensor(a).to(device=device, dtype=dtype)
+    return (t if shape is None else t.reshape(shape)).contiguous()
+
+
 class _CMono(ctypes.Structure):
     _fields_ = [("is_mono", c_void_p), ("K", c_double * 5), ("inv_sigma", c_double)]
 
@@ -143,7 +152,7 @@ class BetweenFactors:
         self.losses = [robust_loss(x) for x in loss] if isinstance(loss, list) else [robust_loss(loss)] * n
         self.host = dict(i=pi, j=pj, meas=meas, sigmas=sig, losses=self.losses)
         dev = torch.device(device)
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        t = lambda a, dt: _upload(a, dev, dt)
         ps = self.pose_stride
         self.node1, self.node2 = t(ps * pi, torch.int32), t(ps * pj, torch.int32)
         self.meas, self.w = t(meas, torch.float64), t(1.0 / sig, torch.float64)
@@ -198,7 +207,7 @@ class PointPriors:
         self.n, self.n_points, self.n_rows = n, int(n_points), len(row_point)
         self.host = dict(idx=idx[order], mean=mean[order], sigmas=sig[order], row_point=row_point, row_ptr=row_ptr)
         dev = torch.device(device)
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        t = lambda a, dt: _upload(a, dev, dt)
         self.row_point, self.row_ptr = t(row_point, torch.int32), t(row_ptr, torch.int32)
         self.mean, self.w = t(mean[order], torch.float64), t(1.0 / sig[order], torch.float64)
         p = (lambda x: _lib.ptr(x)) if n else (lambda x: None)
@@ -483,11 +492,16 @@ class BAMarginals:
         return 0.5 * (C + C.T)
 
 
+# One optional factor family of a solver: its stages over the LM state tuple (`assemble` takes lambda; a no-op where the
+# family has no such stage) and `scal`, the view of its 4-double slot of the trial record.
+_Term = namedtuple("_Term", "error linearize assemble eval_step scal")
+
+
 class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
 
     def __init__(self, problem: StereoBAProblem, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None):
+                 point_priors: Optional[PointPriors] = None, inertial=()):
         self.P = problem
         dev, nP, nL, nO, B = problem.device, problem.n_poses, problem.n_points, problem.n_obs, problem.band
         nN = problem.n_nodes                       # camera-side nodes (= poses unless velocity nodes are interleaved)
@@ -505,21 +519,40 @@ class StereoBASolver:
         self.new_poses = torch.empty((nP, 12), **f64)
         self.new_points = torch.empty((nL, 3), **f64)
         self.work = torch.empty((2 * (nL + 1) + 8,), **f64)
-        # one 40-byte record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised
-        # error at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word; with between
-        # factors [5..7] their three errors in the same order, [8] spare; with landmark priors [9..11] theirs
         self.Q = point_priors if point_priors is not None and point_priors.n else None      # no factors: no hooks
-        self._trial = torch.zeros((12 if self.Q is not None else 5 if between is None else 9,), **f64)
-        self.scal = self._trial[:4]
-        self.status = self._trial[4:].view(torch.int32)[:1]
         self.B = between
+        # The optional factor families present, as (name of the slot view, error, linearize, assemble, eval_step), in the
+        # canonical order between, landmark priors, inertial (`inertial`: the stages an inertial subclass passes).  Every
+        # stage runs the stereo step first and then the terms in this order, which is what keeps:
+        #   - linearize() before the landmark priors' linearize, which adds into V and gl; both before schur() and
+        #     before _check_points (a prior can make a landmark determinate)
+        #   - between_assemble() after schur() and before the inertial assemble, which copies gs into its right-hand side
+        #   - eval_step() before every other eval_step: they read new_poses / new_points
+        terms = []
+        if between is not None:
+            terms.append(("btw_scal", lambda s: self.between_error(s[0]), lambda s: self.between_linearize(s[0]),
+                          lambda lam: self.between_assemble(), lambda s: self.between_eval_step(s[0])))
+        if self.Q is not None:
+            terms.append(("pp_scal", lambda s: self.point_prior_error(s[-1]), lambda s: self.point_prior_linearize(s[-1]),
+                          lambda lam: None, lambda s: self.point_prior_eval_step(s[-1])))
+        terms += inertial
+        # one record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised error
+        # at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word, then one slot of 4 per
+        # term in list order: its three errors in the same order and a spare
+        self._trial = torch.zeros((5 + 4 * len(terms),), **f64)
+        self.scal = self._trial[:4]
+        self.status = self._trial[4:5].view(torch.int32)[:1]
+        self._terms = []
+        for i, (name, *stages) in enumerate(terms):
+            slot = self._trial[5 + 4 * i:9 + 4 * i]
+            setattr(self, name, slot)
+            self._terms.append(_Term(*stages, slot))
         if between is not None:
             if between.pose_stride != problem.pose_stride or between.n_poses != nP:
                 raise ValueError("BetweenFactors built for another problem (pose_stride / n_poses differ)")
             if between.span * problem.pose_stride > B:
                 raise ValueError(f"a between factor spans {between.span} poses, more than the problem's band of {B} nodes: "
                                  "build the StereoBAProblem with between_span=BetweenFactors.span")
-            self.btw_scal = self._trial[5:8]
             self.btw_lin = torch.empty((between.n, 120), **f64)
             self.btw_err = torch.empty((1,), **f64)
             self.btw_work = torch.empty((int(_lib.load().vus_between_work_doubles(between.addr())),), **f64)
@@ -527,7 +560,6 @@ class StereoBASolver:
         if self.Q is not None:
             if self.Q.n_points != nL:
                 raise ValueError(f"PointPriors built for {self.Q.n_points} landmarks, the problem has {nL}")
-            self.pp_scal = self._trial[9:12]
             self.pp_err = torch.empty((1,), **f64)
             self.pp_work = torch.empty((int(_lib.load().vus_point_prior_work_doubles(self.Q.addr())),), **f64)
             _lib.call("vus_point_prior_check", self.Q.addr(), _lib.current_stream_ptr())
@@ -682,12 +714,10 @@ class StereoBASolver:
                       _lib.current_stream_ptr())
 
     def _trial_errors(self, rec):
-        """[linearise error, linearised error at the step, new error] of the stereo factors, priors, between factors and
-        landmark priors from one trial record"""
-        if self.B is None and self.Q is None:
-            return [float(x) for x in rec[:3]]
-        return [float(rec[k]) + (float(rec[5 + k]) if self.B is not None else 0.0) +
-                (float(rec[9 + k]) if self.Q is not None else 0.0) for k in range(3)]
+        """[linearise error, linearised error at the step, new error] from one trial record: the stereo factors' and pose
+        priors', plus every term's in list order"""
+        v = rec.tolist()
+        return [sum((v[slot + k] for slot in range(5, len(v), 4)), v[k]) for k in range(3)]
 
     # -- marginal covariances (gtsam.Marginals) ---------------------------------------------------------------------
     def _check_points(self):
@@ -769,12 +799,20 @@ class StereoBASolver:
         point and no damping: S at lambda = 0, its one-sided factor, the selected inversion of the band and the landmark
         covariances.  Raises IndeterminantSystem when the information matrix is not positive definite.  Reuses the
         solver's workspace; a later optimize() is unaffected."""
-        values = (poses.to(torch.float64).contiguous(), points.to(torch.float64).contiguous())
+        values, Sigma, nodes, pc = self._marginal_parts((poses, points), points_cov)
+        return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, nodes), pc)
+
+    def _marginal_parts(self, values, points_cov, correct=None):
+        """What every marginals() starts from: (`values` as contiguous float64, the band Sigma of the camera-side
+        covariance, the pose nodes, the landmark covariances or None).  `correct(Sigma)`, if given, amends the band in
+        place before the landmark covariances are formed from it."""
+        values = tuple(x.to(torch.float64).contiguous() for x in values)
         self._marginal_factor(values)
         Sigma = self._selinv()
+        if correct is not None:
+            correct(Sigma)
         nodes = torch.arange(self.P.n_poses, device=self.P.device) * self.P.pose_stride
-        pc = self._point_cov(Sigma) if points_cov else None
-        return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, nodes), pc)
+        return values, Sigma, nodes, self._point_cov(Sigma) if points_cov else None
 
     def _exact_covariance_columns(self, values, nodes, U=None, Snb=None):
         """The joint covariance of `nodes` from exact columns of S^-1: vus_ba_band_solve_multi with at most 8 unit
@@ -803,41 +841,46 @@ class StereoBASolver:
         return 0.5 * (J + J.T)
 
     def _linearize_all(self, values):
-        poses, points = values
-        self.linearize(poses, points)
-        self.point_prior_linearize(points)          # before the check: a prior can make a landmark determinate
+        self._lm_linearize(values)
         self._check_points()
-        self.between_linearize(poses)
 
     def _assemble_zero(self):
-        self.schur(0.0)
-        self.between_assemble()
+        self._assemble(0.0)
 
     # -- Levenberg-Marquardt ----------------------------------------------------------------------
-    # The stages of one LM iteration over a tuple of state tensors; the inertial solvers extend them.
+    # The stages of one LM iteration over a tuple of state tensors (poses first, points last): the stereo step, then
+    # each term of self._terms (the order and what depends on it: __init__).
     _NEW_STATE = ("new_poses", "new_points")      # the buffers a trial writes, one per state tensor
 
     def _lm_error(self, state) -> float:
-        return self.error(*state) + self.between_error(state[0]) + self.point_prior_error(state[1])
+        return sum((term.error(state) for term in self._terms), self.error(state[0], state[-1]))
 
     def _lm_linearize(self, state):
-        self.linearize(*state)
-        self.point_prior_linearize(state[1])
-        self.between_linearize(state[0])
+        self.linearize(state[0], state[-1])
+        for term in self._terms:
+            term.linearize(state)
+
+    def _assemble(self, lam):
+        self.schur(lam)
+        for term in self._terms:
+            term.assemble(lam)
+
+    def _solve(self, lam):
+        self.band_solve()
 
     def _lm_solve(self, lam):
-        self.schur(lam)
-        self.between_assemble()
-        self.band_solve()
+        self._assemble(lam)
+        self._solve(lam)
         self.backsub()
 
     def _lm_eval(self, state):
-        """Evaluate the trial step; (status, [linearised error at 0, at the step, new error]) from ONE blocking read."""
-        self.eval_step(*state)
-        self.between_eval_step(state[0])
-        self.point_prior_eval_step(state[1])
+        """Evaluate the trial step; (status, [linearised error at 0, at the step, new error]) of the whole graph, every
+        term's scalars included, from ONE blocking read of the trial record."""
+        self.eval_step(state[0], state[-1])
+        for term in self._terms:
+            term.eval_step(state)
         rec = self._trial.cpu()
-        return int(rec[4:].view(torch.int32)[0]), self._trial_errors(rec)
+        return int(rec[4:5].view(torch.int32)[0]), self._trial_errors(rec)
 
     def _lm_swap(self, state):
         """Accept the trial: its buffers become the state, the old state tensors the next trial's buffers."""
@@ -954,13 +997,13 @@ class _InertialFactors:
         self.dev = torch.device(device)
         z = []
         self.imu_i, self.imu_j = self._pair(imu, self._IMU_REFUSAL)
-        self.imu_pim = self._t(imu[2] if imu else z, torch.float64, (-1, 148))
-        self.imu_W = self._t(imu[3] if imu else z, torch.float64, (-1, 81))
-        self.dvl_pose = self._t(dvl[0] if dvl else z, torch.int32, (-1,))
-        self.dvl_meas = self._t(dvl[1] if dvl else z, torch.float64, (-1, 3))
+        self.imu_pim = _upload(imu[2] if imu else z, self.dev, torch.float64, (-1, 148))
+        self.imu_W = _upload(imu[3] if imu else z, self.dev, torch.float64, (-1, 81))
+        self.dvl_pose = _upload(dvl[0] if dvl else z, self.dev, torch.int32, (-1,))
+        self.dvl_meas = _upload(dvl[1] if dvl else z, self.dev, torch.float64, (-1, 3))
         self.dvl_w = self._inv(dvl[2] if dvl else z, (-1,))
-        self.vp_idx = self._t(vprior[0] if vprior else z, torch.int32, (-1,))
-        self.vp_v = self._t(vprior[1] if vprior else z, torch.float64, (-1, 3))
+        self.vp_idx = _upload(vprior[0] if vprior else z, self.dev, torch.int32, (-1,))
+        self.vp_v = _upload(vprior[1] if vprior else z, self.dev, torch.float64, (-1, 3))
         self.vp_w = self._inv(vprior[2] if vprior else z, (-1, 3))
         self._c_prefix = (self.imu_i.numel(), self._pp(self.imu_i), self._pp(self.imu_j), self._pp(self.imu_pim),
                           self._pp(self.imu_W), (c_double * 3)(*[float(g) for g in gravity]), self.dvl_pose.numel(),
@@ -968,17 +1011,14 @@ class _InertialFactors:
                           self._pp(self.vp_idx), self._pp(self.vp_v), self._pp(self.vp_w))
         self.n_factors = self.imu_i.numel() + self.dvl_pose.numel() + self.vp_idx.numel()
 
-    def _t(self, x, dt, shape):
-        return torch.as_tensor(x).to(device=self.dev, dtype=dt).reshape(shape).contiguous()
-
     def _inv(self, sigma, shape):
         """1/sigma on the device: the whitening weight of a diagonal noise model"""
-        return (1.0 / self._t(sigma, torch.float64, shape)).contiguous()
+        return (1.0 / _upload(sigma, self.dev, torch.float64, shape)).contiguous()
 
     def _pair(self, fac, refusal):
         """(i, j) index tensors of a factor that must join consecutive variables (j = i + 1)"""
-        i = self._t(fac[0] if fac else [], torch.int32, (-1,))
-        j = self._t(fac[1] if fac else [], torch.int32, (-1,))
+        i = _upload(fac[0] if fac else [], self.dev, torch.int32, (-1,))
+        j = _upload(fac[1] if fac else [], self.dev, torch.int32, (-1,))
         if i.numel() and bool((j - i != 1).any()):
             raise NotImplementedError(refusal)
         return i, j
@@ -1011,10 +1051,10 @@ class NavBiasFactors(_InertialFactors):
         z = []
         self.bb_i, self.bb_j = self._pair(bbetween, "BetweenFactorConstantBias between non-consecutive biases is not "
                                                     "supported")
-        self.bb_meas = self._t(bbetween[2] if bbetween else z, torch.float64, (-1, 6))
+        self.bb_meas = _upload(bbetween[2] if bbetween else z, self.dev, torch.float64, (-1, 6))
         self.bb_w = self._inv(bbetween[3] if bbetween else z, (-1, 6))
-        self.bp_idx = self._t(bprior[0] if bprior else z, torch.int32, (-1,))
-        self.bp_mean = self._t(bprior[1] if bprior else z, torch.float64, (-1, 6))
+        self.bp_idx = _upload(bprior[0] if bprior else z, self.dev, torch.int32, (-1,))
+        self.bp_mean = _upload(bprior[1] if bprior else z, self.dev, torch.float64, (-1, 6))
         self.bp_w = self._inv(bprior[2] if bprior else z, (-1, 6))
         pp = self._pp
         self.c = _CNavBias(*self._c_prefix, self.bb_i.numel(), pp(self.bb_i), pp(self.bb_j), pp(self.bb_meas),
@@ -1039,7 +1079,9 @@ class _InertialBASolver(StereoBASolver):
     def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None):
         if problem.pose_stride != self.POSE_STRIDE:
             raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
-        super().__init__(problem, between, point_priors)
+        nav3 = lambda stage: lambda s: stage(*s[:3])          # state = (poses, vels, bias, points)
+        super().__init__(problem, between, point_priors, inertial=[
+            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav3(self.nav_eval_step))])
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
         f64 = dict(dtype=torch.float64, device=dev)
@@ -1047,7 +1089,6 @@ class _InertialBASolver(StereoBASolver):
         self.gnav = torch.empty((nN, 6), **f64)
         self.new_vels = torch.empty((nP, 3), **f64)
         self.new_bias = torch.empty((6,) if bias_rows is None else (bias_rows, 6), **f64)
-        self.nav_scal = torch.zeros((4,), **f64)
         self.nav_work = torch.empty((int(getattr(_lib.load(), self._ABI + "_work_doubles")(nav.addr())),), **f64)
 
     def nav_error(self, poses, vels, bias) -> float:
@@ -1055,48 +1096,6 @@ class _InertialBASolver(StereoBASolver):
         _lib.call(self._ABI + "_error", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(bias), p(self.nav_scal),
                   p(self.nav_work), _lib.current_stream_ptr())
         return float(self.nav_scal[0].item())
-
-    def _linearize_all(self, values):
-        poses, vels, bias, points = values
-        self.linearize(poses, points)
-        self.point_prior_linearize(points)
-        self._check_points()
-        self.nav_linearize(poses, vels, bias)
-        self.between_linearize(poses)
-
-    def _assemble_zero(self):
-        self.schur(0.0)
-        self.between_assemble()             # before nav_assemble: vus_nav_assemble copies -gs into its right-hand side
-        self.nav_assemble(0.0)
-
-    def _lm_error(self, state):
-        poses, vels, bias, points = state
-        return (self.error(poses, points) + self.nav_error(poses, vels, bias) + self.between_error(poses) +
-                self.point_prior_error(points))
-
-    def _lm_linearize(self, state):
-        poses, vels, bias, points = state
-        self.linearize(poses, points)
-        self.point_prior_linearize(points)
-        self.nav_linearize(poses, vels, bias)
-        self.between_linearize(poses)
-
-    def _lm_solve(self, lam):
-        self.schur(lam)
-        self.between_assemble()
-        self.nav_assemble(lam)
-        self.nav_solve(lam)
-        self.backsub()
-
-    def _lm_eval(self, state):
-        poses, vels, bias, points = state
-        self.eval_step(poses, points)
-        self.nav_eval_step(poses, vels, bias)
-        self.between_eval_step(poses)
-        self.point_prior_eval_step(points)
-        rec, nsc = self._trial.cpu(), self.nav_scal.cpu()         # stereo (+ between) scalars + status, then the inertial scalars
-        sc = self._trial_errors(rec)
-        return int(rec[4:].view(torch.int32)[0]), [sc[k] + float(nsc[k]) for k in range(3)]
 
     def optimize(self, poses, vels, bias, points, params: Optional[LMParams] = None):
         """Returns (poses, vels, bias, points, LMReport); inputs untouched."""
@@ -1148,6 +1147,8 @@ class NavBASolver(_InertialBASolver):
         _lib.call("vus_nav_border_solve", self.P.n_nodes, p(self.rhs), p(self.Scb), p(self.Sbb), p(self.gb), float(lam),
                   p(self.dp), p(self.db), st)
 
+    _solve = nav_solve
+
     def nav_eval_step(self, poses, vels, bias):
         p = _lib.ptr
         _lib.call("vus_nav_eval_step", self.N.addr(), self.P.n_poses, p(poses), p(vels), p(bias), p(self.dp), p(self.db),
@@ -1163,21 +1164,18 @@ class NavBASolver(_InertialBASolver):
         """StereoBASolver.marginals for the whole graph: the camera-side band of A^-1 (poses and velocity nodes, one-sided
         7-right-hand-side solve at lambda = 0), then the shared-bias border (vus_nav_border_covariance), then the landmark
         covariances from the corrected band."""
-        c = lambda x: x.to(torch.float64).contiguous()
-        values = (c(poses), c(vels), c(bias), c(points))
-        self._marginal_factor(values)
-        Sigma = self._selinv()
         nN, nP = self.P.n_nodes, self.P.n_poses
-        p, st = _lib.ptr, _lib.current_stream_ptr()
+        p = _lib.ptr
         f64 = dict(dtype=torch.float64, device=self.P.device)
         Snb, Sbb, ok = torch.empty((nN, 36), **f64), torch.empty((36,), **f64), torch.empty((1,), **f64)
-        _lib.call("vus_nav_border_covariance", nN, self.P.band, p(self.rhs), p(self.Scb), p(self.Sbb), p(Sigma), p(Snb),
-                  p(Sbb), p(ok), st)
-        if float(ok.item()) != 1.0:
-            raise IndeterminantSystem("bias", 0)
+
+        def border(Sigma):
+            _lib.call("vus_nav_border_covariance", nN, self.P.band, p(self.rhs), p(self.Scb), p(self.Sbb), p(Sigma), p(Snb),
+                      p(Sbb), p(ok), _lib.current_stream_ptr())
+            if float(ok.item()) != 1.0:
+                raise IndeterminantSystem("bias", 0)
+        values, Sigma, pose_nodes, pc = self._marginal_parts((poses, vels, bias, points), points_cov, border)
         U = self.rhs[1:7].clone()
-        pose_nodes = torch.arange(nP, device=self.P.device) * 2
-        pc = self._point_cov(Sigma) if points_cov else None
         vel = Sigma[pose_nodes + 1, 0].reshape(nP, 6, 6)[:, :3, :3]
         return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, pose_nodes), pc, U=U, vel_cov=vel,
                            bias_cov=Sbb.reshape(6, 6), node_bias_cov=Snb.reshape(nN, 6, 6))
@@ -1205,7 +1203,7 @@ class NavBiasBASolver(_InertialBASolver):
                   p(self.Sband), p(self.gs), _lib.current_stream_ptr())
 
     def nav_solve(self, lam):
-        self.band_solve()
+        self.band_solve()           # no border: the same as the stereo solver's _solve
 
     def nav_eval_step(self, poses, vels, biases):
         p = _lib.ptr
@@ -1218,16 +1216,11 @@ class NavBiasBASolver(_InertialBASolver):
         lambda = 0 and its selected inversion -- no border step, every bias is a band node.  The BAMarginals carries
         vel_cov [n, 3, 3] and biases_cov [n, 6, 6] (B(i) is node 3i + 2, for joint()).  Raises IndeterminantSystem("bias",
         i) for a bias B(i) with neither a prior nor a between-factor."""
-        c = lambda x: x.to(torch.float64).contiguous()
-        values = (c(poses), c(vels), c(biases), c(points))
         free = self.N.unconstrained_biases(self.P.n_poses)
         if len(free):
             raise IndeterminantSystem("bias", int(free[0]))
-        self._marginal_factor(values)
-        Sigma = self._selinv()
+        values, Sigma, nodes, pc = self._marginal_parts((poses, vels, biases, points), points_cov)
         nP = self.P.n_poses
-        nodes = torch.arange(nP, device=self.P.device) * 3
-        pc = self._point_cov(Sigma) if points_cov else None
         return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, nodes), pc,
                            vel_cov=Sigma[nodes + 1, 0].reshape(nP, 6, 6)[:, :3, :3],
                            biases_cov=Sigma[nodes + 2, 0].reshape(nP, 6, 6))
