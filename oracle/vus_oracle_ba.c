@@ -72,51 +72,26 @@ static void so3_expmap(const double* w, double* R) {
     }
 }
 
-/* gtsam SO3::Logmap (the 4.0/4.1 form; near pi uses the simple axis formulas). */
-static void so3_logmap(const double* R, double* w) {
-  double tr = R[0] + R[4] + R[8];
-  if (tr + 1.0 < 1e-10) {
-    if (fabs(R[8] + 1.0) > 1e-5) {
-      double k = M_PI / sqrt(2.0 + 2.0 * R[8]);
-      w[0] = k * R[2]; w[1] = k * R[5]; w[2] = k * (1.0 + R[8]);
-    } else if (fabs(R[4] + 1.0) > 1e-5) {
-      double k = M_PI / sqrt(2.0 + 2.0 * R[4]);
-      w[0] = k * R[1]; w[1] = k * (1.0 + R[4]); w[2] = k * R[7];
-    } else {
-      double k = M_PI / sqrt(2.0 + 2.0 * R[0]);
-      w[0] = k * (1.0 + R[0]); w[1] = k * R[3]; w[2] = k * R[6];
-    }
-    return;
-  }
-  double mag;
-  double tr3 = tr - 3.0;
-  if (tr3 < -1e-7) {
-    double th = acos((tr - 1.0) / 2.0);
-    mag = th / (2.0 * sin(th));
-  } else {
-    mag = 0.5 - tr3 / 12.0;
-  }
-  w[0] = mag * (R[7] - R[5]);
-  w[1] = mag * (R[2] - R[6]);
-  w[2] = mag * (R[3] - R[1]);
-}
+/* SO3::Logmap: the one copy of vus_oracle_nav.c (accurate up to pi). */
+void vus_so3_logmap_cpu(const double* R, double* w);
+static void so3_logmap(const double* R, double* w) { vus_so3_logmap_cpu(R, w); }
 
-/* Pose3::Expmap(xi = (w, v)) -> (R, t). */
+/* Pose3::Expmap(xi = (w, v)) -> (R, t), t = V v = v + b (w x v) + c (w x (w x v)) with b = (1 - cos th) / th^2 and
+ * c = (th - sin th) / th^3: a few eps |v| at every angle (the cancellation in c is scaled by th^2 |v|). */
 static void se3_expmap(const double* xi, double* R, double* t) {
   const double* w = xi;
   const double* v = xi + 3;
   so3_expmap(w, R);
   double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double b = 0.5, c = 1.0 / 6.0;
   if (th2 > 2.220446049250313e-16) {
-    double wv = w[0] * v[0] + w[1] * v[1] + w[2] * v[2];
-    double c[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
-    for (int r = 0; r < 3; ++r) {
-      double Rc = R[3 * r] * c[0] + R[3 * r + 1] * c[1] + R[3 * r + 2] * c[2];
-      t[r] = (c[r] - Rc + w[r] * wv) / th2;
-    }
-  } else {
-    t[0] = v[0]; t[1] = v[1]; t[2] = v[2];
+    double th = sqrt(th2), sh = sin(0.5 * th);
+    b = 2.0 * sh * sh / th2;
+    c = (th - sin(th)) / (th2 * th);
   }
+  double wv[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
+  double wwv[3] = {w[1] * wv[2] - w[2] * wv[1], w[2] * wv[0] - w[0] * wv[2], w[0] * wv[1] - w[1] * wv[0]};
+  for (int r = 0; r < 3; ++r) t[r] = v[r] + b * wv[r] + c * wwv[r];
 }
 
 /* Pose3::Logmap((R, t)) -> xi. */
@@ -125,8 +100,10 @@ static void se3_logmap(const double* R, const double* t, double* xi) {
   so3_logmap(R, w);
   double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   xi[0] = w[0]; xi[1] = w[1]; xi[2] = w[2];
-  if (th < 1e-10) {
-    xi[3] = t[0]; xi[4] = t[1]; xi[5] = t[2];
+  if (th < 1e-10) { /* V^-1 t = t - w x t / 2 + O(th^2 |t|) */
+    xi[3] = t[0] - 0.5 * (w[1] * t[2] - w[2] * t[1]);
+    xi[4] = t[1] - 0.5 * (w[2] * t[0] - w[0] * t[2]);
+    xi[5] = t[2] - 0.5 * (w[0] * t[1] - w[1] * t[0]);
     return;
   }
   double k[3] = {w[0] / th, w[1] / th, w[2] / th};

@@ -59,12 +59,22 @@ void vus_so3_expmap_cpu(const double* w, double* R) {
   for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + s * W[i] + c * WW[i];
 }
 
+/* Log of SO(3).  Below tr = -0.4 (angles above 134 degrees) the angle is atan2(|v| / 2, (tr - 1) / 2), v the antisymmetric
+ * part, and the axis the column of the largest diagonal entry of (R + R^T) / 2 - cos th I, signed by v (acos and the
+ * division by sin th lose accuracy like eps / sin^2 th towards pi); above it gtsam's SO3::Logmap.  The one Log of the
+ * oracle. */
 void vus_so3_logmap_cpu(const double* R, double* w) {
   double tr = R[0] + R[4] + R[8];
-  if (tr + 1.0 < 1e-10) {
-    if (fabs(R[8] + 1.0) > 1e-5) { double k = M_PI / sqrt(2.0 + 2.0 * R[8]); w[0] = k * R[2]; w[1] = k * R[5]; w[2] = k * (1.0 + R[8]); }
-    else if (fabs(R[4] + 1.0) > 1e-5) { double k = M_PI / sqrt(2.0 + 2.0 * R[4]); w[0] = k * R[1]; w[1] = k * (1.0 + R[4]); w[2] = k * R[7]; }
-    else { double k = M_PI / sqrt(2.0 + 2.0 * R[0]); w[0] = k * (1.0 + R[0]); w[1] = k * R[3]; w[2] = k * R[6]; }
+  if (tr < -0.4) {
+    double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    double c = 0.5 * (tr - 1.0);
+    double th = atan2(0.5 * sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), c);
+    int i = R[0] >= R[4] ? (R[0] >= R[8] ? 0 : 2) : (R[4] >= R[8] ? 1 : 2);
+    double a[3];
+    for (int j = 0; j < 3; ++j) a[j] = 0.5 * (R[3 * j + i] + R[3 * i + j]) - (j == i ? c : 0.0);
+    double k = th / sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (v[0] * a[0] + v[1] * a[1] + v[2] * a[2] < 0.0) k = -k;
+    w[0] = k * a[0]; w[1] = k * a[1]; w[2] = k * a[2];
     return;
   }
   double mag, tr3 = tr - 3.0;
@@ -81,7 +91,10 @@ void vus_so3_jr_cpu(const double* w, double* J) {
   mat3_mul(W, W, WW);
   double a, b;
   if (th2 < 1e-10) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-  else { double th = sqrt(th2); a = (1.0 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+  else { /* 1 - cos th as 2 sin^2(th / 2): no cancellation */
+    double th = sqrt(th2), sh = sin(0.5 * th);
+    a = 2.0 * sh * sh / th2; b = (th - sin(th)) / (th2 * th);
+  }
   for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * W[i] + b * WW[i];
 }
 void vus_so3_jr_inv_cpu(const double* w, double* J) {
@@ -91,7 +104,10 @@ void vus_so3_jr_inv_cpu(const double* w, double* J) {
   mat3_mul(W, W, WW);
   double b;
   if (th2 < 1e-10) b = 1.0 / 12.0 + th2 / 720.0;
-  else { double th = sqrt(th2); b = 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th)); }
+  else { /* (1 + cos th) / sin th as 1 / tan(th / 2): accurate up to pi */
+    double th = sqrt(th2);
+    b = 1.0 / th2 - 1.0 / (2.0 * th * tan(0.5 * th));
+  }
   for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) + 0.5 * W[i] + b * WW[i];
 }
 

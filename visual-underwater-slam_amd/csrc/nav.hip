@@ -20,14 +20,13 @@
 #include <cstring>
 #include <vector>
 #include "vus_common.h"
+#include "se3_device.h"   // so3_expmap / so3_logmap: one copy for every pose kernel
 
 namespace {
 
 // ---- device math: SO(3) helpers and the ImuFactor residual / Jacobian --------------------------------------------------
 constexpr int PIM_DT = 0, PIM_DR = 1, PIM_DP = 10, PIM_DV = 13, PIM_DR_DBG = 16, PIM_DP_DBA = 25, PIM_DP_DBG = 34,
               PIM_DV_DBA = 43, PIM_DV_DBG = 52, PIM_BIAS = 61, PIM_N = 148;
-constexpr double kEps = 2.220446049250313e-16;
-constexpr double kPi = 3.14159265358979323846;
 
 __device__ __forceinline__ void skew(const double* w, double* S) {
   S[0] = 0; S[1] = -w[2]; S[2] = w[1]; S[3] = w[2]; S[4] = 0; S[5] = -w[0]; S[6] = -w[1]; S[7] = w[0]; S[8] = 0;
@@ -53,41 +52,16 @@ __device__ __forceinline__ void mtv(const double* A, const double* v, double* o)
   for (int r = 0; r < 3; ++r) o[r] = A[r] * v[0] + A[3 + r] * v[1] + A[6 + r] * v[2];
 }
 
-__device__ void so3_exp(const double* w, double* R) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  double W[9], WW[9];
-  skew(w, W);
-  if (th2 <= kEps) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = W[i] + (i % 4 == 0 ? 1.0 : 0.0);
-    return;
-  }
-  const double th = sqrt(th2), s = sin(th) / th, sh = sin(0.5 * th), c = 2.0 * sh * sh / th2;
-  mm(W, W, WW);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + s * W[i] + c * WW[i];
-}
-__device__ void so3_log(const double* R, double* w) {
-  const double tr = R[0] + R[4] + R[8];
-  if (tr + 1.0 < 1e-10) {
-    if (fabs(R[8] + 1.0) > 1e-5) { double k = kPi / sqrt(2.0 + 2.0 * R[8]); w[0] = k * R[2]; w[1] = k * R[5]; w[2] = k * (1.0 + R[8]); }
-    else if (fabs(R[4] + 1.0) > 1e-5) { double k = kPi / sqrt(2.0 + 2.0 * R[4]); w[0] = k * R[1]; w[1] = k * (1.0 + R[4]); w[2] = k * R[7]; }
-    else { double k = kPi / sqrt(2.0 + 2.0 * R[0]); w[0] = k * (1.0 + R[0]); w[1] = k * R[3]; w[2] = k * R[6]; }
-    return;
-  }
-  double mag;
-  const double tr3 = tr - 3.0;
-  if (tr3 < -1e-7) { const double th = acos((tr - 1.0) / 2.0); mag = th / (2.0 * sin(th)); }
-  else mag = 0.5 - tr3 / 12.0;
-  w[0] = mag * (R[7] - R[5]); w[1] = mag * (R[2] - R[6]); w[2] = mag * (R[3] - R[1]);
-}
 __device__ void so3_jr(const double* w, double* J) {
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   double W[9], WW[9];
   skew(w, W); mm(W, W, WW);
   double a, b;
   if (th2 < 1e-10) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-  else { const double th = sqrt(th2); a = (1.0 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+  else {   // 1 - cos th as 2 sin^2(th / 2): its cancellation cost eps / th in a W (2e-11 at th = 1e-5)
+    const double th = sqrt(th2), sh = sin(0.5 * th);
+    a = 2.0 * sh * sh / th2; b = (th - sin(th)) / (th2 * th);
+  }
 #pragma unroll
   for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * W[i] + b * WW[i];
 }
@@ -97,7 +71,10 @@ __device__ void so3_jr_inv(const double* w, double* J) {
   skew(w, W); mm(W, W, WW);
   double b;
   if (th2 < 1e-10) b = 1.0 / 12.0 + th2 / 720.0;
-  else { const double th = sqrt(th2); b = 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th)); }
+  else {   // (1 + cos th) / sin th as 1 / tan(th / 2): the quotient lost eps / sin th towards pi
+    const double th = sqrt(th2);
+    b = 1.0 / th2 - 1.0 / (2.0 * th * tan(0.5 * th));
+  }
 #pragma unroll
   for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) + 0.5 * W[i] + b * WW[i];
 }
@@ -112,7 +89,7 @@ __device__ void imu_factor(const double* Ti, const double* vi, const double* Tj,
   for (int k = 0; k < 3; ++k) { dba[k] = bias[k] - pim[PIM_BIAS + k]; dbg[k] = bias[3 + k] - pim[PIM_BIAS + 3 + k]; }
   double phi[3], Ephi[9], dRc[9], dPc[3], dVc[3], t3[3], t3b[3];
   mv(pim + PIM_DR_DBG, dbg, phi);
-  so3_exp(phi, Ephi);
+  so3_expmap(phi, Ephi);
   mm(pim + PIM_DR, Ephi, dRc);
   mv(pim + PIM_DP_DBA, dba, t3); mv(pim + PIM_DP_DBG, dbg, t3b);
 #pragma unroll
@@ -125,7 +102,7 @@ __device__ void imu_factor(const double* Ti, const double* vi, const double* Tj,
   double RjtRi[9], E[9], rR[3];
   mtm(Rj, Ri, RjtRi);
   mm(RjtRi, dRc, E);
-  so3_log(E, rR);
+  so3_logmap(E, rR);
   double RidP[3], RidV[3], dpw[3], dvw[3], rP[3], rV[3];
   mv(Ri, dPc, RidP); mv(Ri, dVc, RidV);
 #pragma unroll
@@ -849,7 +826,7 @@ inline void expmap_jr(const double* w, double* R, double* Jr) {
     b = 1.0 / 6.0 - th2 / 120.0;
   } else {
     const double th = std::sqrt(th2);
-    a = (1.0 - std::cos(th)) / th2;
+    a = s2;                                  // (1 - cos th) / th^2 without the cancellation
     b = (th - std::sin(th)) / (th2 * th);
   }
   for (int i = 0; i < 9; ++i) Jr[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * W[i] + b * W2[i];

@@ -1,4 +1,4 @@
-// se3_device.h -- device helpers shared by the pose kernels of ba.hip and between.hip: SE(3) in gtsam's Pose3 / Rot3
+// se3_device.h -- device helpers shared by the pose kernels of ba.hip, between.hip and nav.hip: SE(3) in gtsam's Pose3 / Rot3
 // conventions (tangent order (omega, v), retract T * Exp(xi), local Log(T^-1 T2)) and the robust-loss table of
 // include/vus_robust.h.  Internal linkage: every translation unit that includes it gets its own copy.
 #pragma once
@@ -8,7 +8,6 @@
 namespace {
 
 constexpr double kEps = 2.220446049250313e-16;
-constexpr double kPi = 3.14159265358979323846;
 
 // ---------------------------------------------------------------------------------------------
 // Lie-group helpers (gtsam Pose3 / Rot3 conventions; mirrored independently by the CPU oracle)
@@ -35,19 +34,25 @@ __device__ void so3_expmap(const double* w, double* R) {
     }
 }
 
+// Log of SO(3).  acos(cos th) and the division by sin th lose accuracy like eps / sin^2 th towards pi (3e-14 at 3.04 rad,
+// 1e-5 at pi - 1e-5), so below tr = -0.4 (angles above 134 degrees, sin^2 th < 1/2) the angle comes from
+// atan2(sin th, cos th) with sin th = |v| / 2, v the antisymmetric part, and the axis from the symmetric part
+// (R + R^T) / 2 = cos th I + (1 - cos th) a a^T: the column of its largest diagonal entry, signed by v.  Accurate to a few
+// eps up to pi itself (where the sign of the axis is arbitrary).  The branches for tr >= -0.4 are gtsam's SO3::Logmap
+// (4.0/4.1 form) unchanged.
 __device__ void so3_logmap(const double* R, double* w) {
   const double tr = R[0] + R[4] + R[8];
-  if (tr + 1.0 < 1e-10) {
-    if (fabs(R[8] + 1.0) > 1e-5) {
-      double k = kPi / sqrt(2.0 + 2.0 * R[8]);
-      w[0] = k * R[2]; w[1] = k * R[5]; w[2] = k * (1.0 + R[8]);
-    } else if (fabs(R[4] + 1.0) > 1e-5) {
-      double k = kPi / sqrt(2.0 + 2.0 * R[4]);
-      w[0] = k * R[1]; w[1] = k * (1.0 + R[4]); w[2] = k * R[7];
-    } else {
-      double k = kPi / sqrt(2.0 + 2.0 * R[0]);
-      w[0] = k * (1.0 + R[0]); w[1] = k * R[3]; w[2] = k * R[6];
-    }
+  if (tr < -0.4) {
+    const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    const double c = 0.5 * (tr - 1.0);
+    const double th = atan2(0.5 * sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), c);
+    const int i = R[0] >= R[4] ? (R[0] >= R[8] ? 0 : 2) : (R[4] >= R[8] ? 1 : 2);
+    double a[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) a[j] = 0.5 * (R[3 * j + i] + R[3 * i + j]) - (j == i ? c : 0.0);
+    double k = th / sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (v[0] * a[0] + v[1] * a[1] + v[2] * a[2] < 0.0) k = -k;
+    w[0] = k * a[0]; w[1] = k * a[1]; w[2] = k * a[2];
     return;
   }
   double mag;
@@ -63,24 +68,25 @@ __device__ void so3_logmap(const double* R, double* w) {
   w[2] = mag * (R[3] - R[1]);
 }
 
-// out = T * Exp(xi)
+// out = T * Exp(xi).  The translation of Exp is V v = v + b (w x v) + c (w x (w x v)), b = (1 - cos th) / th^2,
+// c = (th - sin th) / th^3: summed in this form its error is a few eps |v| at every angle (the cancellation in c is
+// scaled by th^2 |v|), where (I - R)(w x v) / th^2 loses eps |v| / th and the first-order Exp below kEps dropped b.
 __device__ void pose_retract(const double* T, const double* xi, double* out) {
   double Re[9], te[3];
   so3_expmap(xi, Re);
   const double* w = xi;
   const double* v = xi + 3;
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double b = 0.5, c = 1.0 / 6.0;
   if (th2 > kEps) {
-    double wv = w[0] * v[0] + w[1] * v[1] + w[2] * v[2];
-    double c[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double Rc = Re[3 * r] * c[0] + Re[3 * r + 1] * c[1] + Re[3 * r + 2] * c[2];
-      te[r] = (c[r] - Rc + w[r] * wv) / th2;
-    }
-  } else {
-    te[0] = v[0]; te[1] = v[1]; te[2] = v[2];
+    const double th = sqrt(th2), sh = sin(0.5 * th);
+    b = 2.0 * sh * sh / th2;
+    c = (th - sin(th)) / (th2 * th);
   }
+  const double wv[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
+  const double wwv[3] = {w[1] * wv[2] - w[2] * wv[1], w[2] * wv[0] - w[0] * wv[2], w[0] * wv[1] - w[1] * wv[0]};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) te[r] = v[r] + b * wv[r] + c * wwv[r];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
 #pragma unroll
@@ -103,8 +109,10 @@ __device__ void pose_local(const double* T, const double* T2, double* xi) {
   so3_logmap(R, w);
   const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   xi[0] = w[0]; xi[1] = w[1]; xi[2] = w[2];
-  if (th < 1e-10) {
-    xi[3] = t[0]; xi[4] = t[1]; xi[5] = t[2];
+  if (th < 1e-10) {   // V^-1 t = t - w x t / 2 + O(th^2 |t|)
+    xi[3] = t[0] - 0.5 * (w[1] * t[2] - w[2] * t[1]);
+    xi[4] = t[1] - 0.5 * (w[2] * t[0] - w[0] * t[2]);
+    xi[5] = t[2] - 0.5 * (w[0] * t[1] - w[1] * t[0]);
     return;
   }
   const double k[3] = {w[0] / th, w[1] / th, w[2] / th};

@@ -194,24 +194,28 @@ class Pose3:
         w, v = xi[:3], xi[3:]
         R = Rot3.Expmap(w)._R
         th2 = float(w @ w)
+        b, c = 0.5, 1.0 / 6.0                     # t = V v = v + b w x v + c w x (w x v), as csrc/se3_device.h sums it
         if th2 > np.finfo(float).eps:
-            c = np.cross(w, v)
-            t = (c - R @ c + w * float(w @ v)) / th2
-        else:
-            t = v.copy()
+            th = math.sqrt(th2)
+            b, c = 2.0 * math.sin(0.5 * th) ** 2 / th2, (th - math.sin(th)) / (th2 * th)
+        wv = np.cross(w, v)
+        t = v + b * wv + c * np.cross(w, wv)
         return Pose3(Rot3(R), t)
 
     @staticmethod
     def Logmap(T):
         R, t = T._R, T._t
         tr = float(np.trace(R))
-        if tr + 1.0 < 1e-10:                      # rotation by pi
-            if abs(R[2, 2] + 1.0) > 1e-5:
-                w = math.pi / math.sqrt(2.0 + 2.0 * R[2, 2]) * np.array([R[0, 2], R[1, 2], 1.0 + R[2, 2]])
-            elif abs(R[1, 1] + 1.0) > 1e-5:
-                w = math.pi / math.sqrt(2.0 + 2.0 * R[1, 1]) * np.array([R[0, 1], 1.0 + R[1, 1], R[2, 1]])
-            else:
-                w = math.pi / math.sqrt(2.0 + 2.0 * R[0, 0]) * np.array([1.0 + R[0, 0], R[1, 0], R[2, 0]])
+        if tr < -0.4:                             # above 134 degrees: atan2 and the symmetric part (csrc/se3_device.h)
+            v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+            c = 0.5 * (tr - 1.0)
+            th = math.atan2(0.5 * float(np.linalg.norm(v)), c)
+            i = int(np.argmax(np.diag(R)))
+            a = 0.5 * (R[:, i] + R[i, :])
+            a[i] -= c
+            w = th / float(np.linalg.norm(a)) * a
+            if float(v @ a) < 0.0:
+                w = -w
         else:
             tr3 = tr - 3.0
             if tr3 < -1e-7:
@@ -222,7 +226,7 @@ class Pose3:
             w = mag * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
         th = float(np.linalg.norm(w))
         if th < 1e-10:
-            return np.concatenate([w, t])
+            return np.concatenate([w, t - 0.5 * np.cross(w, t)])
         k = w / th
         WT = np.cross(k, t)
         v = t - (0.5 * th) * WT + (1.0 - th / (2.0 * math.tan(0.5 * th))) * np.cross(k, WT)

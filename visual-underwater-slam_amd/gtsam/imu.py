@@ -30,7 +30,7 @@ def so3_jr(w):
         a, b = 0.5 - th2 / 24.0, 1.0 / 6.0 - th2 / 120.0
     else:
         th = np.sqrt(th2)
-        a, b = (1.0 - np.cos(th)) / th2, (th - np.sin(th)) / (th2 * th)
+        a, b = 2.0 * np.sin(0.5 * th) ** 2 / th2, (th - np.sin(th)) / (th2 * th)
     return np.eye(3) - a * W + b * (W @ W)
 
 
