@@ -163,8 +163,24 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
   const long bv[2] = {(long)g_blur_mfma_table.v[0][l], (long)g_blur_mfma_table.v[1][l]};
   const uint8_t* img8 = reinterpret_cast<const uint8_t*>(s_img);
   constexpr unsigned long long SIGN = 0x8080808080808080ull;
+  // TILED: nothing about the bounds depends on the block.  Whole 16-column blocks (W % 16 == 0) make the x bound the
+  // loop's uniform end, the y bounds are one lane mask per row block, and a lane's pixels of block j lie 128 j bytes
+  // past those of block 0.
+  const int j_end = TILED ? min(TW / 16, (W - x0) / 16) : TW / 16;
+  bool row_ok[2] = {false, false};
+  uint32_t tiled_off[2] = {0u, 0u};
+  uint8_t* const tiled_plane = blur_out + (size_t)n * H * W;
+  if (TILED) {
+    j_first = __builtin_amdgcn_readfirstlane(j_first);   // a wave's blocks: the loop counter is a scalar
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+      const int ly = 16 * nb + m;
+      row_ok[nb] = ly < TH && y0 + ly < H;
+      tiled_off[nb] = vus_tiled_offset(y0 + ly, x0 + 4 * g, W);
+    }
+  }
 #pragma unroll 1   // (measured, round 4: other unroll factors change nothing)
-  for (int j = j_first; j < TW / 16; j += j_step) {
+  for (int j = j_first; j < j_end; j += j_step) {
     v4i32_t ch[2];
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
@@ -196,7 +212,7 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
       const uint32_t v = __builtin_amdgcn_perm(q[1], q[0], 0x0c0c0602u) | __builtin_amdgcn_perm(q[3], q[2], 0x06020c0cu);
       const int ly = 16 * nb + m, gy = y0 + ly, gx = x0 + 16 * j + 4 * g;
       if (TILED) {
-        if (ly < TH && gy < H && gx < W) __builtin_memcpy(blur_out + (size_t)n * H * W + vus_tiled_offset(gy, gx, W), &v, 4);
+        if (row_ok[nb]) __builtin_memcpy(tiled_plane + (tiled_off[nb] + (uint32_t)(VUS_TILE_BW * VUS_TILE_BH * j)), &v, 4);
       } else if (ly < TH && gy < H) {
         uint8_t* o = blur_out + ((size_t)n * H + gy) * W + gx;
         if (gx + 3 < W) {
@@ -213,7 +229,8 @@ __device__ __forceinline__ void blur_tile_mfma(const uint32_t* s_img, uint8_t* _
 
 // One 128 x 24 tile of image n, in phases:
 //   staging     the 144 x 32 window into s_img, and the (min, max) of every staged dword into s_mm;
-//   pass 1a     strip pre-test from the extrema: strips that may hold a corner are listed in s_strip;
+//   pass 1a     strip pre-test from the extrema: strips that may hold a corner are listed in s_strip (three passes of
+//               the workgroup over the tile's own 32 x 24 strips, one short pass of two waves over the ring of 116);
 //   pass 1b     per-pixel pre-test of the listed strips: pixels that may be corners are listed in s_work;
 //   pass 2      exact score of the listed pixels into s_score (zeroed by pass 1a);
 //   then, as the instance asks: the score tile written out (WRITE_SCORE); non-max suppression over s_work, the
@@ -328,38 +345,59 @@ __device__ __forceinline__ void fast_tile_body(
     // a pixel that passes the per-pixel test, 47 % against 45 % at fast_threshold 10 (single frames on the CPU; the
     // counting build on the bench stream says 18.2 % of a tile's strips are listed and 3.9 % of its pixels pass pass 1b).
     // The per-pixel test then runs on the listed strips only.
-    // Thread = fixed strip column, S_RPP rows per pass (no per-item division; the LDS addresses of a pass differ from
-    // the first one's by constants).  All passes are evaluated first and listed with ONE LDS atomic per wave.
-    constexpr int S_RPP = NTHREADS / SC_DW;                       // 7 rows of 34 strips per pass
-    constexpr int NIT = (SC_ROWS + S_RPP - 1) / S_RPP;
-    const int sr0 = tid / SC_DW, ss = tid - sr0 * SC_DW;
-    const int gx = x0 - 4 + 4 * ss;
-    const bool col_ok = sr0 < S_RPP && gx + 3 >= 3 && gx < W - 3;
-    const int ci0 = (sr0 + 3) * IMG_DW + ss;
+    // Thread = one strip of the tile proper: 32 x 24 strips = three full passes of the workgroup, eight rows of 32 per
+    // pass (the LDS addresses of a pass differ from the first one's by constants).  The 116 strips of the ring (score
+    // rows 0 and 25, score columns 0 and 33) take one further pass on waves 0 and 1, behind a wave-uniform branch.
+    // All passes are evaluated first and listed with ONE LDS atomic per wave.
+    static_assert(STRIPS == 32 && (TH * STRIPS) % NTHREADS == 0, "pass 1a: thread = (row tid >> 5, strip tid & 31)");
+    constexpr int S_RPP = NTHREADS / STRIPS;                      // 8 rows of 32 strips per pass
+    constexpr int NMAIN = TH / S_RPP;
+    constexpr int NIT = NMAIN + 1;                                // + the ring pass
+    static_assert(SC_DW + TH <= 64 && SC_ROWS == TH + 2 && SC_DW == STRIPS + 2, "pass 1a: the ring pass is a row and a column per wave");
+    // the strip test proper; (sr, ss) = score row / strip column, ci = the strip's left neighbour in s_img / s_mm
+    auto strip_test = [&](int sr, int ss, int ci) -> bool {
+      const int gy = y0 - 1 + sr, gx = x0 - 4 + 4 * ss;
+      // 0 <= gx < W - 3 and 3 <= gy < H - 3, one unsigned comparison each
+      if (!((uint32_t)gx < (uint32_t)max(W - 3, 0) && (uint32_t)(gy - 3) < (uint32_t)max(H - 6, 0))) return false;
+      // the (min, max) pairs read as the two bytes they are: ten ds_read_u8 instead of five ds_read_u16 + shifts /
+      // masks (3.01 -> 2.96 ms per 1000 stereo frames)
+      const uint8_t* mm8 = reinterpret_cast<const uint8_t*>(s_mm) + 2 * ci;
+      const int ma_lo = mm8[0], ma_hi = mm8[1], pmin = mm8[2], pmax = mm8[3], mc_lo = mm8[4], mc_hi = mm8[5];
+      const int mn_lo = mm8[2 - 6 * IMG_DW], mn_hi = mm8[3 - 6 * IMG_DW], ms_lo = mm8[2 + 6 * IMG_DW], ms_hi = mm8[3 + 6 * IMG_DW];
+      const uint32_t b = s_img[ci + 1];
+      const int b0 = byte_of(b, 0), b3 = byte_of(b, 3);
+      const int hi = min(max(mn_hi, ms_hi), max3i(ma_hi, mc_hi, max(b0, b3)));
+      const int lo = max(min(mn_lo, ms_lo), min3i(ma_lo, mc_lo, min(b0, b3)));
+      return hi > pmin + thr || lo < pmax - thr;
+    };
+    const int sr0 = 1 + (tid >> 5), ss0 = 1 + (tid & 31);
     unsigned long long bal[NIT];
     bool pass[NIT];
+    int ent[NIT];                                                 // s_strip entries
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
+    for (int it = 0; it < NMAIN; ++it) {
       const int sr = sr0 + it * S_RPP;
-      pass[it] = false;
-      if (sr0 < S_RPP && sr < SC_ROWS) {
-        const int gy = y0 - 1 + sr;
-        if (col_ok && gy >= 3 && gy < H - 3) {
-          const int ci = ci0 + it * S_RPP * IMG_DW;
-          // the (min, max) pairs read as the two bytes they are: ten ds_read_u8 instead of five ds_read_u16 + shifts /
-          // masks (3.01 -> 2.96 ms per 1000 stereo frames)
-          const uint8_t* mm8 = reinterpret_cast<const uint8_t*>(s_mm) + 2 * ci;
-          const int ma_lo = mm8[0], ma_hi = mm8[1], pmin = mm8[2], pmax = mm8[3], mc_lo = mm8[4], mc_hi = mm8[5];
-          const int mn_lo = mm8[2 - 6 * IMG_DW], mn_hi = mm8[3 - 6 * IMG_DW], ms_lo = mm8[2 + 6 * IMG_DW], ms_hi = mm8[3 + 6 * IMG_DW];
-          const uint32_t b = s_img[ci + 1];
-          const int b0 = byte_of(b, 0), b3 = byte_of(b, 3);
-          const int hi = min(max(mn_hi, ms_hi), max3i(ma_hi, mc_hi, max(b0, b3)));
-          const int lo = max(min(mn_lo, ms_lo), min3i(ma_lo, mc_lo, min(b0, b3)));
-          pass[it] = hi > pmin + thr || lo < pmax - thr;
-        }
-        s_score[sr * SC_DW + ss] = 0u;
-      }
+      pass[it] = strip_test(sr, ss0, (sr0 + 3) * IMG_DW + ss0 + it * S_RPP * IMG_DW);
+      s_score[sr0 * SC_DW + ss0 + it * S_RPP * SC_DW] = 0u;
+      ent[it] = sr * SC_DW + ss0;
       bal[it] = __ballot(pass[it]);
+    }
+    pass[NMAIN] = false;
+    ent[NMAIN] = 0;
+    bal[NMAIN] = 0ull;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (wv < 2) {
+      // wave 0: score row 0, then column 0 of the rows between; wave 1: score row SC_ROWS - 1, then column SC_DW - 1
+      const int l = tid & 63;
+      const bool is_row = l < SC_DW;
+      const int sr = is_row ? wv * (SC_ROWS - 1) : l - (SC_DW - 1);
+      const int ss = is_row ? l : wv * (SC_DW - 1);
+      if (l < SC_DW + TH) {
+        pass[NMAIN] = strip_test(sr, ss, (sr + 3) * IMG_DW + ss);
+        s_score[sr * SC_DW + ss] = 0u;
+        ent[NMAIN] = sr * SC_DW + ss;
+      }
+      bal[NMAIN] = __ballot(pass[NMAIN]);
     }
     int total = 0;
 #pragma unroll
@@ -372,7 +410,7 @@ __device__ __forceinline__ void fast_tile_body(
       for (int it = 0; it < NIT; ++it) {
         if (pass[it])
           s_strip[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[it] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[it], 0))] =
-              (uint16_t)((sr0 + it * S_RPP) * SC_DW + ss);
+              (uint16_t)ent[it];
         base += __popcll(bal[it]);
       }
     }
@@ -494,7 +532,9 @@ __device__ __forceinline__ void fast_tile_body(
       if (gy < border || gy >= H - border || gx < border || gx >= W - border) continue;
       const uint8_t* c = score8 + ent;
       constexpr int RB = 4 * SC_DW;
-      const int m = max(max3i(c[-RB - 1], c[-RB], c[-RB + 1]), max(max(c[-1], c[1]), max3i(c[RB - 1], c[RB], c[RB + 1])));
+      // (int operands throughout: max() of two bytes against an int resolved to the double overload -- six fp64
+      // conversions and maxima per survivor)
+      const int m = max3i(max3i(c[-RB - 1], c[-RB], c[-RB + 1]), max((int)c[-1], (int)c[1]), max3i(c[RB - 1], c[RB], c[RB + 1]));
       if (s > m) {                                                         // strict maximum of its 8 neighbours
         if (HIST) {
           atomicAdd(&hist[256 * n + s], 1);       // a sampled tile yields a few dozen survivors: no LDS stage
