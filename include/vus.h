@@ -548,6 +548,11 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * vus_point_priors and vus_point_prior_check / _linearize / _eval_step / _error. */
 #include "vus_point_prior.h"
 
+/* Partial absolute measurements on keyframe poses (GPSFactor, GPSFactorArm, PoseTranslationPrior3D,
+ * PoseRotationPrior3D), added to Hpp / gp before the Schur step: vus_pose_meas and vus_pose_meas_check / _linearize /
+ * _eval_step / _error / _weights. */
+#include "vus_pose_meas.h"
+
 /* Two-point RANSAC with a known inter-frame rotation on the temporal matches (the nodelet's ransac_threshold,
  * launch/stereo.launch:46), between the track matcher and the id emitter above: vus_two_point_ransac. */
 #include "vus_ransac.h"

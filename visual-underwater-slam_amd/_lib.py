@@ -97,6 +97,12 @@ SIGNATURES = {
     "vus_point_prior_linearize": [_P, _P, _P, _P, _P, _P, _P],
     "vus_point_prior_eval_step": [_P, _P, _P, _P, _P, _P, _P],
     "vus_point_prior_error": [_P, _P, _P, _P, _P],
+    # position and attitude fixes on keyframe poses (include/vus_pose_meas.h)
+    "vus_pose_meas_check": [_P, _P],
+    "vus_pose_meas_linearize": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_pose_meas_eval_step": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_pose_meas_error": [_P, _P, _P, _P, _P],
+    "vus_pose_meas_weights": [_P, _P, _P, _P],
     # host-only tuning knobs of the band solve (tests, A/B timing)
     "vus_ba_set_tuning": [c_int, c_int],
 }
@@ -150,6 +156,8 @@ def load():
     lib.vus_between_work_doubles.restype = ctypes.c_longlong
     lib.vus_point_prior_work_doubles.argtypes = [_P]
     lib.vus_point_prior_work_doubles.restype = ctypes.c_longlong
+    lib.vus_pose_meas_work_doubles.argtypes = [_P]
+    lib.vus_pose_meas_work_doubles.restype = ctypes.c_longlong
     lib.vus_ba_band_selinv_work_doubles.argtypes = [c_int, c_int]
     lib.vus_ba_band_selinv_work_doubles.restype = ctypes.c_longlong
     _lib = lib

@@ -217,6 +217,80 @@ class PointPriors:
         return ctypes.addressof(self.c)
 
 
+class _CPoseMeas(ctypes.Structure):
+    _fields_ = [("n", c_int), ("n_poses", c_int), ("pose_stride", c_int), ("n_rows", c_int), ("row_pose", c_void_p),
+                ("row_ptr", c_void_p), ("kind", c_void_p), ("meas", c_void_p), ("w", c_void_p), ("loss_kind", c_void_p),
+                ("loss_k", c_void_p)]
+
+
+POSE_MEAS_POSITION, POSE_MEAS_ROTATION = 0, 1        # VUS_POSE_MEAS_* of include/vus_pose_meas.h
+
+
+def pose_meas_rows(pose_idx):
+    """The CSR of include/vus_pose_meas.h on the host: (order, row_pose, row_ptr) -- `order` sorts the factors stably by
+    pose (graph order within one pose), row_pose lists the distinct poses ascending, row_ptr [n_rows + 1] points into the
+    sorted factors."""
+    idx = np.asarray(pose_idx, np.int64).reshape(-1)
+    order = np.argsort(idx, kind="stable")
+    row_pose, first = np.unique(idx[order], return_index=True)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return order, i32(row_pose), i32(np.append(first, len(idx)))
+
+
+class PoseMeasurements:
+    """Device-resident vus_pose_meas: partial absolute measurements on the poses X(i), i = `pose_idx`, of a problem with
+    `n_poses` poses at `pose_stride`.  kind [n]: POSE_MEAS_POSITION (GPSFactor, GPSFactorArm, PoseTranslationPrior3D: `meas`
+    row = the measured world position m (3), the lever arm a in the body frame (3), three zeros; r = t + R a - m) or
+    POSE_MEAS_ROTATION (PoseRotationPrior3D: `meas` row = the measured rotation, row-major; r = Log(Rm^T R)).  sigmas [n, 3]
+    (a diagonal model; a depth fix is a position fix with two wide sigmas).  `loss`: one robust model for all of them
+    (robust_loss(): None = Gaussian) or a list (not a tuple) of n, one per factor.  Several factors on one pose, of
+    either kind, are summed.  The factors are sorted stably by pose into the CSR on the host; `host` keeps them in that
+    order and `order` maps a CSR slot to the factor's position in the input.  n = 0 is allowed and is the same as no
+    PoseMeasurements at all."""
+
+    def __init__(self, pose_idx, kind, meas, sigmas, n_poses, pose_stride=1, loss=None, device="cuda:0"):
+        idx = np.asarray(pose_idx, np.int64).reshape(-1)
+        kind = np.asarray(kind, np.int64).reshape(-1)
+        meas = np.asarray(meas, np.float64).reshape(-1, 9)
+        sig = np.asarray(sigmas, np.float64).reshape(-1, 3)
+        n = len(idx)
+        if not (len(kind) == len(meas) == len(sig) == n):
+            raise ValueError(f"pose measurements: {n} pose indices, {len(kind)} kinds, {len(meas)} measurements, {len(sig)} sigmas")
+        if ((idx < 0) | (idx >= n_poses)).any():
+            raise ValueError(f"pose measurements: a pose index outside [0, {int(n_poses)})")
+        if not np.isin(kind, (POSE_MEAS_POSITION, POSE_MEAS_ROTATION)).all():
+            raise ValueError("pose measurements: kind must be POSE_MEAS_POSITION (0) or POSE_MEAS_ROTATION (1)")
+        if not (np.isfinite(sig).all() and (sig > 0).all()):
+            raise ValueError("pose measurements: sigmas must be finite and > 0")
+        if not np.isfinite(meas).all():
+            raise ValueError("pose measurements: measurements must be finite")
+        if int(pose_stride) not in (1, 2, 3):
+            raise ValueError(f"pose_stride={pose_stride}: 1, 2 or 3")
+        if isinstance(loss, list) and len(loss) != n:
+            raise ValueError(f"pose measurements: {len(loss)} robust models for {n} factors")
+        losses = [robust_loss(x) for x in loss] if isinstance(loss, list) else [robust_loss(loss)] * n
+        order, row_pose, row_ptr = pose_meas_rows(idx)
+        self.n, self.n_poses, self.pose_stride, self.n_rows = n, int(n_poses), int(pose_stride), len(row_pose)
+        self.order = order
+        self.losses = [losses[int(f)] for f in order]
+        self.robust = any(k for k, _ in self.losses)
+        self.host = dict(idx=idx[order], kind=kind[order], meas=meas[order], sigmas=sig[order], losses=self.losses,
+                         row_pose=row_pose, row_ptr=row_ptr)
+        dev = torch.device(device)
+        t = lambda a, dt: _upload(a, dev, dt)
+        self.row_pose, self.row_ptr = t(row_pose, torch.int32), t(row_ptr, torch.int32)
+        self.kind = t(kind[order].astype(np.int32), torch.int32)
+        self.meas, self.w = t(meas[order], torch.float64), t(1.0 / sig[order], torch.float64)
+        self.loss_kind = t(np.array([k for k, _ in self.losses], np.int32), torch.int32)
+        self.loss_k = t(np.array([k for _, k in self.losses], np.float64), torch.float64)
+        p = (lambda x: _lib.ptr(x)) if n else (lambda x: None)
+        self.c = _CPoseMeas(n, self.n_poses, self.pose_stride, self.n_rows, p(self.row_pose), p(self.row_ptr), p(self.kind),
+                            p(self.meas), p(self.w), p(self.loss_kind), p(self.loss_k))
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+
 @dataclass
 class LMParams:
     """gtsam.LevenbergMarquardtParams() defaults."""
@@ -247,6 +321,7 @@ class LMReport:
     seconds: float = 0.0
     setup_seconds: float = 0.0
     stereo_weights: Optional[tuple] = None     # gtsam shim, robust stereo factors: (pose keys, landmark keys, final w)
+    pose_meas_weights: Optional[tuple] = None  # gtsam shim, a robust position / attitude fix: (pose keys, final w), graph order
 
 
 def _i32(t):
@@ -501,7 +576,7 @@ class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
 
     def __init__(self, problem: StereoBAProblem, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None, inertial=()):
+                 point_priors: Optional[PointPriors] = None, inertial=(), pose_meas: Optional[PoseMeasurements] = None):
         self.P = problem
         dev, nP, nL, nO, B = problem.device, problem.n_poses, problem.n_points, problem.n_obs, problem.band
         nN = problem.n_nodes                       # camera-side nodes (= poses unless velocity nodes are interleaved)
@@ -520,12 +595,17 @@ class StereoBASolver:
         self.new_points = torch.empty((nL, 3), **f64)
         self.work = torch.empty((2 * (nL + 1) + 8,), **f64)
         self.Q = point_priors if point_priors is not None and point_priors.n else None      # no factors: no hooks
+        self.M = pose_meas if pose_meas is not None and pose_meas.n else None
         self.B = between
         # The optional factor families present, as (name of the slot view, error, linearize, assemble, eval_step), in the
-        # canonical order between, landmark priors, inertial (`inertial`: the stages an inertial subclass passes).  Every
-        # stage runs the stereo step first and then the terms in this order, which is what keeps:
+        # canonical order between, landmark priors, pose measurements, inertial (`inertial`: the stages an inertial
+        # subclass passes).  Every stage runs the stereo step first and then the terms in this order, which is what keeps:
         #   - linearize() before the landmark priors' linearize, which adds into V and gl; both before schur() and
         #     before _check_points (a prior can make a landmark determinate)
+        #   - linearize(), which WRITES Hpp and gp, before the pose measurements' linearize, which adds into them, and that
+        #     before schur(), which reads them.  The pose measurements have no assemble stage and touch nothing the other
+        #     terms read, so their place among the terms is free: they stand next to the landmark priors, the other family
+        #     that enters before the Schur step, and the inertial terms a subclass passes stay last
         #   - between_assemble() after schur() and before the inertial assemble, which copies gs into its right-hand side
         #   - eval_step() before every other eval_step: they read new_poses / new_points
         terms = []
@@ -535,6 +615,9 @@ class StereoBASolver:
         if self.Q is not None:
             terms.append(("pp_scal", lambda s: self.point_prior_error(s[-1]), lambda s: self.point_prior_linearize(s[-1]),
                           lambda lam: None, lambda s: self.point_prior_eval_step(s[-1])))
+        if self.M is not None:
+            terms.append(("pm_scal", lambda s: self.pose_meas_error(s[0]), lambda s: self.pose_meas_linearize(s[0]),
+                          lambda lam: None, lambda s: self.pose_meas_eval_step(s[0])))
         terms += inertial
         # one record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised error
         # at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word, then one slot of 4 per
@@ -563,6 +646,13 @@ class StereoBASolver:
             self.pp_err = torch.empty((1,), **f64)
             self.pp_work = torch.empty((int(_lib.load().vus_point_prior_work_doubles(self.Q.addr())),), **f64)
             _lib.call("vus_point_prior_check", self.Q.addr(), _lib.current_stream_ptr())
+        if self.M is not None:
+            if self.M.pose_stride != problem.pose_stride or self.M.n_poses != nP:
+                raise ValueError(f"PoseMeasurements built for {self.M.n_poses} poses at pose_stride {self.M.pose_stride}, the "
+                                 f"problem has {nP} at pose_stride {problem.pose_stride}")
+            self.pm_err = torch.empty((1,), **f64)
+            self.pm_work = torch.empty((int(_lib.load().vus_pose_meas_work_doubles(self.M.addr())),), **f64)
+            _lib.call("vus_pose_meas_check", self.M.addr(), _lib.current_stream_ptr())
         # two-sided band solve (vus_ba_band_solve_split): worth it once the chain of panel steps is much longer than
         # the band; its workspace (pose-reversed copy of the lower half + the middle system) is allocated once
         self.band_rhs = 1
@@ -712,6 +802,39 @@ class StereoBASolver:
             _lib.call("vus_point_prior_eval_step", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.dl),
                       _lib.ptr(self.new_points), _lib.ptr(self.pp_scal[1:]), _lib.ptr(self.pp_work),
                       _lib.current_stream_ptr())
+
+    # -- position / attitude fixes on poses (include/vus_pose_meas.h); every hook is a no-op without them -------------
+    def pose_meas_error(self, poses) -> float:
+        """Error (sum rho under a robust model) of the pose measurements at poses; 0.0 without them."""
+        if self.M is None:
+            return 0.0
+        _lib.call("vus_pose_meas_error", self.M.addr(), _lib.ptr(poses), _lib.ptr(self.pm_err), _lib.ptr(self.pm_work),
+                  _lib.current_stream_ptr())
+        return float(self.pm_err[0].item())
+
+    def pose_meas_linearize(self, poses):
+        """Hpp, gp += the pose measurements at poses, pm_scal[0] = their linear error at delta = 0: after linearize(),
+        before schur()."""
+        if self.M is not None:
+            _lib.call("vus_pose_meas_linearize", self.M.addr(), _lib.ptr(poses), _lib.ptr(self.Hpp), _lib.ptr(self.gp),
+                      _lib.ptr(self.pm_scal), _lib.ptr(self.pm_work), _lib.current_stream_ptr())
+
+    def pose_meas_eval_step(self, poses):
+        """pm_scal[1] = linearised error at the step dp, pm_scal[2] = error at new_poses (after eval_step)."""
+        if self.M is not None:
+            _lib.call("vus_pose_meas_eval_step", self.M.addr(), _lib.ptr(poses), _lib.ptr(self.dp), _lib.ptr(self.new_poses),
+                      _lib.ptr(self.pm_scal[1:]), _lib.ptr(self.pm_work), _lib.current_stream_ptr())
+
+    def pose_meas_weights(self, poses) -> Optional[torch.Tensor]:
+        """Robust weight w(d) of every pose measurement at poses, in the order the PoseMeasurements were GIVEN (all ones
+        for Gaussian factors); None without them."""
+        if self.M is None:
+            return None
+        w = torch.empty(self.M.n, dtype=torch.float64, device=self.P.device)
+        _lib.call("vus_pose_meas_weights", self.M.addr(), _lib.ptr(poses), _lib.ptr(w), _lib.current_stream_ptr())
+        out = torch.empty_like(w)
+        out[torch.from_numpy(self.M.order).to(self.P.device)] = w            # order: CSR slot -> input position
+        return out
 
     def _trial_errors(self, rec):
         """[linearise error, linearised error at the step, new error] from one trial record: the stereo factors' and pose
@@ -1076,12 +1199,13 @@ class _InertialBASolver(StereoBASolver):
     _ABI = None
     _NEW_STATE = ("new_poses", "new_vels", "new_bias", "new_points")     # state = (poses, vels, bias, points)
 
-    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None):
+    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None, pose_meas=None):
         if problem.pose_stride != self.POSE_STRIDE:
             raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
         nav3 = lambda stage: lambda s: stage(*s[:3])          # state = (poses, vels, bias, points)
         super().__init__(problem, between, point_priors, inertial=[
-            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav3(self.nav_eval_step))])
+            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav3(self.nav_eval_step))],
+            pose_meas=pose_meas)
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
         f64 = dict(dtype=torch.float64, device=dev)
@@ -1113,8 +1237,8 @@ class NavBASolver(_InertialBASolver):
     POSE_STRIDE, SDIAG, _ABI = 2, 4, "vus_nav"
 
     def __init__(self, problem: StereoBAProblem, nav: NavFactors, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None):
-        super().__init__(problem, nav, None, between, point_priors)
+                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None):
+        super().__init__(problem, nav, None, between, point_priors, pose_meas)
         self.band_rhs = 7
         self._alloc_band_work()
         nN = problem.n_nodes
@@ -1189,8 +1313,8 @@ class NavBiasBASolver(_InertialBASolver):
     POSE_STRIDE, SDIAG, _ABI = 3, 5, "vus_navb"
 
     def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None):
-        super().__init__(problem, nav, problem.n_poses, between, point_priors)
+                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None):
+        super().__init__(problem, nav, problem.n_poses, between, point_priors, pose_meas)
 
     def nav_linearize(self, poses, vels, biases):
         p = _lib.ptr

@@ -190,7 +190,7 @@ class ShardedStereoBASolver:
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
                  prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None, mono=None,
-                 point_priors=None):
+                 point_priors=None, pose_meas=None):
         from .ba import StereoBAProblem, StereoBASolver
         if between is not None:
             raise NotImplementedError("BetweenFactorPose3 (ba.BetweenFactors) is not supported by the landmark-sharded solver: "
@@ -204,6 +204,9 @@ class ShardedStereoBASolver:
         if point_priors is not None:
             raise NotImplementedError("priors on observed landmarks (ba.PointPriors) are not supported by the landmark-sharded "
                                       "solver: use StereoBASolver(problem, point_priors=...) on one GPU")
+        if pose_meas is not None:
+            raise NotImplementedError("position / attitude fixes on poses (ba.PoseMeasurements) are not supported by the "
+                                      "landmark-sharded solver: use StereoBASolver(problem, pose_meas=...) on one GPU")
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         obs_pose = torch.as_tensor(obs_pose).to(device)

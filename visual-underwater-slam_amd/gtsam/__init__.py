@@ -10,7 +10,9 @@ module exposes the same names with the same argument meaning, so that
 is the only change batch.py needs for the stereo path; `LevenbergMarquardtOptimizer.optimize()` then
 runs on the MI355X kernels (ba.py / csrc/ba.hip).
 
-Scope: GenericStereoFactor3D, GenericProjectionFactorCal3_S2, PriorFactorPose3, PriorFactorVector, ImuFactor (with
+Scope: GenericStereoFactor3D, GenericProjectionFactorCal3_S2, PriorFactorPose3, PriorFactorVector,
+the partial absolute measurements on a pose GPSFactor, GPSFactorArm, PoseTranslationPrior3D and PoseRotationPrior3D
+(position, position of a transponder off the body origin, attitude; include/vus_pose_meas.h), ImuFactor (with
 PreintegratedImuMeasurements) and the DVL velocity factor (DvlVelocityFactor, the well-formed
 replacement of the reference's CustomFactor) are solved on the GPU.  A generic gtsam.CustomFactor
 (arbitrary Python callback) can be constructed and added, but optimize() refuses it, loudly.
@@ -37,6 +39,7 @@ __all__ = [
     "NonlinearFactorGraph", "Values", "LevenbergMarquardtParams", "LevenbergMarquardtOptimizer",
     "StereoFactorBlock", "symbol_shorthand", "symbol",
     "Point2", "GenericProjectionFactorCal3_S2", "ProjectionFactorBlock",
+    "GPSFactor", "GPSFactorArm", "PoseTranslationPrior3D", "PoseRotationPrior3D",
 ]
 
 
@@ -778,6 +781,106 @@ class BetweenFactorPose3(_Factor):
 
     def noiseModel(self):
         return self._model
+
+
+class _PoseMeasFactor(_Factor):
+    """A partial absolute measurement on one Pose3 (include/vus_pose_meas.h): three residual rows under a 3-dimensional
+    Diagonal / Isotropic / Unit model, optionally wrapped in noiseModel.Robust.  `_kind` is the VUS_POSE_MEAS_* number and
+    `_row9()` the factor's nine measurement doubles."""
+    _kind = 0
+
+    def __init__(self, key, model):
+        super().__init__([key])
+        what = type(self).__name__
+        if not isinstance(model, _NoiseModel):
+            raise RuntimeError(f"{what}: the last argument must be a noise model")
+        if model.dim() != 3:
+            raise RuntimeError(f"{what} needs a 3-dimensional noise model, not one of dimension {model.dim()}")
+        self._model = model
+
+    def noiseModel(self):
+        return self._model
+
+    @staticmethod
+    def _point(p, what):
+        a = np.asarray(p, dtype=float)
+        if a.size != 3 or not np.isfinite(a).all():
+            raise RuntimeError(f"{what} must be a finite 3-vector")
+        return a.reshape(3).copy()
+
+
+class GPSFactor(_PoseMeasFactor):
+    """gtsam.GPSFactor(key, gpsIn, model): the position of the pose measured in the world (navigation) frame, error
+    0.5 |(t - gpsIn) / sigma|^2.  A depth fix is this factor with Diagonal.Sigmas([big, big, sigma_z])."""
+
+    def __init__(self, key, gpsIn, model: _NoiseModel):
+        super().__init__(key, model)
+        self._m = self._point(gpsIn, "GPSFactor: gpsIn")
+
+    def measurementIn(self):
+        return self._m.copy()
+
+    def _row9(self):
+        return np.concatenate([self._m, np.zeros(6)])
+
+
+class GPSFactorArm(_PoseMeasFactor):
+    """gtsam.GPSFactorArm(key, gpsIn, leverArm, model): the world position of an antenna or transponder mounted at
+    `leverArm` in the body frame, error 0.5 |(t + R leverArm - gpsIn) / sigma|^2."""
+
+    def __init__(self, key, gpsIn, leverArm, model: _NoiseModel):
+        super().__init__(key, model)
+        self._m = self._point(gpsIn, "GPSFactorArm: gpsIn")
+        self._arm = self._point(leverArm, "GPSFactorArm: leverArm")
+
+    def measurementIn(self):
+        return self._m.copy()
+
+    def leverArm(self):
+        return self._arm.copy()
+
+    def _row9(self):
+        return np.concatenate([self._m, self._arm, np.zeros(3)])
+
+
+class PoseTranslationPrior3D(_PoseMeasFactor):
+    """gtsam.PoseTranslationPrior3D(key, Point3 or Pose3, model): a prior on the translation of the pose in the world
+    frame (of a Pose3 only the translation is used), error 0.5 |(t - measured) / sigma|^2."""
+
+    def __init__(self, key, measured, model: _NoiseModel):
+        super().__init__(key, model)
+        self._m = self._point(measured.translation() if isinstance(measured, Pose3) else measured,
+                              "PoseTranslationPrior3D: the measurement")
+
+    def measured(self):
+        return self._m.copy()
+
+    def _row9(self):
+        return np.concatenate([self._m, np.zeros(6)])
+
+
+class PoseRotationPrior3D(_PoseMeasFactor):
+    """gtsam.PoseRotationPrior3D(key, Rot3 or Pose3, model): a prior on the rotation of the pose (of a Pose3 only the
+    rotation is used), error 0.5 |Log(measured^T R) / sigma|^2 with the identity as the Jacobian, as gtsam has it."""
+    _kind = 1
+
+    def __init__(self, key, measured, model: _NoiseModel):
+        super().__init__(key, model)
+        if isinstance(measured, Pose3):
+            measured = measured.rotation()
+        if not isinstance(measured, Rot3):
+            raise RuntimeError("PoseRotationPrior3D: the measurement must be a Rot3 or a Pose3")
+        R = measured.matrix()
+        if not np.isfinite(R).all() or np.abs(R.T @ R - np.eye(3)).max() > 1e-9 or np.linalg.det(R) <= 0.0:
+            raise RuntimeError("PoseRotationPrior3D: the measured rotation is not a rotation matrix (orthonormal within 1e-9, "
+                               "det > 0)")
+        self._R = Rot3(R)
+
+    def measured(self):
+        return Rot3(self._R._R)
+
+    def _row9(self):
+        return self._R._R.reshape(9).copy()
 
 
 class PreintegrationParams:

@@ -143,11 +143,12 @@ def _pack_graph(graph, values, device=None):
     is given (2 M observations: ~3 ms on the GPU against ~0.3 s in numpy), else in numpy (CPU tests)."""
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
                    ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias, PriorFactorConstantBias,
-                   BetweenFactorConstantBias, BetweenFactorPose3, GenericProjectionFactorCal3_S2, ProjectionFactorBlock)
+                   BetweenFactorConstantBias, BetweenFactorPose3, GenericProjectionFactorCal3_S2, ProjectionFactorBlock,
+                   _PoseMeasFactor)
     meas, pkeys, lkeys = [], [], []
     mono_n = []                     # per part of meas / pkeys / lkeys: 0 for a stereo part, its length for a mono part
     mono = dict(sigma=None, calib=None, loss=None, sensor=None)
-    between_f = []
+    between_f, pose_meas_f = [], []
     imu_f, dvl_f, bias_f = [], [], []
     from . import _Robust
     from . import _same_sensor
@@ -213,6 +214,8 @@ def _pack_graph(graph, values, device=None):
             prior_pose.append(f)
         elif isinstance(f, BetweenFactorPose3):
             between_f.append(f)
+        elif isinstance(f, _PoseMeasFactor):
+            pose_meas_f.append(f)
         elif isinstance(f, PriorFactorVector):
             prior_vec.append(f)
         elif isinstance(f, ImuFactor):
@@ -319,6 +322,7 @@ def _pack_graph(graph, values, device=None):
             raise RuntimeError(f"Attempting to at the key \"{_sym.key_string(k)}\", which does not exist in the Values.")
         pr_idx.append(j); pr_T.append(f._prior.flat12()); pr_s.append(f._model.sigmas())
     between = _pack_between(pose_keys, between_f) if between_f else None
+    pose_meas = _pack_pose_meas(pose_keys, pose_meas_f) if pose_meas_f else None
     nav = None
     if imu_f or dvl_f or bias_f:
         nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f)
@@ -344,7 +348,7 @@ def _pack_graph(graph, values, device=None):
                 K=calib.vector6() if calib is not None else np.array([1.0, 1.0, 0.0, 0.0, 0.0, 1.0]),
                 mono=mono_flags, mono_K=mono["calib"].vector() if has_mono else None, mono_sigma=mono["sigma"],
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
-                prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between,
+                prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between, pose_meas=pose_meas,
                 point_priors=dict(idx=np.asarray(pp_idx, np.int32), mean=np.asarray(pp_mean, float).reshape(-1, 3),
                                   sigmas=np.asarray(pp_sig, float).reshape(-1, 3)) if pp_idx else None)
 
@@ -367,6 +371,24 @@ def _pack_between(pose_keys, between_f):
     bi, bj = np.asarray(bi, np.int32), np.asarray(bj, np.int32)
     return dict(i=bi, j=bj, meas=np.asarray(bm, float).reshape(-1, 12), sigmas=np.asarray(bs, float).reshape(-1, 6),
                 losses=bl, span=int(np.abs(bi.astype(np.int64) - bj).max()))
+
+
+def _pack_pose_meas(pose_keys, pose_meas_f):
+    """GPSFactor / GPSFactorArm / PoseTranslationPrior3D / PoseRotationPrior3D -> (idx, kind, meas [n, 9], sigmas [n, 3],
+    losses [n], keys [n]) in graph order: pose indices into the sorted Pose3 keys, the VUS_POSE_MEAS_* kinds, the rows of
+    include/vus_pose_meas.h, the diagonal sigmas, each factor's (VUS_LOSS_* kind, k) and its pose key."""
+    from . import _Robust
+    idx, kind, meas, sig, losses, keys = [], [], [], [], [], []
+    for f in pose_meas_f:
+        k = f._keys[0]
+        j = int(np.searchsorted(pose_keys, k))
+        if j >= len(pose_keys) or pose_keys[j] != k:
+            raise RuntimeError(f"Attempting to at the key \"{_sym.key_string(k)}\", which does not exist in the Values.")
+        rob = f._model.robust() if isinstance(f._model, _Robust) else None
+        idx.append(j); kind.append(f._kind); meas.append(f._row9()); sig.append(f._model.sigmas()); keys.append(k)
+        losses.append((rob.kind, rob.k) if rob is not None else (0, 0.0))
+    return dict(idx=np.asarray(idx, np.int32), kind=np.asarray(kind, np.int32), meas=np.asarray(meas, float).reshape(-1, 9),
+                sigmas=np.asarray(sig, float).reshape(-1, 3), losses=losses, keys=np.asarray(keys, np.int64))
 
 
 def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=()):
@@ -488,7 +510,7 @@ def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
 
 def _build_solver(pg, device="cuda:0"):
     from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
-                      BetweenFactors, PointPriors)
+                      BetweenFactors, PointPriors, PoseMeasurements)
     nav = pg.get("nav")
     btw = pg.get("between")
     walk = bool(nav) and nav.get("per_keyframe", False)
@@ -504,14 +526,17 @@ def _build_solver(pg, device="cuda:0"):
                         loss=list(btw["losses"]), device=device) if btw else None
     pp = pg.get("point_priors")
     pf = PointPriors(pp["idx"], pp["mean"], pp["sigmas"], len(pg["lm_keys"]), device=device) if pp else None
+    pm = pg.get("pose_meas")
+    mf = PoseMeasurements(pm["idx"], pm["kind"], pm["meas"], pm["sigmas"], n_poses, pose_stride=stride,
+                          loss=list(pm["losses"]), device=device) if pm else None
     if walk:
         nf = NavBiasFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], bbetween=nav["bbetween"],
                             bprior=nav["bprior"], device=device)
-        return prob, NavBiasBASolver(prob, nf, bf, pf)
+        return prob, NavBiasBASolver(prob, nf, bf, pf, mf)
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
-        return prob, NavBASolver(prob, nf, bf, pf)
-    return prob, StereoBASolver(prob, bf, pf)
+        return prob, NavBASolver(prob, nf, bf, pf, mf)
+    return prob, StereoBASolver(prob, bf, pf, pose_meas=mf)
 
 
 def graph_error(graph, values) -> float:
@@ -522,7 +547,7 @@ def graph_error(graph, values) -> float:
     dev = prob.device
     poses = torch.from_numpy(pg["poses"]).to(dev)
     points = torch.from_numpy(pg["points"]).to(dev)
-    e = sv.error(poses, points) + sv.between_error(poses) + sv.point_prior_error(points)
+    e = sv.error(poses, points) + sv.between_error(poses) + sv.point_prior_error(points) + sv.pose_meas_error(poses)
     if pg.get("nav"):
         e += sv.nav_error(poses, torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev))
     return e + pg["aux"].error()
@@ -576,6 +601,9 @@ class LevenbergMarquardtOptimizer:
             w = sv.stereo_weights(poses, points).cpu().numpy()
             pi, li = (np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x, dtype=np.int64) for x in (pg["pose_idx"], pg["lm_idx"]))
             rep.stereo_weights = (pg["pose_keys"][pi], np.asarray(pg["lm_keys"])[li], w)
+        rep.pose_meas_weights = None
+        if sv.M is not None and sv.M.robust:     # final IRLS weights per position / attitude fix, graph order, by pose key
+            rep.pose_meas_weights = (pg["pose_meas"]["keys"], sv.pose_meas_weights(poses).cpu().numpy())
         poses, points = poses.cpu().numpy(), points.cpu().numpy()
         out = Values(self._initial)
         if nav:
@@ -615,5 +643,7 @@ class LevenbergMarquardtOptimizer:
 
     def report(self):
         """EXTENSION: the LMReport of the last optimize() (error / lambda history, timings).  With robust stereo factors
-        its `stereo_weights` = (pose keys, landmark keys, w) holds every stereo factor's final weight w(d); else None."""
+        its `stereo_weights` = (pose keys, landmark keys, w) holds every stereo factor's final weight w(d); else None.  With
+        a noiseModel.Robust on any GPSFactor / GPSFactorArm / PoseTranslationPrior3D / PoseRotationPrior3D its
+        `pose_meas_weights` = (pose keys, w) holds the final weight of every such factor, in graph order; else None."""
         return self._report
