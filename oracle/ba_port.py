@@ -101,7 +101,10 @@ class BAPort:
         current = self.error(poses, points)
         rep = {"iterations": 0, "outer": 0, "tries": 0, "status": 1, "initial_error": current, "err_hist": [],
                "lambda_hist": [], "truncated": False}
-        while rep["iterations"] < prm["max_iterations"]:
+        at_tol = current <= prm["error_tol"]     # before the first iteration: converged, the state untouched
+        if at_tol:
+            rep["status"] = 0
+        while not at_tol and rep["iterations"] < prm["max_iterations"]:
             lin0 = self.linearize(poses, points)
             new_error, stop, accepted = current, False, False
             while True:

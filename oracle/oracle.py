@@ -295,6 +295,21 @@ class _LMReport(ctypes.Structure):
                 ("err_hist", c_double * 128), ("lambda_hist", c_double * 128)]
 
 
+class _LMTrials(ctypes.Structure):
+    _fields_ = [("lam", c_double * 128), ("lin0", c_double * 128), ("lin1", c_double * 128), ("new1", c_double * 128),
+                ("status", c_int * 128)]
+
+
+def _lm_report(rep, tr):
+    """vus_lm_report as a dict, with `trials` = (lambda, lin0, lin1, new1, status) of each of the first 128 linear solves
+    from the vus_lm_trials of the *_trials_cpu entry points"""
+    n, t = min(rep.outer, 128), min(rep.tries, 128)
+    return {"iterations": rep.iterations, "outer": rep.outer, "tries": rep.tries, "status": rep.status,
+            "initial_error": rep.initial_error, "final_error": rep.final_error, "final_lambda": rep.final_lambda,
+            "err_hist": list(rep.err_hist[:n]), "lambda_hist": list(rep.lambda_hist[:n]),
+            "trials": list(zip(tr.lam[:t], tr.lin0[:t], tr.lin1[:t], tr.new1[:t], tr.status[:t]))}
+
+
 class BAProblem:
     """Host-side (numpy) vus_ba_problem.  `pk` is the dict of ba_pack.pack_observations (numpy or
     CPU torch tensors), priors = (pose_idx [n], T [n,12], sigmas [n,6])."""
@@ -416,13 +431,10 @@ def ba_lm_optimize(P, band, poses, points, **params):
     rep = _LMReport()
     poses = np.array(poses, dtype=np.float64, order="C", copy=True)
     points = np.array(points, dtype=np.float64, order="C", copy=True)
-    _check(lib().vus_ba_lm_optimize_cpu(P.ref(), int(band), ctypes.byref(c), _p(poses), _p(points),
-                                        ctypes.byref(rep)), "ba_lm_optimize")
-    n = min(rep.outer, 128)
-    return poses, points, {"iterations": rep.iterations, "outer": rep.outer, "tries": rep.tries,
-                           "status": rep.status, "initial_error": rep.initial_error,
-                           "final_error": rep.final_error, "final_lambda": rep.final_lambda,
-                           "err_hist": list(rep.err_hist[:n]), "lambda_hist": list(rep.lambda_hist[:n])}
+    tr = _LMTrials()
+    _check(lib().vus_ba_lm_optimize_trials_cpu(P.ref(), int(band), ctypes.byref(c), _p(poses), _p(points),
+                                               ctypes.byref(rep), ctypes.byref(tr)), "ba_lm_optimize")
+    return poses, points, _lm_report(rep, tr)
 
 
 def stereo_factor(T, p, m, K, w):
@@ -529,10 +541,7 @@ def nav_lm_optimize(P, N, poses, vels, bias, points, **params):
     rep = _LMReport()
     cp = lambda a: np.array(a, dtype=np.float64, order="C", copy=True)
     poses, vels, bias, points = cp(poses), cp(vels), cp(bias), cp(points)
-    _check(lib().vus_nav_lm_optimize_cpu(P.ref(), N.ref(), ctypes.byref(c), _p(poses), _p(vels), _p(bias), _p(points),
-                                         ctypes.byref(rep)), "nav_lm_optimize")
-    n = min(rep.outer, 128)
-    return poses, vels, bias, points, {"iterations": rep.iterations, "outer": rep.outer, "tries": rep.tries,
-                                       "status": rep.status, "initial_error": rep.initial_error,
-                                       "final_error": rep.final_error, "final_lambda": rep.final_lambda,
-                                       "err_hist": list(rep.err_hist[:n]), "lambda_hist": list(rep.lambda_hist[:n])}
+    tr = _LMTrials()
+    _check(lib().vus_nav_lm_optimize_trials_cpu(P.ref(), N.ref(), ctypes.byref(c), _p(poses), _p(vels), _p(bias), _p(points),
+                                                ctypes.byref(rep), ctypes.byref(tr)), "nav_lm_optimize")
+    return poses, vels, bias, points, _lm_report(rep, tr)

@@ -519,8 +519,25 @@ typedef struct vus_lm_report {
   double lambda_hist[VUS_LM_HIST]; /* lambda after each outer iteration */
 } vus_lm_report;
 
+/* What the loop throws away, for the callers that ask for it (the *_trials_cpu entry points; vus_lm_report keeps its
+ * layout): per linear solve, the first VUS_LM_HIST of them, its lambda, the linearised error at 0 and at the step, the
+ * error at the trial state (NaN both where the solve failed) and the solve's status. */
+typedef struct vus_lm_trials {
+  double lambda[VUS_LM_HIST], lin0[VUS_LM_HIST], lin1[VUS_LM_HIST], new1[VUS_LM_HIST];
+  int status[VUS_LM_HIST];
+} vus_lm_trials;
+
+int vus_ba_lm_optimize_trials_cpu(const vus_ba_problem* P, int band, const vus_lm_params* prm, double* poses,
+                                  double* points, vus_lm_report* rep, vus_lm_trials* tr);
+
 int vus_ba_lm_optimize_cpu(const vus_ba_problem* P, int band, const vus_lm_params* prm, double* poses,
                            double* points, vus_lm_report* rep) {
+  return vus_ba_lm_optimize_trials_cpu(P, band, prm, poses, points, rep, NULL);
+}
+
+/* tr: NULL, or where the trials are recorded */
+int vus_ba_lm_optimize_trials_cpu(const vus_ba_problem* P, int band, const vus_lm_params* prm, double* poses,
+                                  double* points, vus_lm_report* rep, vus_lm_trials* tr) {
   if (!P || !prm || !poses || !points || !rep || band < 0) return VUS_E_INVALID;
   const int nP = P->n_poses, nL = P->n_points, nO = P->n_obs;
   double* W = malloc(sizeof(double) * 18 * (size_t)nO);
@@ -542,8 +559,11 @@ int vus_ba_lm_optimize_cpu(const vus_ba_problem* P, int band, const vus_lm_param
   double current;
   vus_ba_error_cpu(P, poses, points, &current);
   rep->initial_error = current;
-  rep->status = 1;
-  while (rep->iterations < prm->max_iterations) {
+  /* gtsam's defaultOptimize returns before the first iterate() when the error is already within errorTol (converged)
+   * or maxIterations <= 0 (status 1): the state is untouched */
+  const int at_tol = current <= prm->error_tol;
+  rep->status = at_tol ? 0 : 1;
+  while (!at_tol && rep->iterations < prm->max_iterations) {
     /* ---- iterate(): linearise once, then search lambda ---- */
     double lin0;
     rc = vus_ba_linearize_cpu(P, poses, points, W, V, gl, Hpp, gp, &lin0);
@@ -555,12 +575,17 @@ int vus_ba_lm_optimize_cpu(const vus_ba_problem* P, int band, const vus_lm_param
       rc = vus_ba_schur_cpu(P, NULL, lambda, W, V, gl, Hpp, gp, Vinv, Y, Sb, band, gs, NULL);
       if (rc) break;
       vus_ba_band_solve_cpu(Sb, nP, band, gs, dp, &status);
-      ++rep->tries;
+      const int trial = rep->tries++;
+      if (tr && trial < VUS_LM_HIST) {
+        tr->lambda[trial] = lambda; tr->lin0[trial] = lin0; tr->status[trial] = status;
+        tr->lin1[trial] = tr->new1[trial] = NAN;
+      }
       int success = 0;
       if (status == 0) {
         vus_ba_backsub_cpu(P, W, Vinv, gl, dp, dl);
         double out[2];
         vus_ba_eval_step_cpu(P, poses, points, dp, dl, nposes, npoints, out);
+        if (tr && trial < VUS_LM_HIST) { tr->lin1[trial] = out[0]; tr->new1[trial] = out[1]; }
         double lin_change = lin0 - out[0]; /* oldLinearizedError - newlinearizedError */
         if (lin_change >= 0.0) {           /* "step is valid" */
           double cost_change = current - out[1];

@@ -335,6 +335,14 @@ typedef struct vus_lm_report {
   double lambda_hist[VUS_LM_HIST];
 } vus_lm_report;
 
+/* What the loop throws away, for the callers that ask for it (the *_trials_cpu entry points; vus_lm_report keeps its
+ * layout): per linear solve, the first VUS_LM_HIST of them, its lambda, the linearised error at 0 and at the step, the
+ * error at the trial state (NaN both where the solve failed) and the solve's status. */
+typedef struct vus_lm_trials {
+  double lambda[VUS_LM_HIST], lin0[VUS_LM_HIST], lin1[VUS_LM_HIST], new1[VUS_LM_HIST];
+  int status[VUS_LM_HIST];
+} vus_lm_trials;
+
 int vus_ba_error_cpu(const vus_ba_problem* P, const double* poses, const double* points, double* err);
 int vus_ba_linearize_cpu(const vus_ba_problem* P, const double* poses, const double* points, double* W, double* V,
                          double* gl, double* Hpp, double* gp, double* err);
@@ -466,8 +474,17 @@ int vus_nav_total_error_cpu(const vus_ba_problem* P, const vus_nav_factors* N, c
   return VUS_OK;
 }
 
+int vus_nav_lm_optimize_trials_cpu(const vus_ba_problem* P, const vus_nav_factors* N, const vus_lm_params* prm, double* poses,
+                                   double* vels, double* bias, double* points, vus_lm_report* rep, vus_lm_trials* tr);
+
 int vus_nav_lm_optimize_cpu(const vus_ba_problem* P, const vus_nav_factors* N, const vus_lm_params* prm, double* poses,
                             double* vels, double* bias, double* points, vus_lm_report* rep) {
+  return vus_nav_lm_optimize_trials_cpu(P, N, prm, poses, vels, bias, points, rep, NULL);
+}
+
+/* tr: NULL, or where the trials are recorded */
+int vus_nav_lm_optimize_trials_cpu(const vus_ba_problem* P, const vus_nav_factors* N, const vus_lm_params* prm, double* poses,
+                                   double* vels, double* bias, double* points, vus_lm_report* rep, vus_lm_trials* tr) {
   if (!P || !N || !prm || !poses || !vels || !bias || !points || !rep) return VUS_E_INVALID;
   const int nP = P->n_poses, nL = P->n_points, nO = P->n_obs, nc = 9 * nP + 6;
   double* W = malloc(sizeof(double) * 18 * (size_t)(nO + 1));
@@ -490,8 +507,11 @@ int vus_nav_lm_optimize_cpu(const vus_ba_problem* P, const vus_nav_factors* N, c
   double lambda = prm->lambda_initial;
   double current = nav_total_error(P, N, poses, vels, bias, points);
   rep->initial_error = current;
-  rep->status = 1;
-  while (rep->iterations < prm->max_iterations) {
+  /* gtsam's defaultOptimize returns before the first iterate() when the error is already within errorTol (converged)
+   * or maxIterations <= 0 (status 1): the state is untouched */
+  const int at_tol = current <= prm->error_tol;
+  rep->status = at_tol ? 0 : 1;
+  while (!at_tol && rep->iterations < prm->max_iterations) {
     double lin_stereo;
     vus_ba_linearize_cpu(P, poses, points, W, V, gl, Hpp, gp, &lin_stereo);
     memset(H, 0, sizeof(double) * (size_t)nc * nc);
@@ -536,7 +556,11 @@ int vus_nav_lm_optimize_cpu(const vus_ba_problem* P, const vus_nav_factors* N, c
       }
       for (int k = 0; k < nc; ++k) d[k] = -d[k];
       const int status = dense_cholesky_solve(S, nc, d);
-      ++rep->tries;
+      const int trial = rep->tries++;
+      if (tr && trial < VUS_LM_HIST) {
+        tr->lambda[trial] = lambda; tr->lin0[trial] = lin0; tr->status[trial] = status;
+        tr->lin1[trial] = tr->new1[trial] = NAN;
+      }
       int success = 0;
       if (status == 0) {
         for (int j = 0; j < nL; ++j) {
@@ -581,6 +605,7 @@ int vus_nav_lm_optimize_cpu(const vus_ba_problem* P, const vus_nav_factors* N, c
         for (int k = 0; k < 6; ++k) nbias[k] = bias[k] + d[9 * nP + k];
         for (int k = 0; k < 3 * nL; ++k) npoints[k] = points[k] + dl[k];
         const double nerr = nav_total_error(P, N, nposes, nvels, nbias, npoints);
+        if (tr && trial < VUS_LM_HIST) { tr->lin1[trial] = lin; tr->new1[trial] = nerr; }
         const double lin_change = lin0 - lin;
         if (lin_change >= 0.0) {
           const double cost_change = current - nerr;

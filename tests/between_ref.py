@@ -164,7 +164,10 @@ def lm_optimize(oracle, G, poses, priors=None, P=None, points=None, band=None, m
     lam = lambda_initial
     current = total(poses, points)
     rep["initial_error"] = current
-    while rep["iterations"] < max_iterations:
+    at_tol = current <= error_tol           # before the first iteration: converged, the state untouched
+    if at_tol:
+        rep["status"] = 0
+    while not at_tol and rep["iterations"] < max_iterations:
         new_error, stop, accepted = current, False, False
         Hb, gb, eb, fac = system(oracle, G, poses, n)
         while True:

@@ -150,37 +150,45 @@ def band_blocks(A, n_nodes, band, diagonals=None):
     return out
 
 
+def lm_trial(oracle, s, P, G, poses, vels, biases, points, lam, cholesky=False):
+    """One damped trial of the dense LM at (poses, vels, biases, points): solves the dense camera system (LU; `cholesky`:
+    solve()'s Cholesky of the Jacobi-scaled matrix, a second rounding of the same step), back-substitutes the landmarks
+    (vus_ba_backsub_cpu), takes the stereo linearised and new errors from vus_ba_eval_step_cpu and the inertial ones from
+    the factors.  Returns (lin0, lin1, new1, the trial state)."""
+    n = len(poses)
+    ref = dense_system(oracle, s, P, G, poses, vels, biases, points, lam)
+    x = solve(ref["A"], -ref["g"])[0] if cholesky else np.linalg.solve(ref["A"], -ref["g"])
+    dp, dv, _, db = split_step(x, n)
+    dl = oracle.ba_backsub(P, ref["lin"], ref["sch"]["Vinv"], dp)
+    npo, npt, lin_s, new_s = oracle.ba_eval_step(P, poses, points, dp, dl)
+    lin_n = 0.0
+    for rw, cols in ref["factors"]:
+        r = rw.copy()
+        for node, J in cols:
+            r += J @ x[6 * node:6 * node + J.shape[1]]
+        lin_n += 0.5 * float(r @ r)
+    nv, nb = vels + dv, biases + db
+    new_n = inertial_error(oracle, G, npo, nv, nb)
+    return ref["err"], lin_s + lin_n, new_s + new_n, (npo, nv, nb, npt)
+
+
 def lm_optimize(oracle, s, P, G, poses, vels, biases, points, max_iterations=100, lambda_initial=1e-5, lambda_factor=10.0,
                 lambda_upper=1e5, lambda_lower=0.0, min_model_fidelity=1e-3, rel_tol=1e-5, abs_tol=1e-5, error_tol=0.0):
-    """Dense LM with the oracle LM's iterate / tryLambda / convergence rules (GTSAM's defaults): each trial solves the
-    dense camera system, back-substitutes the landmarks (vus_ba_backsub_cpu), and takes the stereo linearised and new
-    errors from vus_ba_eval_step_cpu and the inertial ones from the factors.  Returns the state and a report with the
-    oracle's keys plus `trials` = [(lambda, accepted)]."""
-    n = len(poses)
+    """Dense LM with the oracle LM's iterate / tryLambda / convergence rules (GTSAM's defaults) over lm_trial().  Returns
+    the state and a report with the oracle's keys plus `trials` = [(lambda, accepted)]."""
     poses, vels, biases, points = (np.array(a, float, copy=True) for a in (poses, vels, biases, points))
     rep = {"iterations": 0, "outer": 0, "tries": 0, "status": 1, "err_hist": [], "lambda_hist": [], "trials": []}
     lam = lambda_initial
     current = total_error(oracle, P, G, poses, vels, biases, points)
     rep["initial_error"] = current
-    while rep["iterations"] < max_iterations:
+    at_tol = current <= error_tol           # before the first iteration: converged, the state untouched
+    if at_tol:
+        rep["status"] = 0
+    while not at_tol and rep["iterations"] < max_iterations:
         new_error, stop, accepted = current, False, False
         while True:
-            ref = dense_system(oracle, s, P, G, poses, vels, biases, points, lam)
-            x = np.linalg.solve(ref["A"], -ref["g"])
-            dp, dv, _, db = split_step(x, n)
-            dl = oracle.ba_backsub(P, ref["lin"], ref["sch"]["Vinv"], dp)
-            npo, npt, lin_s, new_s = oracle.ba_eval_step(P, poses, points, dp, dl)
-            lin_n = 0.0
-            for rw, cols in ref["factors"]:
-                r = rw.copy()
-                for node, J in cols:
-                    r += J @ x[6 * node:6 * node + J.shape[1]]
-                lin_n += 0.5 * float(r @ r)
-            nv, nb = vels + dv, biases + db
-            new_n = inertial_error(oracle, G, npo, nv, nb)
+            lin0, lin1, new1, trial = lm_trial(oracle, s, P, G, poses, vels, biases, points, lam)
             rep["tries"] += 1
-            lin0 = ref["err"]
-            lin1, new1 = lin_s + lin_n, new_s + new_n
             success = False
             if math.isfinite(lin1) and math.isfinite(new1):
                 lin_change = lin0 - lin1
@@ -191,7 +199,7 @@ def lm_optimize(oracle, s, P, G, poses, vels, biases, points, max_iterations=100
                     if abs(cost_change) < rel_tol * current:
                         stop = True
                     if success:
-                        poses, vels, biases, points, new_error = npo, nv, nb, npt, new1
+                        (poses, vels, biases, points), new_error = trial, new1
             rep["trials"].append((lam, success))
             if success:
                 lam = max(lambda_lower, lam / lambda_factor)

@@ -144,6 +144,9 @@ class RobustBA:
             S[6 * i:6 * i + 6, 6 * i:6 * i + 6] += lin["Hpp"][i].reshape(6, 6) + lam * np.eye(6)
         gs = lin["gp"].copy()
         np.add.at(gs, self.op, -np.einsum("nij,nj->ni", Y, lin["gl"][self.ol]))
+        if "pose_H" in lin:         # further factors on poses alone (between factors), undamped: [6 nP]^2 and [6 nP]
+            S = S + lin["pose_H"]
+            gs = gs + lin["pose_g"].reshape(nP, 6)
         Lc = np.linalg.cholesky(S)
         dp = -np.linalg.solve(Lc.T, np.linalg.solve(Lc, gs.reshape(-1))).reshape(nP, 6)
         t = lin["gl"].copy()
@@ -160,8 +163,8 @@ class RobustBA:
         lam = lambdaInitial
         current = self.error(poses, points)
         rep["initial_error"] = current
-        if current <= errorTol or maxIterations <= 0:
-            rep.update(status=0, final_error=current, final_lambda=lam)
+        if current <= errorTol or maxIterations <= 0:       # before the first iteration: converged / max iterations
+            rep.update(status=0 if current <= errorTol else 1, final_error=current, final_lambda=lam)
             return poses, points, rep
         while rep["iterations"] < maxIterations:
             lin = self.linearize(poses, points)

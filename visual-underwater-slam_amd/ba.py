@@ -1034,8 +1034,8 @@ class StereoBASolver:
         lam = prm.lambdaInitial
         current = self._lm_error(state) + (aux.error() if aux else 0.0)
         rep.initial_error = current
-        if current <= prm.errorTol or prm.maxIterations <= 0:
-            rep.status, rep.final_error, rep.final_lambda = 0, current, lam
+        if current <= prm.errorTol or prm.maxIterations <= 0:     # gtsam's defaultOptimize: before the first iterate()
+            rep.status, rep.final_error, rep.final_lambda = (0 if current <= prm.errorTol else 1), current, lam
             return state, rep
         while rep.iterations < prm.maxIterations:
             self._lm_linearize(state)                             # iterate(): linearise once
