@@ -146,13 +146,14 @@ def _raw_calls(Q, points, dl, new_points, V, gl):
     return V.cpu().numpy(), gl.cpu().numpy(), scal.cpu().numpy()
 
 
-def test_many_rows_cross_the_workgroup_boundary_and_two_runs_are_bit_identical(gpu):
-    """310 prior-carrying landmarks (more than one workgroup of 256 rows, no multiple of it) plus the adversarial set, on
-    arbitrary V / gl: the increments and the three scalars against the reference's prior term, and every output of two
-    calls on the same inputs bit for bit"""
+@pytest.mark.parametrize("rows", (256, 257, 310))
+def test_many_rows_cross_the_workgroup_boundary_and_two_runs_are_bit_identical(gpu, rows):
+    """256, 257 or 310 prior-carrying landmarks (exactly one workgroup of 256 rows; a second one with a single live row;
+    more than one and no multiple of it) plus the adversarial set, on arbitrary V / gl: the increments and the three
+    scalars against the reference's prior term, and every output of two calls on the same inputs bit for bit"""
     from visual_underwater_slam_amd import _lib
     from visual_underwater_slam_amd.ba import PointPriors
-    seq, single_lm = ppr.single_sighting(mono_problem.mixed_sequence())
+    seq, single_lm = ppr.single_sighting(mono_problem.mixed_sequence(n_lm=rows))
     nL = len(seq["points_gt"])
     U = synth._hash_uniform
     a = np.arange(3 * nL, dtype=np.int64)
@@ -162,7 +163,7 @@ def test_many_rows_cross_the_workgroup_boundary_and_two_runs_are_bit_identical(g
     mean = np.concatenate([mean0[:4], seq["points_gt"][every] + U(a, 11).reshape(nL, 3) - 0.5, mean0[4:]])
     sig = np.concatenate([sig0[:4], 0.05 + 3.0 * U(a, 12).reshape(nL, 3), sig0[4:]])
     Q = PointPriors(idx, mean, sig, nL)
-    assert (Q.n, Q.n_rows) == (nL + 8, nL) and nL > 256 and nL % 256
+    assert (Q.n, Q.n_rows) == (nL + 8, nL) and nL == rows
     _lib.call("vus_point_prior_check", Q.addr(), _lib.current_stream_ptr())
     assert int(_lib.load().vus_point_prior_work_doubles(Q.addr())) >= 4
     pk = {"n_poses": len(seq["poses_gt"]), "n_points": nL, "n_obs": len(seq["meas"]), "obs_pose": seq["obs_pose"],

@@ -133,7 +133,7 @@ def test_point_priors_host_csr():
     """ba.PointPriors sorts stably by landmark and builds its CSR with numpy before anything is uploaded"""
     from visual_underwater_slam_amd import ba
     idx = [7, 2, 7, 0, 9, 7, 2]
-    order, row_point, row_ptr = ba.point_prior_rows(idx)
+    order, row_point, row_ptr = ba.csr_rows(idx)
     assert order.tolist() == [3, 1, 6, 0, 2, 5, 4]              # graph order within one landmark
     assert row_point.tolist() == [0, 2, 7, 9] and row_ptr.tolist() == [0, 1, 3, 6, 7]
     assert row_point.dtype == np.int32 and row_ptr.dtype == np.int32
@@ -146,7 +146,7 @@ def test_point_priors_host_csr():
     assert Q.row_point.tolist() == [0, 2, 7, 9] and Q.row_ptr.tolist() == [0, 1, 3, 6, 7] and Q.addr()
     empty = ba.PointPriors([], np.zeros((0, 3)), np.zeros((0, 3)), 10, device="cpu")
     assert (empty.n, empty.n_rows) == (0, 0) and empty.c.row_point is None and empty.c.w is None
-    assert ba.point_prior_rows([])[2].tolist() == [0]
+    assert ba.csr_rows([])[2].tolist() == [0]
     for bad in (dict(point_idx=[0, 10]), dict(point_idx=[-1, 0]), dict(mean=np.zeros((3, 3))), dict(sigmas=np.zeros((2, 3))),
                 dict(sigmas=np.full((2, 3), np.inf)), dict(sigmas=-np.ones((2, 3))), dict(mean=np.full((2, 3), np.nan))):
         kw = dict(point_idx=[0, 1], mean=np.zeros((2, 3)), sigmas=np.ones((2, 3)), n_points=10, device="cpu")

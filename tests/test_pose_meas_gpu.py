@@ -68,10 +68,9 @@ def test_raw_entry_points_on_the_general_position_fixture(gpu):
 
 
 # -- 2 ------------------------------------------------------------------------------------------------------------------
-def _many_rows():
-    """310 poses in general position, a factor on every one given in DESCENDING pose order, five factors of both kinds on
+def _many_rows(nP):
+    """nP poses in general position, a factor on every one given in DESCENDING pose order, five factors of both kinds on
     pose 3 in the middle of the list, the six losses in turn"""
-    nP = 310
     U = synth._hash_uniform
     a3 = np.arange(3 * nP, dtype=np.int64)
     poses = np.zeros((nP, 12))
@@ -93,16 +92,18 @@ def _many_rows():
     return poses, pmr.PoseMeasSet(idx, kind, meas, sig, losses)
 
 
+@pytest.mark.parametrize("rows", (256, 257, 310))
 @pytest.mark.parametrize("stride", (1, 2, 3))
-def test_many_rows_cross_the_workgroup_boundary_and_two_runs_are_bit_identical(gpu, stride):
-    """310 factor-carrying poses (more than one workgroup of 256 rows, no multiple of it) on arbitrary Hpp / gp, with the
-    step on the pose nodes of a stride-1, 2 or 3 layout (the other nodes hold NaN): the increments, the four scalars and the
-    weights against the reference, and every output of two calls on the same inputs bit for bit"""
+def test_many_rows_cross_the_workgroup_boundary_and_two_runs_are_bit_identical(gpu, stride, rows):
+    """256, 257 or 310 factor-carrying poses (exactly one workgroup of 256 rows; a second one with a single live row; more
+    than one and no multiple of it) on arbitrary Hpp / gp, with the step on the pose nodes of a stride-1, 2 or 3 layout
+    (the other nodes hold NaN): the increments, the four scalars and the weights against the reference, and every output of
+    two calls on the same inputs bit for bit"""
     from visual_underwater_slam_amd import _lib
-    poses, G = _many_rows()
+    poses, G = _many_rows(rows)
     nP = len(poses)
     M = G.device(nP, pose_stride=stride)
-    assert (M.n, M.n_rows) == (nP + 4, nP) and nP > 256 and nP % 256 and (np.diff(G.idx) < 0).any()
+    assert (M.n, M.n_rows) == (nP + 4, nP) and nP == rows and (np.diff(G.idx) < 0).any()
     _lib.call("vus_pose_meas_check", M.addr(), _lib.current_stream_ptr())
     assert int(_lib.load().vus_pose_meas_work_doubles(M.addr())) >= 4
     U = synth._hash_uniform

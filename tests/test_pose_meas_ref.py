@@ -120,7 +120,7 @@ def test_pose_meas_host_csr():
     """ba.PoseMeasurements sorts stably by pose and builds its CSR with numpy before anything is uploaded"""
     from visual_underwater_slam_amd import ba
     idx = [7, 2, 7, 0, 9, 7, 2]
-    order, row_pose, row_ptr = ba.pose_meas_rows(idx)
+    order, row_pose, row_ptr = ba.csr_rows(idx)
     assert order.tolist() == [3, 1, 6, 0, 2, 5, 4]              # graph order within one pose
     assert row_pose.tolist() == [0, 2, 7, 9] and row_ptr.tolist() == [0, 1, 3, 6, 7]
     assert row_pose.dtype == np.int32 and row_ptr.dtype == np.int32
@@ -139,7 +139,7 @@ def test_pose_meas_host_csr():
     assert one.loss_kind.tolist() == [2] * 7 and not ba.PoseMeasurements(idx, kind, meas, sig, 10, device="cpu").robust
     empty = ba.PoseMeasurements([], [], np.zeros((0, 9)), np.zeros((0, 3)), 10, device="cpu")
     assert (empty.n, empty.n_rows) == (0, 0) and empty.c.row_pose is None and empty.c.w is None and not empty.robust
-    assert ba.pose_meas_rows([])[2].tolist() == [0]
+    assert ba.csr_rows([])[2].tolist() == [0]
     for bad in (dict(pose_idx=[0, 10]), dict(pose_idx=[-1, 0]), dict(kind=[0, 2]), dict(meas=np.zeros((3, 9))),
                 dict(sigmas=np.zeros((2, 3))), dict(sigmas=np.full((2, 3), np.inf)), dict(meas=np.full((2, 9), np.nan)),
                 dict(loss=[None]), dict(pose_stride=4)):

@@ -87,6 +87,40 @@ def _upload(a, device, dtype, shape=None):
     return (t if shape is None else t.reshape(shape)).contiguous()
 
 
+def csr_rows(idx):
+    """The CSR of include/vus_point_prior.h and include/vus_pose_meas.h on the host: (order, row_item, row_ptr) -- `order`
+    sorts the factors stably by their item `idx` (a landmark or a pose; graph order within one item), row_item lists the
+    distinct items ascending, row_ptr [n_rows + 1] points into the sorted factors."""
+    idx = np.asarray(idx, np.int64).reshape(-1)
+    order = np.argsort(idx, kind="stable")
+    row_item, first = np.unique(idx[order], return_index=True)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return order, i32(row_item), i32(np.append(first, len(idx)))
+
+
+def _factor_losses(loss, n, what):
+    """The robust models of the n factors of a set (`what` names it): `loss` is one model for all of them (robust_loss():
+    None = Gaussian) or a list (not a tuple) of n, one per factor -> [(kind, k)] of length n."""
+    if isinstance(loss, list) and len(loss) != n:
+        raise ValueError(f"{what}: {len(loss)} robust models for {n} factors")
+    return [robust_loss(x) for x in loss] if isinstance(loss, list) else [robust_loss(loss)] * n
+
+
+def _upload_losses(losses, device):
+    """(loss_kind int32 [n], loss_k float64 [n]) on the device from [(kind, k)]."""
+    return (_upload(np.array([k for k, _ in losses], np.int32), device, torch.int32),
+            _upload(np.array([k for _, k in losses], np.float64), device, torch.float64))
+
+
+def _require_finite(what, sigmas, **values):
+    """Refuse sigmas that are not finite and > 0, then any of the named `values` arrays that is not finite."""
+    if not (np.isfinite(sigmas).all() and (sigmas > 0).all()):
+        raise ValueError(f"{what}: sigmas must be finite and > 0")
+    for name, v in values.items():
+        if not np.isfinite(v).all():
+            raise ValueError(f"{what}: {name} must be finite")
+
+
 class _CMono(ctypes.Structure):
     _fields_ = [("is_mono", c_void_p), ("K", c_double * 5), ("inv_sigma", c_double)]
 
@@ -143,21 +177,17 @@ class BetweenFactors:
         if (pi == pj).any():
             f = int(np.nonzero(pi == pj)[0][0])
             raise ValueError(f"BetweenFactorPose3 {f} joins pose {int(pi[f])} to itself")
-        if not (np.isfinite(sig).all() and (sig > 0).all()):
-            raise ValueError("between factors: sigmas must be finite and > 0")
+        _require_finite("between factors", sig)
         self.n, self.n_poses, self.pose_stride = n, int(n_poses), int(pose_stride)
         self.span = int(np.abs(pi - pj).max())
-        if isinstance(loss, list) and len(loss) != n:
-            raise ValueError(f"between factors: {len(loss)} robust models for {n} factors")
-        self.losses = [robust_loss(x) for x in loss] if isinstance(loss, list) else [robust_loss(loss)] * n
+        self.losses = _factor_losses(loss, n, "between factors")
         self.host = dict(i=pi, j=pj, meas=meas, sigmas=sig, losses=self.losses)
         dev = torch.device(device)
         t = lambda a, dt: _upload(a, dev, dt)
         ps = self.pose_stride
         self.node1, self.node2 = t(ps * pi, torch.int32), t(ps * pj, torch.int32)
         self.meas, self.w = t(meas, torch.float64), t(1.0 / sig, torch.float64)
-        self.loss_kind = t(np.array([k for k, _ in self.losses], np.int32), torch.int32)
-        self.loss_k = t(np.array([k for _, k in self.losses], np.float64), torch.float64)
+        self.loss_kind, self.loss_k = _upload_losses(self.losses, dev)
         tn, ts, tp, tt = between_targets(ps * pi, ps * pj)
         self.tgt_node, self.tgt_s, self.tgt_ptr, self.tgt_terms = (t(a, torch.int32) for a in (tn, ts, tp, tt))
         p = _lib.ptr
@@ -167,21 +197,18 @@ class BetweenFactors:
     def addr(self):
         return ctypes.addressof(self.c)
 
+    def _fits(self, problem):
+        """Refuse a StereoBAProblem this set was not built for (the solver asks before it uses the set)."""
+        if self.pose_stride != problem.pose_stride or self.n_poses != problem.n_poses:
+            raise ValueError("BetweenFactors built for another problem (pose_stride / n_poses differ)")
+        if self.span * problem.pose_stride > problem.band:
+            raise ValueError(f"a between factor spans {self.span} poses, more than the problem's band of {problem.band} nodes: "
+                             "build the StereoBAProblem with between_span=BetweenFactors.span")
+
 
 class _CPointPriors(ctypes.Structure):
     _fields_ = [("n", c_int), ("n_points", c_int), ("n_rows", c_int), ("row_point", c_void_p), ("row_ptr", c_void_p),
                 ("mean", c_void_p), ("w", c_void_p)]
-
-
-def point_prior_rows(point_idx):
-    """The CSR of include/vus_point_prior.h on the host: (order, row_point, row_ptr) -- `order` sorts the factors stably by
-    landmark (graph order within one landmark), row_point lists the distinct landmarks ascending, row_ptr [n_rows + 1]
-    points into the sorted factors."""
-    idx = np.asarray(point_idx, np.int64).reshape(-1)
-    order = np.argsort(idx, kind="stable")
-    row_point, first = np.unique(idx[order], return_index=True)
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    return order, i32(row_point), i32(np.append(first, len(idx)))
 
 
 class PointPriors:
@@ -199,11 +226,8 @@ class PointPriors:
             raise ValueError(f"point priors: {n} landmark indices, {len(mean)} means, {len(sig)} sigmas")
         if ((idx < 0) | (idx >= n_points)).any():
             raise ValueError(f"point priors: a landmark index outside [0, {int(n_points)})")
-        if not (np.isfinite(sig).all() and (sig > 0).all()):
-            raise ValueError("point priors: sigmas must be finite and > 0")
-        if not np.isfinite(mean).all():
-            raise ValueError("point priors: means must be finite")
-        order, row_point, row_ptr = point_prior_rows(idx)
+        _require_finite("point priors", sig, means=mean)
+        order, row_point, row_ptr = csr_rows(idx)
         self.n, self.n_points, self.n_rows = n, int(n_points), len(row_point)
         self.host = dict(idx=idx[order], mean=mean[order], sigmas=sig[order], row_point=row_point, row_ptr=row_ptr)
         dev = torch.device(device)
@@ -216,6 +240,11 @@ class PointPriors:
     def addr(self):
         return ctypes.addressof(self.c)
 
+    def _fits(self, problem):
+        """Refuse a StereoBAProblem this set was not built for (the solver asks before it uses the set)."""
+        if self.n_points != problem.n_points:
+            raise ValueError(f"PointPriors built for {self.n_points} landmarks, the problem has {problem.n_points}")
+
 
 class _CPoseMeas(ctypes.Structure):
     _fields_ = [("n", c_int), ("n_poses", c_int), ("pose_stride", c_int), ("n_rows", c_int), ("row_pose", c_void_p),
@@ -224,17 +253,6 @@ class _CPoseMeas(ctypes.Structure):
 
 
 POSE_MEAS_POSITION, POSE_MEAS_ROTATION = 0, 1        # VUS_POSE_MEAS_* of include/vus_pose_meas.h
-
-
-def pose_meas_rows(pose_idx):
-    """The CSR of include/vus_pose_meas.h on the host: (order, row_pose, row_ptr) -- `order` sorts the factors stably by
-    pose (graph order within one pose), row_pose lists the distinct poses ascending, row_ptr [n_rows + 1] points into the
-    sorted factors."""
-    idx = np.asarray(pose_idx, np.int64).reshape(-1)
-    order = np.argsort(idx, kind="stable")
-    row_pose, first = np.unique(idx[order], return_index=True)
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    return order, i32(row_pose), i32(np.append(first, len(idx)))
 
 
 class PoseMeasurements:
@@ -260,16 +278,11 @@ class PoseMeasurements:
             raise ValueError(f"pose measurements: a pose index outside [0, {int(n_poses)})")
         if not np.isin(kind, (POSE_MEAS_POSITION, POSE_MEAS_ROTATION)).all():
             raise ValueError("pose measurements: kind must be POSE_MEAS_POSITION (0) or POSE_MEAS_ROTATION (1)")
-        if not (np.isfinite(sig).all() and (sig > 0).all()):
-            raise ValueError("pose measurements: sigmas must be finite and > 0")
-        if not np.isfinite(meas).all():
-            raise ValueError("pose measurements: measurements must be finite")
+        _require_finite("pose measurements", sig, measurements=meas)
         if int(pose_stride) not in (1, 2, 3):
             raise ValueError(f"pose_stride={pose_stride}: 1, 2 or 3")
-        if isinstance(loss, list) and len(loss) != n:
-            raise ValueError(f"pose measurements: {len(loss)} robust models for {n} factors")
-        losses = [robust_loss(x) for x in loss] if isinstance(loss, list) else [robust_loss(loss)] * n
-        order, row_pose, row_ptr = pose_meas_rows(idx)
+        losses = _factor_losses(loss, n, "pose measurements")
+        order, row_pose, row_ptr = csr_rows(idx)
         self.n, self.n_poses, self.pose_stride, self.n_rows = n, int(n_poses), int(pose_stride), len(row_pose)
         self.order = order
         self.losses = [losses[int(f)] for f in order]
@@ -281,14 +294,19 @@ class PoseMeasurements:
         self.row_pose, self.row_ptr = t(row_pose, torch.int32), t(row_ptr, torch.int32)
         self.kind = t(kind[order].astype(np.int32), torch.int32)
         self.meas, self.w = t(meas[order], torch.float64), t(1.0 / sig[order], torch.float64)
-        self.loss_kind = t(np.array([k for k, _ in self.losses], np.int32), torch.int32)
-        self.loss_k = t(np.array([k for _, k in self.losses], np.float64), torch.float64)
+        self.loss_kind, self.loss_k = _upload_losses(self.losses, dev)
         p = (lambda x: _lib.ptr(x)) if n else (lambda x: None)
         self.c = _CPoseMeas(n, self.n_poses, self.pose_stride, self.n_rows, p(self.row_pose), p(self.row_ptr), p(self.kind),
                             p(self.meas), p(self.w), p(self.loss_kind), p(self.loss_k))
 
     def addr(self):
         return ctypes.addressof(self.c)
+
+    def _fits(self, problem):
+        """Refuse a StereoBAProblem this set was not built for (the solver asks before it uses the set)."""
+        if self.pose_stride != problem.pose_stride or self.n_poses != problem.n_poses:
+            raise ValueError(f"PoseMeasurements built for {self.n_poses} poses at pose_stride {self.pose_stride}, the "
+                             f"problem has {problem.n_poses} at pose_stride {problem.pose_stride}")
 
 
 @dataclass
@@ -571,6 +589,10 @@ class BAMarginals:
 # family has no such stage) and `scal`, the view of its 4-double slot of the trial record.
 _Term = namedtuple("_Term", "error linearize assemble eval_step scal")
 
+# The buffers of one add-on family (between, point_prior, pose_meas) that is present: its factor object, `scal` again, the
+# scalar of its stand-alone error and the workspace of vus_<family>_work_doubles.
+_Family = namedtuple("_Family", "factors scal err work")
+
 
 class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
@@ -597,9 +619,13 @@ class StereoBASolver:
         self.Q = point_priors if point_priors is not None and point_priors.n else None      # no factors: no hooks
         self.M = pose_meas if pose_meas is not None and pose_meas.n else None
         self.B = between
-        # The optional factor families present, as (name of the slot view, error, linearize, assemble, eval_step), in the
-        # canonical order between, landmark priors, pose measurements, inertial (`inertial`: the stages an inertial
-        # subclass passes).  Every stage runs the stereo step first and then the terms in this order, which is what keeps:
+        # The add-on factor families, each described once: (C name: its entry points are vus_<name>_<stage>, its hooks
+        # <name>_<stage>; the factor object or None; the name of its slot view; the state tensor its stages read, 0 poses
+        # or -1 points; the arguments of its vus_<name>_check after the factors; whether it has an assemble stage).  The
+        # terms are the families present in this, the canonical order -- between, landmark priors, pose measurements --
+        # and then the inertial ones (`inertial`: the stages an inertial subclass passes, as (name of the slot view, error,
+        # linearize, assemble, eval_step)).  Every stage runs the stereo step first and then the terms in this order,
+        # which is what keeps:
         #   - linearize() before the landmark priors' linearize, which adds into V and gl; both before schur() and
         #     before _check_points (a prior can make a landmark determinate)
         #   - linearize(), which WRITES Hpp and gp, before the pose measurements' linearize, which adds into them, and that
@@ -608,17 +634,16 @@ class StereoBASolver:
         #     that enters before the Schur step, and the inertial terms a subclass passes stay last
         #   - between_assemble() after schur() and before the inertial assemble, which copies gs into its right-hand side
         #   - eval_step() before every other eval_step: they read new_poses / new_points
-        terms = []
-        if between is not None:
-            terms.append(("btw_scal", lambda s: self.between_error(s[0]), lambda s: self.between_linearize(s[0]),
-                          lambda lam: self.between_assemble(), lambda s: self.between_eval_step(s[0])))
-        if self.Q is not None:
-            terms.append(("pp_scal", lambda s: self.point_prior_error(s[-1]), lambda s: self.point_prior_linearize(s[-1]),
-                          lambda lam: None, lambda s: self.point_prior_eval_step(s[-1])))
-        if self.M is not None:
-            terms.append(("pm_scal", lambda s: self.pose_meas_error(s[0]), lambda s: self.pose_meas_linearize(s[0]),
-                          lambda lam: None, lambda s: self.pose_meas_eval_step(s[0])))
-        terms += inertial
+        families = [f for f in (("between", between, "btw_scal", 0, (B,), True),
+                                ("point_prior", self.Q, "pp_scal", -1, (), False),
+                                ("pose_meas", self.M, "pm_scal", 0, (), False)) if f[1] is not None]
+
+        def term(name, slot, at, assembles):
+            stage = lambda st: lambda s: getattr(self, f"{name}_{st}")(s[at])          # the public hook, on its state tensor
+            assemble = (lambda lam: getattr(self, f"{name}_assemble")()) if assembles else (lambda lam: None)
+            return slot, stage("error"), stage("linearize"), assemble, stage("eval_step")
+
+        terms = [term(name, slot, at, assembles) for name, _, slot, at, _, assembles in families] + list(inertial)
         # one record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised error
         # at the step, [2] new error, [3] spare, [4] (as two int32) the band solve's status word, then one slot of 4 per
         # term in list order: its three errors in the same order and a spare
@@ -630,29 +655,14 @@ class StereoBASolver:
             slot = self._trial[5 + 4 * i:9 + 4 * i]
             setattr(self, name, slot)
             self._terms.append(_Term(*stages, slot))
-        if between is not None:
-            if between.pose_stride != problem.pose_stride or between.n_poses != nP:
-                raise ValueError("BetweenFactors built for another problem (pose_stride / n_poses differ)")
-            if between.span * problem.pose_stride > B:
-                raise ValueError(f"a between factor spans {between.span} poses, more than the problem's band of {B} nodes: "
-                                 "build the StereoBAProblem with between_span=BetweenFactors.span")
-            self.btw_lin = torch.empty((between.n, 120), **f64)
-            self.btw_err = torch.empty((1,), **f64)
-            self.btw_work = torch.empty((int(_lib.load().vus_between_work_doubles(between.addr())),), **f64)
-            _lib.call("vus_between_check", between.addr(), B, _lib.current_stream_ptr())
-        if self.Q is not None:
-            if self.Q.n_points != nL:
-                raise ValueError(f"PointPriors built for {self.Q.n_points} landmarks, the problem has {nL}")
-            self.pp_err = torch.empty((1,), **f64)
-            self.pp_work = torch.empty((int(_lib.load().vus_point_prior_work_doubles(self.Q.addr())),), **f64)
-            _lib.call("vus_point_prior_check", self.Q.addr(), _lib.current_stream_ptr())
-        if self.M is not None:
-            if self.M.pose_stride != problem.pose_stride or self.M.n_poses != nP:
-                raise ValueError(f"PoseMeasurements built for {self.M.n_poses} poses at pose_stride {self.M.pose_stride}, the "
-                                 f"problem has {nP} at pose_stride {problem.pose_stride}")
-            self.pm_err = torch.empty((1,), **f64)
-            self.pm_work = torch.empty((int(_lib.load().vus_pose_meas_work_doubles(self.M.addr())),), **f64)
-            _lib.call("vus_pose_meas_check", self.M.addr(), _lib.current_stream_ptr())
+        self._families = {}
+        for name, factors, slot, _, check_args, _ in families:
+            factors._fits(problem)
+            work = torch.empty((int(getattr(_lib.load(), f"vus_{name}_work_doubles")(factors.addr())),), **f64)
+            self._families[name] = _Family(factors, getattr(self, slot), torch.empty((1,), **f64), work)
+            if factors is between:
+                self.btw_lin = torch.empty((between.n, 120), **f64)
+            _lib.call(f"vus_{name}_check", factors.addr(), *check_args, _lib.current_stream_ptr())
         # two-sided band solve (vus_ba_band_solve_split): worth it once the chain of panel steps is much longer than
         # the band; its workspace (pose-reversed copy of the lower half + the middle system) is allocated once
         self.band_rhs = 1
@@ -754,76 +764,62 @@ class StereoBASolver:
         _lib.call(fn, self._pp(), p(poses), p(points), p(self.dp), p(self.dl), p(self.new_poses),
                   p(self.new_points), p(self.scal[1:]), p(self.work), _lib.current_stream_ptr(), *extra)
 
-    # -- between factors (include/vus_between.h); every hook is a no-op without them ---------------------------------
+    # -- the add-on families: between factors (include/vus_between.h), priors on observed landmarks
+    # (include/vus_point_prior.h), position / attitude fixes on poses (include/vus_pose_meas.h).  Every hook is a no-op
+    # without its family.
+    def _family_call(self, name, stage, args) -> bool:
+        """vus_<name>_<stage>(factors, *args(family), stream) if the family is present -- `args` maps its _Family to the
+        arguments in between, tensors standing for their device pointers -- and whether it is."""
+        fam = self._families.get(name)
+        if fam is not None:
+            _lib.call(f"vus_{name}_{stage}", fam.factors.addr(), *(_lib.ptr(a) if torch.is_tensor(a) else a for a in args(fam)),
+                      _lib.current_stream_ptr())
+        return fam is not None
+
+    def _family_error(self, name, x) -> float:
+        ran = self._family_call(name, "error", lambda f: (x, f.err, f.work))
+        return float(self._families[name].err[0].item()) if ran else 0.0
+
     def between_error(self, poses) -> float:
         """Error (sum rho under a robust model) of the between factors at poses; 0.0 without them."""
-        if self.B is None:
-            return 0.0
-        _lib.call("vus_between_error", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.btw_err), _lib.ptr(self.btw_work),
-                  _lib.current_stream_ptr())
-        return float(self.btw_err[0].item())
+        return self._family_error("between", poses)
 
     def between_linearize(self, poses):
         """btw_lin = the per-factor products, btw_scal[0] = their linear error at delta = 0."""
-        if self.B is not None:
-            _lib.call("vus_between_linearize", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.btw_lin), _lib.ptr(self.btw_scal),
-                      _lib.ptr(self.btw_work), _lib.current_stream_ptr())
+        self._family_call("between", "linearize", lambda f: (poses, self.btw_lin, f.scal, f.work))
 
     def between_assemble(self):
         """Sband += the between blocks, gs += their gradient: after schur(), before an inertial assemble."""
-        if self.B is not None:
-            _lib.call("vus_between_assemble", self.B.addr(), _lib.ptr(self.btw_lin), self.P.band, _lib.ptr(self.Sband),
-                      _lib.ptr(self.gs), _lib.current_stream_ptr())
+        self._family_call("between", "assemble", lambda f: (self.btw_lin, self.P.band, self.Sband, self.gs))
 
     def between_eval_step(self, poses):
         """btw_scal[1] = linearised error at the step dp, btw_scal[2] = error at new_poses (after eval_step)."""
-        if self.B is not None:
-            _lib.call("vus_between_eval_step", self.B.addr(), _lib.ptr(poses), _lib.ptr(self.dp), _lib.ptr(self.new_poses),
-                      _lib.ptr(self.btw_scal[1:]), _lib.ptr(self.btw_work), _lib.current_stream_ptr())
+        self._family_call("between", "eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
 
-    # -- priors on observed landmarks (include/vus_point_prior.h); every hook is a no-op without them -----------------
     def point_prior_error(self, points) -> float:
         """Error of the landmark priors at points; 0.0 without them."""
-        if self.Q is None:
-            return 0.0
-        _lib.call("vus_point_prior_error", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.pp_err), _lib.ptr(self.pp_work),
-                  _lib.current_stream_ptr())
-        return float(self.pp_err[0].item())
+        return self._family_error("point_prior", points)
 
     def point_prior_linearize(self, points):
         """V, gl += the landmark priors at points, pp_scal[0] = their error: after linearize(), before schur()."""
-        if self.Q is not None:
-            _lib.call("vus_point_prior_linearize", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.V), _lib.ptr(self.gl),
-                      _lib.ptr(self.pp_scal), _lib.ptr(self.pp_work), _lib.current_stream_ptr())
+        self._family_call("point_prior", "linearize", lambda f: (points, self.V, self.gl, f.scal, f.work))
 
     def point_prior_eval_step(self, points):
         """pp_scal[1] = the priors' error at points + dl, pp_scal[2] = at new_points (after eval_step)."""
-        if self.Q is not None:
-            _lib.call("vus_point_prior_eval_step", self.Q.addr(), _lib.ptr(points), _lib.ptr(self.dl),
-                      _lib.ptr(self.new_points), _lib.ptr(self.pp_scal[1:]), _lib.ptr(self.pp_work),
-                      _lib.current_stream_ptr())
+        self._family_call("point_prior", "eval_step", lambda f: (points, self.dl, self.new_points, f.scal[1:], f.work))
 
-    # -- position / attitude fixes on poses (include/vus_pose_meas.h); every hook is a no-op without them -------------
     def pose_meas_error(self, poses) -> float:
         """Error (sum rho under a robust model) of the pose measurements at poses; 0.0 without them."""
-        if self.M is None:
-            return 0.0
-        _lib.call("vus_pose_meas_error", self.M.addr(), _lib.ptr(poses), _lib.ptr(self.pm_err), _lib.ptr(self.pm_work),
-                  _lib.current_stream_ptr())
-        return float(self.pm_err[0].item())
+        return self._family_error("pose_meas", poses)
 
     def pose_meas_linearize(self, poses):
         """Hpp, gp += the pose measurements at poses, pm_scal[0] = their linear error at delta = 0: after linearize(),
         before schur()."""
-        if self.M is not None:
-            _lib.call("vus_pose_meas_linearize", self.M.addr(), _lib.ptr(poses), _lib.ptr(self.Hpp), _lib.ptr(self.gp),
-                      _lib.ptr(self.pm_scal), _lib.ptr(self.pm_work), _lib.current_stream_ptr())
+        self._family_call("pose_meas", "linearize", lambda f: (poses, self.Hpp, self.gp, f.scal, f.work))
 
     def pose_meas_eval_step(self, poses):
         """pm_scal[1] = linearised error at the step dp, pm_scal[2] = error at new_poses (after eval_step)."""
-        if self.M is not None:
-            _lib.call("vus_pose_meas_eval_step", self.M.addr(), _lib.ptr(poses), _lib.ptr(self.dp), _lib.ptr(self.new_poses),
-                      _lib.ptr(self.pm_scal[1:]), _lib.ptr(self.pm_work), _lib.current_stream_ptr())
+        self._family_call("pose_meas", "eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
 
     def pose_meas_weights(self, poses) -> Optional[torch.Tensor]:
         """Robust weight w(d) of every pose measurement at poses, in the order the PoseMeasurements were GIVEN (all ones
@@ -831,7 +827,7 @@ class StereoBASolver:
         if self.M is None:
             return None
         w = torch.empty(self.M.n, dtype=torch.float64, device=self.P.device)
-        _lib.call("vus_pose_meas_weights", self.M.addr(), _lib.ptr(poses), _lib.ptr(w), _lib.current_stream_ptr())
+        self._family_call("pose_meas", "weights", lambda f: (poses, w))
         out = torch.empty_like(w)
         out[torch.from_numpy(self.M.order).to(self.P.device)] = w            # order: CSR slot -> input position
         return out

@@ -27,6 +27,7 @@
 #include "vus_common.h"
 #include "device_util.h"
 #include "se3_device.h"
+#include "factor_common.h"
 
 namespace {
 
@@ -174,17 +175,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
-}
-
-__device__ __forceinline__ void load12(const double* __restrict__ src, double* dst) {
-#pragma unroll
-  for (int k = 0; k < 12; ++k) dst[k] = src[k];
-}
-
-__device__ __forceinline__ double sym3(const double* v, int r, int c) {
-  // upper-triangle storage xx,xy,xz,yy,yz,zz
-  const int lo = r < c ? r : c, hi = r < c ? c : r;
-  return v[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
 }
 
 // body_P_sensor (include/vus_sensor.h): S and Ad(S^-1), made once on the host (make_sensor) and passed BY VALUE in the

@@ -7,10 +7,13 @@
 //   assemble    thread / element of a target block: the fixed-order sum over the block's CSR list, added to Sband (and gs)
 //   eval        thread / factor   linearised error at the step (old poses) and error at the new poses
 // Errors are summed by the fixed-order reduce of vus_common.hip (vus::reduce_partials).
+// Shared with the other pose kernels (se3_device.h): pose_local, load12, the robust-loss table and its per-factor dispatcher;
+// with the other add-on families (factor_common.h): read_back and the per-factor loss check.
 #include <cmath>
 #include <vector>
 #include "vus_common.h"
 #include "se3_device.h"
+#include "factor_common.h"
 
 namespace {
 
@@ -20,11 +23,6 @@ struct BetweenLin {
   double r[6];                // Log(meas^-1 T1^-1 T2), unwhitened
   double H1[36];              // -Ad(hx^-1), row-major
 };
-
-__device__ __forceinline__ void load12(const double* __restrict__ src, double* dst) {
-#pragma unroll
-  for (int k = 0; k < 12; ++k) dst[k] = src[k];
-}
 
 // residual and H1 of factor f at poses (H2 = I); with WITH_H = false only the residual
 template <bool WITH_H>
@@ -60,20 +58,6 @@ __device__ __forceinline__ void between_factor(const vus_between_factors& B, con
     }
 }
 
-// w and rho of factor f's own robust model (include/vus_robust.h; a kind out of range reads as Gaussian, vus_between_check
-// refuses it)
-__device__ __forceinline__ void factor_weight(const vus_between_factors& B, int f, double d2, double& w, double& rho) {
-  const double k = B.loss_k[f];
-  switch (B.loss_kind[f]) {
-    case VUS_LOSS_HUBER: robust_weight<VUS_LOSS_HUBER>(d2, k, w, rho); break;
-    case VUS_LOSS_CAUCHY: robust_weight<VUS_LOSS_CAUCHY>(d2, k, w, rho); break;
-    case VUS_LOSS_TUKEY: robust_weight<VUS_LOSS_TUKEY>(d2, k, w, rho); break;
-    case VUS_LOSS_GEMAN_MCCLURE: robust_weight<VUS_LOSS_GEMAN_MCCLURE>(d2, k, w, rho); break;
-    case VUS_LOSS_WELSCH: robust_weight<VUS_LOSS_WELSCH>(d2, k, w, rho); break;
-    default: robust_weight<VUS_LOSS_GAUSSIAN>(d2, k, w, rho); break;
-  }
-}
-
 __device__ __forceinline__ double whitened_sq(const double* __restrict__ w, const double* r) {
   double d2 = 0;
 #pragma unroll
@@ -92,7 +76,7 @@ __global__ __launch_bounds__(256) void between_linearize_kernel(vus_between_fact
   for (int k = 0; k < 6; ++k) w[k] = B.w[6 * (size_t)f + k];
   double rw, rho;
   const double d2 = whitened_sq(w, L.r);
-  factor_weight(B, f, d2, rw, rho);
+  robust_weight_of(B.loss_kind, B.loss_k, f, d2, rw, rho);
 #pragma unroll
   for (int k = 0; k < 6; ++k) w2[k] = rw * w[k] * w[k];     // the weighted information of each residual row
   double* o = lin + LIN * (size_t)f;
@@ -153,7 +137,7 @@ __global__ __launch_bounds__(256) void between_eval_kernel(vus_between_factors B
   double rw, rho;
   if (part_lin != nullptr) {
     between_factor<true>(B, poses, f, L);
-    factor_weight(B, f, whitened_sq(w, L.r), rw, rho);
+    robust_weight_of(B.loss_kind, B.loss_k, f, whitened_sq(w, L.r), rw, rho);
     const double* d1 = dp + 6 * (size_t)B.node1[f];
     const double* d2 = dp + 6 * (size_t)B.node2[f];
     double e = 0;
@@ -167,7 +151,7 @@ __global__ __launch_bounds__(256) void between_eval_kernel(vus_between_factors B
     part_lin[f] = 0.5 * rw * e;
   }
   between_factor<false>(B, new_poses, f, L);
-  factor_weight(B, f, whitened_sq(w, L.r), rw, rho);
+  robust_weight_of(B.loss_kind, B.loss_k, f, whitened_sq(w, L.r), rw, rho);
   part_new[f] = rho;
 }
 
@@ -177,15 +161,6 @@ int check_args(const vus_between_factors* B) {
               "bad sizes: n=%d n_nodes=%d pose_stride=%d", B->n, B->n_nodes, B->pose_stride);
   VUS_REQUIRE(B->node1 && B->node2 && B->meas && B->w && B->loss_kind && B->loss_k, "factor arrays are null");
   VUS_REQUIRE(B->n_targets >= 1 && B->tgt_node && B->tgt_s && B->tgt_ptr && B->tgt_terms, "target arrays are null");
-  return VUS_OK;
-}
-
-template <typename T>
-int read_back(const T* src, size_t n, std::vector<T>& dst, hipStream_t st) {
-  dst.resize(n);
-  if (n == 0) return VUS_OK;
-  VUS_CHECK_HIP(hipMemcpyAsync(dst.data(), src, sizeof(T) * n, hipMemcpyDeviceToHost, st));
-  VUS_CHECK_HIP(hipStreamSynchronize(st));
   return VUS_OK;
 }
 
@@ -218,9 +193,7 @@ extern "C" int vus_between_check(const vus_between_factors* B, int band, void* s
                 "factor %d: nodes (%d, %d) are not pose nodes of %d nodes at pose_stride %d", f, n1[f], n2[f], B->n_nodes, ps);
     VUS_REQUIRE(n1[f] != n2[f], "factor %d joins node %d to itself", f, n1[f]);
     VUS_REQUIRE(std::abs(n1[f] - n2[f]) <= band, "factor %d: nodes %d and %d are more than band=%d apart", f, n1[f], n2[f], band);
-    VUS_REQUIRE(kind[f] >= VUS_LOSS_GAUSSIAN && kind[f] <= VUS_LOSS_WELSCH, "factor %d: unknown loss kind %d", f, kind[f]);
-    VUS_REQUIRE(kind[f] == VUS_LOSS_GAUSSIAN || (lk[f] > 0.0 && std::isfinite(lk[f])),
-                "factor %d: loss parameter k=%g must be finite and > 0", f, lk[f]);
+    if (int rc = check_factor_loss(f, kind[f], lk[f])) return rc;
   }
   for (int q = 0; q < B->n_targets; ++q) {
     const int node = tn[q], s = ts[q];

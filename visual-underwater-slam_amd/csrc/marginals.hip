@@ -13,6 +13,7 @@
 // Layouts and the recursion: include/vus_marginals.h, DESIGN.md "Marginal covariances".
 #include "vus_common.h"
 #include "band_index.h"
+#include "factor_common.h"
 #include "../../include/vus_marginals.h"
 
 namespace {
@@ -220,11 +221,6 @@ __global__ void point_check_kernel(int n_points, const double* __restrict__ V, i
   const bool ok = scale > 0.0 && a > eps * scale && m2 > eps * scale * scale && m3 > eps * scale * scale * scale &&
                   isfinite(m3);
   if (!ok) atomicMin(first_bad, j);
-}
-
-__device__ __forceinline__ double sym3(const double* v, int r, int c) {
-  const int lo = r < c ? r : c, hi = r < c ? c : r;
-  return v[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
 }
 
 __global__ void point_cov_init_kernel(int n_points, const double* __restrict__ Vinv, double* __restrict__ cov) {

@@ -6,36 +6,16 @@
 //               stores (a row owns its landmark: no atomics); the row's error to the workgroup's partial
 //   eval        thread / row: the error at p + dl and at new_points (or at p alone for vus_point_prior_error)
 // Errors: a fixed LDS tree per workgroup -> one partial per workgroup in `work` -> vus::reduce_partials in index order.
+// Shared with pose_meas.hip (factor_common.h): that tree (block_partial), the guarded row lookup (csr_row), and on the host
+// read_back, zero_out and the row and weight checks.
 #include <cmath>
 #include <vector>
 #include "vus_common.h"
+#include "factor_common.h"
 
 namespace {
 
 constexpr int WG = 256;       // 4 waves of 64; one row per thread
-
-// the workgroup's sum of `e` (0 for a thread without a row) in a fixed tree order, written by thread 0 to part[block]
-__device__ __forceinline__ void block_partial(double e, double* __restrict__ part) {
-  __shared__ double s[WG];
-  s[threadIdx.x] = e;
-  __syncthreads();
-#pragma unroll
-  for (int o = WG / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = s[0];
-}
-
-// row r of the CSR: its landmark j and factor range [a, b); false for a row a checked factor set cannot hold
-// (vus_point_prior_check refuses it), which then reads and writes nothing
-__device__ __forceinline__ bool row_of(const vus_point_priors& Q, int r, int& j, int& a, int& b) {
-  if (r >= Q.n_rows) return false;
-  j = Q.row_point[r];
-  a = Q.row_ptr[r];
-  b = Q.row_ptr[r + 1];
-  return (unsigned)j < (unsigned)Q.n_points && a >= 0 && a <= b && b <= Q.n;
-}
 
 __device__ __forceinline__ void load3(const double* __restrict__ src, double* dst) {
   dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];      // [n,3] rows are 24 bytes: three double loads
@@ -63,7 +43,7 @@ __global__ __launch_bounds__(WG) void point_prior_linearize_kernel(vus_point_pri
   const int r = blockIdx.x * WG + threadIdx.x;
   int j, a, b;
   double e = 0;
-  if (row_of(Q, r, j, a, b)) {
+  if (csr_row(Q.n_rows, Q.row_point, Q.row_ptr, Q.n_points, Q.n, r, j, a, b)) {
     double p[3], g[3];
     load3(points + 3 * (size_t)j, p);
     load3(gl + 3 * (size_t)j, g);
@@ -85,7 +65,7 @@ __global__ __launch_bounds__(WG) void point_prior_linearize_kernel(vus_point_pri
     gl[3 * (size_t)j] = g[0]; gl[3 * (size_t)j + 1] = g[1]; gl[3 * (size_t)j + 2] = g[2];
     e *= 0.5;
   }
-  block_partial(e, err_part);
+  block_partial<WG>(e, err_part);
 }
 
 // part_lin[block] = the rows' error at points + dl (skipped when part_lin is null), part_new[block] = at new_points
@@ -95,7 +75,7 @@ __global__ __launch_bounds__(WG) void point_prior_eval_kernel(vus_point_priors Q
                                                               double* __restrict__ part_lin, double* __restrict__ part_new) {
   const int r = blockIdx.x * WG + threadIdx.x;
   int j, a, b;
-  const bool has = row_of(Q, r, j, a, b);
+  const bool has = csr_row(Q.n_rows, Q.row_point, Q.row_ptr, Q.n_points, Q.n, r, j, a, b);
   double p[3];
   if (part_lin != nullptr) {                              // uniform over the launch: the barriers below stay convergent
     double e = 0;
@@ -107,7 +87,7 @@ __global__ __launch_bounds__(WG) void point_prior_eval_kernel(vus_point_priors Q
       for (int k = 0; k < 3; ++k) p[k] += d[k];
       e = row_error(Q, a, b, p);
     }
-    block_partial(e, part_lin);
+    block_partial<WG>(e, part_lin);
     __syncthreads();                                      // the LDS tree is reused below
   }
   double e = 0;
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(WG) void point_prior_eval_kernel(vus_point_priors Q
     load3(new_points + 3 * (size_t)j, p);
     e = row_error(Q, a, b, p);
   }
-  block_partial(e, part_new);
+  block_partial<WG>(e, part_new);
 }
 
 int check_args(const vus_point_priors* Q) {
@@ -127,28 +107,11 @@ int check_args(const vus_point_priors* Q) {
   return VUS_OK;
 }
 
-int n_blocks(const vus_point_priors* Q) { return cdiv(Q->n_rows, WG); }
-
-template <typename T>
-int read_back(const T* src, size_t n, std::vector<T>& dst, hipStream_t st) {
-  dst.resize(n);
-  if (n == 0) return VUS_OK;
-  VUS_CHECK_HIP(hipMemcpyAsync(dst.data(), src, sizeof(T) * n, hipMemcpyDeviceToHost, st));
-  VUS_CHECK_HIP(hipStreamSynchronize(st));
-  return VUS_OK;
-}
-
-// n == 0: the sums are 0 and nothing is launched
-int zero_out(double* out, int count, hipStream_t st) {
-  VUS_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(double) * count, st));
-  return VUS_OK;
-}
-
 }  // namespace
 
 extern "C" long long vus_point_prior_work_doubles(const vus_point_priors* Q) {
   if (!Q || Q->n_rows < 0) return 0;
-  return 2ll * n_blocks(Q) + 8;
+  return 2ll * cdiv(Q->n_rows, WG) + 8;
 }
 
 extern "C" int vus_point_prior_check(const vus_point_priors* Q, void* stream) {
@@ -161,15 +124,9 @@ extern "C" int vus_point_prior_check(const vus_point_priors* Q, void* stream) {
   if (int rc = read_back(Q->row_ptr, (size_t)Q->n_rows + 1, ptr, st)) return rc;
   if (int rc = read_back(Q->mean, 3 * (size_t)Q->n, mean, st)) return rc;
   if (int rc = read_back(Q->w, 3 * (size_t)Q->n, w, st)) return rc;
-  VUS_REQUIRE(ptr[0] == 0 && ptr[Q->n_rows] == Q->n, "row_ptr runs from %d to %d, not from 0 to n=%d", ptr[0], ptr[Q->n_rows], Q->n);
-  for (int r = 0; r < Q->n_rows; ++r) {
-    VUS_REQUIRE(rp[r] >= 0 && rp[r] < Q->n_points, "row %d: landmark %d outside [0, %d)", r, rp[r], Q->n_points);
-    VUS_REQUIRE(r == 0 || rp[r] > rp[r - 1], "row_point is not strictly ascending at row %d (%d after %d)", r, rp[r],
-                r ? rp[r - 1] : 0);
-    VUS_REQUIRE(ptr[r + 1] > ptr[r], "row %d (landmark %d) is empty or row_ptr decreases (%d, %d)", r, rp[r], ptr[r], ptr[r + 1]);
-  }
+  if (int rc = check_csr_rows(rp, ptr, Q->n_rows, Q->n, Q->n_points, "row_point", "landmark")) return rc;
   for (size_t k = 0; k < 3 * (size_t)Q->n; ++k) {
-    VUS_REQUIRE(std::isfinite(w[k]) && w[k] > 0.0, "factor %d: weight w=%g must be finite and > 0", (int)(k / 3), w[k]);
+    if (int rc = check_factor_weight((int)(k / 3), w[k])) return rc;
     VUS_REQUIRE(std::isfinite(mean[k]), "factor %d: mean %g is not finite", (int)(k / 3), mean[k]);
   }
   return VUS_OK;
@@ -182,7 +139,7 @@ extern "C" int vus_point_prior_linearize(const vus_point_priors* Q, const double
   hipStream_t st = vus::as_stream(stream);
   if (Q->n == 0) return zero_out(err, 1, st);
   VUS_REQUIRE(points && V && gl && work, "null buffer");
-  const int nb = n_blocks(Q);
+  const int nb = cdiv(Q->n_rows, WG);
   point_prior_linearize_kernel<<<nb, WG, 0, st>>>(*Q, points, V, gl, work);
   vus::reduce_partials(work, nb, err, st);
   VUS_CHECK_LAUNCH("point_prior_linearize");
@@ -196,7 +153,7 @@ extern "C" int vus_point_prior_eval_step(const vus_point_priors* Q, const double
   hipStream_t st = vus::as_stream(stream);
   if (Q->n == 0) return zero_out(out, 2, st);
   VUS_REQUIRE(points && dl && new_points && work, "null buffer");
-  const int nb = n_blocks(Q);
+  const int nb = cdiv(Q->n_rows, WG);
   point_prior_eval_kernel<<<nb, WG, 0, st>>>(*Q, points, dl, new_points, work, work + nb);
   vus::reduce_partials(work, nb, out, st);
   vus::reduce_partials(work + nb, nb, out + 1, st);
@@ -211,7 +168,7 @@ extern "C" int vus_point_prior_error(const vus_point_priors* Q, const double* po
   hipStream_t st = vus::as_stream(stream);
   if (Q->n == 0) return zero_out(err, 1, st);
   VUS_REQUIRE(points && work, "null buffer");
-  const int nb = n_blocks(Q);
+  const int nb = cdiv(Q->n_rows, WG);
   point_prior_eval_kernel<<<nb, WG, 0, st>>>(*Q, nullptr, nullptr, points, nullptr, work + nb);
   vus::reduce_partials(work + nb, nb, err, st);
   VUS_CHECK_LAUNCH("point_prior_error");

@@ -9,56 +9,18 @@
 //               for vus_pose_meas_error)
 //   weights     thread / row: w(d) of its factors
 // Errors: a fixed LDS tree per workgroup -> one partial per workgroup in `work` -> vus::reduce_partials in index order.
+// Shared with the other pose kernels (se3_device.h): so3_logmap, load12, the robust-loss table and its per-factor dispatcher;
+// with point_prior.hip (factor_common.h): that tree (block_partial), the guarded row lookup (csr_row), and on the host
+// read_back, zero_out and the row, weight and loss checks.
 #include <cmath>
 #include <vector>
 #include "vus_common.h"
 #include "se3_device.h"
+#include "factor_common.h"
 
 namespace {
 
 constexpr int WG = 256;       // 4 waves of 64; one row per thread
-
-// the workgroup's sum of `e` (0 for a thread without a row) in a fixed tree order, written by thread 0 to part[block]
-__device__ __forceinline__ void block_partial(double e, double* __restrict__ part) {
-  __shared__ double s[WG];
-  s[threadIdx.x] = e;
-  __syncthreads();
-#pragma unroll
-  for (int o = WG / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = s[0];
-}
-
-// row r of the CSR: its pose i and factor range [a, b); false for a row a checked factor set cannot hold
-// (vus_pose_meas_check refuses it), which then reads and writes nothing
-__device__ __forceinline__ bool row_of(const vus_pose_meas& M, int r, int& i, int& a, int& b) {
-  if (r >= M.n_rows) return false;
-  i = M.row_pose[r];
-  a = M.row_ptr[r];
-  b = M.row_ptr[r + 1];
-  return (unsigned)i < (unsigned)M.n_poses && a >= 0 && a <= b && b <= M.n;
-}
-
-__device__ __forceinline__ void load12(const double* __restrict__ src, double* dst) {
-#pragma unroll
-  for (int k = 0; k < 12; ++k) dst[k] = src[k];
-}
-
-// w and rho of factor f's own robust model (include/vus_robust.h; a kind out of range reads as Gaussian, vus_pose_meas_check
-// refuses it)
-__device__ __forceinline__ void factor_weight(const vus_pose_meas& M, int f, double d2, double& w, double& rho) {
-  const double k = M.loss_k[f];
-  switch (M.loss_kind[f]) {
-    case VUS_LOSS_HUBER: robust_weight<VUS_LOSS_HUBER>(d2, k, w, rho); break;
-    case VUS_LOSS_CAUCHY: robust_weight<VUS_LOSS_CAUCHY>(d2, k, w, rho); break;
-    case VUS_LOSS_TUKEY: robust_weight<VUS_LOSS_TUKEY>(d2, k, w, rho); break;
-    case VUS_LOSS_GEMAN_MCCLURE: robust_weight<VUS_LOSS_GEMAN_MCCLURE>(d2, k, w, rho); break;
-    case VUS_LOSS_WELSCH: robust_weight<VUS_LOSS_WELSCH>(d2, k, w, rho); break;
-    default: robust_weight<VUS_LOSS_GAUSSIAN>(d2, k, w, rho); break;
-  }
-}
 
 // factor f at the pose T (flat12): the unwhitened residual r [3], the whitening w [3], d2 = |W r|^2 and, WITH_J, the
 // unwhitened Jacobian J [3][6] in the tangent order (omega, v)
@@ -112,7 +74,7 @@ __global__ __launch_bounds__(WG) void pose_meas_linearize_kernel(vus_pose_meas M
   const int row = blockIdx.x * WG + threadIdx.x;
   int i, a, b;
   double e = 0;
-  if (row_of(M, row, i, a, b)) {
+  if (csr_row(M.n_rows, M.row_pose, M.row_ptr, M.n_poses, M.n, row, i, a, b)) {
     double T[12];
     load12(poses + 12 * (size_t)i, T);
     double h[21], g[6];
@@ -123,7 +85,7 @@ __global__ __launch_bounds__(WG) void pose_meas_linearize_kernel(vus_pose_meas M
     for (int f = a; f < b; ++f) {
       double r[3], w[3], J[3][6], d2, rw, rho;
       factor_at<true>(M, f, T, r, w, d2, J);
-      factor_weight(M, f, d2, rw, rho);
+      robust_weight_of(M.loss_kind, M.loss_k, f, d2, rw, rho);
       double w2[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) w2[k] = rw * w[k] * w[k];     // the weighted information of each residual row
@@ -144,7 +106,7 @@ __global__ __launch_bounds__(WG) void pose_meas_linearize_kernel(vus_pose_meas M
       G[x] += g[x];
     }
   }
-  block_partial(e, err_part);
+  block_partial<WG>(e, err_part);
 }
 
 // part_lin[block] = the rows' 0.5 sum w |b + J d|^2 at the old poses with d = dp[pose_stride * i] (skipped when part_lin is
@@ -155,7 +117,7 @@ __global__ __launch_bounds__(WG) void pose_meas_eval_kernel(vus_pose_meas M, con
                                                             double* __restrict__ part_lin, double* __restrict__ part_new) {
   const int row = blockIdx.x * WG + threadIdx.x;
   int i, a, b;
-  const bool has = row_of(M, row, i, a, b);
+  const bool has = csr_row(M.n_rows, M.row_pose, M.row_ptr, M.n_poses, M.n, row, i, a, b);
   // one pass per output over ONE instance of the factor code: pass 0 at the old poses with the step, pass 1 at new_poses
   double e_lin = 0, e_new = 0;
   if (has) {
@@ -169,7 +131,7 @@ __global__ __launch_bounds__(WG) void pose_meas_eval_kernel(vus_pose_meas M, con
       for (int f = a; f < b; ++f) {
         double r[3], w[3], J[3][6], d2, rw, rho;
         factor_at<true>(M, f, T, r, w, d2, J);
-        factor_weight(M, f, d2, rw, rho);
+        robust_weight_of(M.loss_kind, M.loss_k, f, d2, rw, rho);
         double s = 0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -184,23 +146,23 @@ __global__ __launch_bounds__(WG) void pose_meas_eval_kernel(vus_pose_meas M, con
     }
   }
   if (part_lin != nullptr) {                              // uniform over the launch: the barriers stay convergent
-    block_partial(e_lin, part_lin);
+    block_partial<WG>(e_lin, part_lin);
     __syncthreads();                                      // the LDS tree is reused below
   }
-  block_partial(e_new, part_new);
+  block_partial<WG>(e_new, part_new);
 }
 
 __global__ __launch_bounds__(WG) void pose_meas_weights_kernel(vus_pose_meas M, const double* __restrict__ poses,
                                                                double* __restrict__ w_out) {
   const int row = blockIdx.x * WG + threadIdx.x;
   int i, a, b;
-  if (!row_of(M, row, i, a, b)) return;
+  if (!csr_row(M.n_rows, M.row_pose, M.row_ptr, M.n_poses, M.n, row, i, a, b)) return;
   double T[12];
   load12(poses + 12 * (size_t)i, T);
   for (int f = a; f < b; ++f) {
     double r[3], w[3], d2, rw, rho;
     factor_at<false>(M, f, T, r, w, d2, nullptr);
-    factor_weight(M, f, d2, rw, rho);
+    robust_weight_of(M.loss_kind, M.loss_k, f, d2, rw, rho);
     w_out[f] = rw;
   }
 }
@@ -215,28 +177,11 @@ int check_args(const vus_pose_meas* M) {
   return VUS_OK;
 }
 
-int n_blocks(const vus_pose_meas* M) { return cdiv(M->n_rows, WG); }
-
-template <typename T>
-int read_back(const T* src, size_t n, std::vector<T>& dst, hipStream_t st) {
-  dst.resize(n);
-  if (n == 0) return VUS_OK;
-  VUS_CHECK_HIP(hipMemcpyAsync(dst.data(), src, sizeof(T) * n, hipMemcpyDeviceToHost, st));
-  VUS_CHECK_HIP(hipStreamSynchronize(st));
-  return VUS_OK;
-}
-
-// n == 0: the sums are 0 and nothing is launched
-int zero_out(double* out, int count, hipStream_t st) {
-  VUS_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(double) * count, st));
-  return VUS_OK;
-}
-
 }  // namespace
 
 extern "C" long long vus_pose_meas_work_doubles(const vus_pose_meas* M) {
   if (!M || M->n_rows < 0) return 0;
-  return 2ll * n_blocks(M) + 8;
+  return 2ll * cdiv(M->n_rows, WG) + 8;
 }
 
 extern "C" int vus_pose_meas_check(const vus_pose_meas* M, void* stream) {
@@ -253,19 +198,12 @@ extern "C" int vus_pose_meas_check(const vus_pose_meas* M, void* stream) {
   if (int rc = read_back(M->w, 3 * (size_t)n, w, st)) return rc;
   if (int rc = read_back(M->loss_kind, n, lkind, st)) return rc;
   if (int rc = read_back(M->loss_k, n, lk, st)) return rc;
-  VUS_REQUIRE(ptr[0] == 0 && ptr[M->n_rows] == n, "row_ptr runs from %d to %d, not from 0 to n=%d", ptr[0], ptr[M->n_rows], n);
-  for (int r = 0; r < M->n_rows; ++r) {
-    VUS_REQUIRE(rp[r] >= 0 && rp[r] < M->n_poses, "row %d: pose %d outside [0, %d)", r, rp[r], M->n_poses);
-    VUS_REQUIRE(r == 0 || rp[r] > rp[r - 1], "row_pose is not strictly ascending at row %d (%d after %d)", r, rp[r],
-                r ? rp[r - 1] : 0);
-    VUS_REQUIRE(ptr[r + 1] > ptr[r], "row %d (pose %d) is empty or row_ptr decreases (%d, %d)", r, rp[r], ptr[r], ptr[r + 1]);
-  }
+  if (int rc = check_csr_rows(rp, ptr, M->n_rows, n, M->n_poses, "row_pose", "pose")) return rc;
   for (int f = 0; f < n; ++f) {
     VUS_REQUIRE(kind[f] == VUS_POSE_MEAS_POSITION || kind[f] == VUS_POSE_MEAS_ROTATION, "factor %d: unknown measurement kind %d",
                 f, kind[f]);
     for (int k = 0; k < 3; ++k)
-      VUS_REQUIRE(std::isfinite(w[3 * (size_t)f + k]) && w[3 * (size_t)f + k] > 0.0, "factor %d: weight w=%g must be finite and > 0",
-                  f, w[3 * (size_t)f + k]);
+      if (int rc = check_factor_weight(f, w[3 * (size_t)f + k])) return rc;
     const double* m = meas.data() + 9 * (size_t)f;
     for (int k = 0; k < 9; ++k) VUS_REQUIRE(std::isfinite(m[k]), "factor %d: measurement %g is not finite", f, m[k]);
     if (kind[f] == VUS_POSE_MEAS_ROTATION) {
@@ -279,9 +217,7 @@ extern "C" int vus_pose_meas_check(const vus_pose_meas* M, void* stream) {
       VUS_REQUIRE(dev <= 1e-9, "factor %d: the measured rotation is not orthonormal (max |R^T R - I| = %g)", f, dev);
       VUS_REQUIRE(det > 0.0, "factor %d: the measured rotation is a reflection (det = %g)", f, det);
     }
-    VUS_REQUIRE(lkind[f] >= VUS_LOSS_GAUSSIAN && lkind[f] <= VUS_LOSS_WELSCH, "factor %d: unknown loss kind %d", f, lkind[f]);
-    VUS_REQUIRE(lkind[f] == VUS_LOSS_GAUSSIAN || (lk[f] > 0.0 && std::isfinite(lk[f])),
-                "factor %d: loss parameter k=%g must be finite and > 0", f, lk[f]);
+    if (int rc = check_factor_loss(f, lkind[f], lk[f])) return rc;
   }
   return VUS_OK;
 }
@@ -293,7 +229,7 @@ extern "C" int vus_pose_meas_linearize(const vus_pose_meas* M, const double* pos
   hipStream_t st = vus::as_stream(stream);
   if (M->n == 0) return zero_out(err, 1, st);
   VUS_REQUIRE(poses && Hpp && gp && work, "null buffer");
-  const int nb = n_blocks(M);
+  const int nb = cdiv(M->n_rows, WG);
   pose_meas_linearize_kernel<<<nb, WG, 0, st>>>(*M, poses, Hpp, gp, work);
   vus::reduce_partials(work, nb, err, st);
   VUS_CHECK_LAUNCH("pose_meas_linearize");
@@ -307,7 +243,7 @@ extern "C" int vus_pose_meas_eval_step(const vus_pose_meas* M, const double* pos
   hipStream_t st = vus::as_stream(stream);
   if (M->n == 0) return zero_out(out, 2, st);
   VUS_REQUIRE(poses && dp && new_poses && work, "null buffer");
-  const int nb = n_blocks(M);
+  const int nb = cdiv(M->n_rows, WG);
   pose_meas_eval_kernel<<<nb, WG, 0, st>>>(*M, poses, dp, new_poses, work, work + nb);
   vus::reduce_partials(work, nb, out, st);
   vus::reduce_partials(work + nb, nb, out + 1, st);
@@ -321,7 +257,7 @@ extern "C" int vus_pose_meas_error(const vus_pose_meas* M, const double* poses, 
   hipStream_t st = vus::as_stream(stream);
   if (M->n == 0) return zero_out(err, 1, st);
   VUS_REQUIRE(poses && work, "null buffer");
-  const int nb = n_blocks(M);
+  const int nb = cdiv(M->n_rows, WG);
   pose_meas_eval_kernel<<<nb, WG, 0, st>>>(*M, nullptr, nullptr, poses, nullptr, work + nb);
   vus::reduce_partials(work + nb, nb, err, st);
   VUS_CHECK_LAUNCH("pose_meas_error");
@@ -332,7 +268,7 @@ extern "C" int vus_pose_meas_weights(const vus_pose_meas* M, const double* poses
   if (int rc = check_args(M)) return rc;
   if (M->n == 0) return VUS_OK;
   VUS_REQUIRE(poses && w_out, "null buffer");
-  pose_meas_weights_kernel<<<n_blocks(M), WG, 0, vus::as_stream(stream)>>>(*M, poses, w_out);
+  pose_meas_weights_kernel<<<cdiv(M->n_rows, WG), WG, 0, vus::as_stream(stream)>>>(*M, poses, w_out);
   VUS_CHECK_LAUNCH("pose_meas_weights");
   return VUS_OK;
 }

@@ -1,6 +1,7 @@
-// se3_device.h -- device helpers shared by the pose kernels of ba.hip, between.hip and nav.hip: SE(3) in gtsam's Pose3 / Rot3
-// conventions (tangent order (omega, v), retract T * Exp(xi), local Log(T^-1 T2)) and the robust-loss table of
-// include/vus_robust.h.  Internal linkage: every translation unit that includes it gets its own copy.
+// se3_device.h -- device helpers shared by the pose kernels of ba.hip, between.hip, pose_meas.hip and nav.hip: SE(3) in gtsam's
+// Pose3 / Rot3 conventions (tangent order (omega, v), retract T * Exp(xi), local Log(T^-1 T2)), the flat12 pose load and the
+// robust-loss table of include/vus_robust.h with its run-time dispatcher.  Internal linkage: every translation unit that
+// includes it gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/vus.h"
@@ -8,6 +9,12 @@
 namespace {
 
 constexpr double kEps = 2.220446049250313e-16;
+
+// a pose (flat12: R row-major, then t) into registers
+__device__ __forceinline__ void load12(const double* __restrict__ src, double* dst) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) dst[k] = src[k];
+}
 
 // ---------------------------------------------------------------------------------------------
 // Lie-group helpers (gtsam Pose3 / Rot3 conventions; mirrored independently by the CPU oracle)
@@ -150,6 +157,21 @@ __device__ __forceinline__ void robust_weight(double d2, double k, double& w, do
   } else {
     w = 1.0;
     rho = 0.5 * d2;
+  }
+}
+
+// w and rho of factor f's own robust model, chosen at run time from the per-factor arrays of a factor set (a kind out of
+// range reads as Gaussian; the set's vus_*_check refuses it)
+__device__ __forceinline__ void robust_weight_of(const int* loss_kind, const double* loss_k, int f, double d2, double& w,
+                                                 double& rho) {
+  const double k = loss_k[f];
+  switch (loss_kind[f]) {
+    case VUS_LOSS_HUBER: robust_weight<VUS_LOSS_HUBER>(d2, k, w, rho); break;
+    case VUS_LOSS_CAUCHY: robust_weight<VUS_LOSS_CAUCHY>(d2, k, w, rho); break;
+    case VUS_LOSS_TUKEY: robust_weight<VUS_LOSS_TUKEY>(d2, k, w, rho); break;
+    case VUS_LOSS_GEMAN_MCCLURE: robust_weight<VUS_LOSS_GEMAN_MCCLURE>(d2, k, w, rho); break;
+    case VUS_LOSS_WELSCH: robust_weight<VUS_LOSS_WELSCH>(d2, k, w, rho); break;
+    default: robust_weight<VUS_LOSS_GAUSSIAN>(d2, k, w, rho); break;
   }
 }
 
