@@ -556,4 +556,9 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Two-point RANSAC with a known inter-frame rotation on the temporal matches (the nodelet's ransac_threshold,
  * launch/stereo.launch:46), between the track matcher and the id emitter above: vus_two_point_ransac. */
 #include "vus_ransac.h"
+
+/* Lens undistortion + stereo rectification of raw images by a Q5 relative remap table, in front of the detector (the
+ * reference hands its nodelet raw topics and a Kalibr calibration, launch/stereo.launch:5-6, 15, 23-25): the per-tile
+ * source boxes of a table and the remap itself. */
+#include "vus_rectify.h"
 #endif /* VUS_H */

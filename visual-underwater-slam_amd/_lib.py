@@ -103,6 +103,9 @@ SIGNATURES = {
     "vus_pose_meas_eval_step": [_P, _P, _P, _P, _P, _P, _P],
     "vus_pose_meas_error": [_P, _P, _P, _P, _P],
     "vus_pose_meas_weights": [_P, _P, _P, _P],
+    # lens undistortion + stereo rectification of raw images (include/vus_rectify.h)
+    "vus_rectify_plan": [_P, c_int, c_int, c_int, _P, _P],
+    "vus_rectify_remap": [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P],
     # host-only tuning knobs of the band solve (tests, A/B timing)
     "vus_ba_set_tuning": [c_int, c_int],
 }

@@ -251,7 +251,7 @@ def imu_delta_rotations(imu, params: "gtsam.PreintegrationParams") -> np.ndarray
 def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, disparity_sign: int = 1,
                  params: Optional[ImageProcessorParams] = None, bulk: bool = True, frontend: Optional[StereoOrbFrontend] = None,
                  gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None, ransac_px: float = 0.0,
-                 ransac_rotation: str = "imu"):
+                 ransac_rotation: str = "imu", rectifier=None):
     """Images to optimised trajectory: frames uint8 [F,2,H,W] on the GPU (one stereo pair per keyframe), odom_poses
     [F,12] (the odometry estimate of every keyframe = initial value of X(i) AND the camera transform get_landmarks
     uses), imu [F-1][n,>=6] samples between keyframes, dvl [F,3].  gate_px > 0 applies BatchSequence.gate_factors (bulk
@@ -259,9 +259,20 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     transform of get_landmarks and of the gate is odom_pose o body_P_sensor.  ransac_px > 0 (the nodelet's
     ransac_threshold, stereo.launch:46: 3) runs StereoOrbFrontend.reject_track_outliers on the temporal matches before
     the ids are issued, with the inter-frame rotation from the gyro samples (ransac_rotation="imu": deltaRij() of every
-    interval, zero bias) or from odom_poses ("odom"); stages then holds "ransac_info".  Returns (results Values,
-    BatchSequence, stages dict)."""
+    interval, zero bias) or from odom_poses ("odom"); stages then holds "ransac_info".  rectifier: frames are RAW camera
+    images and pass through rectify.StereoRectifier.rectify first; BatchSequence keeps the reference's constant
+    calibration, so the rectifier must produce that camera.  Returns (results Values, BatchSequence, stages dict)."""
     assert ransac_rotation in ("imu", "odom")
+    if rectifier is not None:
+        from . import synth
+        from .frontend import default_camera
+        H, W = frames.shape[2:]
+        if (np.abs(np.asarray(rectifier.camera) - default_camera(H, W)).max() > 1e-9
+                or abs(rectifier.baseline - synth.BASELINE_M) > 1e-9):
+            raise ValueError(f"run_sequence works with the reference's calibration: the rectifier's camera {rectifier.camera} "
+                             f"and baseline {rectifier.baseline} differ from default_camera({H}, {W}) and "
+                             f"{synth.BASELINE_M} -- build it with new_camera=default_camera(H, W)")
+        frames = rectifier.rectify(frames)
     if params is None:
         params = ImageProcessorParams(**SEQUENCE_PARAMS)
     F, _, H, W = frames.shape
