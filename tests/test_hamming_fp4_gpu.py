@@ -8,7 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-CHUNK, QWG = 128, 512   # HM_CHUNK and HM_QWG of csrc/frontend.hip
+CHUNK, QWG = 128, 512   # HM_CHUNK and HM_QWG of csrc/match.hip
 
 
 def _random_desc(rng, n_img, K):

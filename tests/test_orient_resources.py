@@ -2,7 +2,7 @@
 
 orient_rbrief_kernel<*, *, true> waits on patch gathers for most of its time and hides that latency with more waves, so
 its occupancy is part of its speed: 7 waves per SIMD need <= 72 VGPRs (AGPRs included), <= 160 KiB / 7 bytes of LDS per
-256-thread workgroup and no scratch.  This test compiles frontend.hip for gfx950 with the Makefile's own flags and reads
+256-thread workgroup and no scratch.  This test compiles orient.hip for gfx950 with the Makefile's own flags and reads
 the compiler's resource report, so that a later change cannot lower the occupancy unnoticed."""
 import os
 import re
@@ -28,9 +28,9 @@ def _make_var(name):
 def resources(tmp_path_factory):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not found")
-    out = tmp_path_factory.mktemp("orient_res") / "frontend.co"
+    out = tmp_path_factory.mktemp("orient_res") / "orient.co"
     cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", *_make_var("print-offload").split(), "-Wno-unused-function",
-           *_make_var("print-frontend-flags").split(), "--cuda-device-only", "-c", os.path.join(CSRC, "frontend.hip"),
+           *_make_var("print-frontend-flags").split(), "--cuda-device-only", "-c", os.path.join(CSRC, "orient.hip"),
            "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
     p = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-3000:]

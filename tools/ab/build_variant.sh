@@ -2,7 +2,7 @@
 # Build a variant of the library for same-box A/B timing (no GPU needed):
 #   tools/ab/build_variant.sh NAME "-DSOME_SWITCH" [UNIT.hip]  ->  tools/ab/libvus_n_NAME.so (plain) and, when UNIT is
 #   band_solve.hip (the default; the only unit with -DVUS_TIMING marks), libvus_t_NAME.so (-DVUS_TIMING)
-# Only UNIT is rebuilt, with the plain flags (frontend.hip / ransac.hip have theirs: build_frontend_variant.sh); the other
+# Only UNIT is rebuilt, with the plain flags (the front-end units / ransac.hip have theirs: build_frontend_variant.sh); the other
 # objects are those `make` built in visual-underwater-slam_amd/csrc (run it there first), named by `make print-objs`.
 # The .so files are git-ignored; delete them when the experiment is over.
 set -e
