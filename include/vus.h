@@ -557,6 +557,10 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * launch/stereo.launch:46), between the track matcher and the id emitter above: vus_two_point_ransac. */
 #include "vus_ransac.h"
 
+/* Loop-closure measurements: the relative pose of two stereo keyframes that see the same place, by three-point RANSAC on
+ * their triangulated matches and a Gauss-Newton refit, with the normal matrix of the refit: vus_stereo_pair_pose. */
+#include "vus_loop.h"
+
 /* Lens undistortion + stereo rectification of raw images by a Q5 relative remap table, in front of the detector (the
  * reference hands its nodelet raw topics and a Kalibr calibration, launch/stereo.launch:5-6, 15, 23-25): the per-tile
  * source boxes of a table and the remap itself. */

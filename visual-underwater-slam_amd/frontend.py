@@ -116,6 +116,16 @@ class CameraMeasurement:
     features: List[Feature] = field(default_factory=list)
 
 
+@dataclass
+class PairPoses:
+    """Device tensors of one StereoOrbFrontend.relative_poses() call (vus_stereo_pair_pose, include/vus_loop.h)."""
+    T_ab: torch.Tensor            # f64 [n_pairs, 12]  flat12 of T_a^-1 T_b, camera frames
+    JtJ: torch.Tensor             # f64 [n_pairs, 6, 6]  normal matrix of the refit over the final inliers, (omega, v), pixels
+    rss: torch.Tensor             # f64 [n_pairs]  sum of squared residuals over the final inliers, pixels^2
+    info: torch.Tensor            # int32 [n_pairs, 6]  (n, best k, its count, final inliers, status, refit rounds)
+    match_idx_out: torch.Tensor   # int32 [n_pairs, K]  the matches that are final inliers, -1 otherwise
+
+
 class FrontendResult:
     """Device tensors produced by one process() call (views into the front-end's workspace)."""
 
@@ -424,6 +434,64 @@ class StereoOrbFrontend:
                   ptr(rot), cam_h.ctypes.data, thr, int(self.p.ransac_hypotheses), int(self.p.ransac_seed) & 0xFFFFFFFF,
                   ptr(res.track_idx), ptr(info), _lib.current_stream_ptr())
         return info
+
+    def _pair_indices(self, res: FrontendResult, pair_a, pair_b):
+        """(a, b) as int32 [n_pairs] device tensors; frame numbers are checked on the host when they come from it."""
+        out = []
+        for v in (pair_a, pair_b):
+            if not isinstance(v, torch.Tensor):
+                h = np.asarray(v, dtype=np.int64).reshape(-1)
+                assert len(h) >= 1 and (h >= 0).all() and (h < res.n_frames).all(), "pair frame number outside the result"
+                v = torch.from_numpy(h.astype(np.int32))
+            out.append(v.to(device=self.device, dtype=torch.int32).contiguous())
+        assert out[0].shape == out[1].shape and out[0].dim() == 1 and out[0].numel() >= 1
+        return out
+
+    def match_keyframes(self, res: FrontendResult, pair_a, pair_b, max_distance: Optional[int] = None,
+                        cross_check: bool = True) -> torch.Tensor:
+        """Descriptor matches between the LEFT images of arbitrary keyframe pairs (a, b) of `res` -- loop-closure
+        candidates, not neighbours: vus_hamming_match on the pairing (2a, 2b) without a geometric gate, Hamming bound
+        max_distance (default: track_max_distance), and with cross_check the mutual filter against the swapped
+        pairing.  Returns match_idx int32 [n_pairs, K] on the device: left(a) keypoint i -> left(b) keypoint, -1 none."""
+        a, b = self._pair_indices(res, pair_a, pair_b)
+        n, K, ptr = a.numel(), self.p.max_features, _lib.ptr
+        dist = int(self.p.track_max_distance if max_distance is None else max_distance)
+        q, t = (2 * a).contiguous(), (2 * b).contiguous()
+        idx = torch.empty((n, K), dtype=torch.int32, device=self.device)
+        dst = torch.empty((n, K), dtype=torch.int32, device=self.device)
+        st = _lib.current_stream_ptr()
+        _lib.call("vus_hamming_match", ptr(res.desc), ptr(res.kp_keys), ptr(res.kp_count), K, self.H, self.W, ptr(q), ptr(t), n,
+                  -1, 0, 0, dist, ptr(idx), ptr(dst), st)
+        if cross_check:
+            rev = torch.empty((n, K), dtype=torch.int32, device=self.device)
+            _lib.call("vus_hamming_match", ptr(res.desc), ptr(res.kp_keys), ptr(res.kp_count), K, self.H, self.W, ptr(t), ptr(q),
+                      n, -1, 0, 0, dist, ptr(rev), ptr(dst), st)
+            _lib.call("vus_cross_check", ptr(idx), ptr(rev), n, K, ptr(idx), st)
+        return idx
+
+    def relative_poses(self, res: FrontendResult, pair_a, pair_b, match_idx: torch.Tensor, cam5, threshold_px: float = 2.0,
+                       n_hyp: int = 256, seed: int = synth.SEED, refine_iters: int = 10) -> PairPoses:
+        """T_a^-1 T_b of every keyframe pair from its matches (match_keyframes) and the stereo matches of both keyframes:
+        three-point RANSAC on the triangulated points, then refine_iters Gauss-Newton rounds on the left-image
+        reprojection error of the inliers (vus_stereo_pair_pose, include/vus_loop.h; one launch for all pairs).  cam5:
+        (fx, fy, cx, cy) in pixels of this H x W image and the baseline in metres.  Asynchronous on the current stream."""
+        a, b = self._pair_indices(res, pair_a, pair_b)
+        n, K, ptr = a.numel(), self.p.max_features, _lib.ptr
+        assert match_idx.dtype == torch.int32 and match_idx.is_cuda and match_idx.is_contiguous() and \
+            tuple(match_idx.shape) == (n, K), "match_idx: int32 [n_pairs, K] on the device"
+        cam_h = np.ascontiguousarray(cam5.detach().cpu().numpy() if isinstance(cam5, torch.Tensor) else cam5, dtype=np.float64)
+        assert cam_h.size == 5, "cam5: fx, fy, cx, cy, baseline"
+        dev = self.device
+        out = PairPoses(T_ab=torch.empty((n, 12), dtype=torch.float64, device=dev),
+                        JtJ=torch.empty((n, 6, 6), dtype=torch.float64, device=dev),
+                        rss=torch.empty((n,), dtype=torch.float64, device=dev),
+                        info=torch.empty((n, 6), dtype=torch.int32, device=dev),
+                        match_idx_out=torch.empty((n, K), dtype=torch.int32, device=dev))
+        _lib.call("vus_stereo_pair_pose", ptr(match_idx), ptr(a), ptr(b), ptr(res.stereo_idx), ptr(res.kp_keys),
+                  ptr(res.kp_count), res.n_frames, n, K, self.H, self.W, cam_h.ctypes.data, float(threshold_px), int(n_hyp),
+                  int(seed) & 0xFFFFFFFF, int(refine_iters), ptr(out.T_ab), ptr(out.JtJ), ptr(out.rss), ptr(out.match_idx_out),
+                  ptr(out.info), _lib.current_stream_ptr())
+        return out
 
     def stereo_factors(self, ids: torch.Tensor, feats: torch.Tensor, n_ids: int, Rt: torch.Tensor, cam: torch.Tensor,
                        first_frame: int = 1):

@@ -21,13 +21,15 @@ Two documented deviations from the reference's text, both switchable:
     is the reference verbatim; `disparity_sign=+1` evaluates the same formulas with the baseline's sign flipped
     (d / (-baseline) = (uL - uR) / baseline), which is the geometrically valid triangulation.  Both run the same kernel.
 """
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import gtsam
-from .frontend import CameraMeasurement, ImageProcessorParams, StereoOrbFrontend, triangulate
+from . import synth
+from .frontend import CameraMeasurement, ImageProcessorParams, StereoOrbFrontend, default_camera, triangulate
 from .gtsam.symbol_shorthand import B, L, V, X
 
 
@@ -248,10 +250,111 @@ def imu_delta_rotations(imu, params: "gtsam.PreintegrationParams") -> np.ndarray
     return np.array(out, dtype=np.float64).reshape(-1, 3, 3)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Loop closures (EXTENSION: batch.py builds an odometry-like graph only).  Candidates by pose proximity, the relative pose
+# of every candidate pair by StereoOrbFrontend.match_keyframes + relative_poses (include/vus_loop.h), accepted ones as
+# BetweenFactorPose3.
+
+@dataclass
+class LoopClosureParams:
+    min_gap: int = 5                    # keyframes between the two ends of a closure (neighbours are odometry's business)
+    radius_m: float = 1.0               # camera centres at most this far apart in the odometry estimate
+    max_angle_rad: float = 0.7          # optical axes at most this far apart
+    max_per_keyframe: int = 2           # the nearest this many earlier keyframes per keyframe
+    match_max_distance: int = 50        # Hamming bound of match_keyframes
+    threshold_px: float = 2.0           # inlier distance of the three-point RANSAC and the refit
+    n_hyp: int = 256
+    seed: int = synth.SEED
+    refine_iters: int = 10
+    min_inliers: int = 30               # a closure with fewer final inliers is dropped
+    sigma_px: float = 1.0               # floor of the residual scale s
+    robust: Optional[Tuple[str, float]] = None   # e.g. ("Cauchy", 3.0): noiseModel.mEstimator name and parameter
+
+
+def loop_candidates(poses12: np.ndarray, params: LoopClosureParams):
+    """Keyframe pairs (a, b), b - a >= min_gap, whose camera centres lie within radius_m and whose optical axes (the
+    camera's z axis in the world) within max_angle_rad of each other in poses12 [F,12] (camera poses, flat12).  Per b the
+    max_per_keyframe nearest a, ties to the lower a; pairs ordered by b, then by distance.  Host, numpy.  Returns
+    (pair_a, pair_b) int32 arrays."""
+    P = np.ascontiguousarray(poses12, dtype=np.float64).reshape(-1, 12)
+    centre, axis = P[:, 9:], P[:, [2, 5, 8]]
+    pa, pb = [], []
+    for b in range(len(P)):
+        a = np.arange(0, max(b - int(params.min_gap) + 1, 0))
+        if not len(a):
+            continue
+        dist = np.linalg.norm(centre[a] - centre[b], axis=1)
+        ang = np.arccos(np.clip(axis[a] @ axis[b], -1.0, 1.0))
+        ok = (dist <= params.radius_m) & (ang <= params.max_angle_rad)
+        a, dist = a[ok], dist[ok]
+        order = np.lexsort((a, dist))[:max(int(params.max_per_keyframe), 0)]
+        pa += a[order].tolist()
+        pb += [b] * len(order)
+    return np.array(pa, np.int32), np.array(pb, np.int32)
+
+
+def adjoint_map(S: "gtsam.Pose3") -> np.ndarray:
+    """Ad_S in the tangent order (omega, v): S Exp(xi) S^-1 = Exp(Ad_S xi)."""
+    R, t = S.rotation().matrix(), S.translation()
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    A = np.zeros((6, 6))
+    A[:3, :3], A[3:, :3], A[3:, 3:] = R, tx @ R, R
+    return A
+
+
+def loop_closure_measurements(result, params: LoopClosureParams, body_P_sensor: Optional["gtsam.Pose3"] = None):
+    """Host side of the acceptance rule: (accepted [n] bool, measured [n] Pose3 or None, cov [n,6,6], scale [n]) from a
+    frontend.PairPoses.  A pair is accepted iff its status is 0 and its final inliers number at least min_inliers (and
+    its normal matrix can be inverted, which three or more inliers in general position give).  cov = s^2 (JtJ)^-1,
+    s = max(sigma_px, sqrt(rss / (2 n_in - 6))), in the tangent (omega, v) of measured Exp(xi).  With body_P_sensor = S
+    the measurement becomes S T S^-1 (X(i) are body poses) and the covariance Ad_S cov Ad_S^T."""
+    T = result.T_ab.detach().cpu().numpy().reshape(-1, 12)
+    JtJ = result.JtJ.detach().cpu().numpy().reshape(-1, 6, 6)
+    rss = result.rss.detach().cpu().numpy().reshape(-1)
+    info = result.info.detach().cpu().numpy().reshape(-1, 6)
+    n = len(T)
+    accepted = (info[:, 4] == 0) & (info[:, 3] >= int(params.min_inliers))
+    cov, scale, measured = np.zeros((n, 6, 6)), np.zeros(n), [None] * n
+    S = None if body_P_sensor is None else gtsam.Pose3(body_P_sensor)
+    Ad = None if S is None else adjoint_map(S)
+    for c in np.nonzero(accepted)[0]:
+        dof = 2 * int(info[c, 3]) - 6
+        s = max(float(params.sigma_px), float(np.sqrt(rss[c] / dof)) if dof > 0 else 0.0)
+        try:
+            C = (s * s) * np.linalg.inv(JtJ[c])
+        except np.linalg.LinAlgError:
+            C = np.full((6, 6), np.nan)
+        if not (np.isfinite(C).all() and (np.diag(C) > 0).all()):
+            accepted[c] = False
+            continue
+        M = gtsam.Pose3.from_flat12(T[c])
+        if S is not None:
+            M, C = S.compose(M).compose(S.inverse()), Ad @ C @ Ad.T
+        cov[c], scale[c], measured[c] = C, s, M
+    return accepted, measured, cov, scale
+
+
+def loop_closure_factors(result, pairs, params: LoopClosureParams, body_P_sensor: Optional["gtsam.Pose3"] = None):
+    """gtsam.BetweenFactorPose3(X(a), X(b), measured, model) for every accepted pair of `result` (a frontend.PairPoses of
+    pairs = (pair_a, pair_b)); see loop_closure_measurements for the rule and the covariance.  BetweenFactorPose3 takes
+    diagonal models: the sigmas are the square roots of the covariance's diagonal (the marginal sigmas, the conservative
+    choice), wrapped in noiseModel.Robust when params.robust names an mEstimator."""
+    pa, pb = (np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).reshape(-1) for v in pairs)
+    accepted, measured, cov, _ = loop_closure_measurements(result, params, body_P_sensor)
+    out = []
+    for c in np.nonzero(accepted)[0]:
+        model = gtsam.noiseModel.Diagonal.Sigmas(np.sqrt(np.diag(cov[c])))
+        if params.robust is not None:
+            kind, k = params.robust
+            model = gtsam.noiseModel.Robust.Create(getattr(gtsam.noiseModel.mEstimator, kind).Create(float(k)), model)
+        out.append(gtsam.BetweenFactorPose3(X(int(pa[c])), X(int(pb[c])), measured[c], model))
+    return out
+
+
 def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, disparity_sign: int = 1,
                  params: Optional[ImageProcessorParams] = None, bulk: bool = True, frontend: Optional[StereoOrbFrontend] = None,
                  gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None, ransac_px: float = 0.0,
-                 ransac_rotation: str = "imu", rectifier=None):
+                 ransac_rotation: str = "imu", rectifier=None, loop_closure: Optional[LoopClosureParams] = None):
     """Images to optimised trajectory: frames uint8 [F,2,H,W] on the GPU (one stereo pair per keyframe), odom_poses
     [F,12] (the odometry estimate of every keyframe = initial value of X(i) AND the camera transform get_landmarks
     uses), imu [F-1][n,>=6] samples between keyframes, dvl [F,3].  gate_px > 0 applies BatchSequence.gate_factors (bulk
@@ -261,11 +364,12 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     the ids are issued, with the inter-frame rotation from the gyro samples (ransac_rotation="imu": deltaRij() of every
     interval, zero bias) or from odom_poses ("odom"); stages then holds "ransac_info".  rectifier: frames are RAW camera
     images and pass through rectify.StereoRectifier.rectify first; BatchSequence keeps the reference's constant
-    calibration, so the rectifier must produce that camera.  Returns (results Values, BatchSequence, stages dict)."""
+    calibration, so the rectifier must produce that camera.  loop_closure: candidates by pose proximity in odom_poses
+    (loop_candidates on the camera poses), their relative poses from the front end (match_keyframes + relative_poses) and
+    the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
+    "loop_result" (None without a candidate) and "loop_accepted".  Returns (results Values, BatchSequence, stages dict)."""
     assert ransac_rotation in ("imu", "odom")
     if rectifier is not None:
-        from . import synth
-        from .frontend import default_camera
         H, W = frames.shape[2:]
         if (np.abs(np.asarray(rectifier.camera) - default_camera(H, W)).max() > 1e-9
                 or abs(rectifier.baseline - synth.BASELINE_M) > 1e-9):
@@ -294,6 +398,19 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     stages = {"frontend": res, "ids": ids, "feats": feats, "n_ids": n_ids}
     if ransac_info is not None:
         stages["ransac_info"] = ransac_info
+    loop_factors = []
+    if loop_closure is not None:
+        lc = loop_closure
+        pairs = loop_candidates(Rt_cam, lc)
+        loop_result, accepted = None, np.zeros(0, bool)
+        if len(pairs[0]):
+            cam5 = np.concatenate([default_camera(H, W), [seq.baseline]])
+            midx = fe.match_keyframes(res, pairs[0], pairs[1], max_distance=lc.match_max_distance)
+            loop_result = fe.relative_poses(res, pairs[0], pairs[1], midx, cam5, lc.threshold_px, lc.n_hyp, lc.seed,
+                                            lc.refine_iters)
+            accepted = loop_closure_measurements(loop_result, lc, body_P_sensor)[0]
+            loop_factors = loop_closure_factors(loop_result, pairs, lc, body_P_sensor)
+        stages.update(loop_pairs=pairs, loop_result=loop_result, loop_accepted=accepted)
     if bulk:
         for i in range(F):
             seq.odom_accum.append(gtsam.Pose3.from_flat12(Rt[i]))
@@ -316,5 +433,7 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
                     seq.update_imu(s[:3], s[3:6])
             seq.batch_update(pose, dvl[i], msgs[i])
         seq.batch_create(with_landmark=True)
+    for f in loop_factors:
+        seq.graph.push_back(f)
     results = seq.optimize()
     return results, seq, stages
