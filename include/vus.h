@@ -561,6 +561,10 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * their triangulated matches and a Gauss-Newton refit, with the normal matrix of the refit: vus_stereo_pair_pose. */
 #include "vus_loop.h"
 
+/* Loop-closure candidates by appearance: for every ordered pair of keyframes, how many of one keyframe's strongest
+ * descriptors have a near neighbour among the other's (all-pairs Hamming on the FP4 matrix cores, no vocabulary). */
+#include "vus_retrieval.h"
+
 /* Lens undistortion + stereo rectification of raw images by a Q5 relative remap table, in front of the detector (the
  * reference hands its nodelet raw topics and a Kalibr calibration, launch/stereo.launch:5-6, 15, 23-25): the per-tile
  * source boxes of a table and the remap itself. */

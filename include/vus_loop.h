@@ -5,7 +5,8 @@
  * Where it sits: vus_hamming_match on the pairing (left(a), left(b)) of two arbitrary keyframes gives match_idx; the stereo
  * matches of both keyframes (what process() leaves in stereo_idx) give every matched keypoint a depth.  This entry point
  * turns that into T_a^-1 T_b with the normal matrix of its refit, ready to become a BetweenFactor<Pose3> (vus_between.h).
- * Which pairs to try is the caller's business (sequence.loop_candidates: pose proximity).
+ * Which pairs to try is the caller's business (sequence.loop_candidates: pose proximity; sequence.appearance_candidates on
+ * vus_keyframe_similarity, vus_retrieval.h: the descriptors alone).
  *
  *   match_idx   int32 [n_pairs, max_kp]   left(a) keypoint i -> left(b) keypoint j of pair c (-1: none)
  *   pair_a, pair_b  int [n_pairs]         DEVICE: frame numbers of pair c; frame f's left image is image 2f, its right 2f+1
@@ -102,7 +103,7 @@
  * sums candidates t, t + 256, ... in ascending order, a butterfly over each wave and the four waves added in order -- a
  * fixed tree: two runs give the same bits; no atomics on doubles.  Thread 0 solves.
  *
- * NOT IN THIS ENTRY POINT: appearance-only retrieval of the candidates, sub-pixel disparities, a right-image residual. */
+ * NOT IN THIS ENTRY POINT: sub-pixel disparities, a right-image residual. */
 #ifndef VUS_LOOP_H
 #define VUS_LOOP_H
 #include "vus.h"

@@ -36,6 +36,8 @@ SIGNATURES = {
     # relative pose of two stereo keyframes, three-point RANSAC + refit (include/vus_loop.h); `cam` is a host pointer
     "vus_stereo_pair_pose": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_double, c_int, ctypes.c_uint32,
                              c_int, _P, _P, _P, _P, _P, _P],
+    # keyframe similarity for loop-closure candidates by appearance (include/vus_retrieval.h)
+    "vus_keyframe_similarity": [_P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, _P, _P],
     # bundle adjustment (struct arguments are passed by address)
     "vus_ba_linearize": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "vus_ba_schur": [_P, _P, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P],

@@ -1,7 +1,8 @@
 // frontend_common.h -- what two or more units of the stereo ORB front-end for gfx950 (MI355X) share.  The front-end is
 // FAST-9/16 + NMS + smoothing (detect.hip), top-K selection (select.hip), intensity-centroid orientation + rotated BRIEF
 // (orient.hip), brute-force Hamming matching (match.hip), the track ids, the factor emitter and the get_landmarks
-// triangulation of the reference, batch.py:144-176 (track.hip), and the optional scale pyramid (pyramid.hip).
+// triangulation of the reference, batch.py:144-176 (track.hip), the optional scale pyramid (pyramid.hip), and the keyframe
+// similarity that proposes loop-closure candidates from the descriptors (retrieve.hip; it shares fp4_hamming.h with match.hip).
 //
 // Replaces the external `gtsam_vio/ImageProcessorNodelet` the reference wires in at
 // launch/stereo.launch:33-55 (its output is what batch.py:149-154 consumes).  Algorithm

@@ -4,6 +4,7 @@
 // Design notes (MI355X):
 //  * hamming_match keeps the train descriptors in LDS (broadcast reads) and one query per lane.
 #include "frontend_common.h"
+#include "fp4_hamming.h"
 #include <algorithm>
 
 namespace {
@@ -284,42 +285,22 @@ __global__ __launch_bounds__(HR_THREADS) void hamming_match_rows_kernel(
 // (HM_CHUNK - 1 - local train index): one max3 tree per tile and column tile, seeded with the previous
 // best + 32.  Once per chunk it becomes the global key (dot << 16) | (0xFFFF - train index), running
 // signed max = smallest distance, ties to the lowest train index -- the brute-force result, bit for bit.
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef int v8i_t __attribute__((ext_vector_type(8)));
-typedef float v16f_t __attribute__((ext_vector_type(16)));
+// The vector types, the row pitch HM_ROWB, the unit scale word HM_SCALE_A and the expansion helpers (spread_fp4, spread_word,
+// fp4_operand) are shared with the keyframe retrieval (retrieve.hip): fp4_hamming.h.
 #ifndef VUS_HM_CHUNK
 #define VUS_HM_CHUNK 128
 #endif
 constexpr int HM_CHUNK = VUS_HM_CHUNK;   // trains expanded per LDS chunk
 constexpr int HM_KEY_SHIFT = HM_CHUNK == 256 ? 8 : HM_CHUNK == 128 ? 7 : HM_CHUNK == 64 ? 6 : -1;
 static_assert(HM_KEY_SHIFT > 0, "HM_CHUNK must be 64, 128 or 256");
-constexpr int HM_ROWB = 144;             // bytes per expanded row: 128 + 16 (bank spread of the b128 reads)
-constexpr int HM_SCALE_A = 0x7F7F7F7F;   // E8M0 block scales, every byte the same: 2^0 (trains) ...
-constexpr int HM_SCALE_B = (int)(0x01010101u * (0x7F + HM_KEY_SHIFT));   // ... and 2^HM_KEY_SHIFT (queries)
+// E8M0 block scales, every byte the same: HM_SCALE_A = 2^0 (trains) and 2^HM_KEY_SHIFT (queries)
+constexpr int HM_SCALE_B = (int)(0x01010101u * (0x7F + HM_KEY_SHIFT));
 
 #ifndef VUS_HM_QT
 #define VUS_HM_QT 4
 #endif
 constexpr int HM_QT = VUS_HM_QT;         // 32-query column tiles per wave (A fragments and the chunk expansion are shared)
 constexpr int HM_QWG = 4 * 32 * HM_QT;   // queries per workgroup
-
-// 8 descriptor bits (the low byte of b) -> 8 FP4 nibbles, -1.0 (0xA) for a set bit and +1.0 (0x2) for a clear one.
-// The sign is flipped for both operands alike, so every product is unchanged.
-__device__ __forceinline__ int spread_fp4(uint32_t b) {
-  uint32_t x = (b | b << 12) & 0x000F000Fu;         // bits 0-3 -> 0-3, bits 4-7 -> 16-19
-  x = (x | x << 6) & 0x03030303u;                   // bit pairs -> bits 0-1 of each byte
-  return (int)(((x << 3 | x << 6) & 0x88888888u) | 0x22222222u);   // bit 0 -> 3, bit 1 -> 7: sign bits of the nibbles
-}
-
-// one descriptor word (32 bits) -> the 32 FP4 values of one lane's operand of one MFMA: four lookups in the block's
-// 256-entry byte table (one v_lshlrev_b32_sdwa + one ds_read_b32 per byte instead of eight VALU instructions)
-__device__ __forceinline__ v4i_t spread_word(const uint32_t* lut, uint32_t w) {
-  return v4i_t{(int)lut[w & 0xFFu], (int)lut[(w >> 8) & 0xFFu], (int)lut[(w >> 16) & 0xFFu], (int)lut[w >> 24]};
-}
-
-__device__ __forceinline__ v8i_t fp4_operand(v4i_t v) {   // FP4 reads dwords 0-3 of the builtin's 8-dword operand
-  return v8i_t{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
-}
 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 

@@ -469,6 +469,20 @@ class StereoOrbFrontend:
             _lib.call("vus_cross_check", ptr(idx), ptr(rev), n, K, ptr(idx), st)
         return idx
 
+    def keyframe_similarity(self, res: FrontendResult, top: int = 512, max_distance: int = 35, min_gap: int = 0) -> torch.Tensor:
+        """Appearance score of every keyframe pair of `res`, from the LEFT images' descriptors alone (vus_keyframe_similarity,
+        include/vus_retrieval.h): S[b, a] = how many of keyframe b's first `top` descriptors -- its strongest under the
+        global top-K selection; with grid bucketing pass top = max_features -- have a descriptor within max_distance bits
+        among keyframe a's first `top`.  Filled for a <= b - min_gap (t_limit[b] = max(b - min_gap + 1, 0)), 0 elsewhere;
+        directed: S[b, a] is not S[a, b].  Returns int32 [F, F] on the device.  Asynchronous on the current stream."""
+        F, K, ptr = res.n_frames, self.p.max_features, _lib.ptr
+        img = (2 * torch.arange(F, dtype=torch.int32, device=self.device)).contiguous()
+        limit = (torch.arange(F, dtype=torch.int32, device=self.device) - int(min_gap) + 1).clamp_(min=0).contiguous()
+        S = torch.empty((F, F), dtype=torch.int32, device=self.device)
+        _lib.call("vus_keyframe_similarity", ptr(res.desc), ptr(res.kp_count), 2 * F, K, ptr(img), F, ptr(img), F, ptr(limit),
+                  min(int(top), K), int(max_distance), ptr(S), _lib.current_stream_ptr())   # a front end of fewer slots uses all
+        return S
+
     def relative_poses(self, res: FrontendResult, pair_a, pair_b, match_idx: torch.Tensor, cam5, threshold_px: float = 2.0,
                        n_hyp: int = 256, seed: int = synth.SEED, refine_iters: int = 10) -> PairPoses:
         """T_a^-1 T_b of every keyframe pair from its matches (match_keyframes) and the stereo matches of both keyframes:

@@ -255,6 +255,9 @@ def imu_delta_rotations(imu, params: "gtsam.PreintegrationParams") -> np.ndarray
 # of every candidate pair by StereoOrbFrontend.match_keyframes + relative_poses (include/vus_loop.h), accepted ones as
 # BetweenFactorPose3.
 
+CANDIDATE_MODES = ("pose", "appearance", "both")
+
+
 @dataclass
 class LoopClosureParams:
     min_gap: int = 5                    # keyframes between the two ends of a closure (neighbours are odometry's business)
@@ -269,6 +272,15 @@ class LoopClosureParams:
     min_inliers: int = 30               # a closure with fewer final inliers is dropped
     sigma_px: float = 1.0               # floor of the residual scale s
     robust: Optional[Tuple[str, float]] = None   # e.g. ("Cauchy", 3.0): noiseModel.mEstimator name and parameter
+    candidates: str = "pose"            # "pose": loop_candidates (proximity in the odometry); "appearance": appearance_candidates
+                                        # on StereoOrbFrontend.keyframe_similarity (no pose enters); "both": their union
+    appearance_top: int = 512           # descriptors per keyframe that take part (the strongest under global top-K)
+    appearance_max_distance: int = 35   # Hamming bound of a near neighbour; tighter than match_max_distance
+    appearance_min_score: int = 30      # a pair scoring less is not proposed
+
+    def __post_init__(self):
+        if self.candidates not in CANDIDATE_MODES:
+            raise ValueError(f"LoopClosureParams.candidates must be one of {CANDIDATE_MODES}, not {self.candidates!r}")
 
 
 def loop_candidates(poses12: np.ndarray, params: LoopClosureParams):
@@ -291,6 +303,33 @@ def loop_candidates(poses12: np.ndarray, params: LoopClosureParams):
         pa += a[order].tolist()
         pb += [b] * len(order)
     return np.array(pa, np.int32), np.array(pb, np.int32)
+
+
+def appearance_candidates(S, params: LoopClosureParams):
+    """Keyframe pairs (a, b) from the similarity matrix S [F, F] of StereoOrbFrontend.keyframe_similarity (S[b, a]: how
+    many of b's descriptors find a near neighbour in a): per b the a <= b - min_gap with S[b, a] >= appearance_min_score,
+    of those the max_per_keyframe largest scores, ties to the lower a; pairs ordered by b, then descending score, then a.
+    Host, numpy.  Returns (pair_a, pair_b) int32 arrays."""
+    S = np.asarray(S.detach().cpu().numpy() if isinstance(S, torch.Tensor) else S)
+    assert S.ndim == 2 and S.shape[0] == S.shape[1], "S: [F, F]"
+    pa, pb = [], []
+    for b in range(len(S)):
+        a = np.arange(0, max(b - int(params.min_gap) + 1, 0))
+        if not len(a):
+            continue
+        score = S[b, a].astype(np.int64)
+        ok = score >= int(params.appearance_min_score)
+        a, score = a[ok], score[ok]
+        order = np.lexsort((a, -score))[:max(int(params.max_per_keyframe), 0)]
+        pa += a[order].tolist()
+        pb += [b] * len(order)
+    return np.array(pa, np.int32), np.array(pb, np.int32)
+
+
+def union_candidates(first, second):
+    """The union of two pair lists (pair_a, pair_b) without duplicates, ordered by (b, a); int32 arrays."""
+    pairs = sorted({(int(b), int(a)) for pa, pb in (first, second) for a, b in zip(pa, pb)})
+    return np.array([a for _, a in pairs], np.int32), np.array([b for b, _ in pairs], np.int32)
 
 
 def adjoint_map(S: "gtsam.Pose3") -> np.ndarray:
@@ -365,8 +404,9 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     interval, zero bias) or from odom_poses ("odom"); stages then holds "ransac_info".  rectifier: frames are RAW camera
     images and pass through rectify.StereoRectifier.rectify first; BatchSequence keeps the reference's constant
     calibration, so the rectifier must produce that camera.  loop_closure: candidates by pose proximity in odom_poses
-    (loop_candidates on the camera poses), their relative poses from the front end (match_keyframes + relative_poses) and
-    the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
+    (loop_candidates on the camera poses), by appearance (keyframe_similarity + appearance_candidates; stages then also holds
+    "loop_similarity") or both, as LoopClosureParams.candidates says; their relative poses from the front end
+    (match_keyframes + relative_poses) and the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
     "loop_result" (None without a candidate) and "loop_accepted".  Returns (results Values, BatchSequence, stages dict)."""
     assert ransac_rotation in ("imu", "odom")
     if rectifier is not None:
@@ -401,7 +441,13 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     loop_factors = []
     if loop_closure is not None:
         lc = loop_closure
-        pairs = loop_candidates(Rt_cam, lc)
+        pairs = loop_candidates(Rt_cam, lc) if lc.candidates != "appearance" else None
+        if lc.candidates != "pose":
+            sim = fe.keyframe_similarity(res, top=lc.appearance_top, max_distance=lc.appearance_max_distance,
+                                         min_gap=lc.min_gap)
+            stages["loop_similarity"] = sim
+            by_look = appearance_candidates(sim, lc)
+            pairs = by_look if pairs is None else union_candidates(pairs, by_look)
         loop_result, accepted = None, np.zeros(0, bool)
         if len(pairs[0]):
             cam5 = np.concatenate([default_camera(H, W), [seq.baseline]])
