@@ -561,6 +561,10 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * their triangulated matches and a Gauss-Newton refit, with the normal matrix of the refit: vus_stereo_pair_pose. */
 #include "vus_loop.h"
 
+/* Sub-pixel stereo disparities: an integer SAD search around every stereo match on the rectified images and an equiangular
+ * fit of its minimum, in 1/256 px; feeds the u1 column of the features and vus_stereo_pair_pose_q8: vus_stereo_refine. */
+#include "vus_subpixel.h"
+
 /* Loop-closure candidates by appearance: for every ordered pair of keyframes, how many of one keyframe's strongest
  * descriptors have a near neighbour among the other's (all-pairs Hamming on the FP4 matrix cores, no vocabulary). */
 #include "vus_retrieval.h"

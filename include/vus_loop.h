@@ -71,7 +71,8 @@
  *   inlier = Xz > 0 and (ex ex + ey ey) <= thr2 (Xz Xz)
  *
  * -- the left-image reprojection error of a's 3-D point in camera b.  The right image (disparity) of b enters the
- * hypotheses through Q only: with integer disparities its residual is a staircase that pulls the fit.
+ * hypotheses through Q only: with integer disparities its residual is a staircase that pulls the fit (with the refined ones
+ * of vus_stereo_pair_pose_q8 it would not be; a right-image residual is not built).
  * count_k = number of inliers, or -1 for a degenerate sample.  best = the k of the largest count_k, the lowest k on ties;
  * best = -1 (and the count column -1) if n < 3 or every sample is degenerate.
  *
@@ -103,7 +104,20 @@
  * sums candidates t, t + 256, ... in ascending order, a butterfly over each wave and the four waves added in order -- a
  * fixed tree: two runs give the same bits; no atomics on doubles.  Thread 0 solves.
  *
- * NOT IN THIS ENTRY POINT: sub-pixel disparities, a right-image residual. */
+ * SUB-PIXEL DISPARITIES: vus_stereo_pair_pose_q8.  The same arguments plus disp_q8 int32 [n_frames, max_kp], the refined
+ * x_left - x_right of every left keypoint in 1/256 px (what vus_stereo_refine of vus_subpixel.h writes; 0 for an unmatched
+ * slot).  Everything above holds with two changes.  The last candidate condition becomes disp_q8[a,i] >= 256 and
+ * disp_q8[b,j] >= 256 (the index checks on sa and sb stay; the right keypoints' columns are no longer read), and
+ *
+ *   Z1 = fb / (disp_q8[a,i] / 256.0)      Z2 = fb / (disp_q8[b,j] / 256.0)
+ *
+ * (the division by 256.0 is exact).  The 4-byte d2 slot of the LDS layout holds the Q8 integer: the budget per slot and
+ * VUS_LOOP_MAX_KP do not move.  disp_q8 = NULL means integer disparities: the call is then vus_stereo_pair_pose, which runs
+ * this same code with NULL; disp_q8 = 256 (x_left - x_right) gives its bits too.  The kernel is one text instantiated for
+ * the two cases at compile time, so the integer instantiation is the kernel it was before this entry point existed.  The
+ * refit's residual stays left-image only.  Validation is that of vus_stereo_pair_pose.
+ *
+ * NOT IN THESE ENTRY POINTS: a right-image residual in the refit. */
 #ifndef VUS_LOOP_H
 #define VUS_LOOP_H
 #include "vus.h"
@@ -128,6 +142,12 @@ int vus_stereo_pair_pose(const int32_t* match_idx,   /* [n_pairs, max_kp] left(a
                          int32_t* match_idx_out,     /* [n_pairs, max_kp] survivors, -1 otherwise; may alias match_idx */
                          int32_t* info,              /* [n_pairs, 6] */
                          void* stream);
+
+int vus_stereo_pair_pose_q8(const int32_t* match_idx, const int* pair_a, const int* pair_b, const int32_t* stereo_idx,
+                            const uint32_t* kp_keys, const int* kp_count, int n_frames, int n_pairs, int max_kp, int H, int W,
+                            const double* cam, double threshold_px, int n_hyp, uint32_t seed, int refine_iters,
+                            const int32_t* disp_q8,     /* [n_frames, max_kp] refined disparities in 1/256 px, may be NULL */
+                            double* T_ab, double* JtJ, double* rss, int32_t* match_idx_out, int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }

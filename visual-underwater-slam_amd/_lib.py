@@ -36,6 +36,11 @@ SIGNATURES = {
     # relative pose of two stereo keyframes, three-point RANSAC + refit (include/vus_loop.h); `cam` is a host pointer
     "vus_stereo_pair_pose": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_double, c_int, ctypes.c_uint32,
                              c_int, _P, _P, _P, _P, _P, _P],
+    # the same with refined disparities in 1/256 px (may be NULL) in front of the outputs
+    "vus_stereo_pair_pose_q8": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_double, c_int, ctypes.c_uint32,
+                                c_int, _P, _P, _P, _P, _P, _P, _P],
+    # sub-pixel stereo disparities: SAD search + equiangular fit around every stereo match (include/vus_subpixel.h)
+    "vus_stereo_refine": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P],
     # keyframe similarity for loop-closure candidates by appearance (include/vus_retrieval.h)
     "vus_keyframe_similarity": [_P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, _P, _P],
     # bundle adjustment (struct arguments are passed by address)

@@ -1,5 +1,7 @@
-// loop.hip -- vus_stereo_pair_pose (include/vus_loop.h): the relative pose of two stereo keyframes by three-point RANSAC
-// on their triangulated matches and a Gauss-Newton refit of the left-image reprojection error.
+// loop.hip -- vus_stereo_pair_pose and vus_stereo_pair_pose_q8 (include/vus_loop.h): the relative pose of two stereo
+// keyframes by three-point RANSAC on their triangulated matches and a Gauss-Newton refit of the left-image reprojection
+// error.  One kernel text, instantiated twice: Q8 = false takes the integer disparities of the keys (the instantiation the
+// first entry point has always launched), Q8 = true the refined ones of vus_stereo_refine, in 1/256 px.
 //
 // Built with FRONTEND_FLAGS (-ffp-contract=off): every fp64 statement below is the header's, operation by operation, as
 // the numpy restatement of the test suite (tests/loop_ref.py) writes it.  Do not fuse, reorder or "simplify" them.
@@ -23,6 +25,7 @@ struct LpCam {
 struct LpPair {
   const int32_t* mt;        // may alias the output row
   const int32_t *sa, *sb;
+  const int32_t *qa, *qb;   // Q8 only: the disp_q8 rows of the two frames
   const uint32_t *kla, *kra, *klb, *krb;
   int nla, nra, nlb, nrb;
 };
@@ -30,7 +33,7 @@ struct LpPair {
 struct LpCand {
   double Px, Py, Pz;
   float u, v;
-  int d2, j;
+  int d2, j;                // d2: pixels, or 1/256 px (Q8)
 };
 
 // the pair's compacted candidates in LDS
@@ -55,7 +58,15 @@ __device__ __forceinline__ void lp_point(double x, double y, double d, const LpC
   Y = ((y - c.cy) * Z) / c.fy;
 }
 
+// a disparity as the double lp_point divides by: d / 256.0 is exact, and 256 d0 / 256.0 is d0
+template <bool Q8>
+__device__ __forceinline__ double lp_disparity(int d) {
+  if constexpr (Q8) return (double)d / 256.0;
+  else return (double)d;
+}
+
 // slot i of the pair: false unless it is a candidate.  Every index is checked against its clamped count before it is used.
+template <bool Q8>
 __device__ __forceinline__ bool lp_candidate(const LpPair& p, int i, uint32_t W, const LpCam& c, LpCand& o) {
   if (i >= p.nla) return false;
   const int j = p.mt[i];
@@ -66,9 +77,17 @@ __device__ __forceinline__ bool lp_candidate(const LpPair& p, int i, uint32_t W,
   const uint32_t p2 = p.klb[j] & VUS_KEY_POS_MASK, q2 = p.krb[rb] & VUS_KEY_POS_MASK;
   const uint32_t y1 = p1 / W, x1 = p1 - y1 * W, xr1 = q1 - (q1 / W) * W;
   const uint32_t y2 = p2 / W, x2 = p2 - y2 * W, xr2 = q2 - (q2 / W) * W;
-  const int d1 = (int)x1 - (int)xr1, d2 = (int)x2 - (int)xr2;
-  if (d1 < 1 || d2 < 1) return false;
-  lp_point((double)x1, (double)y1, (double)d1, c, o.Px, o.Py, o.Pz);
+  int d1, d2;
+  if constexpr (Q8) {
+    d1 = p.qa[i];
+    d2 = p.qb[j];
+    if (d1 < 256 || d2 < 256) return false;
+  } else {
+    d1 = (int)x1 - (int)xr1;
+    d2 = (int)x2 - (int)xr2;
+    if (d1 < 1 || d2 < 1) return false;
+  }
+  lp_point((double)x1, (double)y1, lp_disparity<Q8>(d1), c, o.Px, o.Py, o.Pz);
   o.u = (float)x2;
   o.v = (float)y2;
   o.d2 = d2;
@@ -102,6 +121,7 @@ __device__ __forceinline__ bool lp_triad(const double (&A)[3], const double (&B)
 }
 
 // T (flat12) of hypothesis k; false for a degenerate sample.  n >= 3.
+template <bool Q8>
 __device__ __forceinline__ bool lp_model(const LpLds& s, int n, uint32_t h, int k, const LpCam& c, double (&T)[12]) {
   const uint32_t r1 = lp_mix(h ^ (uint32_t)(3 * k)), r2 = lp_mix(h ^ (uint32_t)(3 * k + 1)), r3 = lp_mix(h ^ (uint32_t)(3 * k + 2));
   const uint32_t i = r1 % (uint32_t)n, j = (i + 1u + r2 % (uint32_t)(n - 1)) % (uint32_t)n;
@@ -114,7 +134,7 @@ __device__ __forceinline__ bool lp_model(const LpLds& s, int n, uint32_t h, int 
   for (int q = 0; q < 3; ++q) {
     const uint32_t m = idx[q];
     P[q][0] = s.Px[m]; P[q][1] = s.Py[m]; P[q][2] = s.Pz[m];
-    lp_point((double)s.u[m], (double)s.v[m], (double)s.d2[m], c, Q[q][0], Q[q][1], Q[q][2]);
+    lp_point((double)s.u[m], (double)s.v[m], lp_disparity<Q8>(s.d2[m]), c, Q[q][0], Q[q][1], Q[q][2]);
   }
   double F[9], E[9];
   const bool okp = lp_triad(P[0], P[1], P[2], F);
@@ -140,12 +160,13 @@ __device__ __forceinline__ bool lp_inlier(const double (&T)[12], double Px, doub
 }
 
 // the best (count, lowest k) of this lane's hypotheses k = tid, tid + LP_THREADS, ... as ((count + 1) << 12) | (4095 - k)
+template <bool Q8>
 __device__ __forceinline__ uint32_t lp_hypotheses(const LpLds& s, int n, int n_hyp, uint32_t h, const LpCam& c) {
   uint32_t best = 0;
   for (int k = (int)threadIdx.x; k < n_hyp; k += LP_THREADS) {
     double T[12], X[3];
     int cnt = -1;
-    if (lp_model(s, n, h, k, c, T)) {
+    if (lp_model<Q8>(s, n, h, k, c, T)) {
       cnt = 0;
 #pragma unroll 4
       for (int m = 0; m < n; ++m)    // every lane reads the same address: a broadcast, no bank conflict
@@ -253,12 +274,14 @@ __device__ bool lp_solve6(const double (&h)[21], const double (&g)[6], double (&
 }
 
 // One workgroup per pair.  match_idx and out may be the same buffer: a thread reads slot i before it writes it, and only
-// this workgroup touches row c.
+// this workgroup touches row c.  disp_q8 is read by the Q8 instantiation only.
+template <bool Q8>
 __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
     const int32_t* match_idx, const int* __restrict__ pair_a, const int* __restrict__ pair_b,
     const int32_t* __restrict__ stereo_idx, const uint32_t* __restrict__ kp_keys, const int* __restrict__ kp_count,
     int n_frames, int max_kp, uint32_t W, LpCam cam, int n_hyp, uint32_t seed, int refine_iters, double* __restrict__ T_ab,
-    double* __restrict__ JtJ, double* __restrict__ rss, int32_t* out, int32_t* __restrict__ info) {
+    double* __restrict__ JtJ, double* __restrict__ rss, int32_t* out, int32_t* __restrict__ info,
+    const int32_t* __restrict__ disp_q8) {      // last: the arguments of the Q8 = false instantiation keep their offsets
   extern __shared__ double s_lp[];
   __shared__ double s_red[LP_WAVES * LP_SUMS];
   __shared__ double s_T[12];
@@ -273,6 +296,8 @@ __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
   p.mt = match_idx + (size_t)c * max_kp;
   p.sa = stereo_idx + (size_t)fa * max_kp;
   p.sb = stereo_idx + (size_t)fb * max_kp;
+  p.qa = Q8 ? disp_q8 + (size_t)fa * max_kp : nullptr;
+  p.qb = Q8 ? disp_q8 + (size_t)fb * max_kp : nullptr;
   p.kla = kp_keys + (size_t)(2 * fa) * max_kp;
   p.kra = p.kla + max_kp;
   p.klb = kp_keys + (size_t)(2 * fb) * max_kp;
@@ -293,7 +318,7 @@ __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
   int n = 0;
   for (int i0 = 0; i0 < p.nla; i0 += LP_THREADS) {
     LpCand cd;
-    const bool valid = lp_candidate(p, i0 + tid, W, cam, cd);
+    const bool valid = lp_candidate<Q8>(p, i0 + tid, W, cam, cd);
     const unsigned long long mask = __ballot(valid);
     if (lane == 0) s_w[wave] = __popcll(mask);
     __syncthreads();
@@ -316,7 +341,7 @@ __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
   // hypotheses
   const uint32_t h = lp_mix(seed + 0x9E3779B9u * (uint32_t)(c + 1));
   uint32_t key = 0;
-  if (n >= 3) key = lp_hypotheses(s, n, n_hyp, h, cam);
+  if (n >= 3) key = lp_hypotheses<Q8>(s, n, n_hyp, h, cam);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, o));
   if (lane == 0) s_key[wave] = key;
@@ -329,7 +354,7 @@ __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
 
   if (best_count >= 0) {             // n >= 3 and some sample was not degenerate; everything below is uniform over the block
     best = VUS_LOOP_MAX_HYP - 1 - (int)(key & 4095u);
-    lp_model(s, n, h, best, cam, T);
+    lp_model<Q8>(s, n, h, best, cam, T);
     status = 0;
     for (int it = 0;; ++it) {
       n_in = lp_accumulate(s, n, cam, T, s_red, s_w);
@@ -371,7 +396,7 @@ __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
     LpCand cd;
     double X[3];
     int o = -1;
-    if (status == 0 && lp_candidate(p, i, W, cam, cd) && lp_inlier(T, cd.Px, cd.Py, cd.Pz, (double)cd.u, (double)cd.v, cam, X))
+    if (status == 0 && lp_candidate<Q8>(p, i, W, cam, cd) && lp_inlier(T, cd.Px, cd.Py, cd.Pz, (double)cd.u, (double)cd.v, cam, X))
       o = cd.j;
     out[(size_t)c * max_kp + i] = o;
   }
@@ -397,11 +422,13 @@ __global__ __launch_bounds__(LP_THREADS) void stereo_pair_pose_kernel(
 
 }  // namespace
 
-extern "C" int vus_stereo_pair_pose(const int32_t* match_idx, const int* pair_a, const int* pair_b, const int32_t* stereo_idx,
-                                    const uint32_t* kp_keys, const int* kp_count, int n_frames, int n_pairs, int max_kp, int H,
-                                    int W, const double* cam, double threshold_px, int n_hyp, uint32_t seed, int refine_iters,
-                                    double* T_ab, double* JtJ, double* rss, int32_t* match_idx_out, int32_t* info,
-                                    void* stream) {
+namespace {
+
+// both entry points: validation, then the instantiation that disp_q8 selects (null: integer disparities)
+int lp_launch(const int32_t* match_idx, const int* pair_a, const int* pair_b, const int32_t* stereo_idx, const uint32_t* kp_keys,
+              const int* kp_count, const int32_t* disp_q8, int n_frames, int n_pairs, int max_kp, int H, int W, const double* cam,
+              double threshold_px, int n_hyp, uint32_t seed, int refine_iters, double* T_ab, double* JtJ, double* rss,
+              int32_t* match_idx_out, int32_t* info, void* stream) {
   VUS_REQUIRE(match_idx && pair_a && pair_b && stereo_idx && kp_keys && kp_count && cam && T_ab && JtJ && rss &&
                   match_idx_out && info,
               "stereo_pair_pose: null buffer");
@@ -422,12 +449,33 @@ extern "C" int vus_stereo_pair_pose(const int32_t* match_idx, const int* pair_a,
   // LDS: 36 B per keypoint slot (all candidates stay resident), next to 1 KiB of static LDS: 72,000 B at max_kp = 2000 (two
   // workgroups per CU), 147,456 B at 4096
   const size_t lds = (size_t)max_kp * LP_LDS_PER_SLOT;
+  auto* kernel = disp_q8 ? stereo_pair_pose_kernel<true> : stereo_pair_pose_kernel<false>;
   if (lds > 48 * 1024)
-    VUS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stereo_pair_pose_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  stereo_pair_pose_kernel<<<n_pairs, LP_THREADS, lds, vus::as_stream(stream)>>>(
-      match_idx, pair_a, pair_b, stereo_idx, kp_keys, kp_count, n_frames, max_kp, (uint32_t)W, c, n_hyp, seed, refine_iters,
-      T_ab, JtJ, rss, match_idx_out, info);
+    VUS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds));
+  kernel<<<n_pairs, LP_THREADS, lds, vus::as_stream(stream)>>>(match_idx, pair_a, pair_b, stereo_idx, kp_keys, kp_count, n_frames,
+                                                              max_kp, (uint32_t)W, c, n_hyp, seed, refine_iters, T_ab, JtJ, rss,
+                                                              match_idx_out, info, disp_q8);
   VUS_CHECK_LAUNCH("stereo_pair_pose");
   return VUS_OK;
+}
+
+}  // namespace
+
+extern "C" int vus_stereo_pair_pose(const int32_t* match_idx, const int* pair_a, const int* pair_b, const int32_t* stereo_idx,
+                                    const uint32_t* kp_keys, const int* kp_count, int n_frames, int n_pairs, int max_kp, int H,
+                                    int W, const double* cam, double threshold_px, int n_hyp, uint32_t seed, int refine_iters,
+                                    double* T_ab, double* JtJ, double* rss, int32_t* match_idx_out, int32_t* info,
+                                    void* stream) {
+  return lp_launch(match_idx, pair_a, pair_b, stereo_idx, kp_keys, kp_count, nullptr, n_frames, n_pairs, max_kp, H, W, cam,
+                   threshold_px, n_hyp, seed, refine_iters, T_ab, JtJ, rss, match_idx_out, info, stream);
+}
+
+extern "C" int vus_stereo_pair_pose_q8(const int32_t* match_idx, const int* pair_a, const int* pair_b,
+                                       const int32_t* stereo_idx, const uint32_t* kp_keys, const int* kp_count, int n_frames,
+                                       int n_pairs, int max_kp, int H, int W, const double* cam, double threshold_px, int n_hyp,
+                                       uint32_t seed, int refine_iters, const int32_t* disp_q8, double* T_ab, double* JtJ,
+                                       double* rss, int32_t* match_idx_out, int32_t* info, void* stream) {
+  return lp_launch(match_idx, pair_a, pair_b, stereo_idx, kp_keys, kp_count, disp_q8, n_frames, n_pairs, max_kp, H, W, cam,
+                   threshold_px, n_hyp, seed, refine_iters, T_ab, JtJ, rss, match_idx_out, info, stream);
 }

@@ -394,10 +394,34 @@ class StereoOrbFrontend:
                                 f"{self.p.cand_cap}: raise ImageProcessorParams.cand_cap")
 
     # ------------------------------------------------------------------------------------------
-    def feature_tracks(self, res: FrontendResult):
+    def refine_stereo(self, res: FrontendResult, images: torch.Tensor, half_win: int = 5, search: int = 5):
+        """Sub-pixel disparity of every stereo match of `res` (vus_stereo_refine, include/vus_subpixel.h): a SAD search of
+        +-search columns with a (2 half_win + 1)^2 window around the matched right keypoint, on the left keypoint's row, and
+        an equiangular fit of the minimum.  process() keeps no images: `images` is the tensor it was given, uint8
+        [F, 2, H, W] on the GPU.  In pyramid mode the search runs on these level-0 images at the keys' integer level-0
+        positions, whatever level a keypoint was found on.  Returns (disp_q8 int32 [F,K]: x_left - x_right in 1/256 px, 0
+        where there is no match; status uint8 [F,K]: 0 refined, 1 minimum at the edge of the search (the integer disparity
+        is kept), 255 no match).  Asynchronous on the current stream."""
+        assert images.dtype == torch.uint8 and images.is_cuda and images.is_contiguous()
+        F, K = res.n_frames, self.p.max_features
+        assert tuple(images.shape) == (F, 2, self.H, self.W), "images: the [F, 2, H, W] tensor process() was given"
+        disp = torch.empty((F, K), dtype=torch.int32, device=self.device)
+        status = torch.empty((F, K), dtype=torch.uint8, device=self.device)
+        ptr = _lib.ptr
+        _lib.call("vus_stereo_refine", ptr(images), F, self.H, self.W, self.W, ptr(res.stereo_idx), ptr(res.kp_keys),
+                  ptr(res.kp_count), K, int(half_win), int(search), ptr(disp), ptr(status), _lib.current_stream_ptr())
+        return disp, status
+
+    def _check_disparity(self, res: FrontendResult, disparity: torch.Tensor):
+        assert disparity.dtype == torch.int32 and disparity.is_cuda and disparity.is_contiguous() and \
+            tuple(disparity.shape) == (res.n_frames, self.p.max_features), "disparity: int32 [F, K] on the device (refine_stereo)"
+
+    def feature_tracks(self, res: FrontendResult, disparity: Optional[torch.Tensor] = None):
         """GPU CameraMeasurement emitter (vus_track_ids): returns (ids int64 [F,K], feats f64 [F,K,4],
         n_ids).  ids[f,i] >= 0 marks a published feature of frame f with persistent id; feats holds its
-        (u0, v0, u1, v1) in the normalised convention that batch.py:152-154 maps back to pixels."""
+        (u0, v0, u1, v1) in the normalised convention that batch.py:152-154 maps back to pixels.
+        disparity: refine_stereo()'s disp_q8; where ids >= 0 the right column becomes xr = (256 xl - disp_q8) / 256.0
+        (exact in f64) and u1 = 2.0 * xr / W - 1.0, the kernel's own formula: 256 (xl - xr) gives today's bits."""
         F, K = res.n_frames, self.p.max_features
         dev = self.device
         ids = torch.empty((F, K), dtype=torch.int64, device=dev)
@@ -407,6 +431,14 @@ class StereoOrbFrontend:
         _lib.call("vus_track_ids", ptr(res.stereo_idx), ptr(res.track_idx) if F > 1 else None, ptr(res.kp_keys),
                   ptr(res.kp_count), F, K, self.H, self.W, ptr(ids), ptr(feats), ptr(n_ids),
                   _lib.current_stream_ptr())
+        if disparity is not None:
+            self._check_disparity(res, disparity)
+            pos = res.kp_keys[0:2 * F:2].to(torch.int64) & 0xFFFFFF
+            xl = pos - torch.div(pos, self.W, rounding_mode="floor") * self.W
+            xr = (256 * xl - disparity.to(torch.int64)).to(torch.float64) / 256.0
+            # W as a device tensor: torch turns a division by a host scalar into a multiplication by its inverse
+            w = torch.tensor(float(self.W), dtype=torch.float64, device=self.device)
+            feats[:, :, 2] = torch.where(ids >= 0, 2.0 * xr / w - 1.0, feats[:, :, 2])
         return ids, feats, int(n_ids.item())
 
     def reject_track_outliers(self, res: FrontendResult, rot: torch.Tensor, cam=None, threshold_px: Optional[float] = None):
@@ -484,11 +516,15 @@ class StereoOrbFrontend:
         return S
 
     def relative_poses(self, res: FrontendResult, pair_a, pair_b, match_idx: torch.Tensor, cam5, threshold_px: float = 2.0,
-                       n_hyp: int = 256, seed: int = synth.SEED, refine_iters: int = 10) -> PairPoses:
+                       n_hyp: int = 256, seed: int = synth.SEED, refine_iters: int = 10,
+                       disparity: Optional[torch.Tensor] = None) -> PairPoses:
         """T_a^-1 T_b of every keyframe pair from its matches (match_keyframes) and the stereo matches of both keyframes:
         three-point RANSAC on the triangulated points, then refine_iters Gauss-Newton rounds on the left-image
         reprojection error of the inliers (vus_stereo_pair_pose, include/vus_loop.h; one launch for all pairs).  cam5:
-        (fx, fy, cx, cy) in pixels of this H x W image and the baseline in metres.  Asynchronous on the current stream."""
+        (fx, fy, cx, cy) in pixels of this H x W image and the baseline in metres.  disparity: refine_stereo()'s disp_q8 --
+        the depths then come from the refined disparities (vus_stereo_pair_pose_q8).  Asynchronous on the current stream."""
+        if disparity is not None:
+            self._check_disparity(res, disparity)
         a, b = self._pair_indices(res, pair_a, pair_b)
         n, K, ptr = a.numel(), self.p.max_features, _lib.ptr
         assert match_idx.dtype == torch.int32 and match_idx.is_cuda and match_idx.is_contiguous() and \
@@ -501,10 +537,13 @@ class StereoOrbFrontend:
                         rss=torch.empty((n,), dtype=torch.float64, device=dev),
                         info=torch.empty((n, 6), dtype=torch.int32, device=dev),
                         match_idx_out=torch.empty((n, K), dtype=torch.int32, device=dev))
-        _lib.call("vus_stereo_pair_pose", ptr(match_idx), ptr(a), ptr(b), ptr(res.stereo_idx), ptr(res.kp_keys),
-                  ptr(res.kp_count), res.n_frames, n, K, self.H, self.W, cam_h.ctypes.data, float(threshold_px), int(n_hyp),
-                  int(seed) & 0xFFFFFFFF, int(refine_iters), ptr(out.T_ab), ptr(out.JtJ), ptr(out.rss), ptr(out.match_idx_out),
-                  ptr(out.info), _lib.current_stream_ptr())
+        head = (ptr(match_idx), ptr(a), ptr(b), ptr(res.stereo_idx), ptr(res.kp_keys), ptr(res.kp_count), res.n_frames, n, K,
+                self.H, self.W, cam_h.ctypes.data, float(threshold_px), int(n_hyp), int(seed) & 0xFFFFFFFF, int(refine_iters))
+        tail = (ptr(out.T_ab), ptr(out.JtJ), ptr(out.rss), ptr(out.match_idx_out), ptr(out.info), _lib.current_stream_ptr())
+        if disparity is None:
+            _lib.call("vus_stereo_pair_pose", *head, *tail)
+        else:
+            _lib.call("vus_stereo_pair_pose_q8", *head, ptr(disparity), *tail)
         return out
 
     def stereo_factors(self, ids: torch.Tensor, feats: torch.Tensor, n_ids: int, Rt: torch.Tensor, cam: torch.Tensor,
@@ -534,10 +573,10 @@ class StereoOrbFrontend:
         return {"obs_frame": of[:n], "obs_id": oi[:n], "obs_meas": om[:n], "lm_first": first[:n_ids],
                 "lm_point": pt[:n_ids]}
 
-    def camera_measurements(self, res: FrontendResult) -> List[CameraMeasurement]:
+    def camera_measurements(self, res: FrontendResult, disparity: Optional[torch.Tensor] = None) -> List[CameraMeasurement]:
         """Per frame, the published features as CameraMeasurement records (message shape of
-        batch.py:149-154), built from feature_tracks()."""
-        ids, feats, _ = self.feature_tracks(res)
+        batch.py:149-154), built from feature_tracks(); disparity as there."""
+        ids, feats, _ = self.feature_tracks(res, disparity)
         ids, feats = ids.cpu().numpy(), feats.cpu().numpy()
         out = []
         for f in range(res.n_frames):

@@ -283,6 +283,14 @@ class LoopClosureParams:
             raise ValueError(f"LoopClosureParams.candidates must be one of {CANDIDATE_MODES}, not {self.candidates!r}")
 
 
+@dataclass
+class SubpixelParams:
+    """StereoOrbFrontend.refine_stereo (include/vus_subpixel.h): the SAD window is (2 half_win + 1)^2 pixels, shifts of
+    +-search columns around the matched right keypoint are tried."""
+    half_win: int = 5
+    search: int = 5
+
+
 def loop_candidates(poses12: np.ndarray, params: LoopClosureParams):
     """Keyframe pairs (a, b), b - a >= min_gap, whose camera centres lie within radius_m and whose optical axes (the
     camera's z axis in the world) within max_angle_rad of each other in poses12 [F,12] (camera poses, flat12).  Per b the
@@ -393,7 +401,8 @@ def loop_closure_factors(result, pairs, params: LoopClosureParams, body_P_sensor
 def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, disparity_sign: int = 1,
                  params: Optional[ImageProcessorParams] = None, bulk: bool = True, frontend: Optional[StereoOrbFrontend] = None,
                  gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None, ransac_px: float = 0.0,
-                 ransac_rotation: str = "imu", rectifier=None, loop_closure: Optional[LoopClosureParams] = None):
+                 ransac_rotation: str = "imu", rectifier=None, loop_closure: Optional[LoopClosureParams] = None,
+                 subpixel: Optional[SubpixelParams] = None):
     """Images to optimised trajectory: frames uint8 [F,2,H,W] on the GPU (one stereo pair per keyframe), odom_poses
     [F,12] (the odometry estimate of every keyframe = initial value of X(i) AND the camera transform get_landmarks
     uses), imu [F-1][n,>=6] samples between keyframes, dvl [F,3].  gate_px > 0 applies BatchSequence.gate_factors (bulk
@@ -407,7 +416,10 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     (loop_candidates on the camera poses), by appearance (keyframe_similarity + appearance_candidates; stages then also holds
     "loop_similarity") or both, as LoopClosureParams.candidates says; their relative poses from the front end
     (match_keyframes + relative_poses) and the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
-    "loop_result" (None without a candidate) and "loop_accepted".  Returns (results Values, BatchSequence, stages dict)."""
+    "loop_result" (None without a candidate) and "loop_accepted".  subpixel: the stereo matches are refined on the
+    (rectified) images after process() (refine_stereo) and the refined disparities replace the integer ones in the features
+    of either graph builder and in the depths of the loop closures; stages then holds "stereo_disparity" (int32 [F,K], 1/256
+    px) and "stereo_refine_status".  Returns (results Values, BatchSequence, stages dict)."""
     assert ransac_rotation in ("imu", "odom")
     if rectifier is not None:
         H, W = frames.shape[2:]
@@ -433,11 +445,16 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
             dR = np.einsum("pji,pjk->pik", Rb[:-1], Rb[1:])                             # R_p^T R_{p+1}
         rot = torch.from_numpy(ransac_rotations(dR, body_P_sensor)).to(frames.device)
         ransac_info = fe.reject_track_outliers(res, rot, threshold_px=ransac_px)
-    ids, feats, n_ids = fe.feature_tracks(res)
+    disparity = None
+    if subpixel is not None:
+        disparity, refine_status = fe.refine_stereo(res, frames, subpixel.half_win, subpixel.search)
+    ids, feats, n_ids = fe.feature_tracks(res, disparity)
     Rt_cam = Rt if body_P_sensor is None else np.stack([gtsam.Pose3.from_flat12(r).compose(body_P_sensor).flat12() for r in Rt])
     stages = {"frontend": res, "ids": ids, "feats": feats, "n_ids": n_ids}
     if ransac_info is not None:
         stages["ransac_info"] = ransac_info
+    if subpixel is not None:
+        stages.update(stereo_disparity=disparity, stereo_refine_status=refine_status)
     loop_factors = []
     if loop_closure is not None:
         lc = loop_closure
@@ -453,7 +470,7 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
             cam5 = np.concatenate([default_camera(H, W), [seq.baseline]])
             midx = fe.match_keyframes(res, pairs[0], pairs[1], max_distance=lc.match_max_distance)
             loop_result = fe.relative_poses(res, pairs[0], pairs[1], midx, cam5, lc.threshold_px, lc.n_hyp, lc.seed,
-                                            lc.refine_iters)
+                                            lc.refine_iters, disparity=disparity)
             accepted = loop_closure_measurements(loop_result, lc, body_P_sensor)[0]
             loop_factors = loop_closure_factors(loop_result, pairs, lc, body_P_sensor)
         stages.update(loop_pairs=pairs, loop_result=loop_result, loop_accepted=accepted)
@@ -470,7 +487,7 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
         seq.batch_create_from_tracks(factors)
         stages["factors"] = factors
     else:
-        msgs = fe.camera_measurements(res)
+        msgs = fe.camera_measurements(res, disparity)
         for i in range(F):
             pose = gtsam.Pose3.from_flat12(Rt[i])
             seq.set_zed_world_transform(gtsam.Pose3.from_flat12(Rt_cam[i]).rotation(), Rt_cam[i, 9:])
