@@ -12,12 +12,13 @@ dev = torch.device("cuda:0")
 images = bench.make_stream(F, 0, dev)
 fe = StereoOrbFrontend(720, 1280, max_frames=F, params=ImageProcessorParams(), device=dev)
 lib = _lib.load()
-out = (ctypes.c_ulonglong * 4)()
+out = (ctypes.c_ulonglong * 5)()
 fe.process(images); torch.cuda.synchronize()
 lib.vus_debug_fast_counters(out, 1)
 fe.process(images); torch.cuda.synchronize()
 lib.vus_debug_fast_counters(out, 1)
-tiles, strips, pixels = out[0], out[1], out[2]
+tiles, strips, pixels, score_waves, two_sided_waves = out[0], out[1], out[2], out[3], out[4]
 print(f"tiles {tiles}  strips listed per tile {strips / tiles:.1f} of 884 ({100 * strips / tiles / 884:.1f} %)  "
       f"pixels listed per tile {pixels / tiles:.1f} of 3536 ({100 * pixels / tiles / 3536:.2f} %)")
+print(f"exact score: {score_waves / tiles:.2f} wave-iterations per tile, {two_sided_waves} of {score_waves} took the two-sided form")
 print("thresholds of the first images:", fe.fast_thr[:8].tolist())

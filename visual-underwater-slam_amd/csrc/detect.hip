@@ -13,6 +13,11 @@
 //    strips, on four opposite pairs of the circle (N/S, E/W, the two diagonals).  Survivors are
 //    compacted into an LDS work list (DPP wave scan) and the exact score runs on dense lanes, one
 //    pixel per lane, from 17 byte reads around the pixel (v_min3/v_max3 sliding windows);
+//  * the per-pixel pre-test is two comparisons, one per side (bright arcs, dark arcs), and a side it
+//    closes cannot score thr.  Both bits travel with the work-list entry and the exact score walks
+//    the arcs of the open side only (one v_min3 chain, fast_score_side); a wave that holds a pixel
+//    with both sides open takes the two-sided form (fast_score_bytes) for all its lanes.  The bench
+//    stream has no such pixel (profiles/fast_onesided_r07.md);
 //  * non-max suppression runs over that survivor list, not over the tile: a list entry is the pixel's
 //    byte index in the LDS score tile, its eight neighbours are eight byte reads;
 //  * the 7x7 smoothing is two banded int8 GEMMs on the matrix cores (blur_tile_mfma).  In the
@@ -38,11 +43,12 @@ namespace {
 #else
 #define VUS_FAST_EXIT(N)
 #endif
-#ifdef VUS_FAST_DEBUG_COUNT   // counting build (tools/fast_counts.py): tiles, strips listed by pass 1a, pixels listed by pass 1b
-__device__ unsigned long long g_fast_dbg[4];
+#ifdef VUS_FAST_DEBUG_COUNT   // counting build (tools/fast_counts.py): tiles, strips listed by pass 1a, pixels listed by pass 1b,
+                              // wave-iterations of pass 2 and those of them that took the two-sided form (out: 5 values)
+__device__ unsigned long long g_fast_dbg[5];
 extern "C" int vus_debug_fast_counters(unsigned long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fast_dbg), sizeof(g_fast_dbg)) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[4] = {0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_fast_dbg), z, sizeof(z)) != hipSuccess) return -1; }
+  if (reset) { unsigned long long z[5] = {0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_fast_dbg), z, sizeof(z)) != hipSuccess) return -1; }
   return 0;
 }
 #endif
@@ -72,13 +78,13 @@ __device__ __forceinline__ int byte_of(uint32_t w, int i) { return (int)((w >> (
 // fixed byte -- 21 ds_read_b32 + 21 v_alignbyte against the 17 ds_read_u8 here: 2.92 against 2.89 ms per 1000 stereo
 // frames.  Round 3: the same windows on packed i16 pairs (b, 255 - b), one v_pk_min_i16 chain for bright and dark arcs --
 // 95 packed instructions + 17 v_not do not issue faster than the ~160 scalar ones: fast_detect 6.23 against 6.17 ms.)
+constexpr int FAST_DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+constexpr int FAST_DY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
 __device__ __forceinline__ int fast_score_bytes(const uint8_t* c, int rb) {
-  constexpr int DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-  constexpr int DY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
   const int p = c[0];
   int d[16];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) d[k] = (int)c[DY[k] * rb + DX[k]] - p;
+  for (int k = 0; k < 16; ++k) d[k] = (int)c[FAST_DY[k] * rb + FAST_DX[k]] - p;
   int mn3[16], mx3[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
@@ -92,6 +98,36 @@ __device__ __forceinline__ int fast_score_bytes(const uint8_t* c, int rb) {
     best_dark = min(best_dark, max3i(mx3[k], mx3[(k + 3) & 15], mx3[(k + 6) & 15]));
   }
   return max(best_bright, -best_dark) - 1;
+}
+
+// The same score for a pixel whose pre-test left ONE side open (flip = 0: the bright side, flip = 255: the dark side).
+// Closed means that one of the tested opposite pairs has both members within thr of the pixel on that side; every arc
+// of 9 holds a member of every opposite pair, so that side's best arc is worth at most thr - 1 and is never stored: the
+// stored value is the open side's or nothing.  The windows are shift-invariant, so they run on the circle bytes
+// themselves and the centre is subtracted once at the end; the dark side is the bright side of the complemented bytes
+// (b ^ 255 = 255 - b), one full-rate v_xor per circle byte with the lane's flip where the two-sided form has a
+// subtraction:  max over arcs of min(b ^ flip) - (p ^ flip) - 1  =  best_bright - 1  or  -best_dark - 1.
+// 16 v_xor + 16 + 16 v_min3 + 8 v_max3 / v_max against 16 v_sub + 32 + 32 + 16 of the two-sided form.
+// (The windows as the instruction itself: written as min(min(a, b), c) the compiler shares min(a, b) between
+// neighbouring windows and ends with 38 v_min / v_min3 where 32 v_min3 do.)
+__device__ __forceinline__ int min3_window(int a, int b, int c) {
+  int r;
+  asm("v_min3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+__device__ __forceinline__ int fast_score_side(const uint8_t* c, int rb, int flip) {
+  int b[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) b[k] = (int)c[FAST_DY[k] * rb + FAST_DX[k]] ^ flip;
+  int w3[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) w3[k] = min3_window(b[k], b[(k + 1) & 15], b[(k + 2) & 15]);
+  int w9[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) w9[k] = min3_window(w3[k], w3[(k + 3) & 15], w3[(k + 6) & 15]);
+  const int m0 = max3i(w9[0], w9[1], w9[2]), m1 = max3i(w9[3], w9[4], w9[5]), m2 = max3i(w9[6], w9[7], w9[8]);
+  const int m3 = max3i(w9[9], w9[10], w9[11]), m4 = max3i(w9[12], w9[13], w9[14]);
+  return max(max3i(m0, m1, m2), max3i(m3, m4, w9[15])) - ((int)c[0] ^ flip) - 1;
 }
 
 constexpr int VUS_CAND_REGIONS = 8;
@@ -241,7 +277,12 @@ __device__ __forceinline__ void fast_tile_body(
   __shared__ uint32_t s_aux[AUX_DW];                               // the strip pre-test's two u16 tables:
   uint16_t* const s_mm = reinterpret_cast<uint16_t*>(s_aux);       // min | max << 8 of each staged dword
   uint16_t* const s_strip = s_mm + IMG_ROWS * IMG_DW;              // strips that pass the strip test
-  __shared__ uint16_t s_work[SCORES ? SC_ROWS * SC_DW * 4 : 2];    // pixels that pass the pre-test
+  // pixels that pass the pre-test: the pixel's byte index in the score tile (twelve bits) and, in the two top bits,
+  // which sides of the pre-test it passed (WORK_BRIGHT, WORK_DARK)
+  __shared__ uint16_t s_work[SCORES ? SC_ROWS * SC_DW * 4 : 2];
+  constexpr int WORK_SIDE_SHIFT = 14, WORK_INDEX = (1 << 12) - 1;
+  constexpr int WORK_BRIGHT = 1 << WORK_SIDE_SHIFT, WORK_DARK = 2 << WORK_SIDE_SHIFT;
+  static_assert(SC_ROWS * SC_DW * 4 <= WORK_INDEX + 1, "a work-list entry keeps twelve bits for the pixel");
   __shared__ int s_nstrip;
   __shared__ int s_cnt, s_base, s_nwork;
   static_assert(IMG_ROWS * IMG_DW >= TW * TH / 4, "candidate list must fit in the image tile");
@@ -408,7 +449,11 @@ __device__ __forceinline__ void fast_tile_body(
     // 884 strips here and 138 of their pixels go on to the exact score, tools/fast_counts.py.)
     for (int j0 = 0; j0 < nstrip; j0 += NTHREADS) {   // uniform trip count (wave scans inside)
       const int j = j0 + tid;
-      int mask = 0, idx = 0;
+      // side[e]: the pre-test's two comparisons for pixel e of the strip as its two low bits -- bit 0: the bright side is
+      // open, bit 1: the dark side -- above them those of the pixels before it.  Each comparison is the sign of a
+      // difference, shifted in with one v_alignbit: side[3] holds all eight.
+      uint32_t side[4] = {0u, 0u, 0u, 0u};
+      int idx = 0;
       if (j < nstrip) {
         idx = s_strip[j];
         const int sr = idx / SC_DW, ss = idx - sr * SC_DW;
@@ -433,15 +478,21 @@ __device__ __forceinline__ void fast_tile_body(
           const int ne = byte_of(nev, e), sw = byte_of(swv, e), se = byte_of(sev, e), nw = byte_of(nwv, e);
           hi = min3i(hi, max(ne, sw), max(se, nw));
           lo = max3i(lo, min(ne, sw), min(se, nw));
-          mask |= (hi > p + thr || lo < p - thr) ? (1 << e) : 0;
+          // hi > p + thr: the bright side is open; lo < p - thr: the dark side
+          const uint32_t dark = __builtin_amdgcn_alignbit(e ? side[e - 1] : 0u, (uint32_t)(lo - (p - thr)), 31);
+          side[e] = __builtin_amdgcn_alignbit(dark, (uint32_t)((p + thr) - hi), 31);
         }
         if (gx < 3 || gx + 3 >= W - 3) {   // strips straddling the 3-pixel frame (edge tiles only)
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (gx + e < 3 || gx + e >= W - 3) mask &= ~(1 << e);
+            if (gx + e < 3 || gx + e >= W - 3) {
+              side[e] &= ~3u;
+              side[3] &= ~(3u << (2 * (3 - e)));
+            }
         }
       }
-      const int cnt = __popc(mask);
+      const uint32_t listed = (side[3] | (side[3] >> 1)) & 0x55u;   // bit 2 (3 - e): pixel e goes on to the exact score
+      const int cnt = __popc(listed);
       int incl = cnt;   // inclusive wave scan (same DPP sequence as wave_sum_i32)
       incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true);
       incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true);
@@ -456,7 +507,7 @@ __device__ __forceinline__ void fast_tile_body(
       int pos = base + incl - cnt;
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (mask & (1 << e)) s_work[pos++] = (uint16_t)(idx * 4 + e);
+        if (listed & (1u << (2 * (3 - e)))) s_work[pos++] = (uint16_t)(side[e] << WORK_SIDE_SHIFT | (uint32_t)(idx * 4 + e));   // the store keeps 16 bits
     }
   }
 #ifdef VUS_FAST_DEBUG_COUNT
@@ -470,13 +521,28 @@ __device__ __forceinline__ void fast_tile_body(
 
   if (SCORES) {
     // Pass 2 -- exact FAST score of the survivors, one pixel per lane, from the bytes around it in the staged tile.
+    // A pixel that passed one side of the pre-test walks that side's arcs only (fast_score_side): the other side cannot
+    // reach thr.  A pixel that passed both (a mid-grey pixel on an edge of contrast above 2 thr that runs between the
+    // tested pairs; none on the bench stream) needs both chains: a wave with such a lane takes the two-sided form for
+    // all its lanes, behind one ballot.
     const int nwork = s_nwork;
     uint8_t* score8 = reinterpret_cast<uint8_t*>(s_score);
     for (int j = tid; j < nwork; j += NTHREADS) {
-      const int ent = s_work[j];
+      const int went = s_work[j];
+      const int ent = went & WORK_INDEX;
       const int idx = ent >> 2, e = ent & 3;
       const int sr = idx / SC_DW, ss = idx - sr * SC_DW;
-      const int sc = fast_score_bytes(reinterpret_cast<const uint8_t*>(s_img) + (sr + 3) * (4 * IMG_DW) + 4 * (ss + 1) + e, 4 * IMG_DW);
+      const uint8_t* c = reinterpret_cast<const uint8_t*>(s_img) + (sr + 3) * (4 * IMG_DW) + 4 * (ss + 1) + e;
+      int sc;
+      const bool two_sided = __ballot((went & (WORK_BRIGHT | WORK_DARK)) == (WORK_BRIGHT | WORK_DARK)) != 0ull;
+#ifdef VUS_FAST_DEBUG_COUNT
+      if (j == __builtin_amdgcn_readfirstlane(j) && BLUR) { atomicAdd(&g_fast_dbg[3], 1ull); atomicAdd(&g_fast_dbg[4], two_sided ? 1ull : 0ull); }
+#endif
+      if (two_sided) {
+        sc = fast_score_bytes(c, 4 * IMG_DW);
+      } else {
+        sc = fast_score_side(c, 4 * IMG_DW, (went & WORK_BRIGHT) ? 0 : 255);
+      }
       if (sc >= thr) score8[ent] = (uint8_t)sc;
     }
     __syncthreads();
@@ -504,7 +570,7 @@ __device__ __forceinline__ void fast_tile_body(
     const int nwork = s_nwork;
     const uint8_t* score8 = reinterpret_cast<const uint8_t*>(s_score);
     for (int j = tid; j < nwork; j += NTHREADS) {
-      const int ent = s_work[j];
+      const int ent = s_work[j] & WORK_INDEX;
       const int s = score8[ent];
       if (s == 0) continue;
       const int sr = ent / (4 * SC_DW), sx = ent - sr * (4 * SC_DW);     // row / byte column inside the score tile
@@ -717,8 +783,10 @@ __global__ __launch_bounds__(1024) void fast_retry_list_kernel(const int* __rest
   if (threadIdx.x == 0) retry_count[0] = s_n;
 }
 
-// persistent: (listed image, tile) items at fast_threshold; no work, no cost
-__global__ __launch_bounds__(NTHREADS, VUS_FAST_WPE) void fast_retry_kernel(const uint8_t* __restrict__ img, int H, int W, int pitch, int thr,
+// persistent: (listed image, tile) items at fast_threshold; no work, no cost.  The loop around the tile body keeps more
+// alive than the one-tile kernels do: asked for seven waves per SIMD the compiler fits it into 72 VGPRs without scratch
+// (78 and six waves if left alone).
+__global__ __launch_bounds__(NTHREADS, VUS_FAST_WPE > 7 ? VUS_FAST_WPE : 7) void fast_retry_kernel(const uint8_t* __restrict__ img, int H, int W, int pitch, int thr,
                                                               int border, uint32_t* __restrict__ cand_keys, int cand_cap,
                                                               int* __restrict__ cand_count, const int* __restrict__ retry_list,
                                                               const int* __restrict__ retry_count, int tiles_x, int tiles_per_img) {
