@@ -28,14 +28,20 @@ constexpr int OR_DW = 10;                   // 36 bytes cover x-15..x+15 from an
 constexpr int BR_R = VUS_RBRIEF_REACH;      // 18
 constexpr int BR_ROWS = 2 * BR_R + 1;       // 37
 constexpr int BR_DW = 10;                   // 40 bytes cover x-18..x+18 from an aligned start
-constexpr int BR_DW_TILED = 12;             // block-tiled planes: 44 of 48 bytes from an 8-byte aligned start (OrGeom)
+constexpr int BR_DW_TILED = 16;             // block-tiled planes: 64-byte rows in LDS, three 16-byte block rows and a dword of the fourth (OrGeom)
+constexpr int OR_PC = 3;                    // block-tiled planes: 31 + 15 bytes of a centroid patch row lie in three block rows
+constexpr int OR_NP = OR_ROWS * OR_PC;      // 93 pieces of a centroid patch
 constexpr int OR_KP_PER_WAVE = 8;           // keypoints of one wave; the reduce-scatter and the one-store epilogue are written for 8
 
 // Load a (2*RADIUS+1) x (4*DW)-byte patch around (x, y) into registers: every lane issues all of
 // its loads back to back (one memory round trip), the caller stores them to LDS afterwards.
 // A lane moves two dwords per load (dwordx2 at dword alignment): the texture path's cost is per instruction, not per
 // byte.  Measured and not kept, ms per 1000 frames against the 2.82 of 6 dwordx2 per keypoint: 11 dword loads: 3.19;
-// 4 dwordx4 of 48-byte rows: 3.04.
+// 4 dwordx4 of 48-byte rows: 3.04 (dword-aligned, so they straddle 16-byte boundaries).  On block-tiled planes, naturally
+// aligned dwordx4 of whole block rows (below), ms per 1000 stereo frames against the 1.71 of 7 dwordx2 per keypoint: 3.75
+// loads with 9 % more bytes (kept): 1.58; 3.75 loads with 13 % more bytes: 1.61; 4.5 loads with 28 % more bytes: 1.85 --
+// there the cost is per instruction AND per byte, about 0.08 ms per load and keypoint and 0.4 ms per 1000 bytes and
+// keypoint (profiles/orient_block_rows_r08.md).
 typedef uint32_t PatchVec __attribute__((ext_vector_type(2), aligned(1)));
 
 // EXACT: the patch starts at column x - RADIUS whatever its alignment (images whose rows are not dword
@@ -89,67 +95,133 @@ struct PatchRegs {
   }
 };
 
-// The same patch, and the same interface, from a block-tiled plane (include/vus_tiled.h; W % 16 == 0, H % 8 == 0, the
-// pitch is W and goes unused).  The patch starts at the 8-byte boundary below x - RADIUS, so a lane's dwordx2 never
-// leaves a 16-byte block row.  Pixel (y0 + r, xa + 8 c) of vector (r, c) sits at
-//   tiled(y0 & ~7, xa & ~15)  +  16 (y0 & 7) + 16 r + f(q)  +  (p >> 3) (8 W - 128),   p = (y0 & 7) + r,  q = (xa & 8) + 8 c,
-//   f(q) = 128 (q >> 4) + (q & 8)
-// -- the first two terms wave-uniform, 16 r + f(q) a per-lane constant for each of the two values of xa & 8: four
-// vector instructions per vector (add, shift, bit-field extract, multiply-add) on top of the plain form's load.  The
-// three per-lane constants of a vector share ONE register (pk below): 6 bits of row, two 10-bit offsets.
-template <int RADIUS, int DW>
-struct TiledPatchRegs {
-  static_assert(DW % 2 == 0, "row width must be a multiple of the vector width");
-  static constexpr int ROWS = 2 * RADIUS + 1;
-  static constexpr int HW = DW / 2;             // vectors per row
-  static constexpr int N = ROWS * HW;
-  static constexpr int ITERS = (N + 63) / 64;
-  static_assert(ROWS + 7 < 64 && 16 * (ROWS - 1) + 128 * ((8 * HW) >> 4) + 8 < 1024, "pk fields: 6-bit row, 10-bit offsets");
-  PatchVec v[ITERS];
-  uint32_t pk[ITERS];   // this lane's vectors: (patch row r) << 20 | (16 r + f(q), xa & 8 == 8) << 10 | (..., xa & 8 == 0)
+// Patches from a block-tiled plane (include/vus_tiled.h; W % 16 == 0, H % 8 == 0).  A lane's vector is one whole
+// 16-byte block row (dwordx4, naturally aligned: it never straddles a block row), and the patch starts at the 16-byte
+// boundary xa below x - RADIUS.  Piece (r, c) -- pixels (y0 + r, xa + 16 c .. + 15) -- sits at
+//   tiled(y0 & ~7, xa)  +  16 (y0 & 7)  +  16 r + 128 c  +  (p >> 3) (8 W - 128),   p = (y0 & 7) + r
+// -- the first two terms wave-uniform per keypoint, 16 r + 128 c a per-lane constant.  Keypoints whose window leaves the
+// image take the replicate-clamped byte path.
+__device__ __forceinline__ uint4 tiled_piece_clamped(const uint8_t* __restrict__ src, int H, int W, int gy, int gx) {
+  gy = clampi(gy, 0, H - 1);
+  uint32_t w[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    w[j] = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) w[j] |= (uint32_t)src[vus_tiled_offset(gy, clampi(gx + 4 * j + b, 0, W - 1), W)] << (8 * b);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The centroid patches of TWO keypoints, 93 pieces each, dealt to the lanes back to back: piece p = lane + 64 u
+// (u < 3) belongs to keypoint p / 93 and is piece q = p % 93 = 3 r + c of its patch.  Wave-load 0 is all first keypoint,
+// wave-load 2 all second, wave-load 1 changes over at lane SPLIT: 1.5 loads per keypoint.  Pieces 186 .. 191, and the
+// second keypoint's when it is not live, are not read and hold 0.
+struct TiledDiscPair {
+  static constexpr int ITERS = (2 * OR_NP + 63) / 64;   // 3
+  static constexpr int SPLIT = OR_NP - 64;              // 29
+  static_assert(ITERS == 3 && SPLIT > 0 && SPLIT < 64, "wave-load 1 is the only mixed one");
+  static_assert(OR_ROWS + 7 < 64 && 16 * (OR_ROWS - 1) + 128 * (OR_PC - 1) < 1024, "pk fields: 6-bit row, 10-bit offset");
+  uint4 v[ITERS];
+  uint32_t pk[ITERS];   // this lane's pieces: (row r) << 20 | (16 r + 128 c)
 
   __device__ __forceinline__ void init(int /*pitch*/, int lane) {
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) {
-      const int t = min(lane + 64 * u, N - 1);
-      const uint32_t r = (uint32_t)(t / HW), q0 = 8u * (uint32_t)(t % HW), q8 = q0 + 8u;
-      const uint32_t off0 = 16u * r + 128u * (q0 >> 4) + (q0 & 8u), off8 = 16u * r + 128u * (q8 >> 4) + (q8 & 8u);
-      pk[u] = r << 20 | off8 << 10 | off0;
+      const int p = min(lane + 64 * u, 2 * OR_NP - 1), q = p >= OR_NP ? p - OR_NP : p;
+      const uint32_t r = (uint32_t)(q / OR_PC), c = (uint32_t)(q % OR_PC);
+      pk[u] = r << 20 | (16u * r + 128u * c);
     }
   }
-  __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int /*pitch*/, int y, int x,
+  static __device__ __forceinline__ bool inside(int H, int W, int y, int x) {
+    const int xa = (x - OR_R) & ~15;
+    return y - OR_R >= 0 && y + OR_R < H && xa >= 0 && xa + 16 * OR_PC <= W;
+  }
+  // (ya, xa): the first keypoint, (yb, xb): the second, read only if b_live (wave-uniform)
+  __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int ya, int xa, int yb, int xb, bool b_live,
                                        int lane) {
-    const int xa = (x - RADIUS) & ~7, y0 = y - RADIUS;
-    const bool inside = y0 >= 0 && y + RADIUS < H && xa >= 0 && xa + 4 * DW <= W;
-    if (inside) {   // wave-uniform
-      const uint8_t* base = src + vus_tiled_offset(y0 & ~7, xa & ~15, W) + 16 * (y0 & 7);
-      const uint32_t ys = (uint32_t)(y0 & 7) << 20, ystep = 8u * (uint32_t)W - 128u;
-      const uint32_t sel = (xa & 8) != 0 ? 10u : 0u;
-#pragma unroll
-      for (int u = 0; u < ITERS; ++u) {   // (ys + r) >> 3 == (pk + ys) >> 23: the row field has room for ys + r < 64
-        const uint32_t off = ((pk[u] + ys) >> 23) * ystep + __builtin_amdgcn_ubfe(pk[u], sel, 10u);
-        v[u] = *reinterpret_cast<const PatchVec*>(base + (size_t)off);
-      }
-    } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
+    const bool second = lane >= SPLIT;   // of wave-load 1
+    const bool idle2 = lane >= 2 * OR_NP - 128;
+    if (inside(H, W, ya, xa) && (!b_live || inside(H, W, yb, xb))) {   // wave-uniform
+      const int y0a = ya - OR_R, y0b = yb - OR_R;
+      const uint32_t koa = vus_tiled_offset(y0a & ~7, (xa - OR_R) & ~15, W) + 16u * (uint32_t)(y0a & 7);
+      const uint32_t kob = b_live ? vus_tiled_offset(y0b & ~7, (xb - OR_R) & ~15, W) + 16u * (uint32_t)(y0b & 7) : koa;
+      const uint32_t ysa = (uint32_t)(y0a & 7) << 20, ysb = (uint32_t)(y0b & 7) << 20, ystep = 8u * (uint32_t)W - 128u;
+      // (ys + r) >> 3 == (pk + ys) >> 23: the row field has room for ys + r < 64
+      v[0] = *reinterpret_cast<const uint4*>(src + koa + (size_t)(((pk[0] + ysa) >> 23) * ystep + (pk[0] & 1023u)));
+      v[1] = make_uint4(0u, 0u, 0u, 0u);
+      v[2] = make_uint4(0u, 0u, 0u, 0u);
+      if (!second || b_live)
+        v[1] = *reinterpret_cast<const uint4*>(
+            src + (size_t)((second ? kob : koa) + ((pk[1] + (second ? ysb : ysa)) >> 23) * ystep + (pk[1] & 1023u)));
+      if (b_live && !idle2)
+        v[2] = *reinterpret_cast<const uint4*>(src + kob + (size_t)(((pk[2] + ysb) >> 23) * ystep + (pk[2] & 1023u)));
+    } else {        // replicate-clamped, byte by byte (a keypoint of the pair near the image edge)
 #pragma unroll
       for (int u = 0; u < ITERS; ++u) {
-        const int t = min(lane + 64 * u, N - 1);
-        const int r = t / HW, c = t - r * HW;
-        const int gy = clampi(y0 + r, 0, H - 1), gx = xa + 8 * c;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          uint32_t w = 0;
-#pragma unroll
-          for (int b = 0; b < 4; ++b) w |= (uint32_t)src[vus_tiled_offset(gy, clampi(gx + 4 * k + b, 0, W - 1), W)] << (8 * b);
-          v[u][k] = w;
-        }
+        const int p = lane + 64 * u;
+        const bool sec = p >= OR_NP;
+        const int q = sec ? p - OR_NP : p, r = q / OR_PC, c = q - r * OR_PC;
+        const int y = sec ? yb : ya, x = sec ? xb : xa;
+        v[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (p < 2 * OR_NP && (!sec || b_live)) v[u] = tiled_piece_clamped(src, H, W, y - OR_R + r, ((x - OR_R) & ~15) + 16 * c);
       }
     }
   }
-  __device__ __forceinline__ void store(uint32_t* __restrict__ dst, int lane) const {
+};
+
+// The 37-row descriptor patch: 37 + a bytes per row from the 16-byte boundary below x - 18, a = (x - 18) & 15.  Three pieces
+// per row hold 48 of them (111 pieces, two wave-loads): all of the window for a <= 11.  For a > 11 the window ends 1 .. 4
+// bytes into the fourth block row, and ONE dword of that block row is read per patch row (row r in lane r, a third
+// wave-load of 148 bytes) -- wave-uniform per keypoint.  Four whole pieces per row (148 pieces, three dwordx4) for every
+// keypoint cost 1.85 ms per 1000 stereo frames against the 1.71 of the dwordx2 form, for a > 11 only 1.61, this form 1.58
+// (profiles/orient_block_rows_r08.md).  Piece t = lane + 64 u is (r, c) = (t / 3, t % 3): no per-lane constants are kept.
+// In LDS the patch has 64-byte rows, piece (r, c) at 64 r + 16 c, the dword at 64 r + 48; what is not written is not read.
+struct TiledBriefRegs {
+  static constexpr int ROWS = BR_ROWS, N = BR_ROWS * 3;
+  uint4 v[2];
+  uint32_t col;   // a > 11: bytes 48 .. 51 of row `lane`
+
+  static __device__ __forceinline__ bool wide(int x) { return ((x - BR_R) & 15) > 11; }
+  __device__ __forceinline__ void init(int /*pitch*/, int /*lane*/) { col = 0; }
+  __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int /*pitch*/, int y, int x, int lane) {
+    const int xa = (x - BR_R) & ~15, y0 = y - BR_R, rc = min(lane, ROWS - 1);
+    const bool inside = y0 >= 0 && y + BR_R < H && xa >= 0 && xa + (wide(x) ? 64 : 48) <= W;
+    if (inside) {   // wave-uniform
+      const uint8_t* base = src + vus_tiled_offset(y0 & ~7, xa, W) + 16 * (y0 & 7);
+      const uint32_t ys = (uint32_t)(y0 & 7), ystep = 8u * (uint32_t)W - 128u;
 #pragma unroll
-    for (int u = 0; u < ITERS; ++u)
-      if (lane + 64 * u < N) *reinterpret_cast<uint2*>(dst + 2 * (lane + 64 * u)) = make_uint2(v[u][0], v[u][1]);
+      for (int u = 0; u < 2; ++u) {
+        const int t = min(lane + 64 * u, N - 1), r = (t * 171) >> 9, c = t - 3 * r;   // t / 3 for t < 256
+        const uint32_t off = (((uint32_t)r + ys) >> 3) * ystep + 16u * (uint32_t)r + 128u * (uint32_t)c;
+        v[u] = *reinterpret_cast<const uint4*>(base + (size_t)off);
+      }
+      if (wide(x))
+        col = *reinterpret_cast<const uint32_t*>(base + (size_t)((((uint32_t)rc + ys) >> 3) * ystep + 16u * (uint32_t)rc + 384u));
+    } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int t = min(lane + 64 * u, N - 1), r = (t * 171) >> 9, c = t - 3 * r;
+        v[u] = tiled_piece_clamped(src, H, W, y0 + r, xa + 16 * c);
+      }
+      if (wide(x)) {
+        const int gy = clampi(y0 + rc, 0, H - 1);
+        uint32_t w = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) w |= (uint32_t)src[vus_tiled_offset(gy, clampi(xa + 48 + b, 0, W - 1), W)] << (8 * b);
+        col = w;
+      }
+    }
+  }
+  // x: the keypoint the registers were loaded for
+  __device__ __forceinline__ void store(uint32_t* __restrict__ dst, int lane, int x) const {
+    uint4* d = reinterpret_cast<uint4*>(dst);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int t = lane + 64 * u;
+      if (t < N) d[t + ((t * 171) >> 9)] = v[u];   // 64 r + 16 c = 16 (t + r)
+    }
+    if (wide(x) && lane < ROWS) dst[16 * lane + 12] = col;
   }
 };
 
@@ -236,7 +308,6 @@ __device__ __attribute__((aligned(128))) const RotOffTable g_rot_off_table_tiled
 
 constexpr int OR_NV = OR_ROWS * (OR_DW / 2);   // 155 dwordx2 vectors of a centroid patch
 constexpr int OR_WT = 192;                     // weight entries per byte alignment: one per vector, padded to 3 x 64 lanes
-constexpr int OR_WTD = 2 * OR_WT + 1;          // DiscWeightDwTable entries per byte alignment: a zero, then one per patch dword
 
 // The disc weights of orient_rbrief_kernel's s_w as a compile-time table: entry (sh, t) = weights of patch vector t (row
 // t / 5, dword pair t % 5) for a patch whose first column sits sh bytes into its first dword: .x/.y = (dx + 15) inside
@@ -245,73 +316,83 @@ template <int ALIGN>
 struct DiscWeightTable {
   uint32_t v[ALIGN * OR_WT * 4];
 };
+// {(dx + 15) inside the disc else 0, 1 inside the disc else 0} (u8 x 4) of the dword whose byte 0 is pixel (dy, dx0) of the disc
+struct DiscDwordWeight {
+  uint32_t moment, count;
+};
+constexpr DiscDwordWeight disc_dword_weight(int dy, int dx0) {
+  constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
+  DiscDwordWeight w{0u, 0u};
+  if (dy < -OR_R || dy > OR_R) return w;
+  const int um = umax[dy < 0 ? -dy : dy];
+  for (int b = 0; b < 4; ++b) {
+    const int dx = dx0 + b;
+    if (dx >= -um && dx <= um) {
+      w.moment |= (uint32_t)(dx + OR_R) << (8 * b);
+      w.count |= 1u << (8 * b);
+    }
+  }
+  return w;
+}
 template <int ALIGN>
 constexpr DiscWeightTable<ALIGN> make_disc_weight_table() {
-  constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
   DiscWeightTable<ALIGN> r{};
   for (int e = 0; e < ALIGN * OR_WT; ++e) {
     const int sh = e / OR_WT, t = e - sh * OR_WT;
     if (t >= OR_NV) continue;
     const int row = t / (OR_DW / 2), c = t - row * (OR_DW / 2);
-    const int dy = row - OR_R, um = umax[dy < 0 ? -dy : dy];
-    for (int d = 0; d < 2; ++d)
-      for (int b = 0; b < 4; ++b) {
-        const int dx = 4 * (2 * c + d) + b - sh - OR_R;
-        if (dx >= -um && dx <= um) {
-          r.v[4 * e + d] |= (uint32_t)(dx + OR_R) << (8 * b);
-          r.v[4 * e + 2 + d] |= 1u << (8 * b);
-        }
-      }
+    for (int d = 0; d < 2; ++d) {
+      const DiscDwordWeight w = disc_dword_weight(row - OR_R, 4 * (2 * c + d) - sh - OR_R);
+      r.v[4 * e + d] = w.moment;
+      r.v[4 * e + 2 + d] = w.count;
+    }
   }
   return r;
 }
 __device__ __attribute__((aligned(128))) const DiscWeightTable<4> g_disc_weight_table = make_disc_weight_table<4>();
 
-// The tiled form's disc weights, per dword instead of per dword pair (12 KB of LDS instead of the 24 KB of
-// DiscWeightTable<8>): entry (a, j), j >= 1 = {(dx + 15) inside the disc else 0, 1 inside else 0} (u8 x 4) of dword j - 1 of
-// the patch's rows laid end to end (10 dwords each), for a patch whose first column sits a bytes into its first dword;
-// entry (a, 0) and those past the last row are 0.  A patch that starts sh = 4 s + a bytes before its first column
-// weighs its dword d with entry (a, d + 1 - s), so vector t (dwords 2t, 2t + 1) reads entries 2t + 1 - s and 2t + 2 - s.
-// For s = 1 and t at a row start the first of them is the previous row's last dword (or entry 0): dx >= 18 there, 0 as
-// well.  Vectors t >= 155 (padding lanes) read entries past the last row.
+// The tiled form's disc weights, per dword: entry (a, j) = {moment, count} (disc_dword_weight) of dword j - 3 of the patch's rows
+// laid end to end, 12 dwords each (three 16-byte pieces), for a patch whose first column sits a bytes into its first dword;
+// the 3 entries in front and those past the last row are 0.  A patch that starts sh = 4 s + a bytes before its first
+// column (sh < 16) weighs dword d of its piece q = 3 r + c with entry (a, 4 q + d + 3 - s): a lane reads the four of a piece
+// as 32 contiguous bytes.  Entries that fall into the previous row are its dwords 9 .. 11, dx >= 18 there: 0, as the
+// dwords left of the window are.  Pieces 93 .. 98 (the idle lanes of TiledDiscPair's last wave-load) read zeros past the last row.
+constexpr int OR_WTD = 3 + 4 * (3 * 64 - OR_NP) + 4;   // 403 entries per byte alignment: the last piece index is 191 - 93
 struct DiscWeightDwTable {
   uint32_t v[4 * OR_WTD * 2];
 };
 constexpr DiscWeightDwTable make_disc_weight_dw_table() {
-  constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
   DiscWeightDwTable r{};
   for (int e = 0; e < 4 * OR_WTD; ++e) {
-    const int a = e / OR_WTD, d = e - a * OR_WTD - 1;
-    if (d < 0 || d >= OR_ROWS * OR_DW) continue;
-    const int row = d / OR_DW, col = d - row * OR_DW;
-    const int dy = row - OR_R, um = umax[dy < 0 ? -dy : dy];
-    for (int b = 0; b < 4; ++b) {
-      const int dx = 4 * col + b - a - OR_R;
-      if (dx >= -um && dx <= um) {
-        r.v[2 * e] |= (uint32_t)(dx + OR_R) << (8 * b);
-        r.v[2 * e + 1] |= 1u << (8 * b);
-      }
-    }
+    const int a = e / OR_WTD, d = e - a * OR_WTD - 3;
+    if (d < 0 || d >= OR_ROWS * 4 * OR_PC) continue;
+    const int row = d / (4 * OR_PC), col = d - row * (4 * OR_PC);
+    const DiscDwordWeight w = disc_dword_weight(row - OR_R, 4 * col - a - OR_R);
+    r.v[2 * e] = w.moment;
+    r.v[2 * e + 1] = w.count;
   }
   return r;
 }
 __device__ __attribute__((aligned(128))) const DiscWeightDwTable g_disc_weight_dw_table = make_disc_weight_dw_table();
-constexpr bool disc_weight_dw_table_matches() {   // the same weights as the per-pair table of all 8 alignments, every vector
-  constexpr DiscWeightTable<8> pair = make_disc_weight_table<8>();
+constexpr bool disc_weight_dw_table_matches() {   // every dword of every piece at all 16 alignments weighs as the definition says
   constexpr DiscWeightDwTable dw = make_disc_weight_dw_table();
-  for (int sh = 0; sh < 8; ++sh)
-    for (int t = 0; t < OR_WT; ++t) {
-      const int e = (sh & 3) * OR_WTD + 2 * t + 1 - (sh >> 2);
-      const uint32_t* p = pair.v + 4 * (sh * OR_WT + t);
-      if (dw.v[2 * e] != p[0] || dw.v[2 * e + 2] != p[1] || dw.v[2 * e + 1] != p[2] || dw.v[2 * e + 3] != p[3]) return false;
-    }
+  for (int sh = 0; sh < 16; ++sh)
+    for (int q = 0; q < 3 * 64 - OR_NP; ++q)
+      for (int d = 0; d < 4; ++d) {
+        const int e = (sh & 3) * OR_WTD + 4 * q + d + 3 - (sh >> 2);
+        const int r = q / OR_PC, c = q - r * OR_PC;
+        const DiscDwordWeight w = disc_dword_weight(r - OR_R, 16 * c + 4 * d - sh - OR_R);   // 0 for the rows past the patch
+        if (dw.v[2 * e] != w.moment || dw.v[2 * e + 1] != w.count) return false;
+      }
   return true;
 }
-static_assert(disc_weight_dw_table_matches(), "DiscWeightDwTable must weigh every vector as DiscWeightTable<8>");
+static_assert(disc_weight_dw_table_matches(), "DiscWeightDwTable must weigh every dword as disc_dword_weight");
 
 // What orient_rbrief_kernel takes from the plane layout.  Row-major planes: patch rows start on the dword boundary below
-// x - radius (4 alignments; EXACT: at x - radius itself).  Block-tiled planes: on the 8-byte boundary below it (8
-// alignments), so the descriptor patch needs 44 of 48 bytes (12 dwords) per row; the centroid patch's 38 still fit its 40.
+// x - radius (4 alignments; EXACT: at x - radius itself).  Block-tiled planes: on the 16-byte boundary below it (16
+// alignments) and are read as whole 16-byte block rows: three per row of the centroid patch (31 + 15 <= 48 bytes), three
+// per row of the descriptor patch and one dword more where its 37 + a bytes pass 48 (TiledBriefRegs); its rows take 64
+// bytes in LDS.
 template <bool TILED, bool EXACT = false> struct OrGeom {
   static constexpr int ALIGN = 4, BR_DW = ::BR_DW;
   static constexpr int WT_VEC4 = ALIGN * OR_WT;   // uint4 entries of s_w (DiscWeightTable<4>)
@@ -330,26 +411,49 @@ template <bool TILED, bool EXACT = false> struct OrGeom {
 };
 template <bool EXACT> struct OrGeom<true, EXACT> {
   static_assert(!EXACT, "tiled planes are always read from aligned starts");
-  static constexpr int ALIGN = 8, BR_DW = BR_DW_TILED;
+  static constexpr int ALIGN = 16, BR_DW = BR_DW_TILED;
   static constexpr int WT_VEC4 = 4 * OR_WTD * 2 / 4;   // uint4 entries of s_w (DiscWeightDwTable)
-  // 7 waves per SIMD: <= 72 VGPRs (phase A keeps 2 centroid patches in flight, not 4; the bin directions are loaded after
-  // phase A's patches, 8 registers fewer while they are in flight) and <= 23,405 B of LDS (the weights per dword; ONE
-  // descriptor patch buffer per wave -- the ballots of keypoint k have consumed its patch bytes before the patch of k + 1
-  // is stored).  tests/test_orient_resources.py holds these figures.
-  static constexpr int GRP = 2, BLUR_BUF = 1;
+  // 7 waves per SIMD: <= 72 VGPRs (phase A keeps the centroid patches of ONE pair of keypoints in flight, 12 data registers;
+  // the bin directions are loaded after phase A's patches, 8 registers fewer while they are in flight) and <= 23,405 B of
+  // LDS (the weights per dword; ONE descriptor patch buffer per wave -- the ballots of keypoint k have consumed its patch
+  // bytes before the patch of k + 1 is stored).  tests/test_orient_resources.py holds these figures.
+  static constexpr int GRP = 1, BLUR_BUF = 1;   // GRP counts loader objects: one TiledDiscPair
   static constexpr bool BINS_AFTER_PHASE_A = true;
-  typedef TiledPatchRegs<OR_R, OR_DW> Disc;
-  typedef TiledPatchRegs<BR_R, BR_DW> Brief;
+  typedef TiledDiscPair Disc;
+  typedef TiledBriefRegs Brief;
   static constexpr const uint32_t* WEIGHT_TABLE = g_disc_weight_dw_table.v;   // s_w is a copy of it
   static constexpr const uint32_t* ROT_TABLE = g_rot_off_table_tiled.v;
-  // the same uint4 from the per-dword table: {moment, count} of the vector's two dwords are entries 2t + 1 - s, 2t + 2 - s
-  static __device__ __forceinline__ uint4 disc_weights(const uint4* s_w, int sh, int lane, int u) {
-    const uint2* wd = reinterpret_cast<const uint2*>(s_w) + (sh & 3) * OR_WTD + 1 - (sh >> 2) + 2 * lane;
-    const uint2 w0 = wd[128 * u], w1 = wd[128 * u + 1];
-    return make_uint4(w0.x, w1.x, w0.y, w1.y);
+  // Per-lane partial moments (sum dx I, sum dy I) of the two keypoints of a loaded pair, whose patches start sha / shb bytes
+  // before their first columns.  The {moment, count} of a piece's four dwords are 32 contiguous bytes of s_w.  A piece that
+  // was not read holds 0 and adds nothing, whatever weights it meets.
+  static __device__ __forceinline__ void pair_moments(const uint4* s_w, const TiledDiscPair& pr, int sha, int shb, int lane, int& pa_a,
+                                                      int& pq_a, int& pa_b, int& pq_b) {
+    const bool second = lane >= TiledDiscPair::SPLIT;
+    const int ea = (sha & 3) * OR_WTD + 3 - (sha >> 2), eb = (shb & 3) * OR_WTD + 3 - (shb >> 2) - 4 * OR_NP;
+    int mx[3], my[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int e = (u == 0 ? ea : u == 2 ? eb : second ? eb : ea) + 4 * (lane + 64 * u);
+      const uint2* wd = reinterpret_cast<const uint2*>(s_w) + e;
+      const uint32_t d[4] = {pr.v[u].x, pr.v[u].y, pr.v[u].z, pr.v[u].w};
+      uint32_t sx = 0, rs = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint2 w = wd[j];
+        sx = __builtin_amdgcn_udot4(d[j], w.x, sx, false);
+        rs = __builtin_amdgcn_udot4(d[j], w.y, rs, false);
+      }
+      mx[u] = (int)sx - OR_R * (int)rs;
+      my[u] = ((int)(pr.pk[u] >> 20) - OR_R) * (int)rs;
+    }
+    pa_a = mx[0] + (second ? 0 : mx[1]);
+    pq_a = my[0] + (second ? 0 : my[1]);
+    pa_b = mx[2] + (second ? mx[1] : 0);
+    pq_b = my[2] + (second ? my[1] : 0);
   }
 };
-static_assert(2 * OR_R + 1 + 7 <= 4 * OR_DW && 2 * BR_R + 1 + 7 <= 4 * BR_DW_TILED, "tiled patch rows: 8-byte aligned starts");
+static_assert(2 * OR_R + 1 + 15 <= 16 * OR_PC && 2 * BR_R + 1 + 11 <= 48 && 2 * BR_R + 1 + 15 <= 52 && 52 <= 4 * BR_DW_TILED,
+              "tiled patch rows: 16-byte aligned starts; descriptor rows of 48 bytes for a <= 11, 52 beyond");
 static_assert(sizeof(DiscWeightDwTable) == 16 * OrGeom<true>::WT_VEC4, "LDS copy of the tiled weights: whole uint4");
 
 // One workgroup per image: the image's keypoints counting-sorted by 64 x 64-pixel cell (cells in raster order; inside a
@@ -424,8 +528,9 @@ namespace {
 
 // One wave = eight consecutive keypoints of one image, in two phases.
 //  A. orientation of all eight: the 31-row image patches arrive in registers (3 dwordx2 per lane and keypoint, those of
-//     GRP keypoints in flight) and are multiplied right there with the disc weights (v_dot4_u32_u8; the weights of a lane's two dwords
-//     are ONE LDS read): no LDS round trip for the patch.  Per-lane partial moments of the eight keypoints
+//     GRP keypoints in flight; TILED: 3 dwordx4 per lane and PAIR of keypoints, one pair in flight) and are multiplied right
+//     there with the disc weights (v_dot4_u32_u8; the weights of a lane's two dwords are ONE LDS read, those of a tiled
+//     piece's four dwords two): no LDS round trip for the patch.  Per-lane partial moments of the eight keypoints
 //     -> reduce-scatter (fold32 .. allsum8 above) -> lane 8g + j holds m10 / m01 of keypoint g and ranks bins 4j .. 4j+3.
 //  B. descriptors, keypoint by keypoint: the 37-row patch of the smoothed image goes through LDS (BLUR_BUF buffers; the
 //     next keypoint's rows and its bin's test offsets are in flight meanwhile), 8 byte reads + 4 compares per lane; the
@@ -436,7 +541,7 @@ namespace {
 // neighbours and their patch rows share lines in flight; the outputs go to the keypoint's own index.  A schedule only.
 // TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W).  OrGeom carries every difference: the
 // patch loaders, the weight and test-offset tables, the patches in flight.  Phase B's LDS patch stays row-major
-// (48-byte rows), so the ballots are those of the plain form.
+// (64-byte rows), so the ballots are those of the plain form.
 template <bool EXACT, bool ORDERED, bool TILED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS_OR_WPE_TILED : VUS_OR_WPE, 8))) void orient_rbrief_kernel(
     const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int H, int W, int pitch,
@@ -444,7 +549,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
     uint64_t* __restrict__ desc_out, uint8_t* __restrict__ angle_out, int n_img, int chunks_per_img) {
   typedef OrGeom<TILED, EXACT> G;
   __shared__ uint4 s_w[G::WT_VEC4];   // the disc weights for every byte alignment of a centroid patch (G::disc_weights)
-  __shared__ __attribute__((aligned(8))) uint32_t s_blur[4][G::BLUR_BUF][BR_ROWS * G::BR_DW];
+  __shared__ __attribute__((aligned(TILED ? 16 : 8))) uint32_t s_blur[4][G::BLUR_BUF][BR_ROWS * G::BR_DW];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // XCD-aware block -> (image, chunk) map: workgroups are dealt round-robin over the 8 XCDs, so all
@@ -482,9 +587,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
 #pragma unroll
   for (int kk = 0; kk < GRP; ++kk) pr[kk].init(pitch, lane);
   pb.init(W, lane);
-  int mom_dy[3];
+  int mom_dy[3];   // row-major planes: dy of the lane's three vectors (tiled: inside TiledDiscPair's pk)
+  if constexpr (!TILED) {
 #pragma unroll
-  for (int u = 0; u < 3; ++u) mom_dy[u] = min(lane + 64 * u, OR_NV - 1) / (OR_DW / 2) - OR_R;
+    for (int u = 0; u < 3; ++u) mom_dy[u] = min(lane + 64 * u, OR_NV - 1) / (OR_DW / 2) - OR_R;
+  }
   __syncthreads();   // the weight table is complete (the only workgroup-level synchronisation of the kernel)
   if (n_live == 0) {   // wave-uniform: nothing but defined contents for the unused slots
     if (lane < 4 * OR_KP_PER_WAVE && base_i + (lane >> 2) < max_kp) desc_out[((size_t)n * max_kp + base_i) * 4 + lane] = 0;
@@ -494,36 +601,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
 
   // ---- phase A: centroid moments of the eight keypoints, GRP at a time
   int pa[8], pq[8];   // per-lane partials of m10 and m01
+  if constexpr (TILED) {   // pairs of keypoints: three wave-loads hold both patches
 #pragma unroll
-  for (int g = 0; g < 8 / GRP; ++g) {
-#pragma unroll
-    for (int kk = 0; kk < GRP; ++kk) {
-      const int k = GRP * g + kk;
-      if (k < n_live) pr[kk].load(im, H, W, pitch, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
+    for (int g = 0; g < 4; ++g) {
+      const int ya = __builtin_amdgcn_readlane(my_y, 2 * g), xa = __builtin_amdgcn_readlane(my_x, 2 * g);
+      const int yb = __builtin_amdgcn_readlane(my_y, 2 * g + 1), xb = __builtin_amdgcn_readlane(my_x, 2 * g + 1);
+      pa[2 * g] = pq[2 * g] = pa[2 * g + 1] = pq[2 * g + 1] = 0;
+      if (2 * g < n_live) pr[0].load(im, H, W, ya, xa, yb, xb, 2 * g + 1 < n_live, lane);
+      if (2 * g < n_live)
+        G::pair_moments(s_w, pr[0], (xa - OR_R) & 15, (xb - OR_R) & 15, lane, pa[2 * g], pq[2 * g], pa[2 * g + 1], pq[2 * g + 1]);
     }
-    if (g == 8 / GRP - 1)   // the first descriptor patch joins the queue behind the last centroid patches
-      pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
+    // the first descriptor patch: behind the last moments, not behind the last centroid loads -- its up to 12 data registers
+    // on top of the pair's 12 do not fit the 72; the reduce-scatter and the bin ranking run while it is in flight
+    pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
+  } else {
 #pragma unroll
-    for (int kk = 0; kk < GRP; ++kk) {
-      const int k = GRP * g + kk;
-      pa[k] = 0;
-      pq[k] = 0;
-      if (k < n_live) {
-        const int sh = EXACT ? 0 : (__builtin_amdgcn_readlane(my_x, k) - OR_R) & (G::ALIGN - 1);
-        uint32_t sx = 0;
-        int si = 0, sy = 0;
+    for (int g = 0; g < 8 / GRP; ++g) {
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {
-          const uint4 w = G::disc_weights(s_w, sh, lane, u);
-          sx = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.x, sx, false);
-          sx = __builtin_amdgcn_udot4(pr[kk].v[u][1], w.y, sx, false);
-          uint32_t rs = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.z, 0u, false);
-          rs = __builtin_amdgcn_udot4(pr[kk].v[u][1], w.w, rs, false);
-          si += (int)rs;
-          sy += mom_dy[u] * (int)rs;
+      for (int kk = 0; kk < GRP; ++kk) {
+        const int k = GRP * g + kk;
+        if (k < n_live) pr[kk].load(im, H, W, pitch, __builtin_amdgcn_readlane(my_y, k), __builtin_amdgcn_readlane(my_x, k), lane);
+      }
+      if (g == 8 / GRP - 1)   // the first descriptor patch joins the queue behind the last centroid patches
+        pb.load(bl, H, W, W, __builtin_amdgcn_readlane(my_y, 0), __builtin_amdgcn_readlane(my_x, 0), lane);
+#pragma unroll
+      for (int kk = 0; kk < GRP; ++kk) {
+        const int k = GRP * g + kk;
+        pa[k] = 0;
+        pq[k] = 0;
+        if (k < n_live) {
+          const int sh = EXACT ? 0 : (__builtin_amdgcn_readlane(my_x, k) - OR_R) & (G::ALIGN - 1);
+          uint32_t sx = 0;
+          int si = 0, sy = 0;
+#pragma unroll
+          for (int u = 0; u < 3; ++u) {
+            const uint4 w = G::disc_weights(s_w, sh, lane, u);
+            sx = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.x, sx, false);
+            sx = __builtin_amdgcn_udot4(pr[kk].v[u][1], w.y, sx, false);
+            uint32_t rs = __builtin_amdgcn_udot4(pr[kk].v[u][0], w.z, 0u, false);
+            rs = __builtin_amdgcn_udot4(pr[kk].v[u][1], w.w, rs, false);
+            si += (int)rs;
+            sy += mom_dy[u] * (int)rs;
+          }
+          pa[k] = (int)sx - OR_R * si;   // sum dx I over this lane's pixels
+          pq[k] = sy;                    // sum dy I
         }
-        pa[k] = (int)sx - OR_R * si;   // sum dx I over this lane's pixels
-        pq[k] = sy;                    // sum dy I
       }
     }
   }
@@ -570,7 +692,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS
   uint4 to = rot[__builtin_amdgcn_readlane(my_bin, 0) * 64];
   for (int k = 0; k < n_live; ++k) {   // scalar loop
     uint32_t* patch = s_blur[wave][k & (G::BLUR_BUF - 1)];
-    pb.store(patch, lane);
+    if constexpr (TILED) pb.store(patch, lane, __builtin_amdgcn_readlane(my_x, k));
+    else pb.store(patch, lane);
     const uint4 cto = to;
     const int cx = __builtin_amdgcn_readlane(my_x, k);
     if (k + 1 < n_live) {
