@@ -573,4 +573,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * reference hands its nodelet raw topics and a Kalibr calibration, launch/stereo.launch:5-6, 15, 23-25): the per-tile
  * source boxes of a table and the remap itself. */
 #include "vus_rectify.h"
+
+/* Long loop closures as a low-rank correction of the band solve: up to 384 further right-hand sides substituted against
+ * the factor the one-sided band solve leaves in Sband: vus_ba_band_resolve. */
+#include "vus_closure.h"
 #endif /* VUS_H */

@@ -93,6 +93,15 @@ SIGNATURES = {
     "vus_ba_point_check": [_P, c_int, _P, _P],
     "vus_ba_point_covariance": [_P, _P, _P, _P, _P, c_int, _P, _P],
     "vus_nav_border_covariance": [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    # further right-hand sides against the stored band factor (include/vus_closure.h)
+    "vus_ba_band_resolve": [_P, c_int, c_int, _P, c_int, _P, ctypes.c_longlong, _P],
+    # long loop closures as a low-rank term (include/vus_closure.h); the factor set is a vus_between_factors
+    "vus_closure_check": [_P, c_int, _P],
+    "vus_closure_linearize": [_P, _P, _P, _P, _P, _P],
+    "vus_closure_gradient": [_P, _P, _P, _P],
+    "vus_closure_scatter": [_P, _P, _P, _P],
+    "vus_closure_capacitance": [_P, _P, _P, _P, _P],
+    "vus_closure_correct": [_P, _P, _P, _P, _P, c_int, _P, _P],
     # block-tiled image planes of the single-level front-end (include/vus_tiled.h)
     "vus_fast_detect_adaptive_tiled": [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P],
     "vus_orient_rbrief_tiled": [_P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P],
@@ -171,6 +180,8 @@ def load():
     lib.vus_point_prior_work_doubles.restype = ctypes.c_longlong
     lib.vus_pose_meas_work_doubles.argtypes = [_P]
     lib.vus_pose_meas_work_doubles.restype = ctypes.c_longlong
+    lib.vus_closure_work_doubles.argtypes = [_P]
+    lib.vus_closure_work_doubles.restype = ctypes.c_longlong
     lib.vus_ba_band_selinv_work_doubles.argtypes = [c_int, c_int]
     lib.vus_ba_band_selinv_work_doubles.restype = ctypes.c_longlong
     _lib = lib

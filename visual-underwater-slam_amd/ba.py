@@ -163,9 +163,14 @@ class BetweenFactors:
     (either order, several on one pair allowed, i != j), meas [n, 12] flat12 of the measured T_i^-1 T_j, sigmas [n, 6]
     in the tangent order (omega, v).  `loss`: one robust model for all of them (robust_loss(): None = Gaussian) or a list
     (not a tuple) of n, one per factor (Gaussian odometry next to robust loop closures).  Node of pose p = pose_stride p.
-    `span` = the widest pose distance, for StereoBAProblem(between_span=...)."""
+    `span` = the widest pose distance, for StereoBAProblem(between_span=...).
+    `max_span` (None: every factor is added to the band, which widens to the longest of them): factors that span MORE
+    than max_span poses form the long set `.long` (a LongClosures, None if there is none) -- the solver keeps them out of
+    the band and corrects every band solve by their low-rank term (include/vus_closure.h); this set then holds the rest
+    (`n` may be 0) and `span` is the widest of the rest, so that between_span=span keeps the landmark band."""
+    MAX_LONG = 64       # VUS_CLOSURE_MAX
 
-    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride=1, loss=None, device="cuda:0"):
+    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride=1, loss=None, device="cuda:0", max_span=None):
         pi, pj = np.asarray(pose_i, np.int64).reshape(-1), np.asarray(pose_j, np.int64).reshape(-1)
         meas = np.asarray(meas, np.float64).reshape(-1, 12)
         sig = np.asarray(sigmas, np.float64).reshape(-1, 6)
@@ -178,10 +183,26 @@ class BetweenFactors:
             f = int(np.nonzero(pi == pj)[0][0])
             raise ValueError(f"BetweenFactorPose3 {f} joins pose {int(pi[f])} to itself")
         _require_finite("between factors", sig)
+        losses = _factor_losses(loss, n, "between factors")
+        self.long = None
+        if max_span is not None:
+            far = np.abs(pi - pj) > int(max_span)
+            if far.sum() > self.MAX_LONG:
+                raise ValueError(f"between factors: {int(far.sum())} factors span more than max_span={int(max_span)} poses, "
+                                 f"{self.MAX_LONG} long closures are supported: raise max_span (the band widens to it) or "
+                                 "pass fewer closures")
+            if far.any():
+                self.long = LongClosures(pi[far], pj[far], meas[far], sig[far], n_poses, pose_stride,
+                                         [l for l, f in zip(losses, far) if f], device)
+            pi, pj, meas, sig = pi[~far], pj[~far], meas[~far], sig[~far]
+            losses = [l for l, f in zip(losses, far) if not f]
+            n = len(pi)
         self.n, self.n_poses, self.pose_stride = n, int(n_poses), int(pose_stride)
-        self.span = int(np.abs(pi - pj).max())
-        self.losses = _factor_losses(loss, n, "between factors")
+        self.span = int(np.abs(pi - pj).max()) if n else 0
+        self.losses = losses
         self.host = dict(i=pi, j=pj, meas=meas, sigmas=sig, losses=self.losses)
+        if n == 0:          # every factor is a long closure: no in-band set, nothing to upload
+            return
         dev = torch.device(device)
         t = lambda a, dt: _upload(a, dev, dt)
         ps = self.pose_stride
@@ -204,6 +225,22 @@ class BetweenFactors:
         if self.span * problem.pose_stride > problem.band:
             raise ValueError(f"a between factor spans {self.span} poses, more than the problem's band of {problem.band} nodes: "
                              "build the StereoBAProblem with between_span=BetweenFactors.span")
+
+
+class LongClosures(BetweenFactors):
+    """The long set of a BetweenFactors(max_span=...): at most 64 between factors that stay out of the band.  The same
+    vus_between_factors; the solver hands it to vus_closure_* and to vus_between_eval_step / vus_between_error."""
+
+    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride, losses, device):
+        super().__init__(pose_i, pose_j, meas, sigmas, n_poses, pose_stride, list(losses), device)
+        self.min_span = int(np.abs(self.host["i"] - self.host["j"]).min())
+
+    def _fits(self, problem):
+        if self.pose_stride != problem.pose_stride or self.n_poses != problem.n_poses:
+            raise ValueError("BetweenFactors built for another problem (pose_stride / n_poses differ)")
+        if self.min_span * problem.pose_stride <= problem.band:
+            raise ValueError(f"a long closure spans {self.min_span} poses, inside the problem's band of {problem.band} nodes: "
+                             f"build the BetweenFactors with max_span >= {problem.band // problem.pose_stride}")
 
 
 class _CPointPriors(ctypes.Structure):
@@ -340,6 +377,7 @@ class LMReport:
     setup_seconds: float = 0.0
     stereo_weights: Optional[tuple] = None     # gtsam shim, robust stereo factors: (pose keys, landmark keys, final w)
     pose_meas_weights: Optional[tuple] = None  # gtsam shim, a robust position / attitude fix: (pose keys, final w), graph order
+    long_closures: int = 0       # between factors kept out of the band (BetweenFactors(max_span=...))
 
 
 def _i32(t):
@@ -618,11 +656,13 @@ class StereoBASolver:
         self.work = torch.empty((2 * (nL + 1) + 8,), **f64)
         self.Q = point_priors if point_priors is not None and point_priors.n else None      # no factors: no hooks
         self.M = pose_meas if pose_meas is not None and pose_meas.n else None
-        self.B = between
+        self.B = between if between is not None and between.n else None       # the in-band set
+        self.C = between.long if between is not None else None                # the long set (LongClosures) or None
         # The add-on factor families, each described once: (C name: its entry points are vus_<name>_<stage>, its hooks
         # <name>_<stage>; the factor object or None; the name of its slot view; the state tensor its stages read, 0 poses
         # or -1 points; the arguments of its vus_<name>_check after the factors; whether it has an assemble stage).  The
-        # terms are the families present in this, the canonical order -- between, landmark priors, pose measurements --
+        # terms are the families present in this, the canonical order -- between, long closures, landmark priors, pose
+        # measurements --
         # and then the inertial ones (`inertial`: the stages an inertial subclass passes, as (name of the slot view, error,
         # linearize, assemble, eval_step)).  Every stage runs the stereo step first and then the terms in this order,
         # which is what keeps:
@@ -632,9 +672,11 @@ class StereoBASolver:
         #     before schur(), which reads them.  The pose measurements have no assemble stage and touch nothing the other
         #     terms read, so their place among the terms is free: they stand next to the landmark priors, the other family
         #     that enters before the Schur step, and the inertial terms a subclass passes stay last
-        #   - between_assemble() after schur() and before the inertial assemble, which copies gs into its right-hand side
+        #   - between_assemble() and closure_assemble() (the long set's gradient) after schur() and before the inertial
+        #     assemble, which copies gs into its right-hand side
         #   - eval_step() before every other eval_step: they read new_poses / new_points
-        families = [f for f in (("between", between, "btw_scal", 0, (B,), True),
+        families = [f for f in (("between", self.B, "btw_scal", 0, (B,), True),
+                                ("closure", self.C, "clo_scal", 0, (B,), True),
                                 ("point_prior", self.Q, "pp_scal", -1, (), False),
                                 ("pose_meas", self.M, "pm_scal", 0, (), False)) if f[1] is not None]
 
@@ -660,8 +702,12 @@ class StereoBASolver:
             factors._fits(problem)
             work = torch.empty((int(getattr(_lib.load(), f"vus_{name}_work_doubles")(factors.addr())),), **f64)
             self._families[name] = _Family(factors, getattr(self, slot), torch.empty((1,), **f64), work)
-            if factors is between:
-                self.btw_lin = torch.empty((between.n, 120), **f64)
+            if factors is self.B:
+                self.btw_lin = torch.empty((factors.n, 120), **f64)
+            if factors is self.C:       # rows of [J1 J2 r]; U, overwritten by Z = B^-1 U; C = I + U^T Z and its factor
+                self.clo_rows = torch.empty((factors.n, 78), **f64)
+                self.clo_UZ = torch.empty((6 * factors.n, 6 * nN), **f64)
+                self.clo_C = torch.empty((6 * factors.n, 6 * factors.n), **f64)
             _lib.call(f"vus_{name}_check", factors.addr(), *check_args, _lib.current_stream_ptr())
         # two-sided band solve (vus_ba_band_solve_split): worth it once the chain of panel steps is much longer than
         # the band; its workspace (pose-reversed copy of the lower half + the middle system) is allocated once
@@ -674,7 +720,8 @@ class StereoBASolver:
     def _alloc_band_work(self):
         nN, B = self.P.n_nodes, self.P.band
         n = int(_lib.load().vus_ba_band_solve_work_doubles(nN, B, self.band_rhs))
-        self.use_split = n > 0 and nN >= 2 * B + self.SPLIT_MIN_EXTRA
+        # the long closures' correction reads the factor the solve leaves in Sband: the split solves leave it unspecified
+        self.use_split = n > 0 and nN >= 2 * B + self.SPLIT_MIN_EXTRA and self.C is None
         self.band_work = torch.empty((n if self.use_split else 0,), dtype=torch.float64, device=self.P.device)
 
     # -- single kernels (also used by the parity tests) ------------------------------------------
@@ -795,6 +842,50 @@ class StereoBASolver:
     def between_eval_step(self, poses):
         """btw_scal[1] = linearised error at the step dp, btw_scal[2] = error at new_poses (after eval_step)."""
         self._family_call("between", "eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
+
+    # The long set (include/vus_closure.h): its error and step evaluation are the between factors' own entry points on
+    # the long set; linearize keeps the whitened Jacobian rows, assemble adds only their gradient, and the blocks enter
+    # through _closure_correct after the band solve.
+    def _closure_call(self, fn, args) -> bool:
+        fam = self._families.get("closure")
+        if fam is not None:
+            _lib.call(fn, fam.factors.addr(), *(_lib.ptr(a) if torch.is_tensor(a) else a for a in args(fam)),
+                      _lib.current_stream_ptr())
+        return fam is not None
+
+    def closure_error(self, poses) -> float:
+        """Error (sum rho under a robust model) of the long closures at poses; 0.0 without them."""
+        ran = self._closure_call("vus_between_error", lambda f: (poses, f.err, f.work))
+        return float(self._families["closure"].err[0].item()) if ran else 0.0
+
+    def closure_linearize(self, poses):
+        """clo_rows = [J1 J2 r] of every long closure, clo_scal[0] = their linear error at delta = 0."""
+        self._closure_call("vus_closure_linearize", lambda f: (poses, self.clo_rows, f.scal, f.work))
+
+    def closure_assemble(self):
+        """gs += the long closures' gradient (Sband receives nothing of them): where between_assemble() stands."""
+        self._closure_call("vus_closure_gradient", lambda f: (self.clo_rows, self.gs))
+
+    def closure_eval_step(self, poses):
+        """clo_scal[1] = linearised error at the step dp, clo_scal[2] = error at new_poses (after eval_step)."""
+        self._closure_call("vus_between_eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
+
+    def _closure_correct(self, X, n_rhs):
+        """X [n_rhs, 6 n_nodes], solved against the band system whose one-sided factor is in Sband, becomes the solution
+        with the long closures: Z = B^-1 U (vus_ba_band_resolve), C = I + U^T Z, X -= Z C^-1 U^T X.  No-op without them."""
+        if self.C is None:
+            return
+        nN, B = self.P.n_nodes, self.P.band
+        self._closure_call("vus_closure_scatter", lambda f: (self.clo_rows, self.clo_UZ))
+        _lib.call("vus_ba_band_resolve", _lib.ptr(self.Sband), nN, B, _lib.ptr(self.clo_UZ), 6 * self.C.n, None, 0,
+                  _lib.current_stream_ptr())
+        self._closure_call("vus_closure_capacitance", lambda f: (self.clo_rows, self.clo_UZ, self.clo_C))
+        self._closure_call("vus_closure_correct", lambda f: (self.clo_rows, self.clo_UZ, self.clo_C, X, n_rhs, f.work))
+
+    def _refuse_long(self, what):
+        if self.C is not None:
+            raise NotImplementedError(f"{what} with long closures (BetweenFactors(max_span=...)) is not implemented: the band "
+                                      "of the covariance needs a rank-6k update; build the factors without max_span")
 
     def point_prior_error(self, points) -> float:
         """Error of the landmark priors at points; 0.0 without them."""
@@ -925,6 +1016,7 @@ class StereoBASolver:
         """What every marginals() starts from: (`values` as contiguous float64, the band Sigma of the camera-side
         covariance, the pose nodes, the landmark covariances or None).  `correct(Sigma)`, if given, amends the band in
         place before the landmark covariances are formed from it."""
+        self._refuse_long("marginals()")
         values = tuple(x.to(torch.float64).contiguous() for x in values)
         self._marginal_factor(values)
         Sigma = self._selinv()
@@ -936,6 +1028,7 @@ class StereoBASolver:
     def _exact_covariance_columns(self, values, nodes, U=None, Snb=None):
         """The joint covariance of `nodes` from exact columns of S^-1: vus_ba_band_solve_multi with at most 8 unit
         right-hand sides per call, each after a fresh lambda = 0 Schur step (the solve factorises Sband in place)."""
+        self._refuse_long("exact covariance columns")
         nN = self.P.n_nodes
         cols = [6 * q + c for q in nodes for c in range(6)]
         got = np.zeros((len(cols), 6 * nN))
@@ -986,6 +1079,7 @@ class StereoBASolver:
 
     def _solve(self, lam):
         self.band_solve()
+        self._closure_correct(self.dp, 1)
 
     def _lm_solve(self, lam):
         self._assemble(lam)
@@ -1024,7 +1118,7 @@ class StereoBASolver:
     def _levenberg_marquardt(self, state, prm, aux=None):
         """GTSAM's iterate / tryLambda / checkConvergence over copies of `state`; returns (state, LMReport)."""
         state = tuple(x.to(torch.float64).contiguous().clone() for x in state)
-        rep = LMReport(setup_seconds=self.P.setup_seconds)
+        rep = LMReport(setup_seconds=self.P.setup_seconds, long_closures=self.C.n if self.C is not None else 0)
         torch.cuda.synchronize(self.P.device)
         t0 = time.perf_counter()
         lam = prm.lambdaInitial
@@ -1264,6 +1358,7 @@ class NavBASolver(_InertialBASolver):
                       p(self.status), p(self.band_work), st)
         else:
             _lib.call("vus_ba_band_solve_multi", p(self.Sband), self.P.n_nodes, self.P.band, p(self.rhs), 7, p(self.status), st)
+        self._closure_correct(self.rhs, 7)          # all 7 columns, before the bias border is eliminated with them
         _lib.call("vus_nav_border_solve", self.P.n_nodes, p(self.rhs), p(self.Scb), p(self.Sbb), p(self.gb), float(lam),
                   p(self.dp), p(self.db), st)
 

@@ -198,4 +198,37 @@ VUS_HD long long cb_rows(int band, int n_poses, int P, int G, int kk, int a, int
   return have ? blk(band, k0 + kk, i) + 6 * c : -1;
 }
 
+// ---- band_resolve.hip: reads of the FINISHED factor (substitution of further right-hand sides) ---------------------
+// The factor as the one-sided solve leaves it: blocks (i, k) of one panel row-major (the factor itself, or the inverse of
+// the panel's 48 x 48 factor block for band >= PB - 1), blocks left of i's panel TRANSPOSED.  R and K are the row and the
+// summation index of the 48 x K matrix a panel step multiplies with; K may run past the step's last column (the
+// product is padded to whole MFMA steps): such an element is masked here, not by the caller.
+// rs_diag: element (r, c) of the dense diagonal block of the panel at k0 (lower triangle only)
+VUS_HD long long rs_diag(int band, int k0, int nb, int r, int c) {
+  const int r6 = r / 6, c6 = c / 6;
+  const bool ok = r < nb && c <= r && r6 - c6 <= band;
+  return ok ? blk(band, k0 + r6, k0 + c6) + 6 * (r - 6 * r6) + (c - 6 * c6) : -1;
+}
+// the first node a row of the panel at k0 reaches to its left
+VUS_HD int rs_left_start(int band, int k0) { return k0 > band ? k0 - band : 0; }
+// rs_left (forward sweep): L(k0 + R / 6, kstart + K / 6)(R % 6, K % 6), the columns left of the panel
+VUS_HD long long rs_left(int band, int n, int k0, int R, int K) {
+  const int ii = R / 6, r = R - 6 * ii, kk = K / 6, c = K - 6 * kk;
+  const int i = k0 + ii, k = rs_left_start(band, k0) + kk;
+  const bool ok = R < NB && i < n && k < k0 && i - k <= band;
+  return ok ? blk(band, i, k) + 6 * c + r : -1;
+}
+// rs_below (backward sweep): L(k0 + PB + K / 6, k0 + R / 6)(K % 6, R % 6), the rows below the panel, read as L^T
+VUS_HD long long rs_below(int band, int n, int k0, int R, int K) {
+  const int kk = R / 6, c = R - 6 * kk, ii = K / 6, r = K - 6 * ii;
+  const int i = k0 + PB + ii, k = k0 + kk;
+  const bool ok = R < NB && i < n && i - k <= band;
+  return ok ? blk(band, i, k) + 6 * c + r : -1;
+}
+// scalar rows below the panel at k0 that any of its columns reaches
+VUS_HD int rs_below_rows(int band, int n, int k0) {
+  const int iend = n < k0 + PB + band ? n : k0 + PB + band;
+  return iend > k0 + PB ? 6 * (iend - k0 - PB) : 0;
+}
+
 }  // namespace bandidx

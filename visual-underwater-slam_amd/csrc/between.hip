@@ -8,62 +8,18 @@
 //   eval        thread / factor   linearised error at the step (old poses) and error at the new poses
 // Errors are summed by the fixed-order reduce of vus_common.hip (vus::reduce_partials).
 // Shared with the other pose kernels (se3_device.h): pose_local, load12, the robust-loss table and its per-factor dispatcher;
+// with closure.hip (between_device.h): the factor's residual and H1;
 // with the other add-on families (factor_common.h): read_back and the per-factor loss check.
 #include <cmath>
 #include <vector>
 #include "vus_common.h"
 #include "se3_device.h"
+#include "between_device.h"
 #include "factor_common.h"
 
 namespace {
 
 constexpr int LIN = 120;      // per factor: J1^T J1, J1^T J2, J2^T J2 (36 each), J1^T r, J2^T r (6 each)
-
-struct BetweenLin {
-  double r[6];                // Log(meas^-1 T1^-1 T2), unwhitened
-  double H1[36];              // -Ad(hx^-1), row-major
-};
-
-// residual and H1 of factor f at poses (H2 = I); with WITH_H = false only the residual
-template <bool WITH_H>
-__device__ __forceinline__ void between_factor(const vus_between_factors& B, const double* __restrict__ poses, int f,
-                                               BetweenLin& L) {
-  const int ps = B.pose_stride;
-  double T1[12], T2[12], M[12], hx[12];
-  load12(poses + 12 * (size_t)(B.node1[f] / ps), T1);
-  load12(poses + 12 * (size_t)(B.node2[f] / ps), T2);
-  load12(B.meas + 12 * (size_t)f, M);
-  // hx = T1^-1 T2: R = R1^T R2, t = R1^T (t2 - t1)
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) hx[3 * r + c] = T1[r] * T2[c] + T1[3 + r] * T2[3 + c] + T1[6 + r] * T2[6 + c];
-    hx[9 + r] = T1[r] * (T2[9] - T1[9]) + T1[3 + r] * (T2[10] - T1[10]) + T1[6 + r] * (T2[11] - T1[11]);
-  }
-  pose_local(M, hx, L.r);
-  if (!WITH_H) return;
-  // -Ad(hx^-1) = [[-R^T, 0], [R^T [t]x, -R^T]]   (Ad(T) = [[R, 0], [[t]x R, R]] in the (omega, v) order)
-  const double* R = hx;
-  const double* t = hx + 9;
-  const double tx[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double rt = R[3 * c + r];                     // (R^T)(r, c)
-      L.H1[6 * r + c] = -rt;
-      L.H1[6 * r + 3 + c] = 0.0;
-      L.H1[6 * (3 + r) + 3 + c] = -rt;
-      L.H1[6 * (3 + r) + c] = R[r] * tx[c] + R[3 + r] * tx[3 + c] + R[6 + r] * tx[6 + c];
-    }
-}
-
-__device__ __forceinline__ double whitened_sq(const double* __restrict__ w, const double* r) {
-  double d2 = 0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) d2 += (w[k] * r[k]) * (w[k] * r[k]);
-  return d2;
-}
 
 __global__ __launch_bounds__(256) void between_linearize_kernel(vus_between_factors B, const double* __restrict__ poses,
                                                                 double* __restrict__ lin, double* __restrict__ err_part) {

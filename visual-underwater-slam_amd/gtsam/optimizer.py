@@ -29,6 +29,7 @@ class LevenbergMarquardtParams:
         self.errorTol = 0.0
         self.verbosity = "SILENT"
         self.verbosityLM = "SILENT"
+        self.longClosureSpan = None      # EXTENSION (setLongClosureSpan)
 
     # gtsam's accessor spelling
     def setlambdaInitial(self, v): self.lambdaInitial = float(v)
@@ -43,6 +44,12 @@ class LevenbergMarquardtParams:
     def setErrorTol(self, v): self.errorTol = float(v)
     def setVerbosity(self, v): self.verbosity = str(v)
     def setVerbosityLM(self, v): self.verbosityLM = str(v)
+    def setLongClosureSpan(self, m):
+        """EXTENSION (not in gtsam): BetweenFactorPose3 whose keys lie more than m poses apart stay out of the band of the
+        reduced camera system and enter every solve as a low-rank correction (ba.BetweenFactors(max_span=m)); None, the
+        default, adds every between factor to the band, which widens to the longest of them."""
+        self.longClosureSpan = None if m is None else int(m)
+    def getLongClosureSpan(self): return self.longClosureSpan
     def getlambdaInitial(self): return self.lambdaInitial
     def getlambdaFactor(self): return self.lambdaFactor
     def getlambdaUpperBound(self): return self.lambdaUpperBound
@@ -508,7 +515,9 @@ def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
     return bias_keys, biases, bbetween, bprior
 
 
-def _build_solver(pg, device="cuda:0"):
+def _build_solver(pg, device="cuda:0", long_span=None):
+    """long_span: LevenbergMarquardtParams.longClosureSpan -- between factors spanning more poses form the long set, and
+    the band follows the rest."""
     from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
                       BetweenFactors, PointPriors, PoseMeasurements)
     nav = pg.get("nav")
@@ -516,14 +525,20 @@ def _build_solver(pg, device="cuda:0"):
     walk = bool(nav) and nav.get("per_keyframe", False)
     stride = (3 if walk else 2) if nav else 1
     n_poses = len(pg["pose_keys"])
+    between_span = btw["span"] if btw else 0
+    if btw and long_span is not None:
+        spans = np.abs(btw["i"].astype(np.int64) - btw["j"])
+        between_span = int(spans[spans <= long_span].max(initial=0))
     prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
                            prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
-                           loss=pg.get("loss"), between_span=btw["span"] if btw else 0,
+                           loss=pg.get("loss"), between_span=between_span,
                            body_P_sensor=pg.get("body_P_sensor"), mono=pg.get("mono"), mono_K=pg.get("mono_K"),
                            mono_sigma=pg.get("mono_sigma"))
+    # a factor the landmark band already covers stays in the band whatever long_span says
+    max_span = None if long_span is None else max(int(long_span), prob.band // stride)
     bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
-                        loss=list(btw["losses"]), device=device) if btw else None
+                        loss=list(btw["losses"]), device=device, max_span=max_span) if btw else None
     pp = pg.get("point_priors")
     pf = PointPriors(pp["idx"], pp["mean"], pp["sigmas"], len(pg["lm_keys"]), device=device) if pp else None
     pm = pg.get("pose_meas")
@@ -547,7 +562,8 @@ def graph_error(graph, values) -> float:
     dev = prob.device
     poses = torch.from_numpy(pg["poses"]).to(dev)
     points = torch.from_numpy(pg["points"]).to(dev)
-    e = sv.error(poses, points) + sv.between_error(poses) + sv.point_prior_error(points) + sv.pose_meas_error(poses)
+    e = (sv.error(poses, points) + sv.between_error(poses) + sv.closure_error(poses) + sv.point_prior_error(points) +
+         sv.pose_meas_error(poses))
     if pg.get("nav"):
         e += sv.nav_error(poses, torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev))
     return e + pg["aux"].error()
@@ -580,7 +596,7 @@ class LevenbergMarquardtOptimizer:
                 marks.append((name, time.perf_counter()))
         pg = _pack_graph(self._graph, self._initial, self._device)
         mark("pack_graph_host+upload")
-        prob, sv = _build_solver(pg, self._device)
+        prob, sv = _build_solver(pg, self._device, self._params.longClosureSpan)
         mark("structure+workspace")
         aux = pg["aux"] if pg["aux"].keys else None
         nav = pg.get("nav")

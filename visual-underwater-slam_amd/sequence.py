@@ -21,7 +21,7 @@ Two documented deviations from the reference's text, both switchable:
     is the reference verbatim; `disparity_sign=+1` evaluates the same formulas with the baseline's sign flipped
     (d / (-baseline) = (uL - uR) / baseline), which is the geometrically valid triangulation.  Both run the same kernel.
 """
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -277,8 +277,13 @@ class LoopClosureParams:
     appearance_top: int = 512           # descriptors per keyframe that take part (the strongest under global top-K)
     appearance_max_distance: int = 35   # Hamming bound of a near neighbour; tighter than match_max_distance
     appearance_min_score: int = 30      # a pair scoring less is not proposed
+    # closures joining keyframes further apart stay out of the band of the reduced camera system
+    # (LevenbergMarquardtParams.setLongClosureSpan); None: the band widens to them.  An init-only argument kept as a plain
+    # attribute: the fields above stay the parameters of finding and measuring closures
+    long_span: InitVar[Optional[int]] = None
 
-    def __post_init__(self):
+    def __post_init__(self, long_span=None):
+        self.long_span = None if long_span is None else int(long_span)
         if self.candidates not in CANDIDATE_MODES:
             raise ValueError(f"LoopClosureParams.candidates must be one of {CANDIDATE_MODES}, not {self.candidates!r}")
 
@@ -416,7 +421,8 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     (loop_candidates on the camera poses), by appearance (keyframe_similarity + appearance_candidates; stages then also holds
     "loop_similarity") or both, as LoopClosureParams.candidates says; their relative poses from the front end
     (match_keyframes + relative_poses) and the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
-    "loop_result" (None without a candidate) and "loop_accepted".  subpixel: the stereo matches are refined on the
+    "loop_result" (None without a candidate) and "loop_accepted", and with LoopClosureParams.long_span "long_closures" (how
+    many the optimiser kept out of the band).  subpixel: the stereo matches are refined on the
     (rectified) images after process() (refine_stereo) and the refined disparities replace the integer ones in the features
     of either graph builder and in the depths of the loop closures; stages then holds "stereo_disparity" (int32 [F,K], 1/256
     px) and "stereo_refine_status".  Returns (results Values, BatchSequence, stages dict)."""
@@ -498,5 +504,10 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
         seq.batch_create(with_landmark=True)
     for f in loop_factors:
         seq.graph.push_back(f)
-    results = seq.optimize()
+    if loop_closure is None or loop_closure.long_span is None:
+        return seq.optimize(), seq, stages
+    lm = gtsam.LevenbergMarquardtParams()
+    lm.setLongClosureSpan(loop_closure.long_span)
+    results = seq.optimize(lm)
+    stages["long_closures"] = seq.optimizer.report().long_closures
     return results, seq, stages
