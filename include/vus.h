@@ -577,4 +577,5 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Long loop closures as a low-rank correction of the band solve: up to 384 further right-hand sides substituted against
  * the factor the one-sided band solve leaves in Sband: vus_ba_band_resolve. */
 #include "vus_closure.h"
+#include "vus_clahe.h"
 #endif /* VUS_H */

@@ -125,6 +125,9 @@ SIGNATURES = {
     # lens undistortion + stereo rectification of raw images (include/vus_rectify.h)
     "vus_rectify_plan": [_P, c_int, c_int, c_int, _P, _P],
     "vus_rectify_remap": [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P],
+    # contrast-limited adaptive histogram equalisation in front of the detector (include/vus_clahe.h)
+    "vus_clahe_luts": [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P],
+    "vus_clahe_apply": [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P],
     # host-only tuning knobs of the band solve (tests, A/B timing)
     "vus_ba_set_tuning": [c_int, c_int],
 }

@@ -407,7 +407,7 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
                  params: Optional[ImageProcessorParams] = None, bulk: bool = True, frontend: Optional[StereoOrbFrontend] = None,
                  gate_px: float = GATE_PX, body_P_sensor: Optional["gtsam.Pose3"] = None, ransac_px: float = 0.0,
                  ransac_rotation: str = "imu", rectifier=None, loop_closure: Optional[LoopClosureParams] = None,
-                 subpixel: Optional[SubpixelParams] = None):
+                 subpixel: Optional[SubpixelParams] = None, enhancer=None):
     """Images to optimised trajectory: frames uint8 [F,2,H,W] on the GPU (one stereo pair per keyframe), odom_poses
     [F,12] (the odometry estimate of every keyframe = initial value of X(i) AND the camera transform get_landmarks
     uses), imu [F-1][n,>=6] samples between keyframes, dvl [F,3].  gate_px > 0 applies BatchSequence.gate_factors (bulk
@@ -425,7 +425,9 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     many the optimiser kept out of the band).  subpixel: the stereo matches are refined on the
     (rectified) images after process() (refine_stereo) and the refined disparities replace the integer ones in the features
     of either graph builder and in the depths of the loop closures; stages then holds "stereo_disparity" (int32 [F,K], 1/256
-    px) and "stereo_refine_status".  Returns (results Values, BatchSequence, stages dict)."""
+    px) and "stereo_refine_status".  enhancer: a clahe.Clahe (anything with enhance(frames)); the frames -- rectified
+    first when there is a rectifier -- pass through it before process(), and everything downstream, refine_stereo included,
+    sees the enhanced images.  Returns (results Values, BatchSequence, stages dict)."""
     assert ransac_rotation in ("imu", "odom")
     if rectifier is not None:
         H, W = frames.shape[2:]
@@ -435,6 +437,8 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
                              f"and baseline {rectifier.baseline} differ from default_camera({H}, {W}) and "
                              f"{synth.BASELINE_M} -- build it with new_camera=default_camera(H, W)")
         frames = rectifier.rectify(frames)
+    if enhancer is not None:
+        frames = enhancer.enhance(frames)
     if params is None:
         params = ImageProcessorParams(**SEQUENCE_PARAMS)
     F, _, H, W = frames.shape
