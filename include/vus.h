@@ -116,7 +116,9 @@ int vus_select_topk(const uint32_t* cand_keys, const int* cand_count, int n_img,
  * (launch/stereo.launch:36-39): the image is cut into grid_row x grid_col cells (cell of a pixel:
  * cy = y * grid_row / H, cx = x * grid_col / W, integer division) and every cell keeps its per_cell smallest
  * keys.  Output: cells in row-major order, each cell's keys ascending, packed from slot 0;
- * kp_count = number kept (<= min(max_kp, grid_row * grid_col * per_cell)); unused tail = VUS_KEY_INVALID. */
+ * kp_count = number kept (<= min(max_kp, grid_row * grid_col * per_cell)); unused tail = VUS_KEY_INVALID.
+ * The candidates are the first min(max(cand_count, 0), cand_cap) keys; VUS_KEY_INVALID and a key whose position is
+ * H * W or more belong to no cell; a key present twice is kept once.  1 <= H, W < 32768, grid_row, grid_col <= 256. */
 int vus_select_grid(const uint32_t* cand_keys, const int* cand_count, int n_img, int cand_cap, int H, int W,
                     int grid_row, int grid_col, int per_cell, int max_kp, uint32_t* kp_keys, int* kp_count,
                     void* stream);
@@ -150,12 +152,18 @@ int vus_orient_rbrief_ordered(const uint8_t* img, const uint8_t* blur, int n_img
  * vus_resize_bilinear: bilinear down/up-sampling with pixel-centre alignment and 11-bit weights, all
  * integer:  for destination column dx:  num = (2 dx + 1) Ws - Wd, den = 2 Wd, ix = floor(num / den),
  * wx = round-half-up(2048 (num - ix den) / den); source columns clamp(ix), clamp(ix + 1) (rows alike);
- * out = (sum of the four products w * p + 2^21) >> 22.  dst: uint8 [n_img, Hd, pitch_d]. */
+ * out = (sum of the four products w * p + 2^21) >> 22.  dst: uint8 [n_img, Hd, pitch_d].
+ * Accepted: source 7 <= Hs, Ws with Hs Ws <= 2^24 and Hs pitch_s < 2^31; destination 1 <= Hd <= 524280, 1 <= Wd <= 2^30;
+ * n_img <= 65535; no alignment of either buffer or pitch is asked for.  The statement holds at every accepted shape: where
+ * num or the weight's numerator would leave 32 bits (beyond (2 Nd - 1) Ns + Nd < 2^31 and 4097 Nd < 2^32 on either axis,
+ * e.g. a 7 x 40000 strip resized to 7 x 33333) the coefficients are computed in 64 bits. */
 int vus_resize_bilinear(const uint8_t* src, int n_img, int Hs, int Ws, int pitch_s, uint8_t* dst,
                         int Hd, int Wd, int pitch_d, void* stream);
 
 /* Append level `level`'s keypoints (first min(lvl_count, lvl_max_kp) entries of every image, in
  * order) to the merged per-image lists at slot kp_count[img], up to max_kp; kp_count is advanced.
+ * A negative level count is an empty level, and a list whose kp_count is max_kp or more on entry is full: both append
+ * nothing and leave kp_count as it is (kp_count never decreases; nothing at or beyond slot max_kp is written).
  * Before the first level the caller zeroes kp_count and fills kp_keys with VUS_KEY_INVALID.
  * Positions are mapped to level 0 with pixel-centre alignment, in 1/16 pixel:
  *   xq = floor(((2 x + 1) * 8 * W0 + Wl / 2) / Wl) - 8   (yq alike; level 0: 16 x),

@@ -256,7 +256,8 @@ int vus_select_grid_cpu(const uint32_t* cand_keys, const int* cand_count, int n_
         for (int i = 0; i < cnt; ++i) {
           const uint32_t k = keys[i];
           const int pos = (int)(k & VUS_KEY_POS_MASK), y = pos / W, x = pos - y * W;
-          if (y * grid_row / H != cy || x * grid_col / W != cx) continue;
+          if ((long long)pos >= (long long)H * W) continue;   /* not a pixel: belongs to no cell */
+          if ((long long)y * grid_row / H != cy || (long long)x * grid_col / W != cx) continue;
           if (have_last && k <= last) continue;
           if (k < best) best = k;
         }
@@ -434,6 +435,7 @@ int vus_pyramid_append_cpu(const uint32_t* lvl_keys, const int* lvl_count, const
     const int base = kp_count[n];
     int cnt = lvl_count[n] < lvl_max_kp ? lvl_count[n] : lvl_max_kp;
     if (cnt > max_kp - base) cnt = max_kp - base;
+    if (cnt < 0) cnt = 0;   /* a negative level count, a list that is full (or over-full) on entry: nothing appended */
     for (int t = 0; t < cnt; ++t) {
       const uint32_t key = lvl_keys[(size_t)n * lvl_max_kp + t];
       const int pos = (int)(key & VUS_KEY_POS_MASK), y = pos / Wl, x = pos - y * Wl;

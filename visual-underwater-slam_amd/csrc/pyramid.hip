@@ -7,14 +7,30 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // optional scale pyramid: bilinear resize (11-bit weights, pixel-centre alignment) and the
 // level-major merge of per-level keypoints (include/vus.h)
-// all quantities fit 32 bits for images up to 2^24 pixels: num < 2 Ns Nd, rem * 2048 < 2^12 Nd
+// WIDE = false: 32-bit arithmetic, exact while num and the negative numerator's rounding term fit an int and
+// rem * 2048 + Nd fits an unsigned -- (2 Nd - 1) Ns + Nd < 2^31 and 4097 Nd < 2^32, which the entry point checks for both axes
+// (resize_fits_32_bits).  WIDE = true: the same statement in 64 bits, for every other shape the entry point accepts.
+template <bool WIDE>
 __device__ __forceinline__ void resize_coeff(int d, int Ns, int Nd, int& i0, int& i1, int& w) {
-  const int num = (2 * d + 1) * Ns - Nd, den = 2 * Nd;
-  const int ix = num >= 0 ? (int)((unsigned)num / (unsigned)den) : -(int)((unsigned)(-num + den - 1) / (unsigned)den);
-  const unsigned rem = (unsigned)(num - ix * den);
-  w = (int)((rem * 2048u + (unsigned)Nd) / (unsigned)den);
+  int ix;
+  if constexpr (WIDE) {
+    const long long num = (long long)(2 * d + 1) * Ns - Nd, den = 2ll * Nd;
+    const long long q = num >= 0 ? num / den : -((-num + den - 1) / den);
+    const long long rem = num - q * den;
+    w = (int)((rem * 2048 + Nd) / den);
+    ix = (int)q;   // -1 <= q <= Ns
+  } else {
+    const int num = (2 * d + 1) * Ns - Nd, den = 2 * Nd;
+    ix = num >= 0 ? (int)((unsigned)num / (unsigned)den) : -(int)((unsigned)(-num + den - 1) / (unsigned)den);
+    const unsigned rem = (unsigned)(num - ix * den);
+    w = (int)((rem * 2048u + (unsigned)Nd) / (unsigned)den);
+  }
   i0 = min(max(ix, 0), Ns - 1);
   i1 = min(max(ix + 1, 0), Ns - 1);
+}
+
+bool resize_fits_32_bits(int Ns, int Nd) {
+  return (2ll * Nd - 1) * Ns + Nd < (1ll << 31) && 4097ll * Nd < (1ll << 32);
 }
 
 // One thread per 4 destination columns of an RS_ROWS-row strip.  The kernel is bound by the number of
@@ -30,6 +46,7 @@ __device__ __forceinline__ uint32_t window_byte(uint32_t w0, uint32_t w1, uint32
 }
 
 constexpr int RS_THREADS = 64;   // 256 columns per workgroup: little waste on rows that are not a multiple of 1024
+template <bool WIDE>
 __global__ __launch_bounds__(RS_THREADS) void resize_bilinear_kernel(const uint8_t* __restrict__ src, int Hs, int Ws,
                                                               int pitch_s, uint8_t* __restrict__ dst, int Hd, int Wd,
                                                               int pitch_d) {
@@ -38,8 +55,8 @@ __global__ __launch_bounds__(RS_THREADS) void resize_bilinear_kernel(const uint8
   const int ys = blockIdx.y * RS_ROWS;
   if (threadIdx.x < RS_ROWS) {
     int y0, y1, wy;
-    resize_coeff(min(ys + (int)threadIdx.x, Hd - 1), Hs, Hd, y0, y1, wy);
-    s_y[threadIdx.x][0] = y0 * pitch_s;
+    resize_coeff<WIDE>(min(ys + (int)threadIdx.x, Hd - 1), Hs, Hd, y0, y1, wy);
+    s_y[threadIdx.x][0] = y0 * pitch_s;   // < Hs * pitch_s <= INT_MAX (checked by the entry point)
     s_y[threadIdx.x][1] = y1 * pitch_s;
     s_y[threadIdx.x][2] = wy;
   }
@@ -49,7 +66,7 @@ __global__ __launch_bounds__(RS_THREADS) void resize_bilinear_kernel(const uint8
   uint8_t* d = dst + (size_t)blockIdx.z * Hd * pitch_d;
   int x0[4], x1[4], wx[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) resize_coeff(min(xb + j, Wd - 1), Ws, Wd, x0[j], x1[j], wx[j]);
+  for (int j = 0; j < 4; ++j) resize_coeff<WIDE>(min(xb + j, Wd - 1), Ws, Wd, x0[j], x1[j], wx[j]);
   const int start = max(min(x0[0], Ws - 12), 0);
   const bool windowed = Ws >= 12 && x1[3] - start < 12;
   int o0[4], o1[4];
@@ -100,10 +117,17 @@ extern "C" int vus_resize_bilinear(const uint8_t* src, int n_img, int Hs, int Ws
   if (int rc = check_image_args(src, n_img, Hs, Ws, pitch_s)) return rc;
   VUS_REQUIRE(dst != nullptr, "dst is null");
   VUS_REQUIRE(Hd >= 1 && Wd >= 1 && pitch_d >= Wd, "bad destination size %dx%d pitch %d", Hd, Wd, pitch_d);
+  VUS_REQUIRE((long long)Hs * pitch_s <= 2147483647ll, "source of %d rows of pitch %d exceeds 2^31 bytes", Hs, pitch_s);
+  VUS_REQUIRE(Hd <= 65535 * RS_ROWS && Wd <= (1 << 30), "destination %dx%d exceeds the grid (%d rows, 2^30 columns)", Wd, Hd,
+              65535 * RS_ROWS);
   if (n_img == 0) return VUS_OK;
   VUS_REQUIRE(n_img <= 65535, "n_img=%d exceeds the grid's z extent", n_img);
   const dim3 grid((Wd + 4 * RS_THREADS - 1) / (4 * RS_THREADS), (Hd + RS_ROWS - 1) / RS_ROWS, n_img);
-  resize_bilinear_kernel<<<grid, RS_THREADS, 0, vus::as_stream(stream)>>>(src, Hs, Ws, pitch_s, dst, Hd, Wd, pitch_d);
+  // the workload's shapes (a x1.2 pyramid of a camera image) stay on the 32-bit instantiation
+  if (resize_fits_32_bits(Hs, Hd) && resize_fits_32_bits(Ws, Wd))
+    resize_bilinear_kernel<false><<<grid, RS_THREADS, 0, vus::as_stream(stream)>>>(src, Hs, Ws, pitch_s, dst, Hd, Wd, pitch_d);
+  else
+    resize_bilinear_kernel<true><<<grid, RS_THREADS, 0, vus::as_stream(stream)>>>(src, Hs, Ws, pitch_s, dst, Hd, Wd, pitch_d);
   VUS_CHECK_LAUNCH("resize_bilinear");
   return VUS_OK;
 }
@@ -122,7 +146,7 @@ __global__ __launch_bounds__(256) void pyramid_append_kernel(const uint32_t* __r
   const int n = blockIdx.x;
   const int base = kp_count[n];
   int cnt = min(lvl_count[n], lvl_max_kp);
-  cnt = min(cnt, max_kp - base);
+  cnt = max(min(cnt, max_kp - base), 0);   // a negative level count, a list that is full or over-full on entry: nothing appended
   __syncthreads();   // every thread has read the old count
   for (int t = threadIdx.x; t < cnt; t += 256) {
     const size_t li = (size_t)n * lvl_max_kp + t;

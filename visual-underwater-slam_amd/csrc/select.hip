@@ -276,7 +276,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_grid_kernel(const uint32_t
       for (int i = tid; i < cnt; i += SEL_THREADS) {
         const uint32_t k = keys[i];
         const int pos = (int)(k & VUS_KEY_POS_MASK), y = pos / W, x = pos - y * W;
-        if (y * grid_row / H == cy && x * grid_col / W == cx && !(have_last && k <= last)) best = min(best, k);
+        // pos < H * W: a key that names no pixel belongs to no cell (and y * grid_row stays below 2^23)
+        if (pos < H * W && y * grid_row / H == cy && x * grid_col / W == cx && !(have_last && k <= last)) best = min(best, k);
       }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, off));
