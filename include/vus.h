@@ -569,6 +569,10 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * their triangulated matches and a Gauss-Newton refit, with the normal matrix of the refit: vus_stereo_pair_pose. */
 #include "vus_loop.h"
 
+/* The second stage of a loop-closure measurement: a two-view refit with the inlier points left free and both stereo
+ * observations of every point in the sum; the pose and its whitened information from the Schur-reduced 6 x 6 system. */
+#include "vus_pair_bundle.h"
+
 /* Sub-pixel stereo disparities: an integer SAD search around every stereo match on the rectified images and an equiangular
  * fit of its minimum, in 1/256 px; feeds the u1 column of the features and vus_stereo_pair_pose_q8: vus_stereo_refine. */
 #include "vus_subpixel.h"

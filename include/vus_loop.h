@@ -72,7 +72,7 @@
  *
  * -- the left-image reprojection error of a's 3-D point in camera b.  The right image (disparity) of b enters the
  * hypotheses through Q only: with integer disparities its residual is a staircase that pulls the fit (with the refined ones
- * of vus_stereo_pair_pose_q8 it would not be; a right-image residual is not built).
+ * of vus_stereo_pair_pose_q8 it is not: the second stage of vus_pair_bundle.h takes it into a refit).
  * count_k = number of inliers, or -1 for a degenerate sample.  best = the k of the largest count_k, the lowest k on ties;
  * best = -1 (and the count column -1) if n < 3 or every sample is degenerate.
  *
@@ -117,7 +117,8 @@
  * the two cases at compile time, so the integer instantiation is the kernel it was before this entry point existed.  The
  * refit's residual stays left-image only.  Validation is that of vus_stereo_pair_pose.
  *
- * NOT IN THESE ENTRY POINTS: a right-image residual in the refit. */
+ * NOT IN THESE ENTRY POINTS: a right-image residual in the refit.  It is a second stage behind them, vus_stereo_pair_bundle
+ * (vus_pair_bundle.h): both stereo observations of every final inlier, the points left free. */
 #ifndef VUS_LOOP_H
 #define VUS_LOOP_H
 #include "vus.h"

@@ -39,6 +39,9 @@ SIGNATURES = {
     # the same with refined disparities in 1/256 px (may be NULL) in front of the outputs
     "vus_stereo_pair_pose_q8": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_double, c_int, ctypes.c_uint32,
                                 c_int, _P, _P, _P, _P, _P, _P, _P],
+    # the two-view refit behind them, points left free (include/vus_pair_bundle.h); `cam` is a host pointer
+    "vus_stereo_pair_bundle": [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_double, c_double,
+                               c_double, c_int, _P, _P, _P, _P, _P, _P, _P],
     # sub-pixel stereo disparities: SAD search + equiangular fit around every stereo match (include/vus_subpixel.h)
     "vus_stereo_refine": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P],
     # keyframe similarity for loop-closure candidates by appearance (include/vus_retrieval.h)

@@ -124,6 +124,20 @@ class PairPoses:
     rss: torch.Tensor             # f64 [n_pairs]  sum of squared residuals over the final inliers, pixels^2
     info: torch.Tensor            # int32 [n_pairs, 6]  (n, best k, its count, final inliers, status, refit rounds)
     match_idx_out: torch.Tensor   # int32 [n_pairs, K]  the matches that are final inliers, -1 otherwise
+    pair_a: Optional[torch.Tensor] = None      # int32 [n_pairs]  the frame numbers the call was made with (what
+    pair_b: Optional[torch.Tensor] = None      # refine_relative_poses() runs its second stage on)
+
+
+@dataclass
+class PairBundle:
+    """Device tensors of one StereoOrbFrontend.refine_relative_poses() call (vus_stereo_pair_bundle,
+    include/vus_pair_bundle.h): the two-view refit behind relative_poses()."""
+    T_ab: torch.Tensor            # f64 [n_pairs, 12]  flat12 of T_a^-1 T_b, camera frames
+    S: torch.Tensor               # f64 [n_pairs, 6, 6]  reduced normal matrix of the pose, (omega, v), whitened
+    chi2: torch.Tensor            # f64 [n_pairs]  sum of whitened squared residuals over the final active points (6 each)
+    points: torch.Tensor          # f64 [n_pairs, K, 3]  refined point of every final active slot in camera a, zero elsewhere
+    info: torch.Tensor            # int32 [n_pairs, 6]  (n, active in round 0, final active, status, rounds, 0)
+    match_idx_out: torch.Tensor   # int32 [n_pairs, K]  the matches of the final active points, -1 otherwise
 
 
 class FrontendResult:
@@ -536,7 +550,7 @@ class StereoOrbFrontend:
                         JtJ=torch.empty((n, 6, 6), dtype=torch.float64, device=dev),
                         rss=torch.empty((n,), dtype=torch.float64, device=dev),
                         info=torch.empty((n, 6), dtype=torch.int32, device=dev),
-                        match_idx_out=torch.empty((n, K), dtype=torch.int32, device=dev))
+                        match_idx_out=torch.empty((n, K), dtype=torch.int32, device=dev), pair_a=a, pair_b=b)
         head = (ptr(match_idx), ptr(a), ptr(b), ptr(res.stereo_idx), ptr(res.kp_keys), ptr(res.kp_count), res.n_frames, n, K,
                 self.H, self.W, cam_h.ctypes.data, float(threshold_px), int(n_hyp), int(seed) & 0xFFFFFFFF, int(refine_iters))
         tail = (ptr(out.T_ab), ptr(out.JtJ), ptr(out.rss), ptr(out.match_idx_out), ptr(out.info), _lib.current_stream_ptr())
@@ -544,6 +558,39 @@ class StereoOrbFrontend:
             _lib.call("vus_stereo_pair_pose", *head, *tail)
         else:
             _lib.call("vus_stereo_pair_pose_q8", *head, ptr(disparity), *tail)
+        return out
+
+    def refine_relative_poses(self, res: FrontendResult, pair_poses: PairPoses, cam5, sigma_uv_px: float, sigma_disp_px: float,
+                              gate: float = 4.0, iters: int = 10, disparity: Optional[torch.Tensor] = None) -> PairBundle:
+        """The second stage behind relative_poses() on the pairs of that call (pair_poses.pair_a, pair_b): from its poses and final inliers, `iters` rounds of
+        a two-view refit in which the inlier points are free and both stereo observations (x, y, d) of every point enter,
+        weighted by sigma_uv_px and sigma_disp_px; a point takes part while its whitened error is at most `gate` sigmas
+        (vus_stereo_pair_bundle, include/vus_pair_bundle.h; one launch for all pairs).  A pair relative_poses() gave a
+        non-zero status is passed through (status 4).  disparity: the disp_q8 given to relative_poses().  Asynchronous on
+        the current stream."""
+        if disparity is not None:
+            self._check_disparity(res, disparity)
+        pp = pair_poses
+        assert pp.pair_a is not None and pp.pair_b is not None, "pair_poses: what relative_poses() returned"
+        a, b = self._pair_indices(res, pp.pair_a, pp.pair_b)
+        n, K, ptr = a.numel(), self.p.max_features, _lib.ptr
+        assert tuple(pp.match_idx_out.shape) == (n, K) and tuple(pp.T_ab.shape) == (n, 12) and tuple(pp.info.shape) == (n, 6) \
+            and pp.match_idx_out.is_contiguous() and pp.T_ab.is_contiguous() and pp.info.is_contiguous(), \
+            "pair_poses: relative_poses() of the same pairs"
+        cam_h = np.ascontiguousarray(cam5.detach().cpu().numpy() if isinstance(cam5, torch.Tensor) else cam5, dtype=np.float64)
+        assert cam_h.size == 5, "cam5: fx, fy, cx, cy, baseline"
+        dev = self.device
+        out = PairBundle(T_ab=torch.empty((n, 12), dtype=torch.float64, device=dev),
+                         S=torch.empty((n, 6, 6), dtype=torch.float64, device=dev),
+                         chi2=torch.empty((n,), dtype=torch.float64, device=dev),
+                         points=torch.empty((n, K, 3), dtype=torch.float64, device=dev),
+                         info=torch.empty((n, 6), dtype=torch.int32, device=dev),
+                         match_idx_out=torch.empty((n, K), dtype=torch.int32, device=dev))
+        _lib.call("vus_stereo_pair_bundle", ptr(pp.match_idx_out), ptr(a), ptr(b), ptr(res.stereo_idx), ptr(res.kp_keys),
+                  ptr(res.kp_count), res.n_frames, n, K, self.H, self.W, cam_h.ctypes.data,
+                  None if disparity is None else ptr(disparity), ptr(pp.T_ab), ptr(pp.info), float(sigma_uv_px),
+                  float(sigma_disp_px), float(gate), int(iters), ptr(out.T_ab), ptr(out.S), ptr(out.chi2), ptr(out.points),
+                  ptr(out.match_idx_out), ptr(out.info), _lib.current_stream_ptr())
         return out
 
     def stereo_factors(self, ids: torch.Tensor, feats: torch.Tensor, n_ids: int, Rt: torch.Tensor, cam: torch.Tensor,

@@ -256,6 +256,7 @@ def imu_delta_rotations(imu, params: "gtsam.PreintegrationParams") -> np.ndarray
 # BetweenFactorPose3.
 
 CANDIDATE_MODES = ("pose", "appearance", "both")
+REFIT_MODES = ("left", "stereo")
 
 
 @dataclass
@@ -281,11 +282,31 @@ class LoopClosureParams:
     # (LevenbergMarquardtParams.setLongClosureSpan); None: the band widens to them.  An init-only argument kept as a plain
     # attribute: the fields above stay the parameters of finding and measuring closures
     long_span: InitVar[Optional[int]] = None
+    # The refit behind the three-point RANSAC, init-only arguments kept as plain attributes like long_span.
+    # refit "left": the left-image refit of relative_poses is the measurement; "stereo": the two-view refit of
+    # refine_relative_poses behind it (include/vus_pair_bundle.h), refine_iters rounds, with
+    # sigma_uv_px the standard deviation of a left pixel position, sigma_disp_px that of a disparity -- None: 0.6 px with
+    # integer disparities, 0.12 px with subpixel, their RMS errors within 1.5 px (profiles/subpixel.md: 0.599 and 0.120) --
+    # and gate_sigma the whitened error, in sigmas, up to which a point takes part
+    refit: InitVar[str] = "left"
+    sigma_uv_px: InitVar[float] = 0.5
+    sigma_disp_px: InitVar[Optional[float]] = None
+    gate_sigma: InitVar[float] = 4.0
 
-    def __post_init__(self, long_span=None):
+    def __post_init__(self, long_span=None, refit="left", sigma_uv_px=0.5, sigma_disp_px=None, gate_sigma=4.0):
         self.long_span = None if long_span is None else int(long_span)
         if self.candidates not in CANDIDATE_MODES:
             raise ValueError(f"LoopClosureParams.candidates must be one of {CANDIDATE_MODES}, not {self.candidates!r}")
+        if refit not in REFIT_MODES:
+            raise ValueError(f"LoopClosureParams.refit must be one of {REFIT_MODES}, not {refit!r}")
+        self.refit = refit
+        self.sigma_uv_px = float(sigma_uv_px)
+        self.sigma_disp_px = None if sigma_disp_px is None else float(sigma_disp_px)
+        self.gate_sigma = float(gate_sigma)
+
+    def disparity_sigma(self, subpixel: bool) -> float:
+        """sigma_disp_px, or its default for integer (False) or refined (True) disparities."""
+        return float(self.sigma_disp_px) if self.sigma_disp_px is not None else (0.12 if subpixel else 0.6)
 
 
 @dataclass
@@ -359,19 +380,27 @@ def loop_closure_measurements(result, params: LoopClosureParams, body_P_sensor: 
     frontend.PairPoses.  A pair is accepted iff its status is 0 and its final inliers number at least min_inliers (and
     its normal matrix can be inverted, which three or more inliers in general position give).  cov = s^2 (JtJ)^-1,
     s = max(sigma_px, sqrt(rss / (2 n_in - 6))), in the tangent (omega, v) of measured Exp(xi).  With body_P_sensor = S
-    the measurement becomes S T S^-1 (X(i) are body poses) and the covariance Ad_S cov Ad_S^T."""
+    the measurement becomes S T S^-1 (X(i) are body poses) and the covariance Ad_S cov Ad_S^T.
+    From a frontend.PairBundle (refit="stereo") the count is that of the final active points, and cov = s^2 S^-1 with
+    s = max(1, sqrt(chi2 / (3 n_active - 6))): S is whitened already, six residuals per point and three unknowns each."""
     T = result.T_ab.detach().cpu().numpy().reshape(-1, 12)
-    JtJ = result.JtJ.detach().cpu().numpy().reshape(-1, 6, 6)
-    rss = result.rss.detach().cpu().numpy().reshape(-1)
     info = result.info.detach().cpu().numpy().reshape(-1, 6)
     n = len(T)
-    accepted = (info[:, 4] == 0) & (info[:, 3] >= int(params.min_inliers))
+    if hasattr(result, "chi2"):                    # a PairBundle
+        JtJ = result.S.detach().cpu().numpy().reshape(-1, 6, 6)
+        rss = result.chi2.detach().cpu().numpy().reshape(-1)
+        count, status, per_point, floor = info[:, 2], info[:, 3], 3, 1.0
+    else:
+        JtJ = result.JtJ.detach().cpu().numpy().reshape(-1, 6, 6)
+        rss = result.rss.detach().cpu().numpy().reshape(-1)
+        count, status, per_point, floor = info[:, 3], info[:, 4], 2, float(params.sigma_px)
+    accepted = (status == 0) & (count >= int(params.min_inliers))
     cov, scale, measured = np.zeros((n, 6, 6)), np.zeros(n), [None] * n
     S = None if body_P_sensor is None else gtsam.Pose3(body_P_sensor)
     Ad = None if S is None else adjoint_map(S)
     for c in np.nonzero(accepted)[0]:
-        dof = 2 * int(info[c, 3]) - 6
-        s = max(float(params.sigma_px), float(np.sqrt(rss[c] / dof)) if dof > 0 else 0.0)
+        dof = per_point * int(count[c]) - 6
+        s = max(floor, float(np.sqrt(rss[c] / dof)) if dof > 0 else 0.0)
         try:
             C = (s * s) * np.linalg.inv(JtJ[c])
         except np.linalg.LinAlgError:
@@ -420,8 +449,10 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
     calibration, so the rectifier must produce that camera.  loop_closure: candidates by pose proximity in odom_poses
     (loop_candidates on the camera poses), by appearance (keyframe_similarity + appearance_candidates; stages then also holds
     "loop_similarity") or both, as LoopClosureParams.candidates says; their relative poses from the front end
-    (match_keyframes + relative_poses) and the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
-    "loop_result" (None without a candidate) and "loop_accepted", and with LoopClosureParams.long_span "long_closures" (how
+    (match_keyframes + relative_poses; with LoopClosureParams.refit = "stereo" the two-view refit of refine_relative_poses
+    behind it) and the accepted ones added to the graph as BetweenFactorPose3, on either path; stages then holds "loop_pairs",
+    "loop_result" (None without a candidate; a PairBundle with refit = "stereo", and "loop_stage_one" then holds the
+    PairPoses it started from) and "loop_accepted", and with LoopClosureParams.long_span "long_closures" (how
     many the optimiser kept out of the band).  subpixel: the stereo matches are refined on the
     (rectified) images after process() (refine_stereo) and the refined disparities replace the integer ones in the features
     of either graph builder and in the depths of the loop closures; stages then holds "stereo_disparity" (int32 [F,K], 1/256
@@ -481,6 +512,11 @@ def run_sequence(frames: torch.Tensor, odom_poses: np.ndarray, imu, dvl, dispari
             midx = fe.match_keyframes(res, pairs[0], pairs[1], max_distance=lc.match_max_distance)
             loop_result = fe.relative_poses(res, pairs[0], pairs[1], midx, cam5, lc.threshold_px, lc.n_hyp, lc.seed,
                                             lc.refine_iters, disparity=disparity)
+            if lc.refit == "stereo":
+                stages["loop_stage_one"] = loop_result
+                loop_result = fe.refine_relative_poses(res, loop_result, cam5, lc.sigma_uv_px,
+                                                       lc.disparity_sigma(subpixel is not None), lc.gate_sigma,
+                                                       lc.refine_iters, disparity=disparity)
             accepted = loop_closure_measurements(loop_result, lc, body_P_sensor)[0]
             loop_factors = loop_closure_factors(loop_result, pairs, lc, body_P_sensor)
         stages.update(loop_pairs=pairs, loop_result=loop_result, loop_accepted=accepted)
