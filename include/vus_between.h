@@ -11,6 +11,11 @@
  * Each factor may carry its own robust model (include/vus_robust.h, Block reweighting; Gaussian odometry next to robust
  * loop closures): its whitened residual and Jacobian rows are scaled by sqrt(w(|W r|)).  The linear slots hold
  * 0.5 sum w |b + J delta|^2, the nonlinear ones sum rho(|W r|).
+ * Full-covariance models (noiseModel.Gaussian): with `sqrt_info` set, W of factor f is its upper-triangular R, R^T R = cov^-1,
+ * in place of diag(1/sigma) in every formula above -- whitened residual R r, whitened Jacobians R H1 and R, d = |R r| for
+ * the robust weight, which stays one weight per factor (Block).  Every factor of such a set uses its R (a diagonal factor
+ * carries R = diag(1/sigma)) and `w` is not read.  J2^T J2 = w R^T R is then a full block.  Any R with R^T R = cov^-1 gives
+ * the same error and the same products up to round-off; the kernels sum over the residual rows in ascending order.
  *
  * Nodes: endpoint node = pose_stride * pose (pose_stride 1, 2 or 3 as in vus_ba_problem), so one set of kernels serves
  * every node layout.  Either key order is allowed, several factors on one pair are summed, node1 == node2 is invalid.
@@ -47,16 +52,23 @@ typedef struct vus_between_factors {
   const int* tgt_s;           /* [n_targets] block diagonal s: the block is (node, node - s) */
   const int* tgt_ptr;         /* [n_targets + 1] CSR row pointers into tgt_terms */
   const int* tgt_terms;       /* [tgt_ptr[n_targets]] 4 f + kind, in summation order */
+  const double* sqrt_info;    /* NULL: the diagonal model of `w`, exactly as before the field existed.  Else [n, 36] row-major:
+                                 per factor the upper-triangular R with R^T R = cov^-1 (positive diagonal); whitened
+                                 residual R r, whitened Jacobians R H1 and R.  The kernels read the 21 entries on and above
+                                 the diagonal only; `w` is then not read (and may be NULL).  Appended last: a caller that
+                                 fills the fields before it and zero-initialises the struct keeps the diagonal model. */
 } vus_between_factors;
 
 /* Host-side validation of a factor set against a band of `band` nodes (reads the index arrays back: one blocking copy per
  * array).  Every node in [0, n_nodes), node1 != node2, |node1 - node2| <= band, every loss kind known with a finite
- * k > 0, every target inside the band with its terms in range and of the right block.  The other entry points check
- * sizes and pointers only: call this once per factor set. */
+ * k > 0, every target inside the band with its terms in range and of the right block; with `sqrt_info`, every entry on or
+ * above the diagonal finite and every diagonal entry > 0 (the factor's number is in the message).  The other entry points
+ * check sizes and pointers only: call this once per factor set. */
 int vus_between_check(const vus_between_factors* B, int band, void* stream);
 
 /* Per factor at `poses` [n_poses, 12], whitened and (robust-)weighted:  lin [n, 120] = J1^T J1 (36), J1^T J2 (36, row-major,
- * rows of node1), J2^T J2 (36), J1^T r (6), J2^T r (6);  err[0] = 0.5 sum w |b|^2, the linear error at delta = 0.
+ * rows of node1), J2^T J2 (36: diagonal under a diagonal model, full under sqrt_info), J1^T r (6), J2^T r (6);  err[0] =
+ * 0.5 sum w |b|^2, the linear error at delta = 0.
  * work: vus_between_work_doubles(B) doubles. */
 int vus_between_linearize(const vus_between_factors* B, const double* poses, double* lin, double* err, double* work,
                           void* stream);

@@ -46,12 +46,14 @@ int vus_ba_band_resolve(const double* L, int n_nodes, int band, double* X, int n
 
 /* Host-side validation, once per factor set (reads the index arrays back): 1 <= n <= VUS_CLOSURE_MAX, every node a pose
  * node in [0, n_nodes), every loss known, and |node1 - node2| > band for every factor: one inside the band belongs to
- * vus_between_assemble. */
+ * vus_between_assemble; with `sqrt_info` (full-covariance models, include/vus_between.h), its entries as vus_between_check
+ * checks them. */
 int vus_closure_check(const vus_between_factors* B, int band, void* stream);
 long long vus_closure_work_doubles(const vus_between_factors* B);
 
 /* rows [n, 78] at `poses` [n_poses, 12]: J1 (36, row-major: residual row x tangent column of node1), J2 (36), r (6), whitened
- * and scaled by sqrt(w(|W r|));  err[0] = 0.5 sum |r|^2, the linear error at delta = 0.  work: vus_closure_work_doubles. */
+ * and scaled by sqrt(w(|W r|)) -- W = diag(1/sigma), or the factor's R under sqrt_info: J2 is then sqrt(w) R, upper-triangular,
+ * all 36 entries written;  err[0] = 0.5 sum |r|^2, the linear error at delta = 0.  work: vus_closure_work_doubles. */
 int vus_closure_linearize(const vus_between_factors* B, const double* poses, double* rows, double* err, double* work,
                           void* stream);
 

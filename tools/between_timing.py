@@ -3,7 +3,10 @@ median of --reps after a warm-up) and a whole LM (synchronised host clock) at
   - BASELINE.json configs[2] (synth.CONFIGS2_BA: 2000 keyframes, 50 k landmarks) without between factors, and with 2000
     odometry factors plus ~50 loop closures inside the landmark band;
   - a pose-only graph of 10 k poses (prior + odometry chain + in-band closures).
-Writes one JSON.
+Each graph with between factors runs under the diagonal models and again with EVERY factor under a full-covariance model
+(vus_between_factors.sqrt_info; keys ending in "_full"): the same sigmas turned by a seeded rotation of the tangent space
+(condition 25).  The measurements stay as drawn, so the full graphs are other estimation problems and their trial counts
+may differ; the stage times and the time per trial are what compares.  Writes one JSON.
 
     python tools/between_timing.py [--reps 20] [--json out.json]
 """
@@ -43,6 +46,15 @@ def between_set(rng, truth, pairs, noise=0.002):
         meas.append(m.flat12())
     sig = np.tile([0.01, 0.01, 0.01, 0.05, 0.05, 0.05], (len(pairs), 1))
     return np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs]), np.array(meas), sig
+
+
+def full_models(rng, sig):
+    """sqrt_info [n, 6, 6] of the covariances Q diag(sig^2) Q^T, Q a seeded rotation per factor: upper Cholesky of cov^-1."""
+    R = np.empty((len(sig), 6, 6))
+    for f, s in enumerate(sig):
+        Q, _ = np.linalg.qr(rng.standard_normal((6, 6)))
+        R[f] = np.linalg.cholesky((Q / (s * s)) @ Q.T).T
+    return R
 
 
 def lm_seconds(sv, state):
@@ -91,31 +103,34 @@ def main():
         i = int(rng.integers(0, n_kf - lm_band))
         pairs.append((i, i + int(rng.integers(2, max(lm_band, 3)))))
     bi, bj, bm, bs = between_set(rng, seq["poses_gt"], pairs)
-    bf = BetweenFactors(bi, bj, bm, bs, n_kf)
-    prob = StereoBAProblem(*args, **kw, between_span=bf.span)
-    sv = StereoBASolver(prob, bf)
-    st = stages(sv, state[0], a.reps)
-    t1, rep1 = lm_seconds(sv, state)
-    res["configs2_between"] = {"factors": len(pairs), "band": prob.band, "lm_s": t1, "iterations": rep1.iterations,
-                               "tries": rep1.tries, "lm_ms_per_try": 1e3 * t1 / max(rep1.tries, 1), **st}
-    del sv, prob
+    for key, R in (("configs2_between", None), ("configs2_between_full", full_models(rng, bs))):
+        bf = BetweenFactors(bi, bj, bm, bs, n_kf, sqrt_info=R)
+        prob = StereoBAProblem(*args, **kw, between_span=bf.span)
+        sv = StereoBASolver(prob, bf)
+        st = stages(sv, state[0], a.reps)
+        t1, rep1 = lm_seconds(sv, state)
+        res[key] = {"factors": len(pairs), "band": prob.band, "lm_s": t1, "iterations": rep1.iterations,
+                    "tries": rep1.tries, "lm_ms_per_try": 1e3 * t1 / max(rep1.tries, 1), **st}
+        del sv, prob
 
     n = 10000
     truth = np.stack([Pose3.Expmap(np.r_[0, 0, 0.01 * k, 0.5 * k, 0.1 * np.sin(0.05 * k), 0]).flat12() for k in range(n)])
     pairs = [(k - 1, k) for k in range(1, n)] + [(k, k + 30) for k in range(0, n - 30, 100)]
     bi, bj, bm, bs = between_set(rng, truth, pairs)
-    bf = BetweenFactors(bi, bj, bm, bs, n)
     z = np.zeros(0, np.int32)
-    prob = StereoBAProblem(z, z, np.zeros((0, 3)), n, 0, np.array([1.0, 1, 0, 0, 0, 1]), 1.0, prior_pose=[0],
-                           prior_T=truth[:1], prior_sigmas=np.full((1, 6), 1e-3), between_span=bf.span)
-    sv = StereoBASolver(prob, bf)
     init = np.stack([Pose3.from_flat12(T).retract(0.01 * rng.standard_normal(6)).flat12() for T in truth])
     init[0] = truth[0]
     pstate = (d(init), torch.zeros((0, 3), dtype=torch.float64, device="cuda"))
-    st = stages(sv, pstate[0], a.reps)
-    t2, rep2 = lm_seconds(sv, pstate)
-    res["pose_graph_10k"] = {"poses": n, "factors": len(pairs), "band": prob.band, "lm_s": t2, "iterations": rep2.iterations,
-                             "tries": rep2.tries, "status": rep2.status, "lm_ms_per_try": 1e3 * t2 / max(rep2.tries, 1), **st}
+    for key, R in (("pose_graph_10k", None), ("pose_graph_10k_full", full_models(rng, bs))):
+        bf = BetweenFactors(bi, bj, bm, bs, n, sqrt_info=R)
+        prob = StereoBAProblem(z, z, np.zeros((0, 3)), n, 0, np.array([1.0, 1, 0, 0, 0, 1]), 1.0, prior_pose=[0],
+                               prior_T=truth[:1], prior_sigmas=np.full((1, 6), 1e-3), between_span=bf.span)
+        sv = StereoBASolver(prob, bf)
+        st = stages(sv, pstate[0], a.reps)
+        t2, rep2 = lm_seconds(sv, pstate)
+        res[key] = {"poses": n, "factors": len(pairs), "band": prob.band, "lm_s": t2, "iterations": rep2.iterations,
+                    "tries": rep2.tries, "status": rep2.status, "lm_ms_per_try": 1e3 * t2 / max(rep2.tries, 1), **st}
+        del sv, prob
     line = json.dumps(res)
     print(line)
     if a.json:

@@ -134,7 +134,39 @@ class _CBetween(ctypes.Structure):
     _fields_ = [("n", c_int), ("n_nodes", c_int), ("pose_stride", c_int), ("node1", c_void_p), ("node2", c_void_p),
                 ("meas", c_void_p), ("w", c_void_p), ("loss_kind", c_void_p), ("loss_k", c_void_p), ("n_targets", c_int),
                 ("tgt_node", c_void_p),
-                ("tgt_s", c_void_p), ("tgt_ptr", c_void_p), ("tgt_terms", c_void_p)]
+                ("tgt_s", c_void_p), ("tgt_ptr", c_void_p), ("tgt_terms", c_void_p),
+                ("sqrt_info", c_void_p)]     # appended: built from the 14 fields before it, it is NULL (diagonal models)
+
+
+def _require_sqrt_info(what, R, n):
+    """sqrt_info of n factors as [n, 6, 6]: finite, upper-triangular (every entry below the diagonal exactly 0) with a
+    positive diagonal -- the R of include/vus_between.h with R^T R = cov^-1."""
+    R = np.array(R, dtype=np.float64)
+    if R.size != 36 * n or R.ndim not in (2, 3):
+        raise ValueError(f"{what}: sqrt_info must be [n, 6, 6] or [n, 36] for n={n} factors, not an array of shape {R.shape}")
+    R = R.reshape(n, 6, 6)
+    if not np.isfinite(R).all():
+        raise ValueError(f"{what}: sqrt_info must be finite")
+    if np.tril(R, -1).any():
+        f = int(np.nonzero(np.tril(R, -1).reshape(n, -1).any(axis=1))[0][0])
+        raise ValueError(f"{what}: sqrt_info of factor {f} is not upper-triangular (an entry below the diagonal is not 0)")
+    if not (np.diagonal(R, axis1=1, axis2=2) > 0).all():
+        f = int(np.nonzero((np.diagonal(R, axis1=1, axis2=2) <= 0).any(axis=1))[0][0])
+        raise ValueError(f"{what}: sqrt_info of factor {f} needs a positive diagonal")
+    return R
+
+
+def sqrt_info_of(covariances):
+    """Per-factor covariances [n, 6, 6] (symmetric positive definite) -> (R [n, 6, 6], sigmas [n, 6]): R the upper Cholesky
+    factor of cov^-1 (R^T R = cov^-1, positive diagonal), sigmas the roots of the covariance diagonals."""
+    C = np.array(covariances, dtype=np.float64).reshape(-1, 6, 6)
+    if not np.isfinite(C).all():
+        raise ValueError("between factors: covariances must be finite")
+    try:
+        R = np.stack([np.linalg.cholesky(np.linalg.inv(c)).T for c in C]) if len(C) else np.zeros((0, 6, 6))
+    except np.linalg.LinAlgError:
+        raise ValueError("between factors: a covariance is not positive definite") from None
+    return R, np.sqrt(np.diagonal(C, axis1=1, axis2=2))
 
 
 def between_targets(node1, node2):
@@ -167,10 +199,21 @@ class BetweenFactors:
     `max_span` (None: every factor is added to the band, which widens to the longest of them): factors that span MORE
     than max_span poses form the long set `.long` (a LongClosures, None if there is none) -- the solver keeps them out of
     the band and corrects every band solve by their low-rank term (include/vus_closure.h); this set then holds the rest
-    (`n` may be 0) and `span` is the widest of the rest, so that between_span=span keeps the landmark band."""
+    (`n` may be 0) and `span` is the widest of the rest, so that between_span=span keeps the landmark band.
+    `sqrt_info` (None: the diagonal models of `sigmas`, nothing else is uploaded): [n, 6, 6] or [n, 36], per factor the
+    upper-triangular R with R^T R = cov^-1 of a full-covariance model (noiseModel.Gaussian); every factor then whitens with
+    its R (a diagonal one carries diag(1/sigma)) and the rows of `sigmas` are not used.  BetweenFactors.from_covariances
+    factors per-factor covariances on the host."""
     MAX_LONG = 64       # VUS_CLOSURE_MAX
 
-    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride=1, loss=None, device="cuda:0", max_span=None):
+    @classmethod
+    def from_covariances(cls, pose_i, pose_j, meas, covariances, n_poses, **kw):
+        """The set under full-covariance models given as covariances [n, 6, 6] (tangent order (omega, v))."""
+        R, sig = sqrt_info_of(covariances)
+        return cls(pose_i, pose_j, meas, sig, n_poses, sqrt_info=R, **kw)
+
+    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride=1, loss=None, device="cuda:0", max_span=None,
+                 sqrt_info=None):
         pi, pj = np.asarray(pose_i, np.int64).reshape(-1), np.asarray(pose_j, np.int64).reshape(-1)
         meas = np.asarray(meas, np.float64).reshape(-1, 12)
         sig = np.asarray(sigmas, np.float64).reshape(-1, 6)
@@ -183,6 +226,7 @@ class BetweenFactors:
             f = int(np.nonzero(pi == pj)[0][0])
             raise ValueError(f"BetweenFactorPose3 {f} joins pose {int(pi[f])} to itself")
         _require_finite("between factors", sig)
+        R = None if sqrt_info is None else _require_sqrt_info("between factors", sqrt_info, n)
         losses = _factor_losses(loss, n, "between factors")
         self.long = None
         if max_span is not None:
@@ -193,14 +237,16 @@ class BetweenFactors:
                                  "pass fewer closures")
             if far.any():
                 self.long = LongClosures(pi[far], pj[far], meas[far], sig[far], n_poses, pose_stride,
-                                         [l for l, f in zip(losses, far) if f], device)
+                                         [l for l, f in zip(losses, far) if f], device,
+                                         sqrt_info=None if R is None else R[far])
             pi, pj, meas, sig = pi[~far], pj[~far], meas[~far], sig[~far]
+            R = None if R is None else R[~far]
             losses = [l for l, f in zip(losses, far) if not f]
             n = len(pi)
         self.n, self.n_poses, self.pose_stride = n, int(n_poses), int(pose_stride)
         self.span = int(np.abs(pi - pj).max()) if n else 0
         self.losses = losses
-        self.host = dict(i=pi, j=pj, meas=meas, sigmas=sig, losses=self.losses)
+        self.host = dict(i=pi, j=pj, meas=meas, sigmas=sig, losses=self.losses, sqrt_info=R)
         if n == 0:          # every factor is a long closure: no in-band set, nothing to upload
             return
         dev = torch.device(device)
@@ -212,8 +258,10 @@ class BetweenFactors:
         tn, ts, tp, tt = between_targets(ps * pi, ps * pj)
         self.tgt_node, self.tgt_s, self.tgt_ptr, self.tgt_terms = (t(a, torch.int32) for a in (tn, ts, tp, tt))
         p = _lib.ptr
+        self.sqrt_info = None if R is None else t(R.reshape(n, 36), torch.float64)
         self.c = _CBetween(n, ps * self.n_poses, ps, p(self.node1), p(self.node2), p(self.meas), p(self.w),
-                           p(self.loss_kind), p(self.loss_k), len(tn), p(self.tgt_node), p(self.tgt_s), p(self.tgt_ptr), p(self.tgt_terms))
+                           p(self.loss_kind), p(self.loss_k), len(tn), p(self.tgt_node), p(self.tgt_s), p(self.tgt_ptr), p(self.tgt_terms),
+                           None if R is None else p(self.sqrt_info))
 
     def addr(self):
         return ctypes.addressof(self.c)
@@ -231,8 +279,8 @@ class LongClosures(BetweenFactors):
     """The long set of a BetweenFactors(max_span=...): at most 64 between factors that stay out of the band.  The same
     vus_between_factors; the solver hands it to vus_closure_* and to vus_between_eval_step / vus_between_error."""
 
-    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride, losses, device):
-        super().__init__(pose_i, pose_j, meas, sigmas, n_poses, pose_stride, list(losses), device)
+    def __init__(self, pose_i, pose_j, meas, sigmas, n_poses, pose_stride, losses, device, sqrt_info=None):
+        super().__init__(pose_i, pose_j, meas, sigmas, n_poses, pose_stride, list(losses), device, sqrt_info=sqrt_info)
         self.min_span = int(np.abs(self.host["i"] - self.host["j"]).min())
 
     def _fits(self, problem):

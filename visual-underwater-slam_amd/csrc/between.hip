@@ -8,7 +8,8 @@
 //   eval        thread / factor   linearised error at the step (old poses) and error at the new poses
 // Errors are summed by the fixed-order reduce of vus_common.hip (vus::reduce_partials).
 // Shared with the other pose kernels (se3_device.h): pose_local, load12, the robust-loss table and its per-factor dispatcher;
-// with closure.hip (between_device.h): the factor's residual and H1;
+// with closure.hip (between_device.h): the factor's residual and H1, and the whitening of a full-covariance model
+// (vus_between_factors.sqrt_info: the kernels that whiten are templates on the model form, picked on the host);
 // with the other add-on families (factor_common.h): read_back and the per-factor loss check.
 #include <cmath>
 #include <vector>
@@ -21,12 +22,57 @@ namespace {
 
 constexpr int LIN = 120;      // per factor: J1^T J1, J1^T J2, J2^T J2 (36 each), J1^T r, J2^T r (6 each)
 
+// FULL: the factors carry a full-covariance model (B.sqrt_info); the diagonal instantiation is the kernel as it was.
+template <bool FULL>
 __global__ __launch_bounds__(256) void between_linearize_kernel(vus_between_factors B, const double* __restrict__ poses,
                                                                 double* __restrict__ lin, double* __restrict__ err_part) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= B.n) return;
   BetweenLin L;
   between_factor<true>(B, poses, f, L);
+  if constexpr (FULL) {
+    // the rows of the long path (closure.hip): A = s R H1, Rs = s R, b = s R r with s = sqrt(w(|R r|)); then
+    // J1^T J1 = A^T A,  J1^T J2 = A^T Rs,  J2^T J2 = Rs^T Rs,  J1^T b = A^T b,  J2^T b = Rs^T b  (= H1^T M H1, H1^T M, M,
+    // H1^T M r, M r with the information M = w R^T R); every sum runs over the residual rows in ascending order
+    SqrtInfo S;
+    load_sqrt_info(B, f, S);
+    double b[6], A[36], rw, rho;
+    whiten6(S, 1.0, L.r, b);
+    const double d2 = norm_sq6(b);
+    robust_weight_of(B.loss_kind, B.loss_k, f, d2, rw, rho);
+    const double sw = sqrt(rw);
+    whiten66(S, sw, L.H1, A);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] *= sw;
+#pragma unroll
+    for (int k = 0; k < 21; ++k) S.R[k] *= sw;
+    double* o = lin + LIN * (size_t)f;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double s11 = 0, s12 = 0, s22 = 0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s11 += A[6 * k + a] * A[6 * k + c];
+#pragma unroll
+        for (int k = 0; k <= c; ++k) s12 += A[6 * k + a] * S.R[SqrtInfo::at(k, c)];
+#pragma unroll
+        for (int k = 0; k <= (a < c ? a : c); ++k) s22 += S.R[SqrtInfo::at(k, a)] * S.R[SqrtInfo::at(k, c)];
+        o[6 * a + c] = s11;
+        o[36 + 6 * a + c] = s12;
+        o[72 + 6 * a + c] = s22;
+      }
+      double g1 = 0, g2 = 0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) g1 += A[6 * k + a] * b[k];
+#pragma unroll
+      for (int k = 0; k <= a; ++k) g2 += S.R[SqrtInfo::at(k, a)] * b[k];
+      o[108 + a] = g1;
+      o[114 + a] = g2;
+    }
+    err_part[f] = 0.5 * rw * d2;
+    return;
+  }
   double w[6], w2[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) w[k] = B.w[6 * (size_t)f + k];
@@ -81,11 +127,40 @@ __global__ __launch_bounds__(256) void between_assemble_kernel(vus_between_facto
 }
 
 // part_lin[f] = 0.5 w |b + J1 d1 + J2 d2|^2 at the old poses, part_new[f] = rho at the new poses
+template <bool FULL>
 __global__ __launch_bounds__(256) void between_eval_kernel(vus_between_factors B, const double* __restrict__ poses,
                                                            const double* __restrict__ dp, const double* __restrict__ new_poses,
                                                            double* __restrict__ part_lin, double* __restrict__ part_new) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= B.n) return;
+  if constexpr (FULL) {
+    BetweenLin L;
+    SqrtInfo S;
+    double b[6], rw, rho;
+    if (part_lin != nullptr) {
+      between_factor<true>(B, poses, f, L);
+      const double* d1 = dp + 6 * (size_t)B.node1[f];
+      const double* d2 = dp + 6 * (size_t)B.node2[f];
+      double v[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        v[k] = L.r[k] + d2[k];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) v[k] += L.H1[6 * k + c] * d1[c];
+      }
+      load_sqrt_info(B, f, S);
+      whiten6(S, 1.0, L.r, b);
+      robust_weight_of(B.loss_kind, B.loss_k, f, norm_sq6(b), rw, rho);
+      whiten6(S, 1.0, v, b);
+      part_lin[f] = 0.5 * rw * norm_sq6(b);
+    }
+    between_factor<false>(B, new_poses, f, L);
+    load_sqrt_info(B, f, S);
+    whiten6(S, 1.0, L.r, b);
+    robust_weight_of(B.loss_kind, B.loss_k, f, norm_sq6(b), rw, rho);
+    part_new[f] = rho;
+    return;
+  }
   double w[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) w[k] = B.w[6 * (size_t)f + k];
@@ -115,7 +190,7 @@ int check_args(const vus_between_factors* B) {
   VUS_REQUIRE(B != nullptr, "between factors are null");
   VUS_REQUIRE(B->n >= 1 && B->n_nodes >= 2 && B->pose_stride >= 1 && B->pose_stride <= 3 && B->n_nodes % B->pose_stride == 0,
               "bad sizes: n=%d n_nodes=%d pose_stride=%d", B->n, B->n_nodes, B->pose_stride);
-  VUS_REQUIRE(B->node1 && B->node2 && B->meas && B->w && B->loss_kind && B->loss_k, "factor arrays are null");
+  VUS_REQUIRE(B->node1 && B->node2 && B->meas && (B->w || B->sqrt_info) && B->loss_kind && B->loss_k, "factor arrays are null");
   VUS_REQUIRE(B->n_targets >= 1 && B->tgt_node && B->tgt_s && B->tgt_ptr && B->tgt_terms, "target arrays are null");
   return VUS_OK;
 }
@@ -151,6 +226,7 @@ extern "C" int vus_between_check(const vus_between_factors* B, int band, void* s
     VUS_REQUIRE(std::abs(n1[f] - n2[f]) <= band, "factor %d: nodes %d and %d are more than band=%d apart", f, n1[f], n2[f], band);
     if (int rc = check_factor_loss(f, kind[f], lk[f])) return rc;
   }
+  if (int rc = check_sqrt_info(B->sqrt_info, B->n, st)) return rc;
   for (int q = 0; q < B->n_targets; ++q) {
     const int node = tn[q], s = ts[q];
     VUS_REQUIRE(node >= 0 && node < B->n_nodes && s >= 0 && s <= band && s <= node, "target %d: block (%d, s=%d) outside the band",
@@ -173,7 +249,8 @@ extern "C" int vus_between_linearize(const vus_between_factors* B, const double*
   if (int rc = check_args(B)) return rc;
   VUS_REQUIRE(poses && lin && err && work, "null buffer");
   hipStream_t st = vus::as_stream(stream);
-  between_linearize_kernel<<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, lin, work);
+  if (B->sqrt_info) between_linearize_kernel<true><<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, lin, work);
+  else between_linearize_kernel<false><<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, lin, work);
   vus::reduce_partials(work, B->n, err, st);
   VUS_CHECK_LAUNCH("between_linearize");
   return VUS_OK;
@@ -196,7 +273,8 @@ extern "C" int vus_between_eval_step(const vus_between_factors* B, const double*
   hipStream_t st = vus::as_stream(stream);
   double* part_lin = work;
   double* part_new = work + B->n;
-  between_eval_kernel<<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, dp, new_poses, part_lin, part_new);
+  if (B->sqrt_info) between_eval_kernel<true><<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, dp, new_poses, part_lin, part_new);
+  else between_eval_kernel<false><<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, dp, new_poses, part_lin, part_new);
   vus::reduce_partials(part_lin, B->n, out, st);
   vus::reduce_partials(part_new, B->n, out + 1, st);
   VUS_CHECK_LAUNCH("between_eval_step");
@@ -207,7 +285,8 @@ extern "C" int vus_between_error(const vus_between_factors* B, const double* pos
   if (int rc = check_args(B)) return rc;
   VUS_REQUIRE(poses && err && work, "null buffer");
   hipStream_t st = vus::as_stream(stream);
-  between_eval_kernel<<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, nullptr, poses, nullptr, work + B->n);
+  if (B->sqrt_info) between_eval_kernel<true><<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, nullptr, poses, nullptr, work + B->n);
+  else between_eval_kernel<false><<<cdiv(B->n, 256), 256, 0, st>>>(*B, poses, nullptr, poses, nullptr, work + B->n);
   vus::reduce_partials(work + B->n, B->n, err, st);
   VUS_CHECK_LAUNCH("between_error");
   return VUS_OK;

@@ -25,12 +25,34 @@ namespace {
 constexpr int ROW = VUS_CLOSURE_ROW;                 // J1 (36), J2 (36), r (6)
 constexpr int MAX_M = 6 * VUS_CLOSURE_MAX;           // columns of U
 
+// FULL: the factors carry a full-covariance model (B.sqrt_info); the diagonal instantiation is the kernel as it was.
+template <bool FULL>
 __global__ __launch_bounds__(64) void closure_linearize_kernel(vus_between_factors B, const double* __restrict__ poses,
                                                                double* __restrict__ rows, double* __restrict__ err_part) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= B.n) return;
   BetweenLin L;
   between_factor<true>(B, poses, f, L);
+  if constexpr (FULL) {
+    // sw R H1, sw R (upper-triangular, the zeros written), sw R r: the whitening of the in-band path (between_device.h)
+    SqrtInfo S;
+    load_sqrt_info(B, f, S);
+    double b[6], rw, rho;
+    whiten6(S, 1.0, L.r, b);
+    const double d2 = norm_sq6(b);
+    robust_weight_of(B.loss_kind, B.loss_k, f, d2, rw, rho);
+    const double sw = sqrt(rw);
+    double* o = rows + ROW * (size_t)f;
+    whiten66(S, sw, L.H1, o);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) o[36 + 6 * q + c] = c >= q ? S.R[SqrtInfo::at(q, c >= q ? c : q)] * sw : 0.0;
+      o[72 + q] = b[q] * sw;
+    }
+    err_part[f] = 0.5 * rw * d2;
+    return;
+  }
   double w[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) w[k] = B.w[6 * (size_t)f + k];
@@ -168,7 +190,7 @@ int check_args(const vus_between_factors* B) {
   VUS_REQUIRE(B->n >= 1 && B->n <= VUS_CLOSURE_MAX, "n=%d long closures, [1, %d] are supported", B->n, VUS_CLOSURE_MAX);
   VUS_REQUIRE(B->n_nodes >= 2 && B->pose_stride >= 1 && B->pose_stride <= 3 && B->n_nodes % B->pose_stride == 0,
               "bad sizes: n_nodes=%d pose_stride=%d", B->n_nodes, B->pose_stride);
-  VUS_REQUIRE(B->node1 && B->node2 && B->meas && B->w && B->loss_kind && B->loss_k, "factor arrays are null");
+  VUS_REQUIRE(B->node1 && B->node2 && B->meas && (B->w || B->sqrt_info) && B->loss_kind && B->loss_k, "factor arrays are null");
   return VUS_OK;
 }
 
@@ -197,7 +219,7 @@ extern "C" int vus_closure_check(const vus_between_factors* B, int band, void* s
                 "in-band between factors", f, n1[f], n2[f], band);
     if (int rc = check_factor_loss(f, kind[f], lk[f])) return rc;
   }
-  return VUS_OK;
+  return check_sqrt_info(B->sqrt_info, B->n, st);
 }
 
 extern "C" int vus_closure_linearize(const vus_between_factors* B, const double* poses, double* rows, double* err,
@@ -205,7 +227,8 @@ extern "C" int vus_closure_linearize(const vus_between_factors* B, const double*
   if (int rc = check_args(B)) return rc;
   VUS_REQUIRE(poses && rows && err && work, "null buffer");
   hipStream_t st = vus::as_stream(stream);
-  closure_linearize_kernel<<<cdiv(B->n, 64), 64, 0, st>>>(*B, poses, rows, work);
+  if (B->sqrt_info) closure_linearize_kernel<true><<<cdiv(B->n, 64), 64, 0, st>>>(*B, poses, rows, work);
+  else closure_linearize_kernel<false><<<cdiv(B->n, 64), 64, 0, st>>>(*B, poses, rows, work);
   vus::reduce_partials(work, B->n, err, st);
   VUS_CHECK_LAUNCH("closure_linearize");
   return VUS_OK;

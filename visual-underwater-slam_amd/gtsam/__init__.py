@@ -384,6 +384,99 @@ class _Unit(_NoiseModel):
         return _Unit(np.ones(int(dim)))
 
 
+class _Gaussian(_NoiseModel):
+    """gtsam.noiseModel.Gaussian: a full-covariance model, held as the upper-triangular R with R^T R = cov^-1; a vector is
+    whitened as R v, a Jacobian as R H.  R() is the upper Cholesky factor of the information matrix (positive diagonal)
+    whichever constructor was used -- GTSAM's behaviour as recalled, not checked against a build (SqrtInformation there
+    keeps the matrix it is given); any R with R^T R = cov^-1 gives the same error.  Covariance / Information /
+    SqrtInformation return the Diagonal model for an exactly diagonal matrix (GTSAM's smart = true).
+    BetweenFactorPose3 takes it (include/vus_between.h, sqrt_info); every other factor refuses it at construction."""
+
+    def __init__(self, R):
+        self._R = R
+        self._cov = np.linalg.inv(R.T @ R)
+        self._cov = 0.5 * (self._cov + self._cov.T)
+        super().__init__(np.sqrt(np.diag(self._cov)))
+
+    @staticmethod
+    def _square(M, what):
+        M = np.array(M, dtype=float)
+        if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] == 0:
+            raise RuntimeError(f"noiseModel.Gaussian.{what}: a square matrix is expected, not an array of shape {M.shape}")
+        if not np.isfinite(M).all():
+            raise RuntimeError(f"noiseModel.Gaussian.{what}: the matrix must be finite")
+        return M
+
+    @staticmethod
+    def _from_spd(M, what, inverse):
+        """The model of the symmetric positive definite M = the information (or, with `inverse`, the covariance)."""
+        M = _Gaussian._square(M, what)
+        if np.abs(M - M.T).max() > 1e-9 * np.abs(M).max():
+            raise RuntimeError(f"noiseModel.Gaussian.{what}: the matrix is not symmetric (relative 1e-9)")
+        M = 0.5 * (M + M.T)
+        try:
+            np.linalg.cholesky(M)
+            info = np.linalg.inv(M) if inverse else M
+            R = np.linalg.cholesky(0.5 * (info + info.T)).T
+        except np.linalg.LinAlgError:
+            raise RuntimeError(f"noiseModel.Gaussian.{what}: the matrix is not positive definite") from None
+        if not np.isfinite(R).all():
+            raise RuntimeError(f"noiseModel.Gaussian.{what}: the matrix is not positive definite")
+        if not (M - np.diag(np.diag(M))).any():
+            return _Diagonal(np.sqrt(np.diag(M)) if inverse else 1.0 / np.sqrt(np.diag(M)))
+        return _Gaussian(np.triu(R))
+
+    @staticmethod
+    def Covariance(covariance, smart=True):
+        return _Gaussian._from_spd(covariance, "Covariance", True)
+
+    @staticmethod
+    def Information(information, smart=True):
+        return _Gaussian._from_spd(information, "Information", False)
+
+    @staticmethod
+    def SqrtInformation(R, smart=True):
+        R = _Gaussian._square(R, "SqrtInformation")
+        if np.linalg.matrix_rank(R) < R.shape[0]:
+            raise RuntimeError("noiseModel.Gaussian.SqrtInformation: the matrix is singular")
+        return _Gaussian._from_spd(R.T @ R, "SqrtInformation", False)
+
+    def R(self):
+        return self._R.copy()
+
+    def information(self):
+        return self._R.T @ self._R
+
+    def covariance(self):
+        return self._cov.copy()
+
+    def whiten(self, v):
+        return self._R @ np.asarray(v, dtype=float).reshape(-1)
+
+    def Whiten(self, H):
+        return self._R @ np.asarray(H, dtype=float)
+
+    def is_isotropic(self):
+        return False
+
+
+def _sqrt_info_of(model):
+    """The [d, d] whitening matrix of a Gaussian or diagonal model (the noise of a Robust one): R, or diag(1 / sigma)."""
+    noise = model._noise if isinstance(model, _Robust) else model
+    return noise._R.copy() if isinstance(noise, _Gaussian) else np.diag(1.0 / noise._sigmas)
+
+
+def _is_full(model):
+    """The model (or the noise of a Robust one) is a full-covariance noiseModel.Gaussian."""
+    return isinstance(model._noise if isinstance(model, _Robust) else model, _Gaussian)
+
+
+def _refuse_full(model, what):
+    if isinstance(model, _NoiseModel) and _is_full(model):
+        raise NotImplementedError(f"{what}: a full-covariance noiseModel.Gaussian is supported on BetweenFactorPose3 only; use a "
+                                  "Diagonal / Isotropic / Unit model here")
+
+
 class _MEstimator:
     """gtsam.noiseModel.mEstimator.Base: a robust loss rho(d) of the whitened residual norm d and its IRLS weight
     w(d) = rho'(d) / d, GTSAM's default Block reweighting (one weight per factor).  `kind` is the VUS_LOSS_* number of
@@ -518,6 +611,7 @@ def _stereo_model_key(model):
 class noiseModel:  # namespace, as in gtsam
     Base = _NoiseModel
     Diagonal = _Diagonal
+    Gaussian = _Gaussian
     Isotropic = _Isotropic
     Unit = _Unit
     Robust = _Robust
@@ -581,6 +675,7 @@ class GenericStereoFactor3D(_Factor):
     def __init__(self, measured: StereoPoint2, model: _NoiseModel, poseKey: int, landmarkKey: int,
                  K: Cal3_S2Stereo, body_P_sensor: Optional[Pose3] = None):
         super().__init__([poseKey, landmarkKey])
+        _refuse_full(model, "GenericStereoFactor3D")
         if model.dim() != 3:
             raise RuntimeError("GenericStereoFactor3D needs a 3-dimensional noise model")
         self._measured, self._model, self._K = measured, model, K
@@ -614,6 +709,7 @@ class GenericProjectionFactorCal3_S2(_Factor):
     def __init__(self, measured, model: _NoiseModel, poseKey: int, pointKey: int, K: Cal3_S2,
                  body_P_sensor: Optional[Pose3] = None):
         super().__init__([poseKey, pointKey])
+        _refuse_full(model, "GenericProjectionFactorCal3_S2")
         if model.dim() != 2:
             raise RuntimeError("GenericProjectionFactorCal3_S2 needs a 2-dimensional noise model")
         if not isinstance(K, Cal3_S2):
@@ -647,6 +743,7 @@ class ProjectionFactorBlock(_Factor):
         self.landmark_keys = np.ascontiguousarray(pointKeys, dtype=np.int64).reshape(-1)
         if not (len(self.meas) == len(self.pose_keys) == len(self.landmark_keys)):
             raise RuntimeError("ProjectionFactorBlock: arrays differ in length")
+        _refuse_full(model, "ProjectionFactorBlock")
         if model.dim() != 2:
             raise RuntimeError("ProjectionFactorBlock needs a 2-dimensional noise model")
         if not isinstance(K, Cal3_S2):
@@ -687,6 +784,7 @@ class StereoFactorBlock(_Factor):
         self.landmark_keys = np.ascontiguousarray(landmarkKeys, dtype=np.int64).reshape(-1)
         if not (len(self.meas) == len(self.pose_keys) == len(self.landmark_keys)):
             raise RuntimeError("StereoFactorBlock: arrays differ in length")
+        _refuse_full(model, "StereoFactorBlock")
         if model.dim() != 3:
             raise RuntimeError("StereoFactorBlock needs a 3-dimensional noise model")
         self._model, self._K = model, K
@@ -721,6 +819,7 @@ class _PriorFactor(_Factor):
 
 class PriorFactorPose3(_PriorFactor):
     def __init__(self, key, prior: Pose3, model: _NoiseModel):           # batch.py:281
+        _refuse_full(model, "PriorFactorPose3")
         if model.dim() != 6:
             raise RuntimeError("PriorFactorPose3 needs a 6-dimensional noise model")
         _refuse_robust(model, "PriorFactorPose3")
@@ -730,6 +829,7 @@ class PriorFactorPose3(_PriorFactor):
 class PriorFactorVector(_PriorFactor):
     def __init__(self, key, prior, model: _NoiseModel):                  # batch.py:282
         prior = np.asarray(prior, dtype=float).reshape(-1).copy()
+        _refuse_full(model, type(self).__name__)
         if model.dim() != prior.size:
             raise RuntimeError("PriorFactorVector: noise model dimension differs from the vector's")
         _refuse_robust(model, "PriorFactorVector")
@@ -752,18 +852,21 @@ class PriorFactorPoint3(PriorFactorVector):
 
 class PriorFactorConstantBias(_PriorFactor):
     def __init__(self, key, prior: _ConstantBias, model: _NoiseModel):
+        _refuse_full(model, "PriorFactorConstantBias")
         super().__init__(key, prior, model)
 
 
 class BetweenFactorConstantBias(_Factor):
     def __init__(self, key1, key2, measured, model):
         super().__init__([key1, key2])
+        _refuse_full(model, "BetweenFactorConstantBias")
         self._measured, self._model = measured, model
 
 
 class BetweenFactorPose3(_Factor):
     """gtsam.BetweenFactorPose3(key1, key2, measured, model): error 0.5 |Log(measured^-1 (X1^-1 X2))|^2 in the whitening of
-    a 6-dimensional Diagonal / Isotropic / Unit model, optionally wrapped in noiseModel.Robust (include/vus_between.h).
+    a 6-dimensional Diagonal / Isotropic / Unit model or a full-covariance noiseModel.Gaussian (whitening R r, R^T R =
+    cov^-1), optionally wrapped in noiseModel.Robust (include/vus_between.h).
     Odometry (consecutive keys) and loop closures (any two keyframes) alike; the two keys must differ."""
 
     def __init__(self, key1, key2, measured: Pose3, model: _NoiseModel):
@@ -794,6 +897,7 @@ class _PoseMeasFactor(_Factor):
         what = type(self).__name__
         if not isinstance(model, _NoiseModel):
             raise RuntimeError(f"{what}: the last argument must be a noise model")
+        _refuse_full(model, what)
         if model.dim() != 3:
             raise RuntimeError(f"{what} needs a 3-dimensional noise model, not one of dimension {model.dim()}")
         self._model = model
@@ -973,6 +1077,7 @@ class DvlVelocityFactor(_Factor):
 
     def __init__(self, model: _NoiseModel, velKey: int, poseKey: int, measured):
         super().__init__([velKey, poseKey])
+        _refuse_full(model, "DvlVelocityFactor")
         _refuse_robust(model, "DvlVelocityFactor")
         if model.dim() != 3 or not model.is_isotropic():
             raise NotImplementedError("DvlVelocityFactor needs an isotropic 3-dimensional noise model (batch.py:98)")

@@ -361,9 +361,11 @@ def _pack_graph(graph, values, device=None):
 
 
 def _pack_between(pose_keys, between_f):
-    """BetweenFactorPose3 -> (i, j, meas [n, 12], sigmas [n, 6], losses [n], span): pose indices into the sorted Pose3 keys,
-    the measured poses, the diagonal sigmas, each factor's (VUS_LOSS_* kind, k) and the widest pose distance."""
-    from . import _Robust
+    """BetweenFactorPose3 -> (i, j, meas [n, 12], sigmas [n, 6], losses [n], span, sqrt_info): pose indices into the sorted
+    Pose3 keys, the measured poses, the sigmas (the roots of the covariance diagonal under a full model), each factor's
+    (VUS_LOSS_* kind, k), the widest pose distance, and sqrt_info [n, 6, 6] = every factor's R (diag(1 / sigma) for a
+    diagonal one) when at least one factor carries a full-covariance noiseModel.Gaussian, else None."""
+    from . import _Robust, _is_full, _sqrt_info_of
     bi, bj, bm, bs, bl = [], [], [], [], []
     for f in between_f:
         idx = []
@@ -376,8 +378,10 @@ def _pack_between(pose_keys, between_f):
         bi.append(idx[0]); bj.append(idx[1]); bm.append(f._measured.flat12()); bs.append(f._model.sigmas())
         bl.append((rob.kind, rob.k) if rob is not None else (0, 0.0))
     bi, bj = np.asarray(bi, np.int32), np.asarray(bj, np.int32)
+    full = any(_is_full(f._model) for f in between_f)
     return dict(i=bi, j=bj, meas=np.asarray(bm, float).reshape(-1, 12), sigmas=np.asarray(bs, float).reshape(-1, 6),
-                losses=bl, span=int(np.abs(bi.astype(np.int64) - bj).max()))
+                losses=bl, span=int(np.abs(bi.astype(np.int64) - bj).max()),
+                sqrt_info=np.stack([_sqrt_info_of(f._model) for f in between_f]) if full else None)
 
 
 def _pack_pose_meas(pose_keys, pose_meas_f):
@@ -538,7 +542,8 @@ def _build_solver(pg, device="cuda:0", long_span=None):
     # a factor the landmark band already covers stays in the band whatever long_span says
     max_span = None if long_span is None else max(int(long_span), prob.band // stride)
     bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
-                        loss=list(btw["losses"]), device=device, max_span=max_span) if btw else None
+                        loss=list(btw["losses"]), device=device, max_span=max_span,
+                        sqrt_info=btw.get("sqrt_info")) if btw else None
     pp = pg.get("point_priors")
     pf = PointPriors(pp["idx"], pp["mean"], pp["sigmas"], len(pg["lm_keys"]), device=device) if pp else None
     pm = pg.get("pose_meas")

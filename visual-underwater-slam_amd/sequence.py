@@ -257,6 +257,7 @@ def imu_delta_rotations(imu, params: "gtsam.PreintegrationParams") -> np.ndarray
 
 CANDIDATE_MODES = ("pose", "appearance", "both")
 REFIT_MODES = ("left", "stereo")
+NOISE_MODES = ("diagonal", "full")
 
 
 @dataclass
@@ -292,14 +293,21 @@ class LoopClosureParams:
     sigma_uv_px: InitVar[float] = 0.5
     sigma_disp_px: InitVar[Optional[float]] = None
     gate_sigma: InitVar[float] = 4.0
+    # The noise model of the emitted BetweenFactorPose3, init-only and kept as a plain attribute too.  "diagonal": the
+    # marginal sigmas of the measurement's covariance; "full": the whole covariance (noiseModel.Gaussian.Covariance)
+    noise: InitVar[str] = "diagonal"
 
-    def __post_init__(self, long_span=None, refit="left", sigma_uv_px=0.5, sigma_disp_px=None, gate_sigma=4.0):
+    def __post_init__(self, long_span=None, refit="left", sigma_uv_px=0.5, sigma_disp_px=None, gate_sigma=4.0,
+                      noise="diagonal"):
         self.long_span = None if long_span is None else int(long_span)
         if self.candidates not in CANDIDATE_MODES:
             raise ValueError(f"LoopClosureParams.candidates must be one of {CANDIDATE_MODES}, not {self.candidates!r}")
         if refit not in REFIT_MODES:
             raise ValueError(f"LoopClosureParams.refit must be one of {REFIT_MODES}, not {refit!r}")
+        if noise not in NOISE_MODES:
+            raise ValueError(f"LoopClosureParams.noise must be one of {NOISE_MODES}, not {noise!r}")
         self.refit = refit
+        self.noise = noise
         self.sigma_uv_px = float(sigma_uv_px)
         self.sigma_disp_px = None if sigma_disp_px is None else float(sigma_disp_px)
         self.gate_sigma = float(gate_sigma)
@@ -417,14 +425,18 @@ def loop_closure_measurements(result, params: LoopClosureParams, body_P_sensor: 
 
 def loop_closure_factors(result, pairs, params: LoopClosureParams, body_P_sensor: Optional["gtsam.Pose3"] = None):
     """gtsam.BetweenFactorPose3(X(a), X(b), measured, model) for every accepted pair of `result` (a frontend.PairPoses of
-    pairs = (pair_a, pair_b)); see loop_closure_measurements for the rule and the covariance.  BetweenFactorPose3 takes
-    diagonal models: the sigmas are the square roots of the covariance's diagonal (the marginal sigmas, the conservative
-    choice), wrapped in noiseModel.Robust when params.robust names an mEstimator."""
+    pairs = (pair_a, pair_b)); see loop_closure_measurements for the rule and the covariance.  params.noise = "diagonal"
+    (the default): a Diagonal model whose sigmas are the square roots of the covariance's diagonal (the marginal sigmas,
+    which drop the correlation of rotation and translation: the conservative choice); "full": the whole covariance as
+    noiseModel.Gaussian.Covariance(cov).  Either is wrapped in noiseModel.Robust when params.robust names an mEstimator."""
     pa, pb = (np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v).reshape(-1) for v in pairs)
     accepted, measured, cov, _ = loop_closure_measurements(result, params, body_P_sensor)
     out = []
     for c in np.nonzero(accepted)[0]:
-        model = gtsam.noiseModel.Diagonal.Sigmas(np.sqrt(np.diag(cov[c])))
+        if params.noise == "full":
+            model = gtsam.noiseModel.Gaussian.Covariance(cov[c])
+        else:
+            model = gtsam.noiseModel.Diagonal.Sigmas(np.sqrt(np.diag(cov[c])))
         if params.robust is not None:
             kind, k = params.robust
             model = gtsam.noiseModel.Robust.Create(getattr(gtsam.noiseModel.mEstimator, kind).Create(float(k)), model)
