@@ -7,7 +7,7 @@
  * The hot step is Z: the substitution of up to 6 * 64 further right-hand sides against the factor the band solve has left
  * behind (vus_ba_band_resolve); the rest are small kernels over the long factors.  A trial runs
  *     vus_closure_linearize (once per linearisation), vus_ba_schur, vus_closure_gradient, the one-sided band solve,
- *     vus_closure_scatter, vus_ba_band_resolve, vus_closure_capacitance, vus_closure_correct.
+ *     vus_closure_scatter, vus_ba_band_resolve, vus_closure_capacitance, vus_closure_diag_max, vus_closure_correct.
  * All pointers are device pointers, every call is asynchronous on `stream`, allocates nothing and returns 0 or a negative
  * VUS_E_* code, as in vus.h.  The arguments are checked on the host before anything is launched.
  */
@@ -73,6 +73,12 @@ int vus_closure_capacitance(const vus_between_factors* B, const double* rows, co
  * the system with the long closures.  1 <= n_rhs <= VUS_CLOSURE_MAX_RHS.  work: vus_closure_work_doubles. */
 int vus_closure_correct(const vus_between_factors* B, const double* rows, const double* Z, const double* C, double* X,
                         int n_rhs, double* work, void* stream);
+
+/* out[0] = max_i C_ii = max_i sum_{c <= i} L_ic^2 from the factor vus_closure_capacitance has left in C: 1 + the largest
+ * weight of a closure row against the band system.  The correction cancels x0 = B^-1 b down to x by about that factor,
+ * so the low-rank path loses that many digits more than a band widened to the closure would (profiles/closure_conditioning.md);
+ * the caller decides what is too large.  NaN if any L_ic^2 on or below the diagonal is NaN.  One workgroup, no read-back. */
+int vus_closure_diag_max(const vus_between_factors* B, const double* C, double* out, void* stream);
 
 #ifdef __cplusplus
 }

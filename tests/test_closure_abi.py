@@ -8,7 +8,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "vus_closure.h")
 SYMBOLS = {"vus_ba_band_resolve": 8, "vus_closure_check": 3, "vus_closure_linearize": 6, "vus_closure_gradient": 4,
-           "vus_closure_scatter": 4, "vus_closure_capacitance": 5, "vus_closure_correct": 8}
+           "vus_closure_scatter": 4, "vus_closure_capacitance": 5, "vus_closure_correct": 8, "vus_closure_diag_max": 4}
 
 
 def _strip(text):
@@ -77,12 +77,15 @@ def test_closure_stages_check_sizes_and_pointers_without_a_gpu():
         refused("vus_closure_capacitance", ctypes.byref(bad), p8, p8, p8, word=word)
         refused("vus_closure_correct", ctypes.byref(bad), p8, p8, p8, p8, 1, p8, word=word)
         refused("vus_closure_check", ctypes.byref(bad), 3, word=word)
+        refused("vus_closure_diag_max", ctypes.byref(bad), p8, p8, word=word)
     refused("vus_closure_linearize", None, p8, p8, p8, p8, word=b"null")
     refused("vus_closure_linearize", ctypes.byref(good), None, p8, p8, p8, word=b"null")
     refused("vus_closure_gradient", ctypes.byref(good), p8, None, word=b"null")
     refused("vus_closure_scatter", ctypes.byref(good), None, p8, word=b"null")
     refused("vus_closure_capacitance", ctypes.byref(good), p8, p8, None, word=b"null")
     refused("vus_closure_correct", ctypes.byref(good), p8, p8, p8, None, 1, p8, word=b"null")
+    refused("vus_closure_diag_max", ctypes.byref(good), None, p8, word=b"null")
+    refused("vus_closure_diag_max", ctypes.byref(good), p8, None, word=b"null")
     for n_rhs in (0, -1, 9):
         refused("vus_closure_correct", ctypes.byref(good), p8, p8, p8, p8, n_rhs, p8, word=b"n_rhs")
     refused("vus_closure_check", ctypes.byref(good), -1, word=b"band")

@@ -105,6 +105,7 @@ SIGNATURES = {
     "vus_closure_scatter": [_P, _P, _P, _P],
     "vus_closure_capacitance": [_P, _P, _P, _P, _P],
     "vus_closure_correct": [_P, _P, _P, _P, _P, c_int, _P, _P],
+    "vus_closure_diag_max": [_P, _P, _P, _P],
     # block-tiled image planes of the single-level front-end (include/vus_tiled.h)
     "vus_fast_detect_adaptive_tiled": [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P],
     "vus_orient_rbrief_tiled": [_P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P],

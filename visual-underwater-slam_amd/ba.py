@@ -426,6 +426,8 @@ class LMReport:
     stereo_weights: Optional[tuple] = None     # gtsam shim, robust stereo factors: (pose keys, landmark keys, final w)
     pose_meas_weights: Optional[tuple] = None  # gtsam shim, a robust position / attitude fix: (pose keys, final w), graph order
     long_closures: int = 0       # between factors kept out of the band (BetweenFactors(max_span=...))
+    closure_max_diag: float = 0.0  # largest max_i C_ii of a trial's capacitance matrix (vus_closure_diag_max); 0 without long closures
+    closure_loss_trials: int = 0   # trials whose max_i C_ii exceeded StereoBASolver.CLOSURE_MAX_DIAG: their steps may have lost digits
 
 
 def _i32(t):
@@ -706,6 +708,7 @@ class StereoBASolver:
         self.M = pose_meas if pose_meas is not None and pose_meas.n else None
         self.B = between if between is not None and between.n else None       # the in-band set
         self.C = between.long if between is not None else None                # the long set (LongClosures) or None
+        self._closure_loss_trials, self._closure_max_diag = 0, 0.0            # what _lm_eval has seen (CLOSURE_MAX_DIAG)
         # The add-on factor families, each described once: (C name: its entry points are vus_<name>_<stage>, its hooks
         # <name>_<stage>; the factor object or None; the name of its slot view; the state tensor its stages read, 0 poses
         # or -1 points; the arguments of its vus_<name>_check after the factors; whether it has an assemble stage).  The
@@ -744,6 +747,8 @@ class StereoBASolver:
         for i, (name, *stages) in enumerate(terms):
             slot = self._trial[5 + 4 * i:9 + 4 * i]
             setattr(self, name, slot)
+            if name == "clo_scal":
+                self._clo_at = 5 + 4 * i
             self._terms.append(_Term(*stages, slot))
         self._families = {}
         for name, factors, slot, _, check_args, _ in families:
@@ -918,9 +923,18 @@ class StereoBASolver:
         """clo_scal[1] = linearised error at the step dp, clo_scal[2] = error at new_poses (after eval_step)."""
         self._closure_call("vus_between_eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
 
+    # max_i C_ii above which LMReport.closure_loss_trials counts a trial.  The correction cancels the band solution by about
+    # that factor: where an odometry dropout leaves the band system held by lambda alone and a long closure bridges it, C_ii
+    # grows like 1 / lambda and the step loses as many digits against the widened band.  profiles/closure_conditioning.md: on
+    # the CPU sweep of tests/closure_cond_ref.py the low-rank solve keeps the widened band's accuracy up to max C_ii = 1.12e8;
+    # a quarter of it.  The trial is counted, not refused: a heavy closure on a sound band system has a large C_ii as well
+    # and loses nothing against the widened band (the profile has both cases).
+    CLOSURE_MAX_DIAG = 2.8e7
+
     def _closure_correct(self, X, n_rhs):
         """X [n_rhs, 6 n_nodes], solved against the band system whose one-sided factor is in Sband, becomes the solution
-        with the long closures: Z = B^-1 U (vus_ba_band_resolve), C = I + U^T Z, X -= Z C^-1 U^T X.  No-op without them."""
+        with the long closures: Z = B^-1 U (vus_ba_band_resolve), C = I + U^T Z, X -= Z C^-1 U^T X.  No-op without them.
+        clo_scal[3] = max_i C_ii (vus_closure_diag_max), which _lm_eval records and holds against CLOSURE_MAX_DIAG."""
         if self.C is None:
             return
         nN, B = self.P.n_nodes, self.P.band
@@ -928,6 +942,7 @@ class StereoBASolver:
         _lib.call("vus_ba_band_resolve", _lib.ptr(self.Sband), nN, B, _lib.ptr(self.clo_UZ), 6 * self.C.n, None, 0,
                   _lib.current_stream_ptr())
         self._closure_call("vus_closure_capacitance", lambda f: (self.clo_rows, self.clo_UZ, self.clo_C))
+        self._closure_call("vus_closure_diag_max", lambda f: (self.clo_C, f.scal[3:]))      # the slot's spare: _lm_eval reads it
         self._closure_call("vus_closure_correct", lambda f: (self.clo_rows, self.clo_UZ, self.clo_C, X, n_rhs, f.work))
 
     def _refuse_long(self, what):
@@ -1141,7 +1156,12 @@ class StereoBASolver:
         for term in self._terms:
             term.eval_step(state)
         rec = self._trial.cpu()
-        return int(rec[4:5].view(torch.int32)[0]), self._trial_errors(rec)
+        errors = self._trial_errors(rec)
+        if self.C is not None:      # max_i C_ii of this trial's capacitance matrix (NaN counts as too large)
+            v = float(rec[self._clo_at + 3])
+            self._closure_max_diag = max(self._closure_max_diag, v if v == v else math.inf)
+            self._closure_loss_trials += int(not v <= self.CLOSURE_MAX_DIAG)
+        return int(rec[4:5].view(torch.int32)[0]), errors
 
     def _lm_swap(self, state):
         """Accept the trial: its buffers become the state, the old state tensors the next trial's buffers."""
@@ -1167,6 +1187,7 @@ class StereoBASolver:
         """GTSAM's iterate / tryLambda / checkConvergence over copies of `state`; returns (state, LMReport)."""
         state = tuple(x.to(torch.float64).contiguous().clone() for x in state)
         rep = LMReport(setup_seconds=self.P.setup_seconds, long_closures=self.C.n if self.C is not None else 0)
+        self._closure_loss_trials, self._closure_max_diag = 0, 0.0
         torch.cuda.synchronize(self.P.device)
         t0 = time.perf_counter()
         lam = prm.lambdaInitial
@@ -1231,6 +1252,7 @@ class StereoBASolver:
         torch.cuda.synchronize(self.P.device)
         rep.seconds = time.perf_counter() - t0
         rep.final_error, rep.final_lambda = current, lam
+        rep.closure_loss_trials, rep.closure_max_diag = self._closure_loss_trials, self._closure_max_diag
         return state, rep
 
 

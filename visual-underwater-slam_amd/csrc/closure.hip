@@ -131,20 +131,39 @@ __global__ __launch_bounds__(256) void closure_cap_entries_kernel(vus_between_fa
   C[t] = (a == b ? 1.0 : 0.0) + u_dot(B, rows, a, Z + (size_t)b * (6 * (size_t)B.n_nodes));
 }
 
-// thread = row i.  Column j: s_i = C_ij - sum_{c < j} C_ic C_jc (the columns before j are final), then the pivot's root
+// thread = row i.  Column j: s_i = C_ij - sum_{c < j} C_ic C_jc (the columns before j are final), then the pivot's root.
+// The products are summed first and taken from C_ij once: C is I plus a term that is small for weak closures, and a running
+// difference would round at the size of C_ij in each of up to 383 steps (12 x LAPACK's residual at m = 384 on the MI355X).
 __global__ __launch_bounds__(MAX_M) void closure_cap_chol_kernel(int m, double* C) {
   const int i = threadIdx.x;
   __shared__ double piv;
   for (int j = 0; j < m; ++j) {
     double s = 0.0;
     if (i >= j && i < m) {
-      s = C[i * m + j];
-      for (int c = 0; c < j; ++c) s -= C[i * m + c] * C[j * m + c];
+      double dot = 0.0;
+      for (int c = 0; c < j; ++c) dot += C[i * m + c] * C[j * m + c];
+      s = C[i * m + j] - dot;
     }
     if (i == j) piv = sqrt(s);
     __syncthreads();
     if (i >= j && i < m) C[i * m + j] = i == j ? piv : s / piv;
     __syncthreads();
+  }
+}
+
+// thread = row i of the factor: C_ii = sum_{c <= i} L_ic^2, then the largest over the rows (a NaN row wins)
+__global__ __launch_bounds__(MAX_M) void closure_diag_max_kernel(int m, const double* __restrict__ C, double* __restrict__ out) {
+  const int i = threadIdx.x;
+  __shared__ double v[MAX_M];
+  double s = 0.0;
+  if (i < m)
+    for (int c = 0; c <= i; ++c) s += C[i * m + c] * C[i * m + c];
+  v[i] = s;
+  __syncthreads();
+  if (i == 0) {
+    double best = v[0];
+    for (int a = 1; a < m; ++a) best = (v[a] > best || v[a] != v[a]) ? v[a] : best;
+    out[0] = best;
   }
 }
 
@@ -262,6 +281,14 @@ extern "C" int vus_closure_capacitance(const vus_between_factors* B, const doubl
   VUS_CHECK_LAUNCH("closure_capacitance entries");
   closure_cap_chol_kernel<<<1, MAX_M, 0, st>>>(m, C);
   VUS_CHECK_LAUNCH("closure_capacitance factor");
+  return VUS_OK;
+}
+
+extern "C" int vus_closure_diag_max(const vus_between_factors* B, const double* C, double* out, void* stream) {
+  if (int rc = check_args(B)) return rc;
+  VUS_REQUIRE(C && out, "null buffer");
+  closure_diag_max_kernel<<<1, MAX_M, 0, vus::as_stream(stream)>>>(6 * B->n, C, out);
+  VUS_CHECK_LAUNCH("closure_diag_max");
   return VUS_OK;
 }
 
