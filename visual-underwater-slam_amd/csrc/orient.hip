@@ -40,8 +40,12 @@ constexpr int OR_KP_PER_WAVE = 8;           // keypoints of one wave; the reduce
 // 4 dwordx4 of 48-byte rows: 3.04 (dword-aligned, so they straddle 16-byte boundaries).  On block-tiled planes, naturally
 // aligned dwordx4 of whole block rows (below), ms per 1000 stereo frames against the 1.71 of 7 dwordx2 per keypoint: 3.75
 // loads with 9 % more bytes (kept): 1.58; 3.75 loads with 13 % more bytes: 1.61; 4.5 loads with 28 % more bytes: 1.85 --
-// there the cost is per instruction AND per byte, about 0.08 ms per load and keypoint and 0.4 ms per 1000 bytes and
-// keypoint (profiles/orient_block_rows_r08.md).
+// there the cost followed the instructions AND the bytes, about 0.08 ms per load and keypoint and 0.4 ms per 1000 bytes and
+// keypoint (profiles/orient_block_rows_r08.md).  The L1's ACCESSES are a small part of the per-byte share: with the same
+// bytes in the same loads, dealt so that an even lane and its neighbour read 32 contiguous bytes (PieceRC below), the
+// accesses fall from 216.9 to 128.3 per keypoint and the time from 1.569 to 1.499 ms, about 0.08 ms per 100 accesses and
+// keypoint -- 1000 bytes are 62.5 accesses of 16, 0.05 of their 0.4 ms.  The rest follows the bytes themselves
+// (profiles/orient_lane_dealing_r09.md).
 typedef uint32_t PatchVec __attribute__((ext_vector_type(2), aligned(1)));
 
 // EXACT: the patch starts at column x - RADIUS whatever its alignment (images whose rows are not dword
@@ -113,26 +117,78 @@ __device__ __forceinline__ uint4 tiled_piece_clamped(const uint8_t* __restrict__
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// The centroid patches of TWO keypoints, 93 pieces each, dealt to the lanes back to back: piece p = lane + 64 u
-// (u < 3) belongs to keypoint p / 93 and is piece q = p % 93 = 3 r + c of its patch.  Wave-load 0 is all first keypoint,
-// wave-load 2 all second, wave-load 1 changes over at lane SPLIT: 1.5 loads per keypoint.  Pieces 186 .. 191, and the
+// The DEALING of a patch's pieces to the lanes of its wave-loads: slot -> (r, c), the one definition that the loaders'
+// fast and clamped paths, the LDS stores and the weights follow.  The eight 16-byte rows of a block are ONE 128-byte line,
+// so neighbouring lanes take neighbouring ROWS of one piece column: a lane group then asks for contiguous bytes of one
+// line.  With the piece column fastest (slot = 3 r + c) neighbouring lanes asked three lines, 128 bytes apart, for 16
+// bytes each, and the L1 saw one access per piece: 216.9 per keypoint against 128.3 now, for the same bytes and the same
+// load instructions.  The counts fit a texture path that merges the dwordx4 of an even lane and its neighbour when they
+// are 32 contiguous bytes, and nothing wider (profiles/orient_lane_dealing_r09.md: 1.569 -> 1.499 ms per 1000 stereo frames).
+struct PieceRC {
+  int r, c;   // r >= the patch's rows: an idle slot
+};
+constexpr int BR_PC = 3;                    // whole pieces per row of the descriptor patch (TiledBriefRegs)
+// centroid patch, 93 slots: rows fastest, q = 31 c + r
+__host__ __device__ constexpr PieceRC disc_piece(int q) {
+  const int c = (q >= OR_ROWS ? 1 : 0) + (q >= 2 * OR_ROWS ? 1 : 0);
+  return {q - OR_ROWS * c, c};
+}
+// descriptor patch: four rows of one column, then the next column's -- t = 12 g + 4 c + j holds row 4 g + j; 120 slots, the
+// rows 37 .. 39 of the last group idle.  Its pieces go on to LDS rows of 64 bytes, where a ds_write_b128 serves eight
+// neighbouring lanes at a time on 32 banks: four rows of two columns meet two to a bank, at the instruction's own cost.
+// Rows fastest (t = 37 c + r) meet four to a bank and lost more there than the gather gained: 1.609 ms against the 1.527
+// of the piece column fastest and the 1.499 of this form, the centroid patch as above in all three.
+constexpr int BR_SLOTS = 12 * ((BR_ROWS + 3) / 4);
+__host__ __device__ constexpr PieceRC brief_piece(int t) {
+  const int g = (t * 171) >> 11, w = t - 12 * g;   // t / 12 for t < 128
+  return {4 * g + (w & 3), w >> 2};
+}
+template <int ROWS, int PC, int SLOTS, PieceRC (*PIECE)(int)>
+constexpr bool dealing_is_a_permutation() {   // every piece in exactly one slot, every other slot idle
+  bool seen[ROWS * PC] = {};
+  int n = 0;
+  for (int s = 0; s < SLOTS; ++s) {
+    const PieceRC p = PIECE(s);
+    if (p.r < 0 || p.c < 0 || p.c >= PC) return false;
+    if (p.r >= ROWS) continue;
+    if (seen[p.r * PC + p.c]) return false;
+    seen[p.r * PC + p.c] = true;
+    ++n;
+  }
+  return n == ROWS * PC;
+}
+static_assert(dealing_is_a_permutation<OR_ROWS, OR_PC, OR_NP, disc_piece>(), "centroid patch: 31 x 3 pieces, one slot each");
+static_assert(dealing_is_a_permutation<BR_ROWS, BR_PC, BR_SLOTS, brief_piece>(), "descriptor patch: 37 x 3 pieces, one slot each");
+static_assert(BR_SLOTS <= 128, "descriptor patch: two wave-loads");
+
+// The centroid patches of TWO keypoints, 93 pieces each, dealt to the lanes back to back: slot p = lane + 64 u
+// (u < 3) belongs to keypoint p / 93 and holds piece disc_piece(p % 93) of its patch.  Wave-load 0 is all first keypoint,
+// wave-load 2 all second, wave-load 1 changes over at lane SPLIT: 1.5 loads per keypoint.  Slots 186 .. 191, and the
 // second keypoint's when it is not live, are not read and hold 0.
 struct TiledDiscPair {
   static constexpr int ITERS = (2 * OR_NP + 63) / 64;   // 3
   static constexpr int SPLIT = OR_NP - 64;              // 29
   static_assert(ITERS == 3 && SPLIT > 0 && SPLIT < 64, "wave-load 1 is the only mixed one");
-  static_assert(OR_ROWS + 7 < 64 && 16 * (OR_ROWS - 1) + 128 * (OR_PC - 1) < 1024, "pk fields: 6-bit row, 10-bit offset");
+  // pk, a lane's piece (r, c) in one register: bits 0 .. 9 its byte offset 16 r + 128 c, bits 10 .. 19 its weight index
+  // 3 r + c (OrGeom<true>::pair_moments), bits 20 .. 25 its row, with room for (y0 & 7) + r
+  static constexpr int PK_OFF_BITS = 10, PK_IDX_SHIFT = 10, PK_IDX_BITS = 10, PK_ROW_SHIFT = 20, PK_ROW_BITS = 6;
+  static_assert(16 * (OR_ROWS - 1) + 128 * (OR_PC - 1) < (1 << PK_OFF_BITS) && PK_OFF_BITS <= PK_IDX_SHIFT, "pk: the offset field");
+  static_assert(OR_NP - 1 < (1 << PK_IDX_BITS) && PK_IDX_SHIFT + PK_IDX_BITS <= PK_ROW_SHIFT, "pk: the weight index field");
+  static_assert(OR_ROWS - 1 + 7 < (1 << PK_ROW_BITS) && PK_ROW_SHIFT + PK_ROW_BITS <= 32, "pk: the row field, nothing above it");
   uint4 v[ITERS];
-  uint32_t pk[ITERS];   // this lane's pieces: (row r) << 20 | (16 r + 128 c)
+  uint32_t pk[ITERS];   // this lane's pieces
 
+  static __device__ __forceinline__ int slot_of(int p) { return p >= OR_NP ? p - OR_NP : p; }   // inside its keypoint's patch
   __device__ __forceinline__ void init(int /*pitch*/, int lane) {
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) {
-      const int p = min(lane + 64 * u, 2 * OR_NP - 1), q = p >= OR_NP ? p - OR_NP : p;
-      const uint32_t r = (uint32_t)(q / OR_PC), c = (uint32_t)(q % OR_PC);
-      pk[u] = r << 20 | (16u * r + 128u * c);
+      const PieceRC pc = disc_piece(slot_of(min(lane + 64 * u, 2 * OR_NP - 1)));
+      const uint32_t r = (uint32_t)pc.r, c = (uint32_t)pc.c;
+      pk[u] = r << PK_ROW_SHIFT | (OR_PC * r + c) << PK_IDX_SHIFT | (16u * r + 128u * c);
     }
   }
+  __device__ __forceinline__ int row(int u) const { return (int)(pk[u] >> PK_ROW_SHIFT); }
+  __device__ __forceinline__ int weight_index(int u) const { return (int)((pk[u] >> PK_IDX_SHIFT) & ((1u << PK_IDX_BITS) - 1u)); }
   static __device__ __forceinline__ bool inside(int H, int W, int y, int x) {
     const int xa = (x - OR_R) & ~15;
     return y - OR_R >= 0 && y + OR_R < H && xa >= 0 && xa + 16 * OR_PC <= W;
@@ -146,25 +202,26 @@ struct TiledDiscPair {
       const int y0a = ya - OR_R, y0b = yb - OR_R;
       const uint32_t koa = vus_tiled_offset(y0a & ~7, (xa - OR_R) & ~15, W) + 16u * (uint32_t)(y0a & 7);
       const uint32_t kob = b_live ? vus_tiled_offset(y0b & ~7, (xb - OR_R) & ~15, W) + 16u * (uint32_t)(y0b & 7) : koa;
-      const uint32_t ysa = (uint32_t)(y0a & 7) << 20, ysb = (uint32_t)(y0b & 7) << 20, ystep = 8u * (uint32_t)W - 128u;
-      // (ys + r) >> 3 == (pk + ys) >> 23: the row field has room for ys + r < 64
-      v[0] = *reinterpret_cast<const uint4*>(src + koa + (size_t)(((pk[0] + ysa) >> 23) * ystep + (pk[0] & 1023u)));
+      const uint32_t ysa = (uint32_t)(y0a & 7) << PK_ROW_SHIFT, ysb = (uint32_t)(y0b & 7) << PK_ROW_SHIFT, ystep = 8u * (uint32_t)W - 128u;
+      constexpr int BLK = PK_ROW_SHIFT + 3;                   // (ys + r) >> 3 == (pk + ys) >> BLK: the row field has room for ys + r < 64
+      constexpr uint32_t OFF = (1u << PK_OFF_BITS) - 1u;
+      v[0] = *reinterpret_cast<const uint4*>(src + koa + (size_t)(((pk[0] + ysa) >> BLK) * ystep + (pk[0] & OFF)));
       v[1] = make_uint4(0u, 0u, 0u, 0u);
       v[2] = make_uint4(0u, 0u, 0u, 0u);
       if (!second || b_live)
         v[1] = *reinterpret_cast<const uint4*>(
-            src + (size_t)((second ? kob : koa) + ((pk[1] + (second ? ysb : ysa)) >> 23) * ystep + (pk[1] & 1023u)));
+            src + (size_t)((second ? kob : koa) + ((pk[1] + (second ? ysb : ysa)) >> BLK) * ystep + (pk[1] & OFF)));
       if (b_live && !idle2)
-        v[2] = *reinterpret_cast<const uint4*>(src + kob + (size_t)(((pk[2] + ysb) >> 23) * ystep + (pk[2] & 1023u)));
+        v[2] = *reinterpret_cast<const uint4*>(src + kob + (size_t)(((pk[2] + ysb) >> BLK) * ystep + (pk[2] & OFF)));
     } else {        // replicate-clamped, byte by byte (a keypoint of the pair near the image edge)
 #pragma unroll
       for (int u = 0; u < ITERS; ++u) {
         const int p = lane + 64 * u;
         const bool sec = p >= OR_NP;
-        const int q = sec ? p - OR_NP : p, r = q / OR_PC, c = q - r * OR_PC;
+        const PieceRC pc = disc_piece(slot_of(min(p, 2 * OR_NP - 1)));
         const int y = sec ? yb : ya, x = sec ? xb : xa;
         v[u] = make_uint4(0u, 0u, 0u, 0u);
-        if (p < 2 * OR_NP && (!sec || b_live)) v[u] = tiled_piece_clamped(src, H, W, y - OR_R + r, ((x - OR_R) & ~15) + 16 * c);
+        if (p < 2 * OR_NP && (!sec || b_live)) v[u] = tiled_piece_clamped(src, H, W, y - OR_R + pc.r, ((x - OR_R) & ~15) + 16 * pc.c);
       }
     }
   }
@@ -175,14 +232,21 @@ struct TiledDiscPair {
 // bytes into the fourth block row, and ONE dword of that block row is read per patch row (row r in lane r, a third
 // wave-load of 148 bytes) -- wave-uniform per keypoint.  Four whole pieces per row (148 pieces, three dwordx4) for every
 // keypoint cost 1.85 ms per 1000 stereo frames against the 1.71 of the dwordx2 form, for a > 11 only 1.61, this form 1.58
-// (profiles/orient_block_rows_r08.md).  Piece t = lane + 64 u is (r, c) = (t / 3, t % 3): no per-lane constants are kept.
+// (profiles/orient_block_rows_r08.md).  Slot t = lane + 64 u holds piece brief_piece(t), worked out from the lane number where
+// it is used: the struct keeps no per-lane constants.
 // In LDS the patch has 64-byte rows, piece (r, c) at 64 r + 16 c, the dword at 64 r + 48; what is not written is not read.
 struct TiledBriefRegs {
-  static constexpr int ROWS = BR_ROWS, N = BR_ROWS * 3;
+  static constexpr int ROWS = BR_ROWS;
   uint4 v[2];
   uint32_t col;   // a > 11: bytes 48 .. 51 of row `lane`
 
   static __device__ __forceinline__ bool wide(int x) { return ((x - BR_R) & 15) > 11; }
+  // the piece that the lane's slot lane + 64 u is loaded with: an idle slot reads a piece of the last row again (its line is
+  // in flight anyway) and is not stored
+  static __device__ __forceinline__ PieceRC loaded_piece(int lane, int u) {
+    const PieceRC p = brief_piece(min(lane + 64 * u, BR_SLOTS - 1));
+    return {min(p.r, ROWS - 1), p.c};
+  }
   __device__ __forceinline__ void init(int /*pitch*/, int /*lane*/) { col = 0; }
   __device__ __forceinline__ void load(const uint8_t* __restrict__ src, int H, int W, int /*pitch*/, int y, int x, int lane) {
     const int xa = (x - BR_R) & ~15, y0 = y - BR_R, rc = min(lane, ROWS - 1);
@@ -192,8 +256,8 @@ struct TiledBriefRegs {
       const uint32_t ys = (uint32_t)(y0 & 7), ystep = 8u * (uint32_t)W - 128u;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const int t = min(lane + 64 * u, N - 1), r = (t * 171) >> 9, c = t - 3 * r;   // t / 3 for t < 256
-        const uint32_t off = (((uint32_t)r + ys) >> 3) * ystep + 16u * (uint32_t)r + 128u * (uint32_t)c;
+        const PieceRC p = loaded_piece(lane, u);
+        const uint32_t off = (((uint32_t)p.r + ys) >> 3) * ystep + 16u * (uint32_t)p.r + 128u * (uint32_t)p.c;
         v[u] = *reinterpret_cast<const uint4*>(base + (size_t)off);
       }
       if (wide(x))
@@ -201,8 +265,8 @@ struct TiledBriefRegs {
     } else {        // replicate-clamped, byte by byte (keypoints near the image edge)
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const int t = min(lane + 64 * u, N - 1), r = (t * 171) >> 9, c = t - 3 * r;
-        v[u] = tiled_piece_clamped(src, H, W, y0 + r, xa + 16 * c);
+        const PieceRC p = loaded_piece(lane, u);
+        v[u] = tiled_piece_clamped(src, H, W, y0 + p.r, xa + 16 * p.c);
       }
       if (wide(x)) {
         const int gy = clampi(y0 + rc, 0, H - 1);
@@ -219,7 +283,8 @@ struct TiledBriefRegs {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int t = lane + 64 * u;
-      if (t < N) d[t + ((t * 171) >> 9)] = v[u];   // 64 r + 16 c = 16 (t + r)
+      const PieceRC p = brief_piece(min(t, BR_SLOTS - 1));
+      if (t < BR_SLOTS && p.r < ROWS) d[(BR_DW_TILED / 4) * p.r + p.c] = v[u];   // 64 r + 16 c
     }
     if (wide(x) && lane < ROWS) dst[16 * lane + 12] = col;
   }
@@ -429,11 +494,12 @@ template <bool EXACT> struct OrGeom<true, EXACT> {
   static __device__ __forceinline__ void pair_moments(const uint4* s_w, const TiledDiscPair& pr, int sha, int shb, int lane, int& pa_a,
                                                       int& pq_a, int& pa_b, int& pq_b) {
     const bool second = lane >= TiledDiscPair::SPLIT;
-    const int ea = (sha & 3) * OR_WTD + 3 - (sha >> 2), eb = (shb & 3) * OR_WTD + 3 - (shb >> 2) - 4 * OR_NP;
+    const int ea = (sha & 3) * OR_WTD + 3 - (sha >> 2), eb = (shb & 3) * OR_WTD + 3 - (shb >> 2);
     int mx[3], my[3];
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
-      const int e = (u == 0 ? ea : u == 2 ? eb : second ? eb : ea) + 4 * (lane + 64 * u);
+      // the weights stay laid out by 3 r + c, whatever slot the piece was dealt to
+      const int e = (u == 0 ? ea : u == 2 ? eb : second ? eb : ea) + 4 * pr.weight_index(u);
       const uint2* wd = reinterpret_cast<const uint2*>(s_w) + e;
       const uint32_t d[4] = {pr.v[u].x, pr.v[u].y, pr.v[u].z, pr.v[u].w};
       uint32_t sx = 0, rs = 0;
@@ -444,7 +510,7 @@ template <bool EXACT> struct OrGeom<true, EXACT> {
         rs = __builtin_amdgcn_udot4(d[j], w.y, rs, false);
       }
       mx[u] = (int)sx - OR_R * (int)rs;
-      my[u] = ((int)(pr.pk[u] >> 20) - OR_R) * (int)rs;
+      my[u] = (pr.row(u) - OR_R) * (int)rs;
     }
     pa_a = mx[0] + (second ? 0 : mx[1]);
     pq_a = my[0] + (second ? 0 : my[1]);
@@ -540,7 +606,8 @@ namespace {
 // cell, the unused slots mapped to themselves), so that the eight keypoints of a wave and the 32 of a workgroup are
 // neighbours and their patch rows share lines in flight; the outputs go to the keypoint's own index.  A schedule only.
 // TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W).  OrGeom carries every difference: the
-// patch loaders, the weight and test-offset tables, the patches in flight.  Phase B's LDS patch stays row-major
+// patch loaders (which lane holds which 16-byte piece: disc_piece, brief_piece -- neighbouring lanes, neighbouring rows of
+// one 128-byte line), the weight and test-offset tables, the patches in flight.  Phase B's LDS patch stays row-major
 // (64-byte rows), so the ballots are those of the plain form.
 template <bool EXACT, bool ORDERED, bool TILED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS_OR_WPE_TILED : VUS_OR_WPE, 8))) void orient_rbrief_kernel(
