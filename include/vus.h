@@ -590,4 +590,8 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * the factor the one-sided band solve leaves in Sband: vus_ba_band_resolve. */
 #include "vus_closure.h"
 #include "vus_clahe.h"
+
+/* Fixed-lag smoothing: a dense Gaussian prior over a window of consecutive poses as one more add-on factor family, and the
+ * marginalisation of the head of the reduced camera system that forms such a prior. */
+#include "vus_fixed_lag.h"
 #endif /* VUS_H */

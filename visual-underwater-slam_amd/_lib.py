@@ -126,6 +126,13 @@ SIGNATURES = {
     "vus_pose_meas_eval_step": [_P, _P, _P, _P, _P, _P, _P],
     "vus_pose_meas_error": [_P, _P, _P, _P, _P],
     "vus_pose_meas_weights": [_P, _P, _P, _P],
+    # fixed-lag smoothing: the dense prior over a pose window and the head marginalisation (include/vus_fixed_lag.h)
+    "vus_window_prior_check": [_P, c_int, _P],
+    "vus_window_prior_linearize": [_P, _P, _P, _P, _P, _P],
+    "vus_window_prior_assemble": [_P, _P, c_int, _P, _P, _P],
+    "vus_window_prior_eval_step": [_P, _P, _P, _P, _P, _P, _P],
+    "vus_window_prior_error": [_P, _P, _P, _P, _P],
+    "vus_ba_band_marginalize": [_P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P],
     # lens undistortion + stereo rectification of raw images (include/vus_rectify.h)
     "vus_rectify_plan": [_P, c_int, c_int, c_int, _P, _P],
     "vus_rectify_remap": [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P],
@@ -189,6 +196,10 @@ def load():
     lib.vus_pose_meas_work_doubles.restype = ctypes.c_longlong
     lib.vus_closure_work_doubles.argtypes = [_P]
     lib.vus_closure_work_doubles.restype = ctypes.c_longlong
+    lib.vus_window_prior_work_doubles.argtypes = [_P]
+    lib.vus_window_prior_work_doubles.restype = ctypes.c_longlong
+    lib.vus_ba_band_marginalize_work_doubles.argtypes = [c_int, c_int, c_int]
+    lib.vus_ba_band_marginalize_work_doubles.restype = ctypes.c_longlong
     lib.vus_ba_band_selinv_work_doubles.argtypes = [c_int, c_int]
     lib.vus_ba_band_selinv_work_doubles.restype = ctypes.c_longlong
     _lib = lib

@@ -394,6 +394,53 @@ class PoseMeasurements:
                              f"problem has {problem.n_poses} at pose_stride {problem.pose_stride}")
 
 
+class _CWindowPrior(ctypes.Structure):
+    _fields_ = [("n_poses", c_int), ("first", c_int), ("m", c_int), ("x0", c_void_p), ("H", c_void_p), ("g", c_void_p),
+                ("c", c_double)]
+
+
+class WindowPrior:
+    """Device-resident vus_window_prior (include/vus_fixed_lag.h): a dense Gaussian prior over the m consecutive poses
+    first .. first + m - 1 of a problem with `n_poses` poses at pose_stride 1 -- what a fixed-lag smoother leaves of the
+    keyframes it has marginalised.  x0 [m, 12] the linearisation poses, H [6 m, 6 m] symmetric (positive semi-definite is
+    enough), g [6 m] the gradient at x0, c the constant: error(x) = c + g^T d + 0.5 d^T H d with d the stack of
+    Local(x0_i, x_i).  `span` = m - 1, for StereoBAProblem(between_span=...).  Arrays or device tensors are accepted; the
+    library's check (the solver runs it) refuses a non-finite, asymmetric or negative-diagonal H."""
+
+    def __init__(self, first, x0, H, g, c, n_poses, device="cuda:0"):
+        dev = torch.device(device)
+        self.x0 = _upload(x0, dev, torch.float64, (-1, 12))
+        m = self.x0.shape[0]
+        self.first, self.m, self.n_poses, self.c_const = int(first), int(m), int(n_poses), float(c)
+        if m < 1:
+            raise ValueError("window prior: at least one pose is needed")
+        if self.first < 0 or self.first + m > self.n_poses:
+            raise ValueError(f"window prior: poses {self.first} .. {self.first + m - 1} outside [0, {self.n_poses})")
+        self.H = _upload(H, dev, torch.float64)
+        self.g = _upload(g, dev, torch.float64).reshape(-1)
+        if tuple(self.H.shape) != (6 * m, 6 * m) or self.g.numel() != 6 * m:
+            raise ValueError(f"window prior: H {tuple(self.H.shape)} and g [{self.g.numel()}] for m={m} poses; "
+                             f"[{6 * m}, {6 * m}] and [{6 * m}] are expected")
+        self.n, self.span, self.pose_stride = 1, m - 1, 1
+        p = _lib.ptr
+        self.c = _CWindowPrior(self.n_poses, self.first, m, p(self.x0), p(self.H), p(self.g), self.c_const)
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+    def _fits(self, problem):
+        """Refuse a StereoBAProblem this prior was not built for (the solver asks before it uses the prior)."""
+        if problem.pose_stride != 1:
+            raise ValueError(f"WindowPrior serves pose_stride 1 only, the problem has pose_stride {problem.pose_stride} "
+                             "(inertial layouts are not supported)")
+        if self.n_poses != problem.n_poses or self.first + self.m > problem.n_poses:
+            raise ValueError(f"WindowPrior on poses {self.first} .. {self.first + self.m - 1} of {self.n_poses}, the problem "
+                             f"has {problem.n_poses} poses")
+        if self.m - 1 > problem.band:
+            raise ValueError(f"the window prior spans {self.m - 1} poses, more than the problem's band of {problem.band} nodes: "
+                             "build the StereoBAProblem with between_span=WindowPrior.span")
+
+
 @dataclass
 class LMParams:
     """gtsam.LevenbergMarquardtParams() defaults."""
@@ -686,7 +733,8 @@ class StereoBASolver:
     """Workspace + LM loop.  Buffers are allocated once; optimize() allocates nothing."""
 
     def __init__(self, problem: StereoBAProblem, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None, inertial=(), pose_meas: Optional[PoseMeasurements] = None):
+                 point_priors: Optional[PointPriors] = None, inertial=(), pose_meas: Optional[PoseMeasurements] = None,
+                 window_prior: Optional[WindowPrior] = None):
         self.P = problem
         dev, nP, nL, nO, B = problem.device, problem.n_poses, problem.n_points, problem.n_obs, problem.band
         nN = problem.n_nodes                       # camera-side nodes (= poses unless velocity nodes are interleaved)
@@ -708,12 +756,13 @@ class StereoBASolver:
         self.M = pose_meas if pose_meas is not None and pose_meas.n else None
         self.B = between if between is not None and between.n else None       # the in-band set
         self.C = between.long if between is not None else None                # the long set (LongClosures) or None
+        self.WP = window_prior                                                # the dense prior over a pose window or None
         self._closure_loss_trials, self._closure_max_diag = 0, 0.0            # what _lm_eval has seen (CLOSURE_MAX_DIAG)
         # The add-on factor families, each described once: (C name: its entry points are vus_<name>_<stage>, its hooks
         # <name>_<stage>; the factor object or None; the name of its slot view; the state tensor its stages read, 0 poses
         # or -1 points; the arguments of its vus_<name>_check after the factors; whether it has an assemble stage).  The
-        # terms are the families present in this, the canonical order -- between, long closures, landmark priors, pose
-        # measurements --
+        # terms are the families present in this, the canonical order -- between, long closures, the window prior, landmark
+        # priors, pose measurements --
         # and then the inertial ones (`inertial`: the stages an inertial subclass passes, as (name of the slot view, error,
         # linearize, assemble, eval_step)).  Every stage runs the stereo step first and then the terms in this order,
         # which is what keeps:
@@ -728,6 +777,7 @@ class StereoBASolver:
         #   - eval_step() before every other eval_step: they read new_poses / new_points
         families = [f for f in (("between", self.B, "btw_scal", 0, (B,), True),
                                 ("closure", self.C, "clo_scal", 0, (B,), True),
+                                ("window_prior", self.WP, "wp_scal", 0, (B,), True),
                                 ("point_prior", self.Q, "pp_scal", -1, (), False),
                                 ("pose_meas", self.M, "pm_scal", 0, (), False)) if f[1] is not None]
 
@@ -757,6 +807,8 @@ class StereoBASolver:
             self._families[name] = _Family(factors, getattr(self, slot), torch.empty((1,), **f64), work)
             if factors is self.B:
                 self.btw_lin = torch.empty((factors.n, 120), **f64)
+            if factors is self.WP:      # the gradient g + H delta at the linearisation
+                self.wp_grad = torch.empty((6 * factors.m,), **f64)
             if factors is self.C:       # rows of [J1 J2 r]; U, overwritten by Z = B^-1 U; C = I + U^T Z and its factor
                 self.clo_rows = torch.empty((factors.n, 78), **f64)
                 self.clo_UZ = torch.empty((6 * factors.n, 6 * nN), **f64)
@@ -949,6 +1001,65 @@ class StereoBASolver:
         if self.C is not None:
             raise NotImplementedError(f"{what} with long closures (BetweenFactors(max_span=...)) is not implemented: the band "
                                       "of the covariance needs a rank-6k update; build the factors without max_span")
+
+    # The dense prior over a pose window (include/vus_fixed_lag.h): what a fixed-lag smoother leaves of marginalised keyframes.
+    def window_prior_error(self, poses) -> float:
+        """Error c + g^T d + 0.5 d^T H d of the window prior at poses; 0.0 without one."""
+        return self._family_error("window_prior", poses)
+
+    def window_prior_linearize(self, poses):
+        """wp_grad = g + H delta, wp_scal[0] = the prior's error at poses (its linear error at a zero step)."""
+        self._family_call("window_prior", "linearize", lambda f: (poses, self.wp_grad, f.scal, f.work))
+
+    def window_prior_assemble(self):
+        """Sband += the blocks of H, gs += wp_grad: after schur(), before an inertial assemble."""
+        self._family_call("window_prior", "assemble", lambda f: (self.wp_grad, self.P.band, self.Sband, self.gs))
+
+    def window_prior_eval_step(self, poses):
+        """wp_scal[1] = linearised error at the step dp, wp_scal[2] = error at new_poses (after eval_step)."""
+        self._family_call("window_prior", "eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
+
+    def marginalize_head(self, poses, points, n_drop) -> WindowPrior:
+        """Eliminate every landmark and the first `n_drop` poses of THIS solver's problem at (poses, points) and return the
+        Gaussian prior that leaves on its remaining poses n_drop .. n_poses - 1: a WindowPrior with first = 0,
+        m = n_poses - n_drop and x0 = poses[n_drop:], for a problem of those m poses.  The solver is one built from exactly
+        the factors to be absorbed (choosing them is the smoother's job); nothing of it is changed.  The linear system is
+        the one marginals() uses -- no damping, the robust weights of that point; H = S_RR - S_RM S_MM^-1 S_MR and
+        g = g_R - S_RM S_MM^-1 g_M from vus_ba_band_marginalize, and c = the linear error at a zero step of all terms
+        - 0.5 g_M^T S_MM^-1 g_M - 0.5 sum_l gl_l^T V_l^-1 gl_l, the minimum of the linearised cost over everything eliminated.
+        Raises IndeterminantSystem("point", j) / ("node", i) where the eliminated part is not positive definite."""
+        self._refuse_long("marginalize_head()")
+        if self.P.pose_stride != 1:
+            raise NotImplementedError("marginalize_head() serves pose_stride 1 only (inertial layouts are not supported)")
+        nN, B, k = self.P.n_nodes, self.P.band, int(n_drop)
+        if not 1 <= k < nN:
+            raise ValueError(f"marginalize_head: n_drop={k} outside [1, n_poses={nN})")
+        if nN - k > B + 1:
+            raise ValueError(f"marginalize_head: the {nN - k} remaining poses do not fit the band of {B} nodes: build the "
+                             f"StereoBAProblem with between_span={nN - k - 1}")
+        values = (poses.to(torch.float64).contiguous(), points.to(torch.float64).contiguous())
+        self._linearize_all(values)
+        self._assemble_zero()
+        n = 6 * (nN - k)
+        f64 = dict(dtype=torch.float64, device=self.P.device)
+        H, g, quad = torch.empty((n, n), **f64), torch.empty((n,), **f64), torch.empty((1,), **f64)
+        status = torch.empty((1,), dtype=torch.int32, device=self.P.device)
+        work = torch.empty((int(_lib.load().vus_ba_band_marginalize_work_doubles(nN, B, k)),), **f64)
+        p = _lib.ptr
+        _lib.call("vus_ba_band_marginalize", p(self.Sband), nN, B, p(self.gs), k, p(H), p(g), p(quad), p(status), p(work),
+                  _lib.current_stream_ptr())
+        bad = int(status.item())
+        if bad > 0:
+            raise IndeterminantSystem("node", (bad - 1) // 6)
+        lin0 = self._trial_errors(self._trial.cpu())[0]
+        land = 0.0
+        if self.P.n_points:     # gl^T V^-1 gl per landmark; Vinv is what the Schur step at lambda = 0 left (upper triangle)
+            vi, gl = self.Vinv, self.gl
+            x, y, z = gl[:, 0], gl[:, 1], gl[:, 2]
+            land = float((vi[:, 0] * x * x + vi[:, 3] * y * y + vi[:, 5] * z * z
+                          + 2.0 * (vi[:, 1] * x * y + vi[:, 2] * x * z + vi[:, 4] * y * z)).sum().item())
+        c = lin0 - 0.5 * float(quad.item()) - 0.5 * land
+        return WindowPrior(0, values[0][k:], H, g, c, nN - k, device=self.P.device)
 
     def point_prior_error(self, points) -> float:
         """Error of the landmark priors at points; 0.0 without them."""
@@ -1359,7 +1470,11 @@ class _InertialBASolver(StereoBASolver):
     _ABI = None
     _NEW_STATE = ("new_poses", "new_vels", "new_bias", "new_points")     # state = (poses, vels, bias, points)
 
-    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None, pose_meas=None):
+    def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None, pose_meas=None,
+                 window_prior=None):
+        if window_prior is not None:
+            raise NotImplementedError(f"a dense prior over a pose window (ba.WindowPrior) is not supported by {type(self).__name__}: "
+                                      "the family serves the pose-only layout (StereoBASolver)")
         if problem.pose_stride != self.POSE_STRIDE:
             raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
         nav3 = lambda stage: lambda s: stage(*s[:3])          # state = (poses, vels, bias, points)
@@ -1397,8 +1512,8 @@ class NavBASolver(_InertialBASolver):
     POSE_STRIDE, SDIAG, _ABI = 2, 4, "vus_nav"
 
     def __init__(self, problem: StereoBAProblem, nav: NavFactors, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None):
-        super().__init__(problem, nav, None, between, point_priors, pose_meas)
+                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None, window_prior=None):
+        super().__init__(problem, nav, None, between, point_priors, pose_meas, window_prior)
         self.band_rhs = 7
         self._alloc_band_work()
         nN = problem.n_nodes
@@ -1474,8 +1589,8 @@ class NavBiasBASolver(_InertialBASolver):
     POSE_STRIDE, SDIAG, _ABI = 3, 5, "vus_navb"
 
     def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None):
-        super().__init__(problem, nav, problem.n_poses, between, point_priors, pose_meas)
+                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None, window_prior=None):
+        super().__init__(problem, nav, problem.n_poses, between, point_priors, pose_meas, window_prior)
 
     def nav_linearize(self, poses, vels, biases):
         p = _lib.ptr

@@ -190,8 +190,11 @@ class ShardedStereoBASolver:
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
                  prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None, mono=None,
-                 point_priors=None, pose_meas=None):
+                 point_priors=None, pose_meas=None, window_prior=None):
         from .ba import StereoBAProblem, StereoBASolver
+        if window_prior is not None:
+            raise NotImplementedError("a dense prior over a pose window (ba.WindowPrior) is not supported by the "
+                                      "landmark-sharded solver: use StereoBASolver(problem, window_prior=...) on one GPU")
         if between is not None:
             raise NotImplementedError("BetweenFactorPose3 (ba.BetweenFactors) is not supported by the landmark-sharded solver: "
                                       "use StereoBASolver(problem, between) on one GPU")

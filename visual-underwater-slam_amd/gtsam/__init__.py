@@ -1091,6 +1091,114 @@ class CustomFactor(_Factor):
         self._model, self._fn = model, error_function
 
 
+class HessianFactor(_Factor):
+    """gtsam.HessianFactor(js, Gs, gs, f): upstream's n-way constructor.  `Gs` are the upper-triangle blocks G11, G12, ..,
+    G1n, G22, .. in row-major order, `gs` one vector per key, and the error is 0.5 (f - 2 x^T g + x^T G x): upstream's g is
+    MINUS the gradient at x = 0.  The conversion happens once, here: the factor keeps the dense symmetric G, the gradient
+    -g and the constant f / 2, which is what include/vus_fixed_lag.h takes."""
+
+    def __init__(self, js, Gs, gs, f):
+        super().__init__(js)
+        n = len(self._keys)
+        gs = [np.asarray(g, dtype=float).reshape(-1) for g in gs]
+        Gs = [np.asarray(G, dtype=float) for G in Gs]
+        if len(gs) != n or len(Gs) != n * (n + 1) // 2:
+            raise RuntimeError(f"HessianFactor: {n} keys need {n} vectors and {n * (n + 1) // 2} upper-triangle blocks, not "
+                               f"{len(gs)} and {len(Gs)}")
+        if len(set(self._keys)) != n:
+            raise RuntimeError("HessianFactor: a key appears twice")
+        dims = [len(g) for g in gs]
+        off = np.concatenate([[0], np.cumsum(dims)]).astype(int)
+        G = np.zeros((off[-1], off[-1]))
+        it = iter(Gs)
+        for a in range(n):
+            for b in range(a, n):
+                blk = next(it)
+                if blk.shape != (dims[a], dims[b]):
+                    raise RuntimeError(f"HessianFactor: block ({a}, {b}) is {blk.shape}, ({dims[a]}, {dims[b]}) is expected")
+                G[off[a]:off[a + 1], off[b]:off[b + 1]] = blk
+                if b > a:
+                    G[off[b]:off[b + 1], off[a]:off[a + 1]] = blk.T
+        self._dims, self._G = dims, G
+        self._grad, self._c = -np.concatenate(gs) if n else np.zeros(0), 0.5 * float(f)
+
+    @classmethod
+    def _from_dense(cls, keys, H, grad, c, dim=6):
+        """The factor over `keys` (`dim` values each) with information H, GRADIENT grad and constant c."""
+        self = cls.__new__(cls)
+        _Factor.__init__(self, keys)
+        n = len(self._keys)
+        self._dims = [dim] * n
+        self._G = np.array(H, dtype=float).reshape(dim * n, dim * n)
+        self._grad, self._c = np.array(grad, dtype=float).reshape(dim * n), float(c)
+        return self
+
+    def information(self):
+        return self._G.copy()
+
+    def linearTerm(self):
+        """upstream's g = minus the gradient"""
+        return -self._grad
+
+    def constantTerm(self):
+        return 2.0 * self._c
+
+    def error(self, delta):
+        """0.5 (f - 2 x^T g + x^T G x) at the stacked vector x, the keys in the factor's order."""
+        x = np.asarray(delta, dtype=float).reshape(-1)
+        return float(self._c + self._grad @ x + 0.5 * x @ self._G @ x)
+
+
+class LinearContainerFactor(_Factor):
+    """gtsam.LinearContainerFactor(factor, linearizationPoint): a linear factor held in a nonlinear graph, evaluated at
+    delta = Local(linearizationPoint, values).  Served for a HessianFactor over Pose3 keys that are consecutive in the
+    graph's sorted pose table, at most one per graph: the optimizer lowers it to a ba.WindowPrior (the dense prior a
+    fixed-lag smoother leaves of marginalised keyframes); anything else is refused with the reason when the graph is packed."""
+
+    def __init__(self, factor, linearizationPoint):
+        if not isinstance(factor, HessianFactor):
+            raise NotImplementedError(f"LinearContainerFactor holds a HessianFactor here, not a {type(factor).__name__}")
+        super().__init__(factor.keys())
+        self._factor = factor
+        self._point = Values()
+        for k in self._keys:
+            if not linearizationPoint.exists(k):
+                raise RuntimeError(f"Attempting to at the key \"{symbol_shorthand.key_string(k)}\", which does not exist in the Values.")
+            self._point.insert(k, linearizationPoint._at(k, object, "at"))
+
+    def factor(self):
+        return self._factor
+
+    def linearizationPoint(self):
+        return self._point
+
+    def _window(self, pose_keys):
+        """(first, x0 [m, 12], H, g, c) over the sorted Pose3 keys `pose_keys` of a graph's Values, or the refusal."""
+        f = self._factor
+        if not self._keys:
+            raise NotImplementedError("LinearContainerFactor: a factor without keys")
+        if any(d != 6 for d in f._dims):
+            raise NotImplementedError("LinearContainerFactor: every key must be a Pose3 (6 values), the factor has blocks of "
+                                      f"{sorted(set(f._dims))}")
+        name = symbol_shorthand.key_string
+        for k in self._keys:
+            if not isinstance(self._point._at(k, object, "at"), Pose3):
+                raise NotImplementedError(f"LinearContainerFactor: key {name(k)} is not a Pose3 in the linearisation point; priors "
+                                          "tied to landmarks are not supported")
+        keys = np.asarray(self._keys, dtype=np.int64)
+        order = np.argsort(keys)
+        idx = np.searchsorted(pose_keys, keys[order])
+        for k, j in zip(keys[order].tolist(), idx.tolist()):
+            if j >= len(pose_keys) or pose_keys[j] != k:
+                raise RuntimeError(f"Attempting to at the key \"{name(k)}\", which does not exist in the Values.")
+        if len(idx) > 1 and bool((np.diff(idx) != 1).any()):
+            raise NotImplementedError("LinearContainerFactor: its keys " + ", ".join(name(k) for k in keys[order].tolist())
+                                      + " are not consecutive among the Pose3 keys of the Values")
+        rows = (6 * order[:, None] + np.arange(6)[None, :]).reshape(-1)       # the factor's rows in sorted key order
+        x0 = self._point.pose3_block(keys[order])
+        return int(idx[0]), x0, f._G[np.ix_(rows, rows)], f._grad[rows], f._c
+
+
 class NavState:
     def __init__(self, pose=None, velocity=None):
         self._pose, self._v = pose or Pose3(), np.zeros(3) if velocity is None else np.asarray(velocity, float)

@@ -151,7 +151,8 @@ def _pack_graph(graph, values, device=None):
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
                    ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias, PriorFactorConstantBias,
                    BetweenFactorConstantBias, BetweenFactorPose3, GenericProjectionFactorCal3_S2, ProjectionFactorBlock,
-                   _PoseMeasFactor)
+                   _PoseMeasFactor, LinearContainerFactor)
+    container = None
     meas, pkeys, lkeys = [], [], []
     mono_n = []                     # per part of meas / pkeys / lkeys: 0 for a stereo part, its length for a mono part
     mono = dict(sigma=None, calib=None, loss=None, sensor=None)
@@ -223,6 +224,10 @@ def _pack_graph(graph, values, device=None):
             between_f.append(f)
         elif isinstance(f, _PoseMeasFactor):
             pose_meas_f.append(f)
+        elif isinstance(f, LinearContainerFactor):
+            if container is not None:
+                raise NotImplementedError("more than one LinearContainerFactor in a graph is not supported")
+            container = f
         elif isinstance(f, PriorFactorVector):
             prior_vec.append(f)
         elif isinstance(f, ImuFactor):
@@ -330,8 +335,14 @@ def _pack_graph(graph, values, device=None):
         pr_idx.append(j); pr_T.append(f._prior.flat12()); pr_s.append(f._model.sigmas())
     between = _pack_between(pose_keys, between_f) if between_f else None
     pose_meas = _pack_pose_meas(pose_keys, pose_meas_f) if pose_meas_f else None
+    window = None
+    if container is not None:       # -> ba.WindowPrior: (first pose index, x0 [m, 12], H, gradient, constant)
+        window = dict(zip(("first", "x0", "H", "g", "c"), container._window(pose_keys)))
     nav = None
     if imu_f or dvl_f or bias_f:
+        if window is not None:
+            raise NotImplementedError("a LinearContainerFactor next to inertial factors (ImuFactor, DvlVelocityFactor, bias "
+                                      "factors) is not supported: the dense prior serves the pose-only layout")
         nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f)
     aux = _AuxPriors()
     pp_idx, pp_mean, pp_sig = [], [], []
@@ -356,6 +367,7 @@ def _pack_graph(graph, values, device=None):
                 mono=mono_flags, mono_K=mono["calib"].vector() if has_mono else None, mono_sigma=mono["sigma"],
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
                 prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between, pose_meas=pose_meas,
+                window_prior=window,
                 point_priors=dict(idx=np.asarray(pp_idx, np.int32), mean=np.asarray(pp_mean, float).reshape(-1, 3),
                                   sigmas=np.asarray(pp_sig, float).reshape(-1, 3)) if pp_idx else None)
 
@@ -519,11 +531,12 @@ def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
     return bias_keys, biases, bbetween, bprior
 
 
-def _build_solver(pg, device="cuda:0", long_span=None):
+def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
     """long_span: LevenbergMarquardtParams.longClosureSpan -- between factors spanning more poses form the long set, and
-    the band follows the rest."""
+    the band follows the rest.  min_span: the band is at least this many poses wide (a fixed-lag smoother's sub-problem,
+    whose marginal must fit the band); a LinearContainerFactor's width feeds the band in the same way."""
     from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
-                      BetweenFactors, PointPriors, PoseMeasurements)
+                      BetweenFactors, PointPriors, PoseMeasurements, WindowPrior)
     nav = pg.get("nav")
     btw = pg.get("between")
     walk = bool(nav) and nav.get("per_keyframe", False)
@@ -533,7 +546,11 @@ def _build_solver(pg, device="cuda:0", long_span=None):
     if btw and long_span is not None:
         spans = np.abs(btw["i"].astype(np.int64) - btw["j"])
         between_span = int(spans[spans <= long_span].max(initial=0))
-    prob = StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
+    win = pg.get("window_prior")
+    if win is not None and btw and long_span is not None:
+        raise NotImplementedError("a LinearContainerFactor together with long closures (setLongClosureSpan) is not supported")
+    between_span = max(between_span, int(min_span), len(win["x0"]) - 1 if win is not None else 0)
+    prob =StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
                            prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
                            loss=pg.get("loss"), between_span=between_span,
@@ -556,7 +573,8 @@ def _build_solver(pg, device="cuda:0", long_span=None):
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
         return prob, NavBASolver(prob, nf, bf, pf, mf)
-    return prob, StereoBASolver(prob, bf, pf, pose_meas=mf)
+    wf = WindowPrior(win["first"], win["x0"], win["H"], win["g"], win["c"], n_poses, device=device) if win is not None else None
+    return prob, StereoBASolver(prob, bf, pf, pose_meas=mf, window_prior=wf)
 
 
 def graph_error(graph, values) -> float:
@@ -569,6 +587,8 @@ def graph_error(graph, values) -> float:
     points = torch.from_numpy(pg["points"]).to(dev)
     e = (sv.error(poses, points) + sv.between_error(poses) + sv.closure_error(poses) + sv.point_prior_error(points) +
          sv.pose_meas_error(poses))
+    if pg.get("window_prior") is not None:
+        e += sv.window_prior_error(poses)
     if pg.get("nav"):
         e += sv.nav_error(poses, torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev))
     return e + pg["aux"].error()
