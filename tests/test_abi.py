@@ -4,7 +4,7 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# entry points that return something else than a status code (bound by hand in _lib.load) or have no device work
+# entry points that return something else than a status code or have no device work
 HOST_ONLY = ("vus_abi_version", "vus_last_error", "vus_build_target", "vus_ba_work_doubles", "vus_nav_work_doubles",
              "vus_ba_band_solve_work_doubles", "vus_ba_get_tuning", "vus_pack_work_bytes", "vus_imu_preintegrate",
              "vus_ba_tiles_work_bytes")
@@ -34,6 +34,20 @@ def test_hip_library_exports_every_declared_symbol():
     for name in _declared():
         if name not in HOST_ONLY:
             assert name in L.SIGNATURES, f"{name} missing from _lib.SIGNATURES"
+
+
+def test_every_function_the_reader_finds_is_exported_and_bound_as_the_headers_declare_it():
+    import visual_underwater_slam_amd._lib as L
+    from visual_underwater_slam_amd import _abi
+    functions = _abi.abi().functions
+    assert set(_declared()) <= set(functions) and len(functions) >= 119
+    assert L.SIGNATURES == {name: argtypes for name, (_, argtypes) in functions.items()}
+    raw, lib = ctypes.CDLL(L.LIB_PATH), L.load()
+    for name, (restype, argtypes) in functions.items():
+        assert hasattr(raw, name), f"{name} declared in the headers but not exported"
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+    assert lib.vus_ba_work_doubles.restype is ctypes.c_longlong and lib.vus_last_error.restype is ctypes.c_char_p
 
 
 def test_build_target_is_reported_and_checked_against_the_device_name():

@@ -1,0 +1,109 @@
+"""The C ABI as ctypes, read from the headers: include/vus.h and every include/vus_*.h (but the generated tables of
+vus_orb_tables.h).  One parse per process, on first use.  A declaration this reader cannot read is an error, never a guess."""
+import ctypes
+import functools
+import glob
+import os
+import re
+from collections import namedtuple
+
+INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+
+SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "long long": ctypes.c_longlong,
+           "unsigned long long": ctypes.c_ulonglong, "double": ctypes.c_double, "float": ctypes.c_float,
+           "char": ctypes.c_char, "unsigned char": ctypes.c_ubyte,
+           **{f"{u}int{b}_t": getattr(ctypes, f"c_{u}int{b}") for u in ("", "u") for b in (8, 16, 32, 64)}}
+RETURNS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
+
+# functions: name -> (restype, [argtypes]);  structs: name -> [(field, ctype)];  constants: name -> int
+Abi = namedtuple("Abi", "functions structs constants")
+
+_INT = r"[-+]?\s*(?:0[xX][0-9a-fA-F]+|\d+)[uU]?"
+_DEFINE = re.compile(rf"^[ \t]*#[ \t]*define[ \t]+(VUS_\w+)[ \t]+\(?\s*({_INT})\s*(?:<<\s*({_INT})\s*)?\)?[ \t]*$", re.M)
+_STRUCT = re.compile(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_PROTO = re.compile(r"(.*?)\b(vus_\w+)\s*\(([^()]*)\)", re.S)
+_DECLARATOR = re.compile(r"([\w\s*]*?)(\w*)\s*(?:\[\s*(\w*)\s*\])?")
+
+
+def _int(lit):
+    return int(lit.replace(" ", "").rstrip("uU"), 0)
+
+
+def _ctype(decl, base, constants, fail, member=False):
+    """One declarator (`const double* K`, `gravity[3]`, `n_points` after `int n_poses,`) -> (name, ctype, its scalar type).
+    `base`: the scalar type of the declarators before it on the line, None for the first or only one.  An array is a pointer
+    as a parameter and `ctype * N` as a struct member."""
+    if not member and ("*" in decl or "[" in decl):         # most parameters: nothing more to read
+        return "", ctypes.c_void_p, None
+    bare = " ".join(w for w in decl.split() if w != "const")
+    if base is None and bare in SCALARS:                    # `int`: an unnamed parameter
+        return "", SCALARS[bare], bare
+    m = _DECLARATOR.fullmatch(bare)
+    if not m or (member and not m.group(2)):
+        fail()
+    head, name, dim = m.groups()
+    base = " ".join(head.replace("*", " ").split()) or base
+    if "*" in head or (dim is not None and not member):
+        return name, ctypes.c_void_p, base
+    if base not in SCALARS or (dim is not None and not (dim.isdigit() or dim in constants)):
+        fail()
+    return name, SCALARS[base] if dim is None else SCALARS[base] * (int(dim) if dim.isdigit() else constants[dim]), base
+
+
+def parse(text, where="<string>", constants=None):
+    """The prototypes, structs and integer constants of one header's text.  `constants`: those of the headers read before
+    it (an array length may name one)."""
+    def refuse(decl):
+        def fail():
+            raise ValueError(f"{where}: cannot read the declaration `{' '.join(decl.split())}`")
+        return fail
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text).replace("\\\n", " ")
+    constants = dict(constants or {})
+    for name, a, b in _DEFINE.findall(text):
+        constants[name] = _int(a) << _int(b) if b else _int(a)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M).replace('extern "C" {', " ")
+    structs = {}
+    for body, name in _STRUCT.findall(text):
+        fields = structs[name] = []
+        for member in filter(str.strip, body.split(";")):
+            base = None
+            for decl in member.split(","):
+                field, ctype, base = _ctype(decl, base, constants, refuse(member), member=True)
+                fields.append((field, ctype))
+    text = _STRUCT.sub(" ", text)
+    while re.search(r"\{[^{}]*\}", text):                   # a function DEFINITION goes, head and body
+        text = re.sub(r"[^;{}]*\{[^{}]*\}", " ", text, count=1)
+    functions = {}
+    for decl in filter(lambda d: d.strip(" \n\t}"), text.split(";")):
+        m = _PROTO.fullmatch(decl.strip(" \n\t}"))
+        ret = m and " ".join(m.group(1).replace("*", " * ").split()).replace(" *", "*")
+        if not m or ret not in RETURNS:
+            refuse(decl)()
+        params = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+        functions[m.group(2)] = (RETURNS[ret], [_ctype(p, None, constants, refuse(decl))[1] for p in params])
+    return Abi(functions, structs, constants)
+
+
+@functools.lru_cache(maxsize=None)
+def abi():
+    """The whole ABI; the headers are read the first time this is called."""
+    if not os.path.isdir(INCLUDE_DIR):
+        raise ImportError(f"{INCLUDE_DIR} is missing: the Python binding reads the C ABI from the headers there")
+    paths = [p for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "vus*.h"))) if os.path.basename(p) != "vus_orb_tables.h"]
+    whole = Abi({}, {}, {})
+    for path in paths:                  # vus.h sorts first
+        with open(path) as f:
+            one = parse(f.read(), path, whole.constants)
+        for got, new in zip(whole, one):
+            got.update(new)
+    return whole
+
+
+def const(name):
+    return abi().constants[name]
+
+
+def struct(name):
+    """A ctypes.Structure class with the layout of the header's `typedef struct { ... } name;`."""
+    return type(name, (ctypes.Structure,), {"_fields_": list(abi().structs[name])})

@@ -10,7 +10,7 @@ GPU; this file only sequences launches and reads back three scalars per lambda t
 import ctypes
 import math
 import time
-from ctypes import c_double, c_int, c_void_p
+from ctypes import c_double
 from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -18,23 +18,25 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _lib, ba_pack
+from . import _abi, _lib, ba_pack
 
 
-class _CProblem(ctypes.Structure):
-    _fields_ = [("n_poses", c_int), ("n_points", c_int), ("n_obs", c_int), ("n_priors", c_int),
-                ("K", c_void_p), ("inv_sigma", c_double), ("meas", c_void_p), ("obs_pose", c_void_p),
-                ("obs_point", c_void_p), ("point_ptr", c_void_p), ("obs_ppos", c_void_p),
-                ("pose_ptr", c_void_p), ("pobs_lidx", c_void_p), ("prior_pose", c_void_p),
-                ("prior_T", c_void_p), ("prior_w", c_void_p), ("pose_stride", c_int)]
-
-
-class _CLoss(ctypes.Structure):
-    _fields_ = [("kind", c_int), ("k", c_double)]
-
+# the structs the entry points take by address: their layouts are the headers' (include/vus.h and the vus_*.h next to it)
+_CProblem = _abi.struct("vus_ba_problem")
+_CTiles = _abi.struct("vus_ba_tiles")
+_CLoss = _abi.struct("vus_ba_loss")
+_CSensor = _abi.struct("vus_ba_sensor")
+_CMono = _abi.struct("vus_ba_mono")
+_CBetween = _abi.struct("vus_between_factors")
+_CPointPriors = _abi.struct("vus_point_priors")
+_CPoseMeas = _abi.struct("vus_pose_meas")
+_CWindowPrior = _abi.struct("vus_window_prior")
+_CNav = _abi.struct("vus_nav_factors")
+_CNavBias = _abi.struct("vus_navb_factors")         # the fields of vus_nav_factors, then the bias factors
 
 # VUS_LOSS_* of include/vus_robust.h: robust noise models of the stereo factors (GTSAM mEstimator, Block reweighting)
-LOSS_KINDS = {"gaussian": 0, "huber": 1, "cauchy": 2, "tukey": 3, "geman_mcclure": 4, "welsch": 5}
+LOSS_KINDS = {k: _abi.const("VUS_LOSS_" + k.upper())
+              for k in ("gaussian", "huber", "cauchy", "tukey", "geman_mcclure", "welsch")}
 
 
 def robust_loss(loss):
@@ -55,10 +57,6 @@ def robust_loss(loss):
     if not (math.isfinite(k) and k > 0.0):
         raise ValueError(f"robust loss parameter k={k} must be finite and > 0")
     return kind, k
-
-
-class _CSensor(ctypes.Structure):
-    _fields_ = [("T", c_double * 12)]
 
 
 def sensor_flat12(body_P_sensor):
@@ -119,23 +117,6 @@ def _require_finite(what, sigmas, **values):
     for name, v in values.items():
         if not np.isfinite(v).all():
             raise ValueError(f"{what}: {name} must be finite")
-
-
-class _CMono(ctypes.Structure):
-    _fields_ = [("is_mono", c_void_p), ("K", c_double * 5), ("inv_sigma", c_double)]
-
-
-class _CTiles(ctypes.Structure):
-    _fields_ = [("band", c_int), ("n_tiles", c_int), ("n_units", c_int), ("n_entries", c_int),
-                ("unit_ptr", c_void_p), ("entries", c_void_p), ("order", c_void_p)]
-
-
-class _CBetween(ctypes.Structure):
-    _fields_ = [("n", c_int), ("n_nodes", c_int), ("pose_stride", c_int), ("node1", c_void_p), ("node2", c_void_p),
-                ("meas", c_void_p), ("w", c_void_p), ("loss_kind", c_void_p), ("loss_k", c_void_p), ("n_targets", c_int),
-                ("tgt_node", c_void_p),
-                ("tgt_s", c_void_p), ("tgt_ptr", c_void_p), ("tgt_terms", c_void_p),
-                ("sqrt_info", c_void_p)]     # appended: built from the 14 fields before it, it is NULL (diagonal models)
 
 
 def _require_sqrt_info(what, R, n):
@@ -204,7 +185,7 @@ class BetweenFactors:
     upper-triangular R with R^T R = cov^-1 of a full-covariance model (noiseModel.Gaussian); every factor then whitens with
     its R (a diagonal one carries diag(1/sigma)) and the rows of `sigmas` are not used.  BetweenFactors.from_covariances
     factors per-factor covariances on the host."""
-    MAX_LONG = 64       # VUS_CLOSURE_MAX
+    MAX_LONG = _abi.const("VUS_CLOSURE_MAX")
 
     @classmethod
     def from_covariances(cls, pose_i, pose_j, meas, covariances, n_poses, **kw):
@@ -291,11 +272,6 @@ class LongClosures(BetweenFactors):
                              f"build the BetweenFactors with max_span >= {problem.band // problem.pose_stride}")
 
 
-class _CPointPriors(ctypes.Structure):
-    _fields_ = [("n", c_int), ("n_points", c_int), ("n_rows", c_int), ("row_point", c_void_p), ("row_ptr", c_void_p),
-                ("mean", c_void_p), ("w", c_void_p)]
-
-
 class PointPriors:
     """Device-resident vus_point_priors: PriorFactorPoint3(L(j), mean, model) for j = `point_idx` on landmarks of a
     StereoBAProblem with `n_points` landmarks; mean [n, 3], sigmas [n, 3] (a diagonal model; several priors on one landmark
@@ -331,13 +307,7 @@ class PointPriors:
             raise ValueError(f"PointPriors built for {self.n_points} landmarks, the problem has {problem.n_points}")
 
 
-class _CPoseMeas(ctypes.Structure):
-    _fields_ = [("n", c_int), ("n_poses", c_int), ("pose_stride", c_int), ("n_rows", c_int), ("row_pose", c_void_p),
-                ("row_ptr", c_void_p), ("kind", c_void_p), ("meas", c_void_p), ("w", c_void_p), ("loss_kind", c_void_p),
-                ("loss_k", c_void_p)]
-
-
-POSE_MEAS_POSITION, POSE_MEAS_ROTATION = 0, 1        # VUS_POSE_MEAS_* of include/vus_pose_meas.h
+POSE_MEAS_POSITION, POSE_MEAS_ROTATION = _abi.const("VUS_POSE_MEAS_POSITION"), _abi.const("VUS_POSE_MEAS_ROTATION")
 
 
 class PoseMeasurements:
@@ -392,11 +362,6 @@ class PoseMeasurements:
         if self.pose_stride != problem.pose_stride or self.n_poses != problem.n_poses:
             raise ValueError(f"PoseMeasurements built for {self.n_poses} poses at pose_stride {self.pose_stride}, the "
                              f"problem has {problem.n_poses} at pose_stride {problem.pose_stride}")
-
-
-class _CWindowPrior(ctypes.Structure):
-    _fields_ = [("n_poses", c_int), ("first", c_int), ("m", c_int), ("x0", c_void_p), ("H", c_void_p), ("g", c_void_p),
-                ("c", c_double)]
 
 
 class WindowPrior:
@@ -1370,19 +1335,6 @@ class StereoBASolver:
 # ---------------------------------------------------------------------------------------------
 # graphs with inertial / velocity factors, in two node layouts: one shared IMU bias
 # (vus_nav_*, pose_stride 2) and one bias per keyframe (include/vus_nav_bias.h vus_navb_*, pose_stride 3)
-class _CNav(ctypes.Structure):
-    _fields_ = [("n_imu", c_int), ("imu_i", c_void_p), ("imu_j", c_void_p), ("imu_pim", c_void_p), ("imu_W", c_void_p),
-                ("gravity", c_double * 3), ("n_dvl", c_int), ("dvl_pose", c_void_p), ("dvl_meas", c_void_p),
-                ("dvl_w", c_void_p), ("n_vprior", c_int), ("vprior_idx", c_void_p), ("vprior_v", c_void_p),
-                ("vprior_w", c_void_p)]
-
-
-class _CNavBias(ctypes.Structure):
-    _fields_ = _CNav._fields_ + [("n_bbetween", c_int), ("bb_i", c_void_p), ("bb_j", c_void_p), ("bb_meas", c_void_p),
-                                 ("bb_w", c_void_p), ("n_bprior", c_int), ("bp_idx", c_void_p), ("bp_mean", c_void_p),
-                                 ("bp_w", c_void_p)]
-
-
 class _InertialFactors:
     """The device tensors both factor structs share (IMU, DVL, velocity priors) and the _CNav prefix of the struct."""
     _IMU_REFUSAL = "ImuFactor between non-consecutive poses is not supported"

@@ -8,8 +8,9 @@ batch.  It is the photometric counterpart of `rectify.StereoRectifier`; `sequenc
 puts it between the rectifier and the front end.  Integer arithmetic, bit-equal to its numpy statement; there is no CPU
 fallback.
 """
-MAX_TILES = 32               # VUS_CLAHE_MAX_TILES
-MAX_TILE_PIXELS = 1 << 22    # VUS_CLAHE_MAX_TILE_PIXELS
+from . import _abi
+
+MAX_TILES, MAX_TILE_PIXELS = _abi.const("VUS_CLAHE_MAX_TILES"), _abi.const("VUS_CLAHE_MAX_TILE_PIXELS")
 
 
 def clip_count(clip_limit: float, tw: int, th: int) -> int:

@@ -16,7 +16,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _lib, synth
+from . import _abi, _lib, synth
 
 
 TILE_BW, TILE_BH = 16, 8   # block-tiled planes (include/vus_tiled.h): 16 x 8-pixel blocks of 128 bytes, raster order
@@ -335,7 +335,7 @@ class StereoOrbFrontend:
         """Detect / select / describe on every level, then merge level-major into the per-image lists."""
         p, K, ptr = self.p, self.p.max_features, _lib.ptr
         self.kp_count[:n_img].zero_()
-        self.kp_keys[:n_img].fill_(-1)          # VUS_KEY_INVALID
+        self.kp_keys[:n_img].fill_(_abi.const("VUS_KEY_INVALID") - (1 << 32))        # the uint32 pattern in int32 storage
         self.pyr_cand_max = torch.zeros((1,), dtype=torch.int32, device=self.device)
         prev = images
         for l, L in enumerate(self.levels):

@@ -191,11 +191,12 @@ class StereoRectifier:
     def _upload(self):
         """The device side, on first use: the host part above needs no GPU."""
         import torch
-        from . import _lib
+        from . import _abi, _lib
         _lib.require_gpu()
         self.device = torch.device(self.device)
         self._maps = torch.from_numpy(self.maps_host).to(self.device)
-        tiles_y, tiles_x = -(-self.H // 16), -(-self.W // 64)      # VUS_RECTIFY_TILE_H, _TILE_W
+        tiles_y = -(-self.H // _abi.const("VUS_RECTIFY_TILE_H"))
+        tiles_x = -(-self.W // _abi.const("VUS_RECTIFY_TILE_W"))
         self._boxes = torch.empty((2, tiles_y, tiles_x, 4), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.call("vus_rectify_plan", _lib.ptr(self._maps), 2, self.H, self.W, _lib.ptr(self._boxes),
