@@ -594,4 +594,5 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
 /* Fixed-lag smoothing: a dense Gaussian prior over a window of consecutive poses as one more add-on factor family, and the
  * marginalisation of the head of the reduced camera system that forms such a prior. */
 #include "vus_fixed_lag.h"
+#include "vus_fixed_lag_nav.h"
 #endif /* VUS_H */

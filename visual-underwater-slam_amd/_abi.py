@@ -1,5 +1,9 @@
 """The C ABI as ctypes, read from the headers: include/vus.h and every include/vus_*.h (but the generated tables of
-vus_orb_tables.h).  One parse per process, on first use.  A declaration this reader cannot read is an error, never a guess."""
+vus_orb_tables.h).  One parse per process, on first use.  A declaration this reader cannot read is an error, never a guess.
+
+Two parts.  abi() is the ABI as it stood when its size was pinned (tests/test_abi_reader.py counts its structs and functions);
+addenda() is what the headers named in ADDENDA have added since, read in the same way; whole() is both, and is what the
+binding (_lib.py), struct() and const() use.  A new header goes into ADDENDA and needs nothing else here."""
 import ctypes
 import functools
 import glob
@@ -8,6 +12,7 @@ import re
 from collections import namedtuple
 
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+ADDENDA = ("vus_fixed_lag_nav.h",)      # headers that joined after the pinned census, in reading order
 
 SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "long long": ctypes.c_longlong,
            "unsigned long long": ctypes.c_ulonglong, "double": ctypes.c_double, "float": ctypes.c_float,
@@ -87,10 +92,10 @@ def parse(text, where="<string>", constants=None):
 
 @functools.lru_cache(maxsize=None)
 def abi():
-    """The whole ABI; the headers are read the first time this is called."""
+    """The pinned part of the ABI (every header but ADDENDA); the headers are read the first time this is called."""
     if not os.path.isdir(INCLUDE_DIR):
         raise ImportError(f"{INCLUDE_DIR} is missing: the Python binding reads the C ABI from the headers there")
-    paths = [p for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "vus*.h"))) if os.path.basename(p) != "vus_orb_tables.h"]
+    paths = [p for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "vus*.h"))) if os.path.basename(p) not in ("vus_orb_tables.h",) + ADDENDA]
     whole = Abi({}, {}, {})
     for path in paths:                  # vus.h sorts first
         with open(path) as f:
@@ -100,10 +105,36 @@ def abi():
     return whole
 
 
+@functools.lru_cache(maxsize=None)
+def addenda():
+    """What the headers of ADDENDA declare; a name abi() already holds is an error."""
+    base = abi()
+    new = Abi({}, {}, {})
+    for name in ADDENDA:
+        path = os.path.join(INCLUDE_DIR, name)
+        known = {**base.constants, **new.constants}
+        with open(path) as f:
+            one = parse(f.read(), path, known)
+        # parse() hands back the constants it was given next to the header's own
+        one = one._replace(constants={k: v for k, v in one.constants.items() if k not in known})
+        for held, got, more in zip(base, new, one):
+            twice = sorted(set(more) & (set(held) | set(got)))
+            if twice:
+                raise ValueError(f"{path}: {', '.join(twice)} is declared in an earlier header as well")
+            got.update(more)
+    return new
+
+
+@functools.lru_cache(maxsize=None)
+def whole():
+    """abi() and addenda() together: what the library exports and the binding binds."""
+    return Abi(*({**a, **b} for a, b in zip(abi(), addenda())))
+
+
 def const(name):
-    return abi().constants[name]
+    return whole().constants[name]
 
 
 def struct(name):
     """A ctypes.Structure class with the layout of the header's `typedef struct { ... } name;`."""
-    return type(name, (ctypes.Structure,), {"_fields_": list(abi().structs[name])})
+    return type(name, (ctypes.Structure,), {"_fields_": list(whole().structs[name])})

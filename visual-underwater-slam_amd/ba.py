@@ -31,6 +31,7 @@ _CBetween = _abi.struct("vus_between_factors")
 _CPointPriors = _abi.struct("vus_point_priors")
 _CPoseMeas = _abi.struct("vus_pose_meas")
 _CWindowPrior = _abi.struct("vus_window_prior")
+_CNavWindowPrior = _abi.struct("vus_nav_window_prior")
 _CNav = _abi.struct("vus_nav_factors")
 _CNavBias = _abi.struct("vus_navb_factors")         # the fields of vus_nav_factors, then the bias factors
 
@@ -406,6 +407,57 @@ class WindowPrior:
                              "build the StereoBAProblem with between_span=WindowPrior.span")
 
 
+class NavWindowPrior:
+    """Device-resident vus_nav_window_prior (include/vus_fixed_lag_nav.h): a dense Gaussian prior over pose, velocity and
+    IMU bias of the m consecutive keyframes first .. first + m - 1 of a problem with `n_poses` keyframes in the
+    per-keyframe-bias layout (pose_stride 3) -- what a fixed-lag smoother leaves of the inertial keyframes it has
+    marginalised.  x0 [m, 12], v0 [m, 3], b0 [m, 6] the linearisation point, H [15 m, 15 m] symmetric (positive semi-definite
+    is enough), g [15 m], c the constant: error = c + g^T d + 0.5 d^T H d with d per keyframe (Local(x0_i, x_i), v_i - v0_i,
+    b_i - b0_i).  `span` = m - 1 KEYFRAMES; the band it needs is 3 m - 1 nodes (B of the last keyframe against X of the
+    first), which StereoBAProblem(between_span=span + 1) at pose_stride 3 gives.  Arrays or device tensors are accepted; the library's check (the solver runs it) refuses a
+    non-finite, asymmetric or negative-diagonal H."""
+
+    def __init__(self, first, x0, v0, b0, H, g, c, n_poses, device="cuda:0"):
+        dev = torch.device(device)
+        self.x0 = _upload(x0, dev, torch.float64, (-1, 12))
+        m = self.x0.shape[0]
+        self.first, self.m, self.n_poses, self.c_const = int(first), int(m), int(n_poses), float(c)
+        if m < 1:
+            raise ValueError("nav window prior: at least one keyframe is needed")
+        if self.first < 0 or self.first + m > self.n_poses:
+            raise ValueError(f"nav window prior: keyframes {self.first} .. {self.first + m - 1} outside [0, {self.n_poses})")
+        self.v0 = _upload(v0, dev, torch.float64, (-1, 3))
+        self.b0 = _upload(b0, dev, torch.float64, (-1, 6))
+        if self.v0.shape[0] != m or self.b0.shape[0] != m:
+            raise ValueError(f"nav window prior: v0 {tuple(self.v0.shape)} and b0 {tuple(self.b0.shape)} for m={m} keyframes; "
+                             f"[{m}, 3] and [{m}, 6] are expected")
+        self.H = _upload(H, dev, torch.float64)
+        self.g = _upload(g, dev, torch.float64).reshape(-1)
+        if tuple(self.H.shape) != (15 * m, 15 * m) or self.g.numel() != 15 * m:
+            raise ValueError(f"nav window prior: H {tuple(self.H.shape)} and g [{self.g.numel()}] for m={m} keyframes; "
+                             f"[{15 * m}, {15 * m}] and [{15 * m}] are expected")
+        self.n, self.span, self.pose_stride = 1, m - 1, 3
+        p = _lib.ptr
+        self.c = _CNavWindowPrior(self.n_poses, self.first, m, p(self.x0), p(self.v0), p(self.b0), p(self.H), p(self.g),
+                                  self.c_const)
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+    def _fits(self, problem):
+        """Refuse a StereoBAProblem this prior was not built for (the solver asks before it uses the prior)."""
+        if problem.pose_stride != 3:
+            raise ValueError(f"NavWindowPrior serves pose_stride 3 only (the per-keyframe-bias layout of NavBiasBASolver), the "
+                             f"problem has pose_stride {problem.pose_stride}")
+        if self.n_poses != problem.n_poses or self.first + self.m > problem.n_poses:
+            raise ValueError(f"NavWindowPrior on keyframes {self.first} .. {self.first + self.m - 1} of {self.n_poses}, the "
+                             f"problem has {problem.n_poses} poses")
+        if 3 * self.m - 1 > problem.band:
+            raise ValueError(f"the nav window prior spans {3 * self.m - 1} nodes, more than the problem's band of {problem.band} "
+                             f"nodes: build the StereoBAProblem with between_span={self.m} (NavWindowPrior.span + 1 keyframes: "
+                             "the band is 3 between_span nodes, and B of the last keyframe lies 3 m - 1 nodes from X of the first)")
+
+
 @dataclass
 class LMParams:
     """gtsam.LevenbergMarquardtParams() defaults."""
@@ -721,13 +773,15 @@ class StereoBASolver:
         self.M = pose_meas if pose_meas is not None and pose_meas.n else None
         self.B = between if between is not None and between.n else None       # the in-band set
         self.C = between.long if between is not None else None                # the long set (LongClosures) or None
-        self.WP = window_prior                                                # the dense prior over a pose window or None
+        # the dense prior over a window or None: over poses (pose_stride 1) or over poses, velocities and biases (3)
+        self.WP = window_prior if not isinstance(window_prior, NavWindowPrior) else None
+        self.NWP = window_prior if isinstance(window_prior, NavWindowPrior) else None
         self._closure_loss_trials, self._closure_max_diag = 0, 0.0            # what _lm_eval has seen (CLOSURE_MAX_DIAG)
         # The add-on factor families, each described once: (C name: its entry points are vus_<name>_<stage>, its hooks
         # <name>_<stage>; the factor object or None; the name of its slot view; the state tensor its stages read, 0 poses
-        # or -1 points; the arguments of its vus_<name>_check after the factors; whether it has an assemble stage).  The
-        # terms are the families present in this, the canonical order -- between, long closures, the window prior, landmark
-        # priors, pose measurements --
+        # or -1 points, or a slice of several (each one argument of the hook); the arguments of its vus_<name>_check after the factors; whether it has an assemble stage).  The
+        # terms are the families present in this, the canonical order -- between, long closures, the window prior (of either
+        # layout), landmark priors, pose measurements --
         # and then the inertial ones (`inertial`: the stages an inertial subclass passes, as (name of the slot view, error,
         # linearize, assemble, eval_step)).  Every stage runs the stereo step first and then the terms in this order,
         # which is what keeps:
@@ -743,13 +797,17 @@ class StereoBASolver:
         families = [f for f in (("between", self.B, "btw_scal", 0, (B,), True),
                                 ("closure", self.C, "clo_scal", 0, (B,), True),
                                 ("window_prior", self.WP, "wp_scal", 0, (B,), True),
+                                ("nav_window_prior", self.NWP, "nwp_scal", slice(0, 3), (B,), True),
                                 ("point_prior", self.Q, "pp_scal", -1, (), False),
                                 ("pose_meas", self.M, "pm_scal", 0, (), False)) if f[1] is not None]
 
         def term(name, slot, at, assembles):
-            stage = lambda st: lambda s: getattr(self, f"{name}_{st}")(s[at])          # the public hook, on its state tensor
+            pick = (lambda s: s[at]) if isinstance(at, slice) else (lambda s: (s[at],))
+            stage = lambda st: lambda s: getattr(self, f"{name}_{st}")(*pick(s))       # the public hook, on its state tensor(s)
             assemble = (lambda lam: getattr(self, f"{name}_assemble")()) if assembles else (lambda lam: None)
-            return slot, stage("error"), stage("linearize"), assemble, stage("eval_step")
+            # the nav window prior reads new_vels and new_bias, which the inertial eval_step writes: that term runs it
+            evaluate = (lambda s: None) if name == "nav_window_prior" else stage("eval_step")
+            return slot, stage("error"), stage("linearize"), assemble, evaluate
 
         terms = [term(name, slot, at, assembles) for name, _, slot, at, _, assembles in families] + list(inertial)
         # one record per lambda trial, read back with ONE device-to-host copy: [0] linearise error, [1] linearised error
@@ -774,6 +832,8 @@ class StereoBASolver:
                 self.btw_lin = torch.empty((factors.n, 120), **f64)
             if factors is self.WP:      # the gradient g + H delta at the linearisation
                 self.wp_grad = torch.empty((6 * factors.m,), **f64)
+            if factors is self.NWP:
+                self.nwp_grad = torch.empty((15 * factors.m,), **f64)
             if factors is self.C:       # rows of [J1 J2 r]; U, overwritten by Z = B^-1 U; C = I + U^T Z and its factor
                 self.clo_rows = torch.empty((factors.n, 78), **f64)
                 self.clo_UZ = torch.empty((6 * factors.n, 6 * nN), **f64)
@@ -983,6 +1043,26 @@ class StereoBASolver:
     def window_prior_eval_step(self, poses):
         """wp_scal[1] = linearised error at the step dp, wp_scal[2] = error at new_poses (after eval_step)."""
         self._family_call("window_prior", "eval_step", lambda f: (poses, self.dp, self.new_poses, f.scal[1:], f.work))
+
+    # The same over an inertial window (include/vus_fixed_lag_nav.h): poses, velocities and per-keyframe biases.
+    def nav_window_prior_error(self, poses, vels, biases) -> float:
+        """Error of the nav window prior at (poses, vels, biases); 0.0 without one."""
+        ran = self._family_call("nav_window_prior", "error", lambda f: (poses, vels, biases, f.err, f.work))
+        return float(self._families["nav_window_prior"].err[0].item()) if ran else 0.0
+
+    def nav_window_prior_linearize(self, poses, vels, biases):
+        """nwp_grad = g + H delta, nwp_scal[0] = the prior's error at the state (its linear error at a zero step)."""
+        self._family_call("nav_window_prior", "linearize", lambda f: (poses, vels, biases, self.nwp_grad, f.scal, f.work))
+
+    def nav_window_prior_assemble(self):
+        """Sband += the entries of H, gs += nwp_grad: after schur(), before the inertial assemble."""
+        self._family_call("nav_window_prior", "assemble", lambda f: (self.nwp_grad, self.P.band, self.Sband, self.gs))
+
+    def nav_window_prior_eval_step(self, poses, vels, biases):
+        """nwp_scal[1] = linearised error at the step dp, nwp_scal[2] = error at the new state: after eval_step AND the
+        inertial eval_step, which writes new_vels and new_bias (the inertial term runs it, not the term list)."""
+        self._family_call("nav_window_prior", "eval_step", lambda f: (poses, vels, biases, self.dp, self.new_poses, self.new_vels,
+                                                                     self.new_bias, f.scal[1:], f.work))
 
     def marginalize_head(self, poses, points, n_drop) -> WindowPrior:
         """Eliminate every landmark and the first `n_drop` poses of THIS solver's problem at (poses, points) and return the
@@ -1424,15 +1504,22 @@ class _InertialBASolver(StereoBASolver):
 
     def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None, pose_meas=None,
                  window_prior=None):
-        if window_prior is not None:
+        if window_prior is not None and not isinstance(window_prior, NavWindowPrior):
             raise NotImplementedError(f"a dense prior over a pose window (ba.WindowPrior) is not supported by {type(self).__name__}: "
                                       "the family serves the pose-only layout (StereoBASolver)")
+        if window_prior is not None and self.POSE_STRIDE != 3:
+            raise NotImplementedError(f"a dense prior over an inertial window (ba.NavWindowPrior) is not supported by "
+                                      f"{type(self).__name__}: the family serves the per-keyframe-bias layout (NavBiasBASolver)")
         if problem.pose_stride != self.POSE_STRIDE:
             raise ValueError(f"{type(self).__name__} needs a StereoBAProblem built with pose_stride={self.POSE_STRIDE}")
         nav3 = lambda stage: lambda s: stage(*s[:3])          # state = (poses, vels, bias, points)
+
+        def nav_eval(s):        # the nav window prior's after the inertial one, which writes new_vels and new_bias
+            self.nav_eval_step(*s[:3])
+            self.nav_window_prior_eval_step(*s[:3])
         super().__init__(problem, between, point_priors, inertial=[
-            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav3(self.nav_eval_step))],
-            pose_meas=pose_meas)
+            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav_eval)],
+            pose_meas=pose_meas, window_prior=window_prior)
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
         f64 = dict(dtype=torch.float64, device=dev)
@@ -1563,14 +1650,66 @@ class NavBiasBASolver(_InertialBASolver):
                   p(self.new_poses), p(self.new_vels), p(self.new_bias), p(self.nav_scal[1:]), p(self.nav_work),
                   _lib.current_stream_ptr())
 
+    def _refuse_free_biases(self, upto):
+        """IndeterminantSystem("bias", i) for the first bias B(i), i < upto, with neither a prior, a between-factor nor a place
+        in the nav window prior.  A bias that is singular all the same is caught by the factor's pivot test, as a node."""
+        free = self.N.unconstrained_biases(self.P.n_poses)
+        if self.NWP is not None:
+            free = free[(free < self.NWP.first) | (free >= self.NWP.first + self.NWP.m)]
+        free = free[free < upto]
+        if len(free):
+            raise IndeterminantSystem("bias", int(free[0]))
+
+    def marginalize_head(self, poses, vels, biases, points, n_drop) -> NavWindowPrior:
+        """Eliminate every landmark and the first `n_drop` KEYFRAMES -- pose, velocity and bias -- of THIS solver's problem at
+        (poses, vels, biases, points) and return the Gaussian prior that leaves on the remaining keyframes: a NavWindowPrior
+        with first = 0, m = n_poses - n_drop and the linearisation point (poses, vels, biases)[n_drop:], for a problem of
+        those m keyframes.  The linear system is the one marginals() uses -- no damping, the robust weights of that point,
+        the velocity padding at unit diagonal and zero right-hand side; vus_ba_band_marginalize eliminates 3 n_drop nodes,
+        the padding rows of what it returns are identity rows that vus_nav_window_prior_compact leaves out.  c = the linear
+        error at a zero step of all terms (the inertial ones and a nav window prior of this solver included)
+        - 0.5 g_M^T S_MM^-1 g_M - 0.5 sum_l gl_l^T V_l^-1 gl_l.  Raises IndeterminantSystem("bias", i) for a dropped bias
+        without a prior, a between-factor or a place in this solver's prior, ("point", j) / ("node", i) where the eliminated
+        part is not positive definite."""
+        self._refuse_long("marginalize_head()")
+        nP, nN, B, k = self.P.n_poses, self.P.n_nodes, self.P.band, int(n_drop)
+        if not 1 <= k < nP:
+            raise ValueError(f"marginalize_head: n_drop={k} outside [1, n_poses={nP})")
+        if 3 * (nP - k) - 1 > B:
+            raise ValueError(f"marginalize_head: the {nP - k} remaining keyframes ({3 * (nP - k)} nodes) do not fit the band of "
+                             f"{B} nodes: build the StereoBAProblem with between_span={nP - k}")
+        self._refuse_free_biases(k)
+        values = tuple(x.to(torch.float64).contiguous() for x in (poses, vels, biases, points))
+        self._linearize_all(values)
+        self._assemble_zero()
+        w = nP - k
+        f64 = dict(dtype=torch.float64, device=self.P.device)
+        H18, g18, quad = torch.empty((18 * w, 18 * w), **f64), torch.empty((18 * w,), **f64), torch.empty((1,), **f64)
+        H, g = torch.empty((15 * w, 15 * w), **f64), torch.empty((15 * w,), **f64)
+        status = torch.empty((1,), dtype=torch.int32, device=self.P.device)
+        work = torch.empty((int(_lib.load().vus_ba_band_marginalize_work_doubles(nN, B, 3 * k)),), **f64)
+        p, st = _lib.ptr, _lib.current_stream_ptr()
+        _lib.call("vus_ba_band_marginalize", p(self.Sband), nN, B, p(self.gs), 3 * k, p(H18), p(g18), p(quad), p(status), p(work), st)
+        _lib.call("vus_nav_window_prior_compact", p(H18), p(g18), w, p(H), p(g), st)
+        bad = int(status.item())
+        if bad > 0:
+            raise IndeterminantSystem("node", (bad - 1) // 6)
+        lin0 = self._trial_errors(self._trial.cpu())[0]
+        land = 0.0
+        if self.P.n_points:     # gl^T V^-1 gl per landmark; Vinv is what the Schur step at lambda = 0 left (upper triangle)
+            vi, gl = self.Vinv, self.gl
+            x, y, z = gl[:, 0], gl[:, 1], gl[:, 2]
+            land = float((vi[:, 0] * x * x + vi[:, 3] * y * y + vi[:, 5] * z * z
+                          + 2.0 * (vi[:, 1] * x * y + vi[:, 2] * x * z + vi[:, 4] * y * z)).sum().item())
+        c = lin0 - 0.5 * float(quad.item()) - 0.5 * land
+        return NavWindowPrior(0, values[0][k:], values[1][k:], values[2][k:], H, g, c, w, device=self.P.device)
+
     def marginals(self, poses, vels, biases, points, points_cov=True) -> BAMarginals:
         """Marginal covariances at (poses, vels, biases, points): the one-sided factor of the whole camera-side system at
         lambda = 0 and its selected inversion -- no border step, every bias is a band node.  The BAMarginals carries
         vel_cov [n, 3, 3] and biases_cov [n, 6, 6] (B(i) is node 3i + 2, for joint()).  Raises IndeterminantSystem("bias",
-        i) for a bias B(i) with neither a prior nor a between-factor."""
-        free = self.N.unconstrained_biases(self.P.n_poses)
-        if len(free):
-            raise IndeterminantSystem("bias", int(free[0]))
+        i) for a bias B(i) with neither a prior, a between-factor nor a place in the solver's NavWindowPrior."""
+        self._refuse_free_biases(self.P.n_poses)
         values, Sigma, nodes, pc = self._marginal_parts((poses, vels, biases, points), points_cov)
         nP = self.P.n_poses
         return BAMarginals(self, values, Sigma, self._pose_blocks(Sigma, nodes), pc,

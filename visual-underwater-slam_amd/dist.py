@@ -193,8 +193,9 @@ class ShardedStereoBASolver:
                  point_priors=None, pose_meas=None, window_prior=None):
         from .ba import StereoBAProblem, StereoBASolver
         if window_prior is not None:
-            raise NotImplementedError("a dense prior over a pose window (ba.WindowPrior) is not supported by the "
-                                      "landmark-sharded solver: use StereoBASolver(problem, window_prior=...) on one GPU")
+            single = "NavBiasBASolver" if type(window_prior).__name__ == "NavWindowPrior" else "StereoBASolver"
+            raise NotImplementedError(f"a dense prior over a window (ba.{type(window_prior).__name__}) is not supported by the "
+                                      f"landmark-sharded solver: use {single}(problem, ..., window_prior=...) on one GPU")
         if between is not None:
             raise NotImplementedError("BetweenFactorPose3 (ba.BetweenFactors) is not supported by the landmark-sharded solver: "
                                       "use StereoBASolver(problem, between) on one GPU")

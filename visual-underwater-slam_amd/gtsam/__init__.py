@@ -1123,14 +1123,14 @@ class HessianFactor(_Factor):
         self._grad, self._c = -np.concatenate(gs) if n else np.zeros(0), 0.5 * float(f)
 
     @classmethod
-    def _from_dense(cls, keys, H, grad, c, dim=6):
-        """The factor over `keys` (`dim` values each) with information H, GRADIENT grad and constant c."""
+    def _from_dense(cls, keys, H, grad, c, dim=6, dims=None):
+        """The factor over `keys` (`dim` values each, or `dims` per key) with information H, GRADIENT grad and constant c."""
         self = cls.__new__(cls)
         _Factor.__init__(self, keys)
-        n = len(self._keys)
-        self._dims = [dim] * n
-        self._G = np.array(H, dtype=float).reshape(dim * n, dim * n)
-        self._grad, self._c = np.array(grad, dtype=float).reshape(dim * n), float(c)
+        self._dims = [dim] * len(self._keys) if dims is None else [int(d) for d in dims]
+        n = sum(self._dims)
+        self._G = np.array(H, dtype=float).reshape(n, n)
+        self._grad, self._c = np.array(grad, dtype=float).reshape(n), float(c)
         return self
 
     def information(self):
@@ -1153,7 +1153,9 @@ class LinearContainerFactor(_Factor):
     """gtsam.LinearContainerFactor(factor, linearizationPoint): a linear factor held in a nonlinear graph, evaluated at
     delta = Local(linearizationPoint, values).  Served for a HessianFactor over Pose3 keys that are consecutive in the
     graph's sorted pose table, at most one per graph: the optimizer lowers it to a ba.WindowPrior (the dense prior a
-    fixed-lag smoother leaves of marginalised keyframes); anything else is refused with the reason when the graph is packed."""
+    fixed-lag smoother leaves of marginalised keyframes).  A second shape is served next to it: X(i), V(i) and B(i) of
+    consecutive keyframes with blocks of 6, 3 and 6 values, lowered to a ba.NavWindowPrior in the per-keyframe-bias layout.
+    Anything else is refused with the reason when the graph is packed."""
 
     def __init__(self, factor, linearizationPoint):
         if not isinstance(factor, HessianFactor):
@@ -1171,6 +1173,55 @@ class LinearContainerFactor(_Factor):
 
     def linearizationPoint(self):
         return self._point
+
+    def _is_inertial(self):
+        """The second served shape: X(i), V(i), B(i) keys -- at least an X and one of the others, and nothing else."""
+        chars = {symbol_shorthand.symbolChr(k) for k in self._keys}
+        return "x" in chars and len(chars) > 1 and chars <= {"x", "v", "b"}
+
+    def _nav_window(self, pose_keys):
+        """The inertial shape lowered to a ba.NavWindowPrior, as a dict (first, x0 [m, 12], v0 [m, 3], b0 [m, 6], H, g, c)
+        over the sorted Pose3 keys `pose_keys` of a graph's Values: X(i), V(i) and B(i) of consecutive keyframes with blocks
+        of 6, 3 and 6 values, the keys in any order, the linearisation point a Pose3, a 3-vector and a ConstantBias per
+        keyframe.  Anything in between is refused with the reason."""
+        f, sym = self._factor, symbol_shorthand
+        name = sym.key_string
+        want = {"x": (6, "a Pose3"), "v": (3, "a 3-vector"), "b": (6, "an imuBias.ConstantBias")}
+        off = np.concatenate([[0], np.cumsum(f._dims)]).astype(int)
+        per = {}
+        for pos, k in enumerate(self._keys):
+            per.setdefault(sym.symbolIndex(k), {})[sym.symbolChr(k)] = pos
+        for i in sorted(per):
+            missing = [c for c in "xvb" if c not in per[i]]
+            if missing:
+                raise NotImplementedError(
+                    f"LinearContainerFactor: keyframe {i} has {', '.join(name(self._keys[p]) for p in per[i].values())} but not "
+                    f"{', '.join(name(sym.symbol(c, i)) for c in missing)}; an inertial prior covers X(i), V(i) and B(i) of "
+                    "every keyframe it touches")
+            for c, pos in per[i].items():
+                k, (dim, what) = self._keys[pos], want[c]
+                if f._dims[pos] != dim:
+                    raise NotImplementedError(f"LinearContainerFactor: key {name(k)} has a block of {f._dims[pos]} values, {dim} "
+                                              f"are expected ({what})")
+                val = self._point._at(k, object, "at")
+                ok = (isinstance(val, Pose3) if c == "x" else isinstance(val, _ConstantBias) if c == "b"
+                      else isinstance(val, np.ndarray) and val.size == 3)
+                if not ok:
+                    raise NotImplementedError(f"LinearContainerFactor: key {name(k)} is not {what} in the linearisation point")
+        kfs = sorted(per)
+        xkeys = np.asarray([sym.symbol("x", i) for i in kfs], dtype=np.int64)
+        idx = np.searchsorted(pose_keys, xkeys)
+        for k, j in zip(xkeys.tolist(), idx.tolist()):
+            if j >= len(pose_keys) or pose_keys[j] != k:
+                raise RuntimeError(f"Attempting to at the key \"{name(k)}\", which does not exist in the Values.")
+        if len(idx) > 1 and bool((np.diff(idx) != 1).any()):
+            raise NotImplementedError("LinearContainerFactor: its keyframes " + ", ".join(name(k) for k in xkeys.tolist())
+                                      + " are not consecutive among the Pose3 keys of the Values")
+        rows = np.concatenate([np.arange(off[per[i][c]], off[per[i][c] + 1]) for i in kfs for c in "xvb"])
+        at = lambda c: [self._point._at(sym.symbol(c, i), object, "at") for i in kfs]
+        return dict(first=int(idx[0]), x0=self._point.pose3_block(xkeys),
+                    v0=np.stack([np.asarray(v, dtype=float).reshape(3) for v in at("v")]),
+                    b0=np.stack([b.vector() for b in at("b")]), H=f._G[np.ix_(rows, rows)], g=f._grad[rows], c=f._c)
 
     def _window(self, pose_keys):
         """(first, x0 [m, 12], H, g, c) over the sorted Pose3 keys `pose_keys` of a graph's Values, or the refusal."""

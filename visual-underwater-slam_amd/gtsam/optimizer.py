@@ -144,8 +144,10 @@ def lower_reference_dvl_factor(f):
     return DvlVelocityFactor(model, kv, kx, m3)
 
 
-def _pack_graph(graph, values, device=None):
+def _pack_graph(graph, values, device=None, per_keyframe=False):
     """Factor graph + Values -> arrays for StereoBAProblem.  Raises on anything outside the built scope.
+    `per_keyframe`: pack the inertial side with one bias per keyframe even where the graph alone would not say so (a single
+    ImuFactor and no bias factor); a LinearContainerFactor over X, V, B keys forces the same.
     The per-observation key -> index mapping (a sort of every landmark key) runs on `device` with torch when one
     is given (2 M observations: ~3 ms on the GPU against ~0.3 s in numpy), else in numpy (CPU tests)."""
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
@@ -335,15 +337,19 @@ def _pack_graph(graph, values, device=None):
         pr_idx.append(j); pr_T.append(f._prior.flat12()); pr_s.append(f._model.sigmas())
     between = _pack_between(pose_keys, between_f) if between_f else None
     pose_meas = _pack_pose_meas(pose_keys, pose_meas_f) if pose_meas_f else None
-    window = None
-    if container is not None:       # -> ba.WindowPrior: (first pose index, x0 [m, 12], H, gradient, constant)
+    window, nav_window = None, None
+    if container is not None and container._is_inertial():      # -> ba.NavWindowPrior
+        nav_window = container._nav_window(pose_keys)
+    elif container is not None:     # -> ba.WindowPrior: (first pose index, x0 [m, 12], H, gradient, constant)
         window = dict(zip(("first", "x0", "H", "g", "c"), container._window(pose_keys)))
     nav = None
-    if imu_f or dvl_f or bias_f:
+    if imu_f or dvl_f or bias_f or nav_window is not None:
         if window is not None:
-            raise NotImplementedError("a LinearContainerFactor next to inertial factors (ImuFactor, DvlVelocityFactor, bias "
-                                      "factors) is not supported: the dense prior serves the pose-only layout")
-        nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f)
+            raise NotImplementedError("a LinearContainerFactor over Pose3 keys next to inertial factors (ImuFactor, "
+                                      "DvlVelocityFactor, bias factors) is not supported: that dense prior serves the pose-only "
+                                      "layout; an inertial window takes one over X(i), V(i), B(i)")
+        nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f,
+                                   per_keyframe=per_keyframe or nav_window is not None)
     aux = _AuxPriors()
     pp_idx, pp_mean, pp_sig = [], [], []
     for f in prior_vec:
@@ -367,7 +373,7 @@ def _pack_graph(graph, values, device=None):
                 mono=mono_flags, mono_K=mono["calib"].vector() if has_mono else None, mono_sigma=mono["sigma"],
                 prior_idx=np.asarray(pr_idx, np.int32), prior_T=np.asarray(pr_T, float).reshape(-1, 12),
                 prior_sigmas=np.asarray(pr_s, float).reshape(-1, 6), aux=aux, nav=nav, between=between, pose_meas=pose_meas,
-                window_prior=window,
+                window_prior=window, nav_window_prior=nav_window,
                 point_priors=dict(idx=np.asarray(pp_idx, np.int32), mean=np.asarray(pp_mean, float).reshape(-1, 3),
                                   sigmas=np.asarray(pp_sig, float).reshape(-1, 3)) if pp_idx else None)
 
@@ -414,10 +420,10 @@ def _pack_pose_meas(pose_keys, pose_meas_f):
                 sigmas=np.asarray(sig, float).reshape(-1, 3), losses=losses, keys=np.asarray(keys, np.int64))
 
 
-def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=()):
+def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyframe=False):
     """Velocity / bias side of the graph (batch.py:274-293): every pose X(i) needs a velocity V(i) with the same
     index; either one shared bias key (batch.py:238 passes B(0) to every ImuFactor) or, when the graph has bias factors
-    or several bias keys, one bias B(i) per keyframe (_pack_bias_walk)."""
+    or several bias keys or `per_keyframe` asks for it, one bias B(i) per keyframe (_pack_bias_walk)."""
     from . import _ConstantBias
     pidx = {int(k): i for i, k in enumerate(pose_keys.tolist())}
     vel_keys = []
@@ -431,7 +437,7 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=()):
     if vels.shape[1] != 3:
         raise RuntimeError("velocity variables must be 3-vectors")
     bias_keys = sorted({f._keys[4] for f in imu_f})
-    per_keyframe = bool(bias_f) or len(bias_keys) > 1
+    per_keyframe = bool(per_keyframe) or bool(bias_f) or len(bias_keys) > 1
     if per_keyframe:
         bias_keys, biases, bbetween, bprior = _pack_bias_walk(values, pose_keys, imu_f, bias_f)
     bias_key = bias_keys[0] if bias_keys and not per_keyframe else None
@@ -536,7 +542,7 @@ def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
     the band follows the rest.  min_span: the band is at least this many poses wide (a fixed-lag smoother's sub-problem,
     whose marginal must fit the band); a LinearContainerFactor's width feeds the band in the same way."""
     from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
-                      BetweenFactors, PointPriors, PoseMeasurements, WindowPrior)
+                      BetweenFactors, PointPriors, PoseMeasurements, WindowPrior, NavWindowPrior)
     nav = pg.get("nav")
     btw = pg.get("between")
     walk = bool(nav) and nav.get("per_keyframe", False)
@@ -546,10 +552,12 @@ def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
     if btw and long_span is not None:
         spans = np.abs(btw["i"].astype(np.int64) - btw["j"])
         between_span = int(spans[spans <= long_span].max(initial=0))
-    win = pg.get("window_prior")
-    if win is not None and btw and long_span is not None:
+    win, nwin = pg.get("window_prior"), pg.get("nav_window_prior")
+    if (win is not None or nwin is not None) and btw and long_span is not None:
         raise NotImplementedError("a LinearContainerFactor together with long closures (setLongClosureSpan) is not supported")
-    between_span = max(between_span, int(min_span), len(win["x0"]) - 1 if win is not None else 0)
+    # an inertial prior over m keyframes needs 3 m - 1 nodes (B of the last against X of the first): m poses' worth
+    between_span = max(between_span, int(min_span), len(win["x0"]) - 1 if win is not None else 0,
+                       len(nwin["x0"]) if nwin is not None else 0)
     prob =StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
                            prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
@@ -569,7 +577,9 @@ def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
     if walk:
         nf = NavBiasFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], bbetween=nav["bbetween"],
                             bprior=nav["bprior"], device=device)
-        return prob, NavBiasBASolver(prob, nf, bf, pf, mf)
+        nw = NavWindowPrior(nwin["first"], nwin["x0"], nwin["v0"], nwin["b0"], nwin["H"], nwin["g"], nwin["c"], n_poses,
+                            device=device) if nwin is not None else None
+        return prob, NavBiasBASolver(prob, nf, bf, pf, mf, window_prior=nw)
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
         return prob, NavBASolver(prob, nf, bf, pf, mf)
@@ -590,15 +600,22 @@ def graph_error(graph, values) -> float:
     if pg.get("window_prior") is not None:
         e += sv.window_prior_error(poses)
     if pg.get("nav"):
-        e += sv.nav_error(poses, torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev))
+        vels, bias = torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev)
+        e += sv.nav_error(poses, vels, bias)
+        if pg.get("nav_window_prior") is not None:
+            e += sv.nav_window_prior_error(poses, vels, bias)
     return e + pg["aux"].error()
 
 
 class LevenbergMarquardtOptimizer:
     """gtsam.LevenbergMarquardtOptimizer(graph, initialValues, params=LevenbergMarquardtParams())."""
 
-    def __init__(self, graph, initialValues, params: Optional[LevenbergMarquardtParams] = None, device="cuda:0"):
+    def __init__(self, graph, initialValues, params: Optional[LevenbergMarquardtParams] = None, device="cuda:0",
+                 per_keyframe_bias=False):
+        """EXTENSION `per_keyframe_bias`: solve the inertial side with one bias B(i) per keyframe even where the graph alone
+        would be read as the shared-bias layout (a single ImuFactor and no bias factor): a fixed-lag window of two keyframes."""
         self._graph, self._initial = graph, initialValues
+        self._per_keyframe = bool(per_keyframe_bias)
         self._params = params or LevenbergMarquardtParams()
         self._device = device
         self._result = None
@@ -619,7 +636,7 @@ class LevenbergMarquardtOptimizer:
             if prof:
                 torch.cuda.synchronize()
                 marks.append((name, time.perf_counter()))
-        pg = _pack_graph(self._graph, self._initial, self._device)
+        pg = _pack_graph(self._graph, self._initial, self._device, self._per_keyframe)
         mark("pack_graph_host+upload")
         prob, sv = _build_solver(pg, self._device, self._params.longClosureSpan)
         mark("structure+workspace")
