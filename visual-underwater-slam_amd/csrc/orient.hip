@@ -22,16 +22,21 @@ namespace {
 #ifndef VUS_OR_WPE_TILED
 #define VUS_OR_WPE_TILED 7   // ... for the tiled instances; tests/test_orient_resources.py holds what 7 takes
 #endif
+#ifndef VUS_OR_WPE_TILED_MAX
+#define VUS_OR_WPE_TILED_MAX 7   // ... and not more: with the folded weight table 8 fit (63 VGPRs, 18,720 B of LDS) and are slower
+#endif                           // (profiles/orient_lds_r10.md)
 constexpr int OR_R = 15;                    // disc radius
 constexpr int OR_ROWS = 2 * OR_R + 1;       // 31
 constexpr int OR_DW = 10;                   // 36 bytes cover x-15..x+15 from an aligned start; whole dwordx2 are loaded
 constexpr int BR_R = VUS_RBRIEF_REACH;      // 18
 constexpr int BR_ROWS = 2 * BR_R + 1;       // 37
 constexpr int BR_DW = 10;                   // 40 bytes cover x-18..x+18 from an aligned start
-constexpr int BR_DW_TILED = 16;             // block-tiled planes: 64-byte rows in LDS, three 16-byte block rows and a dword of the fourth (OrGeom)
+constexpr int BR_DW_TILED = 20;             // block-tiled planes: 80-byte rows in LDS, three 16-byte block rows, a dword of the fourth (OrGeom) and 28 bytes of pad
 constexpr int OR_PC = 3;                    // block-tiled planes: 31 + 15 bytes of a centroid patch row lie in three block rows
 constexpr int OR_NP = OR_ROWS * OR_PC;      // 93 pieces of a centroid patch
 constexpr int OR_KP_PER_WAVE = 8;           // keypoints of one wave; the reduce-scatter and the one-store epilogue are written for 8
+constexpr int OR_WFOLD = OR_R + 1;          // block-tiled planes: rows r and 30 - r weigh alike, the weight table holds 16 rows
+constexpr int OR_WROW = 4 * OR_PC + 1;      // ... of 13 eight-byte entries: 12 dwords and a pad, an ODD stride (DiscWeightDwTable)
 
 // Load a (2*RADIUS+1) x (4*DW)-byte patch around (x, y) into registers: every lane issues all of
 // its loads back to back (one memory round trip), the caller stores them to LDS afterwards.
@@ -46,6 +51,12 @@ constexpr int OR_KP_PER_WAVE = 8;           // keypoints of one wave; the reduce
 // accesses fall from 216.9 to 128.3 per keypoint and the time from 1.569 to 1.499 ms, about 0.08 ms per 100 accesses and
 // keypoint -- 1000 bytes are 62.5 accesses of 16, 0.05 of their 0.4 ms.  The rest follows the bytes themselves
 // (profiles/orient_lane_dealing_r09.md).
+// With the gather cut that far the tiled kernel was bound by LDS, not by its loads: the LDS array was busy for 92 % of the
+// launch (210 cycles per keypoint, 147 of them bank conflicts), 94 of the cycles in the weight reads of phase A alone and
+// 74 in the byte reads of phase B.  The weight table in rows of 13 entries, folded (DiscWeightDwTable), and the descriptor
+// patch in rows of 80 bytes (TiledBriefRegs) leave 119 cycles, 60 % of a shorter launch: 1.494 -> 1.375 ms per 1000 stereo
+// frames, nearly all of it from the weights; the waves now wait on their patch loads again.  tools/lds_bank_model.py
+// states the bank rules and gives the conflicts of each layout to within 1 % (profiles/orient_lds_r10.md).
 typedef uint32_t PatchVec __attribute__((ext_vector_type(2), aligned(1)));
 
 // EXACT: the patch starts at column x - RADIUS whatever its alignment (images whose rows are not dword
@@ -133,12 +144,17 @@ __host__ __device__ constexpr PieceRC disc_piece(int q) {
   const int c = (q >= OR_ROWS ? 1 : 0) + (q >= 2 * OR_ROWS ? 1 : 0);
   return {q - OR_ROWS * c, c};
 }
+// ... and the first of the four weight entries of piece (r, c), before the patch's alignment moves it (DiscWeightDwTable)
+__host__ __device__ constexpr int disc_weight_entry(int r, int c) { return OR_WROW * (r < OR_ROWS - 1 - r ? r : OR_ROWS - 1 - r) + 4 * c; }
 // descriptor patch: four rows of one column, then the next column's -- t = 12 g + 4 c + j holds row 4 g + j; 120 slots, the
-// rows 37 .. 39 of the last group idle.  Its pieces go on to LDS rows of 64 bytes, where a ds_write_b128 serves eight
-// neighbouring lanes at a time on 32 banks: four rows of two columns meet two to a bank, at the instruction's own cost.
+// rows 37 .. 39 of the last group idle.  Its pieces go on to LDS rows of 80 bytes (64 when this was measured; the model
+// gives both pitches the same 29 cycles), where a ds_write_b128 serves eight neighbouring lanes at a time on 32 banks: four
+// rows of two columns meet two to a bank, at the instruction's own cost.
 // Rows fastest (t = 37 c + r) meet four to a bank and lost more there than the gather gained: 1.609 ms against the 1.527
 // of the piece column fastest and the 1.499 of this form, the centroid patch as above in all three.
-constexpr int BR_SLOTS = 12 * ((BR_ROWS + 3) / 4);
+constexpr int BR_GROUP_ROWS = 4;            // rows of a group (tools/lds_bank_model.py reads the dealing from these constants)
+constexpr int BR_SLOTS = BR_GROUP_ROWS * BR_PC * ((BR_ROWS + BR_GROUP_ROWS - 1) / BR_GROUP_ROWS);
+static_assert(BR_GROUP_ROWS == 4 && BR_GROUP_ROWS * BR_PC == 12, "brief_piece divides by 12 and by 4 with shifts");
 __host__ __device__ constexpr PieceRC brief_piece(int t) {
   const int g = (t * 171) >> 11, w = t - 12 * g;   // t / 12 for t < 128
   return {4 * g + (w & 3), w >> 2};
@@ -169,11 +185,11 @@ struct TiledDiscPair {
   static constexpr int ITERS = (2 * OR_NP + 63) / 64;   // 3
   static constexpr int SPLIT = OR_NP - 64;              // 29
   static_assert(ITERS == 3 && SPLIT > 0 && SPLIT < 64, "wave-load 1 is the only mixed one");
-  // pk, a lane's piece (r, c) in one register: bits 0 .. 9 its byte offset 16 r + 128 c, bits 10 .. 19 its weight index
-  // 3 r + c (OrGeom<true>::pair_moments), bits 20 .. 25 its row, with room for (y0 & 7) + r
+  // pk, a lane's piece (r, c) in one register: bits 0 .. 9 its byte offset 16 r + 128 c, bits 10 .. 19 the entry of its
+  // weights, disc_weight_entry(r, c) (OrGeom<true>::pair_moments), bits 20 .. 25 its row, with room for (y0 & 7) + r
   static constexpr int PK_OFF_BITS = 10, PK_IDX_SHIFT = 10, PK_IDX_BITS = 10, PK_ROW_SHIFT = 20, PK_ROW_BITS = 6;
   static_assert(16 * (OR_ROWS - 1) + 128 * (OR_PC - 1) < (1 << PK_OFF_BITS) && PK_OFF_BITS <= PK_IDX_SHIFT, "pk: the offset field");
-  static_assert(OR_NP - 1 < (1 << PK_IDX_BITS) && PK_IDX_SHIFT + PK_IDX_BITS <= PK_ROW_SHIFT, "pk: the weight index field");
+  static_assert(disc_weight_entry(OR_R, OR_PC - 1) < (1 << PK_IDX_BITS) && PK_IDX_SHIFT + PK_IDX_BITS <= PK_ROW_SHIFT, "pk: the weight entry field");
   static_assert(OR_ROWS - 1 + 7 < (1 << PK_ROW_BITS) && PK_ROW_SHIFT + PK_ROW_BITS <= 32, "pk: the row field, nothing above it");
   uint4 v[ITERS];
   uint32_t pk[ITERS];   // this lane's pieces
@@ -184,11 +200,11 @@ struct TiledDiscPair {
     for (int u = 0; u < ITERS; ++u) {
       const PieceRC pc = disc_piece(slot_of(min(lane + 64 * u, 2 * OR_NP - 1)));
       const uint32_t r = (uint32_t)pc.r, c = (uint32_t)pc.c;
-      pk[u] = r << PK_ROW_SHIFT | (OR_PC * r + c) << PK_IDX_SHIFT | (16u * r + 128u * c);
+      pk[u] = r << PK_ROW_SHIFT | (uint32_t)disc_weight_entry(pc.r, pc.c) << PK_IDX_SHIFT | (16u * r + 128u * c);
     }
   }
   __device__ __forceinline__ int row(int u) const { return (int)(pk[u] >> PK_ROW_SHIFT); }
-  __device__ __forceinline__ int weight_index(int u) const { return (int)((pk[u] >> PK_IDX_SHIFT) & ((1u << PK_IDX_BITS) - 1u)); }
+  __device__ __forceinline__ int weight_entry(int u) const { return (int)((pk[u] >> PK_IDX_SHIFT) & ((1u << PK_IDX_BITS) - 1u)); }
   static __device__ __forceinline__ bool inside(int H, int W, int y, int x) {
     const int xa = (x - OR_R) & ~15;
     return y - OR_R >= 0 && y + OR_R < H && xa >= 0 && xa + 16 * OR_PC <= W;
@@ -234,7 +250,10 @@ struct TiledDiscPair {
 // keypoint cost 1.85 ms per 1000 stereo frames against the 1.71 of the dwordx2 form, for a > 11 only 1.61, this form 1.58
 // (profiles/orient_block_rows_r08.md).  Slot t = lane + 64 u holds piece brief_piece(t), worked out from the lane number where
 // it is used: the struct keeps no per-lane constants.
-// In LDS the patch has 64-byte rows, piece (r, c) at 64 r + 16 c, the dword at 64 r + 48; what is not written is not read.
+// In LDS the patch has 80-byte rows (BR_DW_TILED), piece (r, c) at 80 r + 16 c, the dword at 80 r + 48; what is not written
+// is not read.  The pitch is for the byte reads of the 256 tests, 32 lanes at a time on 32 banks: with 64-byte rows the rows
+// r and r + 2 share all their banks and the eight reads took 74 LDS cycles per keypoint, 58 of them conflicts; rows of 20
+// dwords spread eight consecutive rows over the banks, 50 cycles (measured: 28 fewer; tests/test_orient_lds_model.py).
 struct TiledBriefRegs {
   static constexpr int ROWS = BR_ROWS;
   uint4 v[2];
@@ -284,9 +303,9 @@ struct TiledBriefRegs {
     for (int u = 0; u < 2; ++u) {
       const int t = lane + 64 * u;
       const PieceRC p = brief_piece(min(t, BR_SLOTS - 1));
-      if (t < BR_SLOTS && p.r < ROWS) d[(BR_DW_TILED / 4) * p.r + p.c] = v[u];   // 64 r + 16 c
+      if (t < BR_SLOTS && p.r < ROWS) d[(BR_DW_TILED / 4) * p.r + p.c] = v[u];   // 80 r + 16 c
     }
-    if (wide(x) && lane < ROWS) dst[16 * lane + 12] = col;
+    if (wide(x) && lane < ROWS) dst[BR_DW_TILED * lane + 12] = col;   // 80 r + 48
   }
 };
 
@@ -416,13 +435,20 @@ constexpr DiscWeightTable<ALIGN> make_disc_weight_table() {
 }
 __device__ __attribute__((aligned(128))) const DiscWeightTable<4> g_disc_weight_table = make_disc_weight_table<4>();
 
-// The tiled form's disc weights, per dword: entry (a, j) = {moment, count} (disc_dword_weight) of dword j - 3 of the patch's rows
-// laid end to end, 12 dwords each (three 16-byte pieces), for a patch whose first column sits a bytes into its first dword;
-// the 3 entries in front and those past the last row are 0.  A patch that starts sh = 4 s + a bytes before its first
-// column (sh < 16) weighs dword d of its piece q = 3 r + c with entry (a, 4 q + d + 3 - s): a lane reads the four of a piece
-// as 32 contiguous bytes.  Entries that fall into the previous row are its dwords 9 .. 11, dx >= 18 there: 0, as the
-// dwords left of the window are.  Pieces 93 .. 98 (the idle lanes of TiledDiscPair's last wave-load) read zeros past the last row.
-constexpr int OR_WTD = 3 + 4 * (3 * 64 - OR_NP) + 4;   // 403 entries per byte alignment: the last piece index is 191 - 93
+// The tiled form's disc weights, per dword: entry (a, j) = {moment, count} (disc_dword_weight), 8 bytes, for a patch whose
+// first column sits a bytes into its first dword.  Rows r and 30 - r of the disc weigh alike, so the table holds the 16 rows
+// dy = -15 .. 0 (OR_WFOLD); a row takes OR_WROW = 13 entries, its 12 dwords (three 16-byte pieces) and a pad, behind 3
+// entries in front of row 0.  A patch that starts sh = 4 s + a bytes before its first column (sh < 16) weighs dword d of its
+// piece (r, c) with entry (a, disc_weight_entry(r, c) + d + 3 - s): a lane reads the four of a piece as 32 contiguous bytes.
+// Entries that fall into the previous row are its pad and its dwords 10 and 11, dx >= 22 there: 0, as the dwords left of the
+// window are.
+// The stride of 13 entries, 104 bytes, is for the LDS banks: the lanes of a wave-load hold neighbouring rows (disc_piece),
+// and the 16 lanes that one half of a ds_read2_b64 serves together then read 16 x 8 bytes that start 26 dwords apart -- 16
+// different even banks of the 32, no two lanes on one bank but where a group spans two piece columns.  With the rows end
+// to end (12 entries, 96 bytes = 24 dwords) four lanes of every group met on each bank pair, and these reads alone kept the
+// LDS array busy for 94 of the kernel's 210 cycles per keypoint (profiles/orient_lds_r10.md).  Folded, the table is 6,880
+// bytes instead of 12,896: half the copy per workgroup, and room in LDS for the descriptor patch's wider rows.
+constexpr int OR_WTD = 3 + OR_WROW * OR_WFOLD + 4;   // 215 entries per byte alignment, a whole number of uint4 in all
 struct DiscWeightDwTable {
   uint32_t v[4 * OR_WTD * 2];
 };
@@ -430,8 +456,9 @@ constexpr DiscWeightDwTable make_disc_weight_dw_table() {
   DiscWeightDwTable r{};
   for (int e = 0; e < 4 * OR_WTD; ++e) {
     const int a = e / OR_WTD, d = e - a * OR_WTD - 3;
-    if (d < 0 || d >= OR_ROWS * 4 * OR_PC) continue;
-    const int row = d / (4 * OR_PC), col = d - row * (4 * OR_PC);
+    if (d < 0 || d >= OR_WROW * OR_WFOLD) continue;
+    const int row = d / OR_WROW, col = d - row * OR_WROW;
+    if (col >= 4 * OR_PC) continue;   // the pad
     const DiscDwordWeight w = disc_dword_weight(row - OR_R, 4 * col - a - OR_R);
     r.v[2 * e] = w.moment;
     r.v[2 * e + 1] = w.count;
@@ -442,13 +469,14 @@ __device__ __attribute__((aligned(128))) const DiscWeightDwTable g_disc_weight_d
 constexpr bool disc_weight_dw_table_matches() {   // every dword of every piece at all 16 alignments weighs as the definition says
   constexpr DiscWeightDwTable dw = make_disc_weight_dw_table();
   for (int sh = 0; sh < 16; ++sh)
-    for (int q = 0; q < 3 * 64 - OR_NP; ++q)
-      for (int d = 0; d < 4; ++d) {
-        const int e = (sh & 3) * OR_WTD + 4 * q + d + 3 - (sh >> 2);
-        const int r = q / OR_PC, c = q - r * OR_PC;
-        const DiscDwordWeight w = disc_dword_weight(r - OR_R, 16 * c + 4 * d - sh - OR_R);   // 0 for the rows past the patch
-        if (dw.v[2 * e] != w.moment || dw.v[2 * e + 1] != w.count) return false;
-      }
+    for (int r = 0; r < OR_ROWS; ++r)
+      for (int c = 0; c < OR_PC; ++c)
+        for (int d = 0; d < 4; ++d) {
+          const int e = (sh & 3) * OR_WTD + disc_weight_entry(r, c) + d + 3 - (sh >> 2);
+          if (e < 0 || e >= 4 * OR_WTD) return false;
+          const DiscDwordWeight w = disc_dword_weight(r - OR_R, 16 * c + 4 * d - sh - OR_R);
+          if (dw.v[2 * e] != w.moment || dw.v[2 * e + 1] != w.count) return false;
+        }
   return true;
 }
 static_assert(disc_weight_dw_table_matches(), "DiscWeightDwTable must weigh every dword as disc_dword_weight");
@@ -456,7 +484,7 @@ static_assert(disc_weight_dw_table_matches(), "DiscWeightDwTable must weigh ever
 // What orient_rbrief_kernel takes from the plane layout.  Row-major planes: patch rows start on the dword boundary below
 // x - radius (4 alignments; EXACT: at x - radius itself).  Block-tiled planes: on the 16-byte boundary below it (16
 // alignments) and are read as whole 16-byte block rows: three per row of the centroid patch (31 + 15 <= 48 bytes), three
-// per row of the descriptor patch and one dword more where its 37 + a bytes pass 48 (TiledBriefRegs); its rows take 64
+// per row of the descriptor patch and one dword more where its 37 + a bytes pass 48 (TiledBriefRegs); its rows take 80
 // bytes in LDS.
 template <bool TILED, bool EXACT = false> struct OrGeom {
   static constexpr int ALIGN = 4, BR_DW = ::BR_DW;
@@ -481,7 +509,10 @@ template <bool EXACT> struct OrGeom<true, EXACT> {
   // 7 waves per SIMD: <= 72 VGPRs (phase A keeps the centroid patches of ONE pair of keypoints in flight, 12 data registers;
   // the bin directions are loaded after phase A's patches, 8 registers fewer while they are in flight) and <= 23,405 B of
   // LDS (the weights per dword; ONE descriptor patch buffer per wave -- the ballots of keypoint k have consumed its patch
-  // bytes before the patch of k + 1 is stored).  tests/test_orient_resources.py holds these figures.
+  // bytes before the patch of k + 1 is stored).  tests/test_orient_resources.py holds these figures.  The kernel uses
+  // 18,720 B: 6,880 of weights (4 alignments x 215 entries: 16 folded rows of 13) and 4 x 37 x 80 of patch buffers; it was
+  // bound by the LDS array's cycles, not by this budget, and both layouts are chosen for the banks (DiscWeightDwTable,
+  // TiledBriefRegs).  18,720 B and the 63 registers the compiler then takes would admit 8 waves; VUS_OR_WPE_TILED_MAX says no.
   static constexpr int GRP = 1, BLUR_BUF = 1;   // GRP counts loader objects: one TiledDiscPair
   static constexpr bool BINS_AFTER_PHASE_A = true;
   typedef TiledDiscPair Disc;
@@ -498,8 +529,8 @@ template <bool EXACT> struct OrGeom<true, EXACT> {
     int mx[3], my[3];
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
-      // the weights stay laid out by 3 r + c, whatever slot the piece was dealt to
-      const int e = (u == 0 ? ea : u == 2 ? eb : second ? eb : ea) + 4 * pr.weight_index(u);
+      // the weights are laid out by the piece's row and column (disc_weight_entry), whatever slot the piece was dealt to
+      const int e = (u == 0 ? ea : u == 2 ? eb : second ? eb : ea) + pr.weight_entry(u);
       const uint2* wd = reinterpret_cast<const uint2*>(s_w) + e;
       const uint32_t d[4] = {pr.v[u].x, pr.v[u].y, pr.v[u].z, pr.v[u].w};
       uint32_t sx = 0, rs = 0;
@@ -520,6 +551,8 @@ template <bool EXACT> struct OrGeom<true, EXACT> {
 };
 static_assert(2 * OR_R + 1 + 15 <= 16 * OR_PC && 2 * BR_R + 1 + 11 <= 48 && 2 * BR_R + 1 + 15 <= 52 && 52 <= 4 * BR_DW_TILED,
               "tiled patch rows: 16-byte aligned starts; descriptor rows of 48 bytes for a <= 11, 52 beyond");
+static_assert(BR_DW_TILED % 4 == 0 && (BR_ROWS - 1) * 4 * BR_DW_TILED + 52 < (1 << 15),
+              "descriptor patch in LDS: rows of whole uint4, every byte offset an int16 of g_rot_off_table_tiled");
 static_assert(sizeof(DiscWeightDwTable) == 16 * OrGeom<true>::WT_VEC4, "LDS copy of the tiled weights: whole uint4");
 
 // One workgroup per image: the image's keypoints counting-sorted by 64 x 64-pixel cell (cells in raster order; inside a
@@ -608,9 +641,9 @@ namespace {
 // TILED: img and blur are block-tiled planes (include/vus_tiled.h, pitch = W).  OrGeom carries every difference: the
 // patch loaders (which lane holds which 16-byte piece: disc_piece, brief_piece -- neighbouring lanes, neighbouring rows of
 // one 128-byte line), the weight and test-offset tables, the patches in flight.  Phase B's LDS patch stays row-major
-// (64-byte rows), so the ballots are those of the plain form.
+// (80-byte rows), so the ballots are those of the plain form.
 template <bool EXACT, bool ORDERED, bool TILED>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS_OR_WPE_TILED : VUS_OR_WPE, 8))) void orient_rbrief_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TILED ? VUS_OR_WPE_TILED : VUS_OR_WPE, TILED ? VUS_OR_WPE_TILED_MAX : 8))) void orient_rbrief_kernel(
     const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int H, int W, int pitch,
     const uint32_t* __restrict__ kp_keys, const int* __restrict__ kp_count, int max_kp, const int* __restrict__ order,
     uint64_t* __restrict__ desc_out, uint8_t* __restrict__ angle_out, int n_img, int chunks_per_img) {
