@@ -181,7 +181,13 @@ int vus_pyramid_append(const uint32_t* lvl_keys, const int* lvl_count, const uin
  * among those passing the gates  |yq - yt| <= max_dy  (max_dy < 0: no gate)  and
  * min_disp <= xq - xt <= max_disp  (only when max_dy >= 0); ties -> lowest train index.
  * No gated candidate -> idx -1, dist 512; best distance > max_dist -> idx -1, dist = that distance.
- * idx_out / dist_out: int32 [n_pairs, max_kp]. */
+ * idx_out / dist_out: int32 [n_pairs, max_kp]; every slot of every pair is written, n_pairs <= 65535.
+ * Counts: a list has min(max(kp_count, 0), max_kp) live slots, whichever kernel serves the call; a query slot past them
+ * gets idx -1, dist 512, and no returned index reaches the train list's live count.
+ * Invalid keys: under a gate (max_dy >= 0) a keypoint whose position  key & VUS_KEY_POS_MASK  is H * W or more
+ * (VUS_KEY_INVALID is one; vus_select_topk can leave such keys in the counted part of an overflowed list) takes no part,
+ * the rule of vus_select_grid: as a query it gets idx -1, dist 512, as a train keypoint it is no candidate of any query.
+ * Without a gate (max_dy < 0) positions are not read, and such a slot matches by its descriptor like any other. */
 int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, const int* kp_count,
                       int max_kp, int H, int W, const int* q_index, const int* t_index, int n_pairs,
                       int max_dy, int min_disp, int max_disp, int max_dist,

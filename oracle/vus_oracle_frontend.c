@@ -467,17 +467,20 @@ int vus_hamming_match_cpu(const uint64_t* desc, const uint32_t* kp_keys, const i
     const uint64_t* dt = desc + (size_t)ti * max_kp * 4;
     const uint32_t* kq = kp_keys + (size_t)qi * max_kp;
     const uint32_t* kt = kp_keys + (size_t)ti * max_kp;
+    /* include/vus.h: counts are clamped to [0, max_kp]; under a gate a keypoint at or beyond H * W takes no part */
+    const int nq = kp_count[qi] < max_kp ? kp_count[qi] : max_kp;
+    const int nt = kp_count[ti] < max_kp ? kp_count[ti] : max_kp;
     for (int i = 0; i < max_kp; ++i) {
       int best = 1 << 20, bidx = -1;
-      if (i < kp_count[qi]) {
-        uint32_t pq = kq[i] & VUS_KEY_POS_MASK;
-        int yq = (int)(pq / (uint32_t)W), xq = (int)(pq % (uint32_t)W);
-        for (int j = 0; j < kp_count[ti]; ++j) {
+      uint32_t pq = i < nq ? kq[i] & VUS_KEY_POS_MASK : 0;
+      int yq = (int)(pq / (uint32_t)W), xq = (int)(pq % (uint32_t)W);
+      if (i < nq && !(max_dy >= 0 && yq >= H)) {
+        for (int j = 0; j < nt; ++j) {
           if (max_dy >= 0) {
             uint32_t pt = kt[j] & VUS_KEY_POS_MASK;
             int yt = (int)(pt / (uint32_t)W), xt = (int)(pt % (uint32_t)W);
             int dy = yq - yt, dx = xq - xt;
-            if (dy > max_dy || dy < -max_dy || dx < min_disp || dx > max_disp) continue;
+            if (yt >= H || dy > max_dy || dy < -max_dy || dx < min_disp || dx > max_disp) continue;
           }
           int dist = 0;
           for (int w = 0; w < 4; ++w) dist += __builtin_popcountll(dq[4 * i + w] ^ dt[4 * j + w]);

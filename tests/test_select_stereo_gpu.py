@@ -148,10 +148,10 @@ def _gpu_match(desc, kp, kc, H, W, q, t, gate):
 
 
 def _check_match(oracle, desc, kp, kc, H, W, q, t, gate):
-    """gate = (max_dy, min_disp, max_disp, max_dist).  The oracle takes the counts clamped to max_kp (the documented
-    behaviour of the library; the oracle itself does not clamp)."""
+    """gate = (max_dy, min_disp, max_disp, max_dist).  Library and oracle both clamp the counts to max_kp (include/vus.h),
+    so the oracle takes them as they are."""
     idx, dist = _gpu_match(desc, kp, kc, H, W, q, t, gate)
-    eidx, edist = oracle.hamming_match(desc, kp, np.minimum(np.asarray(kc, np.int32), kp.shape[1]), W, q, t, *gate, H=H)
+    eidx, edist = oracle.hamming_match(desc, kp, np.asarray(kc, np.int32), W, q, t, *gate, H=H)
     assert np.array_equal(idx, eidx)
     assert np.array_equal(dist, edist)
     return eidx, edist

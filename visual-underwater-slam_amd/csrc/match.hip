@@ -19,7 +19,7 @@ constexpr int MT = VUS_MT;  // train tile
 template <bool GATE>
 __global__ __launch_bounds__(256) void hamming_match_kernel(
     const uint64_t* __restrict__ desc, const uint32_t* __restrict__ kp_keys,
-    const int* __restrict__ kp_count, int max_kp, int W, const int* __restrict__ q_index,
+    const int* __restrict__ kp_count, int max_kp, int W, int Hrows, const int* __restrict__ q_index,
     const int* __restrict__ t_index, int max_dy, int min_disp, int max_disp, int max_dist,
     int32_t* __restrict__ idx_out, int32_t* __restrict__ dist_out) {
   __shared__ uint64_t s_desc[MT * 4];
@@ -29,15 +29,18 @@ __global__ __launch_bounds__(256) void hamming_match_kernel(
   const int qi = q_index[p], ti = t_index[p];
   const int i = blockIdx.x * 256 + tid;
   const int nq = min(kp_count[qi], max_kp), nt = min(kp_count[ti], max_kp);   // a count above max_kp is clamped
-  const bool active = i < nq;
+  bool active = i < nq;
   uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
   int yq = 0, xq = 0;
   if (active) {
     const uint64_t* dq = desc + ((size_t)qi * max_kp + i) * 4;
     q0 = dq[0]; q1 = dq[1]; q2 = dq[2]; q3 = dq[3];
-    uint32_t pq = kp_keys[(size_t)qi * max_kp + i] & VUS_KEY_POS_MASK;
-    yq = (int)(pq / (uint32_t)W);
-    xq = (int)(pq - (uint32_t)yq * (uint32_t)W);
+    if (GATE) {   // without a gate the positions are not read
+      uint32_t pq = kp_keys[(size_t)qi * max_kp + i] & VUS_KEY_POS_MASK;
+      yq = (int)(pq / (uint32_t)W);
+      xq = (int)(pq - (uint32_t)yq * (uint32_t)W);
+      active = yq < Hrows;   // a query outside the image takes no part
+    }
   }
   int best = 1 << 20, bidx = -1;
   const uint64_t* dt = desc + (size_t)ti * max_kp * 4;
@@ -46,10 +49,13 @@ __global__ __launch_bounds__(256) void hamming_match_kernel(
     const int tn = min(MT, nt - t0);
     __syncthreads();
     for (int k = tid; k < tn * 4; k += 256) s_desc[k] = dt[(size_t)t0 * 4 + k];
-    for (int k = tid; k < tn; k += 256) {
-      uint32_t pt = kt[t0 + k] & VUS_KEY_POS_MASK;
-      int yt = (int)(pt / (uint32_t)W);
-      s_xy[k] = (yt << 16) | (int)(pt - (uint32_t)yt * (uint32_t)W);
+    if (GATE) {
+      for (int k = tid; k < tn; k += 256) {
+        uint32_t pt = kt[t0 + k] & VUS_KEY_POS_MASK;
+        int yt = (int)(pt / (uint32_t)W);
+        // a train keypoint outside the image fails the gate: -1 is no (y, x) of a row below Hrows <= 65535
+        s_xy[k] = yt < Hrows ? (yt << 16) | (int)(pt - (uint32_t)yt * (uint32_t)W) : -1;
+      }
     }
     __syncthreads();
     if (active) {
@@ -60,7 +66,7 @@ __global__ __launch_bounds__(256) void hamming_match_kernel(
         if (GATE) {
           int xy = s_xy[j];
           int dy = yq - (int)((unsigned)xy >> 16), dx = xq - (xy & 0xFFFF);
-          ok = dy <= max_dy && dy >= -max_dy && dx >= min_disp && dx <= max_disp;
+          ok = xy != -1 && dy <= max_dy && dy >= -max_dy && dx >= min_disp && dx <= max_disp;
         }
         if (ok && dist < best) { best = dist; bidx = t0 + j; }
       }
@@ -100,11 +106,14 @@ __global__ __launch_bounds__(256) void hamming_match_rows_gather_kernel(
   const uint32_t* kt = kp_keys + (size_t)ti * max_kp;
   for (int r = tid; r <= Hrows; r += 256) s_start[r] = 0;
   __syncthreads();
+  // a train keypoint outside the image (row >= Hrows: VUS_KEY_INVALID is one) is in no bucket; s_xy = -1 tells the
+  // placing pass below to skip it as well ((y << 16) | x >= 0: the index table only fits into LDS for Hrows < 12288)
   for (int j = tid; j < nt; j += 256) {
     const uint32_t pt = kt[j] & VUS_KEY_POS_MASK;
-    const int yt = min((int)(pt / (uint32_t)W), Hrows - 1);
-    s_xy[j] = (yt << 16) | (int)(pt - (uint32_t)(pt / (uint32_t)W) * (uint32_t)W);
-    atomicAdd(&s_start[yt + 1], 1);
+    const int yt = (int)(pt / (uint32_t)W);
+    const bool inside = yt < Hrows;
+    s_xy[j] = inside ? (yt << 16) | (int)(pt - (uint32_t)yt * (uint32_t)W) : -1;
+    if (inside) atomicAdd(&s_start[yt + 1], 1);
   }
   __syncthreads();
   // inclusive scan of s_start[1..Hrows] (counts) -> row starts; 256 threads, chunked
@@ -128,7 +137,8 @@ __global__ __launch_bounds__(256) void hamming_match_rows_gather_kernel(
   __syncthreads();
   for (int r = tid; r < Hrows; r += 256) s_cursor[r] = s_start[r];
   __syncthreads();
-  for (int j = tid; j < nt; j += 256) s_list[atomicAdd(&s_cursor[s_xy[j] >> 16], 1)] = j;
+  for (int j = tid; j < nt; j += 256)
+    if (s_xy[j] >= 0) s_list[atomicAdd(&s_cursor[s_xy[j] >> 16], 1)] = j;
   __syncthreads();
 
   int best = 1 << 20, bidx = -1;
@@ -139,7 +149,7 @@ __global__ __launch_bounds__(256) void hamming_match_rows_gather_kernel(
     const int yq = (int)(pq / (uint32_t)W), xq = (int)(pq - (uint32_t)yq * (uint32_t)W);
     const int r0 = max(0, yq - max_dy), r1 = min(Hrows - 1, yq + max_dy);
     const uint64_t* dt = desc + (size_t)ti * max_kp * 4;
-    if (r0 <= r1) {
+    if (yq < Hrows && r0 <= r1) {   // a query outside the image visits nothing
       for (int c = s_start[r0]; c < s_start[r1 + 1]; ++c) {
         const int j = s_list[c];
         const int dx = xq - (s_xy[j] & 0xFFFF);
@@ -191,19 +201,24 @@ __global__ __launch_bounds__(HR_THREADS) void hamming_match_rows_kernel(
   for (int r = tid; r <= Hrows; r += T) s_start[r] = 0;
   __syncthreads();
   // this thread's train keypoints: row count, and the descriptor on its way while the rows are scanned
+  // t_yx stays -1 for a slot past the count and for a train keypoint outside the image (row >= Hrows: VUS_KEY_INVALID
+  // is one), which is in no bucket: the placing pass below skips exactly these ((y << 16) | x >= 0: the train set only
+  // fits into LDS for Hrows < 12288)
   int t_yx[HR_PER];
   uint64_t t_d[HR_PER][4];
 #pragma unroll
   for (int u = 0; u < HR_PER; ++u) {
     const int j = tid + u * T;
+    t_yx[u] = -1;
     if (j < nt) {
       const uint32_t pt = kt[j] & VUS_KEY_POS_MASK;
       const uint32_t yt = pt / (uint32_t)W;
-      const int yc = min((int)yt, Hrows - 1);
-      t_yx[u] = (yc << 16) | (int)(pt - yt * (uint32_t)W);
+      if (yt < (uint32_t)Hrows) {
+        t_yx[u] = (int)(yt << 16) | (int)(pt - yt * (uint32_t)W);
 #pragma unroll
-      for (int w = 0; w < 4; ++w) t_d[u][w] = dt[(size_t)j * 4 + w];
-      atomicAdd(&s_start[yc + 1], 1);
+        for (int w = 0; w < 4; ++w) t_d[u][w] = dt[(size_t)j * 4 + w];
+        atomicAdd(&s_start[yt + 1], 1);
+      }
     }
   }
   __syncthreads();
@@ -229,7 +244,7 @@ __global__ __launch_bounds__(HR_THREADS) void hamming_match_rows_kernel(
 #pragma unroll
   for (int u = 0; u < HR_PER; ++u) {
     const int j = tid + u * T;
-    if (j < nt) {
+    if (t_yx[u] >= 0) {
       const int c = atomicAdd(&s_cursor[t_yx[u] >> 16], 1);
       s_xi[c] = (uint32_t)(t_yx[u] & 0xFFFF) | ((uint32_t)j << 16);
       s_desc[2 * c] = make_uint4((uint32_t)t_d[u][0], (uint32_t)(t_d[u][0] >> 32), (uint32_t)t_d[u][1], (uint32_t)(t_d[u][1] >> 32));
@@ -246,7 +261,7 @@ __global__ __launch_bounds__(HR_THREADS) void hamming_match_rows_kernel(
       const uint32_t pq = kp_keys[(size_t)qi * max_kp + i] & VUS_KEY_POS_MASK;
       const int yq = (int)(pq / (uint32_t)W), xq = (int)(pq - (uint32_t)yq * (uint32_t)W);
       const int r0 = max(0, yq - max_dy), r1 = min(Hrows - 1, yq + max_dy);
-      if (r0 <= r1) {
+      if (yq < Hrows && r0 <= r1) {   // a query outside the image visits nothing
         const int c_end = s_start[r1 + 1];
         for (int c = s_start[r0]; c < c_end; ++c) {
           const uint32_t xi = s_xi[c];
@@ -324,11 +339,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void h
   const int r = lane & 31, h = lane >> 5;
   const int p = blockIdx.y;
   const int qi = q_index[p], ti = t_index[p];
-  const int nq = kp_count[qi];
+  const int nq = min(max(kp_count[qi], 0), max_kp);          // counts are clamped to [0, max_kp] as on every other path
   const int wq0 = blockIdx.x * HM_QWG + 32 * HM_QT * wave;   // first query of this wave
   const int q0 = wq0 + r;                                     // column tile c holds query q0 + 32 c
   // a workgroup without queries skips the trains; a wave without queries only helps expand them
-  const int nt = blockIdx.x * HM_QWG < nq ? kp_count[ti] : 0;
+  const int nt = blockIdx.x * HM_QWG < nq ? min(max(kp_count[ti], 0), max_kp) : 0;
   const bool wave_busy = wq0 < nq;
   // B fragments: MFMA ks, lane half h <-> descriptor word 2 ks + h
   v4i_t bq[HM_QT][4];
@@ -431,6 +446,9 @@ extern "C" int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, 
   VUS_REQUIRE(max_kp >= 1 && W >= 1 && W < 65536 && H >= 1 && H < 65536, "max_kp=%d H=%d W=%d", max_kp, H, W);
   VUS_REQUIRE(n_pairs >= 0 && n_pairs <= 65535, "n_pairs=%d out of range [0, 65535]", n_pairs);
   if (n_pairs == 0) return VUS_OK;
+  // two keypoints inside the image lie fewer than H <= 65535 rows apart, so a wider gate admits the same pairs; the
+  // rows kernels compute yq + max_dy in int
+  max_dy = std::min(max_dy, 65535);
   dim3 grid((max_kp + 255) / 256, n_pairs);
   const int h_rows = H;   // the gated kernels bucket the train keypoints by image row
   const size_t lds_all = hamming_rows_lds(max_kp, h_rows);                                     // train set resident in LDS
@@ -453,13 +471,13 @@ extern "C" int vus_hamming_match(const uint64_t* desc, const uint32_t* kp_keys, 
   } else {
     if (max_dy >= 0)
       hamming_match_kernel<true><<<grid, 256, 0, vus::as_stream(stream)>>>(
-          desc, kp_keys, kp_count, max_kp, W, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out, dist_out);
+          desc, kp_keys, kp_count, max_kp, W, h_rows, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out, dist_out);
     else if (max_kp <= 65535)   // ungated: FP4 GEMM formulation on the matrix cores
       hamming_match_mfma_kernel<<<dim3((max_kp + HM_QWG - 1) / HM_QWG, n_pairs), 256, 0, vus::as_stream(stream)>>>(
           reinterpret_cast<const uint32_t*>(desc), kp_count, max_kp, q_index, t_index, max_dist, idx_out, dist_out);
     else
       hamming_match_kernel<false><<<grid, 256, 0, vus::as_stream(stream)>>>(
-          desc, kp_keys, kp_count, max_kp, W, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out, dist_out);
+          desc, kp_keys, kp_count, max_kp, W, h_rows, q_index, t_index, max_dy, min_disp, max_disp, max_dist, idx_out, dist_out);
   }
   VUS_CHECK_LAUNCH("hamming_match");
   return VUS_OK;
