@@ -601,4 +601,9 @@ long long vus_ba_work_doubles(const vus_ba_problem* P);
  * marginalisation of the head of the reduced camera system that forms such a prior. */
 #include "vus_fixed_lag.h"
 #include "vus_fixed_lag_nav.h"
+
+/* gtsam.CombinedImuFactor in the per-keyframe-bias layout: the IMU measurement and the bias walk of one interval under
+ * one 15 x 15 covariance -- vus_imu_preintegrate_combined, vus_cimu_factors and vus_cimu_linearize / _assemble /
+ * _eval_step / _error. */
+#include "vus_combined_imu.h"
 #endif /* VUS_H */

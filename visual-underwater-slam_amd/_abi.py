@@ -1,9 +1,12 @@
 """The C ABI as ctypes, read from the headers: include/vus.h and every include/vus_*.h (but the generated tables of
 vus_orb_tables.h).  One parse per process, on first use.  A declaration this reader cannot read is an error, never a guess.
 
-Two parts.  abi() is the ABI as it stood when its size was pinned (tests/test_abi_reader.py counts its structs and functions);
-addenda() is what the headers named in ADDENDA have added since, read in the same way; whole() is both, and is what the
-binding (_lib.py), struct() and const() use.  A new header goes into ADDENDA and needs nothing else here."""
+Three parts.  abi() is the ABI as it stood when its size was pinned (tests/test_abi_reader.py counts its structs and functions);
+addenda() is what the headers named in ADDENDA added next, read in the same way, and whole() is both -- pinned in turn by
+tests/test_fixed_lag_nav_abi.py; supplements() is what the headers named in SUPPLEMENTS have added since.  full() is all
+three, and is what the binding (_lib.py), struct() and const() use.  A new header goes into SUPPLEMENTS and needs nothing
+else here -- as long as no test pins the size of full(): the sizes are pinned per UNION today (abi(), then whole()), which
+is why there are three parts and not one.  Pinning them per header instead would let the parts fold back into one list."""
 import ctypes
 import functools
 import glob
@@ -13,6 +16,9 @@ from collections import namedtuple
 
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 ADDENDA = ("vus_fixed_lag_nav.h",)      # headers that joined after the pinned census, in reading order
+# headers that joined after the size of whole() was pinned as well (tests/test_fixed_lag_nav_abi.py counts it): read in the
+# same way on top of whole(); full() is everything.  A new header goes HERE and needs nothing else
+SUPPLEMENTS = ("vus_combined_imu.h",)
 
 SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "long long": ctypes.c_longlong,
            "unsigned long long": ctypes.c_ulonglong, "double": ctypes.c_double, "float": ctypes.c_float,
@@ -95,7 +101,7 @@ def abi():
     """The pinned part of the ABI (every header but ADDENDA); the headers are read the first time this is called."""
     if not os.path.isdir(INCLUDE_DIR):
         raise ImportError(f"{INCLUDE_DIR} is missing: the Python binding reads the C ABI from the headers there")
-    paths = [p for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "vus*.h"))) if os.path.basename(p) not in ("vus_orb_tables.h",) + ADDENDA]
+    paths = [p for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "vus*.h"))) if os.path.basename(p) not in ("vus_orb_tables.h",) + ADDENDA + SUPPLEMENTS]
     whole = Abi({}, {}, {})
     for path in paths:                  # vus.h sorts first
         with open(path) as f:
@@ -105,12 +111,10 @@ def abi():
     return whole
 
 
-@functools.lru_cache(maxsize=None)
-def addenda():
-    """What the headers of ADDENDA declare; a name abi() already holds is an error."""
-    base = abi()
+def _read_after(base, names):
+    """What the headers `names` declare on top of `base`; a name `base` already holds is an error."""
     new = Abi({}, {}, {})
-    for name in ADDENDA:
+    for name in names:
         path = os.path.join(INCLUDE_DIR, name)
         known = {**base.constants, **new.constants}
         with open(path) as f:
@@ -126,15 +130,33 @@ def addenda():
 
 
 @functools.lru_cache(maxsize=None)
+def addenda():
+    """What the headers of ADDENDA declare; a name abi() already holds is an error."""
+    return _read_after(abi(), ADDENDA)
+
+
+@functools.lru_cache(maxsize=None)
 def whole():
-    """abi() and addenda() together: what the library exports and the binding binds."""
+    """abi() and addenda() together."""
     return Abi(*({**a, **b} for a, b in zip(abi(), addenda())))
 
 
+@functools.lru_cache(maxsize=None)
+def supplements():
+    """What the headers of SUPPLEMENTS declare; a name whole() already holds is an error."""
+    return _read_after(whole(), SUPPLEMENTS)
+
+
+@functools.lru_cache(maxsize=None)
+def full():
+    """whole() and supplements() together: what the library exports and the binding binds."""
+    return Abi(*({**a, **b} for a, b in zip(whole(), supplements())))
+
+
 def const(name):
-    return whole().constants[name]
+    return full().constants[name]
 
 
 def struct(name):
     """A ctypes.Structure class with the layout of the header's `typedef struct { ... } name;`."""
-    return type(name, (ctypes.Structure,), {"_fields_": list(whole().structs[name])})
+    return type(name, (ctypes.Structure,), {"_fields_": list(full().structs[name])})

@@ -10,7 +10,8 @@ LIB_PATH = os.environ.get("VUS_HIP_LIB") or os.path.join(_HERE, "csrc", "libvus_
 
 # name -> argtypes of every function the headers declare (include/vus.h and the vus_*.h it includes; _abi reads them)
 SIGNATURES = {name: argtypes for name, (_, argtypes) in _abi.abi().functions.items()}
-# the same for the headers of _abi.ADDENDA (what joined after the size of the table above was pinned); load() binds both
+# the same for the headers of _abi.ADDENDA (what joined after the size of the table above was pinned); load() binds both and
+# what _abi.SUPPLEMENTS names (_abi.full())
 ADDENDA_SIGNATURES = {name: argtypes for name, (_, argtypes) in _abi.addenda().functions.items()}
 
 TUNE_BAND_MODE, TUNE_CB_MAX_WG, TUNE_LAST_BAND_MODE, TUNE_WIN_FAULT = (
@@ -38,7 +39,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C visual-underwater-slam_amd/csrc`. There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _abi.whole().functions.items():
+    for name, (restype, argtypes) in _abi.full().functions.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library disagree
         fn.argtypes = argtypes
         fn.restype = restype

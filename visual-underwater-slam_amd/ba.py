@@ -34,6 +34,7 @@ _CWindowPrior = _abi.struct("vus_window_prior")
 _CNavWindowPrior = _abi.struct("vus_nav_window_prior")
 _CNav = _abi.struct("vus_nav_factors")
 _CNavBias = _abi.struct("vus_navb_factors")         # the fields of vus_nav_factors, then the bias factors
+_CCombinedImu = _abi.struct("vus_cimu_factors")
 
 # VUS_LOSS_* of include/vus_robust.h: robust noise models of the stereo factors (GTSAM mEstimator, Block reweighting)
 LOSS_KINDS = {k: _abi.const("VUS_LOSS_" + k.upper())
@@ -555,11 +556,13 @@ class StereoBAProblem:
     `mono`: a bool / uint8 array per INPUT observation, nonzero = a monocular GenericProjectionFactor (include/vus_mono.h)
     whose `meas` row is (u, ignored, v) -- the middle slot is never used -- with the calibration `mono_K` = (fx, fy, skew,
     cx, cy) and the sigma `mono_sigma` of all of them.  K and sigma keep serving the stereo rows and are required even when
-    every observation is mono.  None or all zero = a stereo-only problem, which calls the entry points it called before."""
+    every observation is mono.  None or all zero = a stereo-only problem, which calls the entry points it called before.
+    `combined_imu` (pose_stride 3 only): the graph holds CombinedImuFactors, whose joint whitening couples B(i+1) with X(i),
+    five nodes apart: the node band is then at least min(5, n_nodes - 1) instead of 4."""
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None,
                  prior_T=None, prior_sigmas=None, device="cuda:0", band=None, pose_stride=1, loss=None, between_span=0,
-                 body_P_sensor=None, mono=None, mono_K=None, mono_sigma=None):
+                 body_P_sensor=None, mono=None, mono_K=None, mono_sigma=None, combined_imu=False):
         _lib.require_gpu()
         _lib.load()
         dev = torch.device(device)
@@ -582,10 +585,13 @@ class StereoBAProblem:
         if self.pose_stride == 2:       # node layout with velocity nodes: pose blocks are 2 nodes apart,
             # inertial factors reach 3 nodes back, but no further than the graph's first node (a single keyframe: 1)
             st["band"] = min(max(self.pose_stride * st["band"], 3), self.n_nodes - 1)
-        elif self.pose_stride == 3:     # velocity and bias nodes (NavBiasBASolver): an ImuFactor reaches 4 nodes back
-            st["band"] = min(max(self.pose_stride * st["band"], 4), self.n_nodes - 1)
+        elif self.pose_stride == 3:     # velocity and bias nodes (NavBiasBASolver): an ImuFactor reaches 4 nodes back,
+            # a CombinedImuFactor 5 (B(i+1) against X(i))
+            st["band"] = min(max(self.pose_stride * st["band"], 5 if combined_imu else 4), self.n_nodes - 1)
         elif self.pose_stride > 3:
             raise ValueError(f"pose_stride={self.pose_stride}: 1, 2 or 3")
+        if combined_imu and self.pose_stride != 3:
+            raise ValueError(f"combined_imu=True needs pose_stride=3 (the per-keyframe-bias layout), not {self.pose_stride}")
         if band is not None:            # landmark-sharded solve: every rank allocates the global band
             if band < st["band"]:
                 raise ValueError(f"band={band} is smaller than this problem's own band {st['band']}")
@@ -1486,13 +1492,61 @@ class NavBiasFactors(_InertialFactors):
         self.c = _CNavBias(*self._c_prefix, self.bb_i.numel(), pp(self.bb_i), pp(self.bb_j), pp(self.bb_meas),
                            pp(self.bb_w), self.bp_idx.numel(), pp(self.bp_idx), pp(self.bp_mean), pp(self.bp_w))
 
-    def unconstrained_biases(self, n_poses):
-        """Biases with neither a prior nor a between-factor: their information comes from ImuFactors alone, if any."""
+    def unconstrained_biases(self, n_poses, combined=None):
+        """Biases with neither a prior, a between-factor nor a CombinedImuFactor of `combined` (whose rows 9..14 tie B(i) to
+        B(i+1) as a between-factor does): their information comes from ImuFactors alone, if any."""
         seen = np.zeros(n_poses, bool)
         bb_i, bp_idx = self.bb_i.cpu().numpy().astype(np.int64), self.bp_idx.cpu().numpy().astype(np.int64)
-        for a in (bb_i, bb_i + 1, bp_idx):
+        ci = combined.host["i"] if combined is not None else np.zeros(0, np.int64)
+        for a in (bb_i, bb_i + 1, bp_idx, ci, ci + 1):
             seen[a[(a >= 0) & (a < n_poses)]] = True
         return np.nonzero(~seen)[0]
+
+
+class CombinedImuFactors:
+    """Device-resident vus_cimu_factors (include/vus_combined_imu.h): CombinedImuFactor(X(i), V(i), X(i+1), V(i+1), B(i),
+    B(i+1)) for the keyframes `i` [n], with pim [n, 148] the preintegration records and W [n, 225] the 15 x 15 whitening
+    matrices (gtsam/imu.py CombinedPreintegrator.packed() / .whitening()).  `j` (None: i + 1) may name the later keyframes;
+    anything but i + 1 is refused.  An add-on to NavBiasFactors: NavBiasBASolver(problem, nav, combined=...)."""
+
+    def __init__(self, gravity, i, pim, W, device="cuda:0", j=None):
+        i = np.asarray(i, np.int64).reshape(-1)
+        j = i + 1 if j is None else np.asarray(j, np.int64).reshape(-1)
+        pim = np.asarray(pim, np.float64).reshape(-1, 148)
+        W = np.asarray(W, np.float64).reshape(-1, 225)
+        n = len(i)
+        if n == 0 or not (len(j) == len(pim) == len(W) == n):
+            raise ValueError(f"combined IMU factors: {len(i)} / {len(j)} keyframes, {len(pim)} records, {len(W)} whitening matrices")
+        if (j != i + 1).any():
+            f = int(np.nonzero(j != i + 1)[0][0])
+            raise NotImplementedError(f"CombinedImuFactor {f} joins keyframes {int(i[f])} and {int(j[f])}: a CombinedImuFactor "
+                                      "between non-consecutive keyframes is not supported")
+        if (i < 0).any():
+            raise ValueError("combined IMU factors: a negative keyframe index")
+        if not (np.isfinite(pim).all() and np.isfinite(W).all()):
+            raise ValueError("combined IMU factors: pim and W must be finite")
+        self.n = n
+        self.host = dict(i=i, pim=pim, W=W)
+        dev = torch.device(device)
+        self.i, self.j = _upload(i, dev, torch.int32), _upload(j, dev, torch.int32)
+        self.pim, self.W = _upload(pim, dev, torch.float64), _upload(W, dev, torch.float64)
+        p = _lib.ptr
+        self.c = _CCombinedImu(n, p(self.i), p(self.j), p(self.pim), p(self.W), (c_double * 3)(*[float(g) for g in gravity]))
+
+    def addr(self):
+        return ctypes.addressof(self.c)
+
+    def _fits(self, problem):
+        """Refuse a StereoBAProblem this set was not built for (the solver asks before it uses the set)."""
+        if problem.pose_stride != 3:
+            raise ValueError(f"CombinedImuFactors serve pose_stride 3 only (the per-keyframe-bias layout of NavBiasBASolver), "
+                             f"the problem has pose_stride {problem.pose_stride}")
+        if int(self.host["i"].max()) + 1 >= problem.n_poses:
+            raise ValueError(f"CombinedImuFactors: keyframe {int(self.host['i'].max()) + 1} outside the problem's "
+                             f"{problem.n_poses} poses")
+        if problem.band < min(5, problem.n_nodes - 1):
+            raise ValueError(f"a CombinedImuFactor couples nodes 5 apart, more than the problem's band of {problem.band} nodes: "
+                             "build the StereoBAProblem with combined_imu=True")
 
 
 class _InertialBASolver(StereoBASolver):
@@ -1503,7 +1557,7 @@ class _InertialBASolver(StereoBASolver):
     _NEW_STATE = ("new_poses", "new_vels", "new_bias", "new_points")     # state = (poses, vels, bias, points)
 
     def __init__(self, problem: StereoBAProblem, nav, bias_rows, between=None, point_priors=None, pose_meas=None,
-                 window_prior=None):
+                 window_prior=None, more_inertial=()):
         if window_prior is not None and not isinstance(window_prior, NavWindowPrior):
             raise NotImplementedError(f"a dense prior over a pose window (ba.WindowPrior) is not supported by {type(self).__name__}: "
                                       "the family serves the pose-only layout (StereoBASolver)")
@@ -1518,7 +1572,7 @@ class _InertialBASolver(StereoBASolver):
             self.nav_eval_step(*s[:3])
             self.nav_window_prior_eval_step(*s[:3])
         super().__init__(problem, between, point_priors, inertial=[
-            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav_eval)],
+            ("nav_scal", nav3(self.nav_error), nav3(self.nav_linearize), self.nav_assemble, nav_eval), *more_inertial],
             pose_meas=pose_meas, window_prior=window_prior)
         self.N = nav
         dev, nP, nN = problem.device, problem.n_poses, problem.n_nodes
@@ -1551,7 +1605,11 @@ class NavBASolver(_InertialBASolver):
     POSE_STRIDE, SDIAG, _ABI = 2, 4, "vus_nav"
 
     def __init__(self, problem: StereoBAProblem, nav: NavFactors, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None, window_prior=None):
+                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None, window_prior=None,
+                 combined=None):
+        if combined is not None:
+            raise NotImplementedError("CombinedImuFactor (ba.CombinedImuFactors) is not supported by NavBASolver: it ties B(i) to "
+                                      "B(i+1), which the shared-bias layout does not have; use NavBiasBASolver (pose_stride 3)")
         super().__init__(problem, nav, None, between, point_priors, pose_meas, window_prior)
         self.band_rhs = 7
         self._alloc_band_work()
@@ -1624,12 +1682,60 @@ class NavBiasBASolver(_InertialBASolver):
     """LM over poses, velocities, ONE IMU BIAS PER KEYFRAME and landmarks (GTSAM's usual visual-inertial graph).  The
     problem must have been built with pose_stride=3: node 3i = X(i), 3i+1 = V(i) padded to 6, 3i+2 = B(i).  There is no
     border; every lambda trial is one single-right-hand-side band solve (two-sided on long graphs).  optimize() is the
-    common inertial loop, with `bias` the [n_poses, 6] per-keyframe biases."""
+    common inertial loop, with `bias` the [n_poses, 6] per-keyframe biases.
+    `combined`: CombinedImuFactors (include/vus_combined_imu.h) on some or all intervals, one more stage after the inertial
+    one; the problem is then built with combined_imu=True.  Without it nothing this solver launches changes."""
     POSE_STRIDE, SDIAG, _ABI = 3, 5, "vus_navb"
 
     def __init__(self, problem: StereoBAProblem, nav: NavBiasFactors, between: Optional[BetweenFactors] = None,
-                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None, window_prior=None):
-        super().__init__(problem, nav, problem.n_poses, between, point_priors, pose_meas, window_prior)
+                 point_priors: Optional[PointPriors] = None, pose_meas: Optional[PoseMeasurements] = None, window_prior=None,
+                 combined: Optional[CombinedImuFactors] = None):
+        self.CI = combined
+        more = ()
+        if combined is not None:
+            if window_prior is not None:
+                raise NotImplementedError("CombinedImuFactor (ba.CombinedImuFactors) together with a dense prior over an inertial "
+                                          "window (ba.NavWindowPrior) is not supported")
+            combined._fits(problem)
+            nav3 = lambda stage: lambda s: stage(*s[:3])
+            more = [("cimu_scal", nav3(self.cimu_error), nav3(self.cimu_linearize), lambda lam: self.cimu_assemble(),
+                     nav3(self.cimu_eval_step))]
+        super().__init__(problem, nav, problem.n_poses, between, point_priors, pose_meas, window_prior, more_inertial=more)
+        if combined is not None:
+            f64 = dict(dtype=torch.float64, device=problem.device)
+            self.Scimu = torch.empty((problem.n_nodes, 6, 36), **f64)
+            self.gcimu = torch.empty((problem.n_nodes, 6), **f64)
+            self.cimu_err = torch.empty((1,), **f64)
+            self.cimu_work = torch.empty((int(_lib.load().vus_cimu_work_doubles(combined.addr())),), **f64)
+
+    # The CombinedImuFactors (include/vus_combined_imu.h): the stages of the term `cimu_scal`, present only with `combined`.
+    def cimu_error(self, poses, vels, biases) -> float:
+        """Error of the CombinedImuFactors at (poses, vels, biases); 0.0 without them."""
+        if self.CI is None:
+            return 0.0
+        p = _lib.ptr
+        _lib.call("vus_cimu_error", self.CI.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.cimu_err),
+                  p(self.cimu_work), _lib.current_stream_ptr())
+        return float(self.cimu_err[0].item())
+
+    def cimu_linearize(self, poses, vels, biases):
+        """Scimu, gcimu = the factors' blocks and gradient, cimu_scal[0] = their error."""
+        p = _lib.ptr
+        _lib.call("vus_cimu_linearize", self.CI.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.Scimu),
+                  p(self.gcimu), p(self.cimu_scal), p(self.cimu_work), _lib.current_stream_ptr())
+
+    def cimu_assemble(self):
+        """Sband += Scimu, gs += gcimu: after nav_assemble(), which damps the velocity and bias nodes."""
+        p = _lib.ptr
+        _lib.call("vus_cimu_assemble", self.P.n_nodes, self.P.band, p(self.Scimu), p(self.gcimu), p(self.Sband), p(self.gs),
+                  _lib.current_stream_ptr())
+
+    def cimu_eval_step(self, poses, vels, biases):
+        """cimu_scal[1] = linearised error at the step dp, cimu_scal[2] = error at the new state (after nav_eval_step)."""
+        p = _lib.ptr
+        _lib.call("vus_cimu_eval_step", self.CI.addr(), self.P.n_poses, p(poses), p(vels), p(biases), p(self.dp),
+                  p(self.new_poses), p(self.new_vels), p(self.new_bias), p(self.cimu_scal[1:]), p(self.cimu_work),
+                  _lib.current_stream_ptr())
 
     def nav_linearize(self, poses, vels, biases):
         p = _lib.ptr
@@ -1653,7 +1759,7 @@ class NavBiasBASolver(_InertialBASolver):
     def _refuse_free_biases(self, upto):
         """IndeterminantSystem("bias", i) for the first bias B(i), i < upto, with neither a prior, a between-factor nor a place
         in the nav window prior.  A bias that is singular all the same is caught by the factor's pivot test, as a node."""
-        free = self.N.unconstrained_biases(self.P.n_poses)
+        free = self.N.unconstrained_biases(self.P.n_poses, self.CI)
         if self.NWP is not None:
             free = free[(free < self.NWP.first) | (free >= self.NWP.first + self.NWP.m)]
         free = free[free < upto]
@@ -1672,6 +1778,8 @@ class NavBiasBASolver(_InertialBASolver):
         without a prior, a between-factor or a place in this solver's prior, ("point", j) / ("node", i) where the eliminated
         part is not positive definite."""
         self._refuse_long("marginalize_head()")
+        if self.CI is not None:
+            raise NotImplementedError("marginalize_head() with CombinedImuFactors (ba.CombinedImuFactors) is not supported")
         nP, nN, B, k = self.P.n_poses, self.P.n_nodes, self.P.band, int(n_drop)
         if not 1 <= k < nP:
             raise ValueError(f"marginalize_head: n_drop={k} outside [1, n_poses={nP})")

@@ -20,136 +20,9 @@
 #include <cstring>
 #include <vector>
 #include "vus_common.h"
-#include "se3_device.h"   // so3_expmap / so3_logmap: one copy for every pose kernel
+#include "imu_device.h"   // the ImuFactor arithmetic (and through it se3_device.h): one copy for every inertial unit
 
 namespace {
-
-// ---- device math: SO(3) helpers and the ImuFactor residual / Jacobian --------------------------------------------------
-constexpr int PIM_DT = 0, PIM_DR = 1, PIM_DP = 10, PIM_DV = 13, PIM_DR_DBG = 16, PIM_DP_DBA = 25, PIM_DP_DBG = 34,
-              PIM_DV_DBA = 43, PIM_DV_DBG = 52, PIM_BIAS = 61, PIM_N = 148;
-
-__device__ __forceinline__ void skew(const double* w, double* S) {
-  S[0] = 0; S[1] = -w[2]; S[2] = w[1]; S[3] = w[2]; S[4] = 0; S[5] = -w[0]; S[6] = -w[1]; S[7] = w[0]; S[8] = 0;
-}
-__device__ __forceinline__ void mm(const double* A, const double* B, double* C) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
-}
-__device__ __forceinline__ void mtm(const double* A, const double* B, double* C) {   // A^T B
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) C[3 * r + c] = A[r] * B[c] + A[3 + r] * B[3 + c] + A[6 + r] * B[6 + c];
-}
-__device__ __forceinline__ void mv(const double* A, const double* v, double* o) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) o[r] = A[3 * r] * v[0] + A[3 * r + 1] * v[1] + A[3 * r + 2] * v[2];
-}
-__device__ __forceinline__ void mtv(const double* A, const double* v, double* o) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) o[r] = A[r] * v[0] + A[3 + r] * v[1] + A[6 + r] * v[2];
-}
-
-__device__ void so3_jr(const double* w, double* J) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  double W[9], WW[9];
-  skew(w, W); mm(W, W, WW);
-  double a, b;
-  if (th2 < 1e-10) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-  else {   // 1 - cos th as 2 sin^2(th / 2): its cancellation cost eps / th in a W (2e-11 at th = 1e-5)
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    a = 2.0 * sh * sh / th2; b = (th - sin(th)) / (th2 * th);
-  }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * W[i] + b * WW[i];
-}
-__device__ void so3_jr_inv(const double* w, double* J) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  double W[9], WW[9];
-  skew(w, W); mm(W, W, WW);
-  double b;
-  if (th2 < 1e-10) b = 1.0 / 12.0 + th2 / 720.0;
-  else {   // (1 + cos th) / sin th as 1 / tan(th / 2): the quotient lost eps / sin th towards pi
-    const double th = sqrt(th2);
-    b = 1.0 / th2 - 1.0 / (2.0 * th * tan(0.5 * th));
-  }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) J[i] = (i % 4 == 0 ? 1.0 : 0.0) + 0.5 * W[i] + b * WW[i];
-}
-
-// ImuFactor: unwhitened residual r[9] = (theta, p, v) and, when J != nullptr, the Jacobian J[9][24] with
-// columns pose_i(6) vel_i(3) pose_j(6) vel_j(3) bias(6).  Forster et al. 2017 / gtsam ImuFactor.
-__device__ void imu_factor(const double* Ti, const double* vi, const double* Tj, const double* vj, const double* bias,
-                           const double* pim, const double* g, double* r, double* J) {
-  const double dt = pim[PIM_DT];
-  double dba[3], dbg[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { dba[k] = bias[k] - pim[PIM_BIAS + k]; dbg[k] = bias[3 + k] - pim[PIM_BIAS + 3 + k]; }
-  double phi[3], Ephi[9], dRc[9], dPc[3], dVc[3], t3[3], t3b[3];
-  mv(pim + PIM_DR_DBG, dbg, phi);
-  so3_expmap(phi, Ephi);
-  mm(pim + PIM_DR, Ephi, dRc);
-  mv(pim + PIM_DP_DBA, dba, t3); mv(pim + PIM_DP_DBG, dbg, t3b);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) dPc[k] = pim[PIM_DP + k] + t3[k] + t3b[k];
-  mv(pim + PIM_DV_DBA, dba, t3); mv(pim + PIM_DV_DBG, dbg, t3b);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) dVc[k] = pim[PIM_DV + k] + t3[k] + t3b[k];
-  const double* Ri = Ti; const double* pi = Ti + 9;
-  const double* Rj = Tj; const double* pj = Tj + 9;
-  double RjtRi[9], E[9], rR[3];
-  mtm(Rj, Ri, RjtRi);
-  mm(RjtRi, dRc, E);
-  so3_logmap(E, rR);
-  double RidP[3], RidV[3], dpw[3], dvw[3], rP[3], rV[3];
-  mv(Ri, dPc, RidP); mv(Ri, dVc, RidV);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    dpw[k] = pi[k] + vi[k] * dt + 0.5 * g[k] * dt * dt + RidP[k] - pj[k];
-    dvw[k] = vi[k] + g[k] * dt + RidV[k] - vj[k];
-  }
-  mtv(Rj, dpw, rP); mtv(Rj, dvw, rV);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { r[k] = rR[k]; r[3 + k] = rP[k]; r[6 + k] = rV[k]; }
-  if (!J) return;
-  for (int k = 0; k < 9 * 24; ++k) J[k] = 0.0;
-  double JrInv[9], JrInvNeg[9], M[9], M2[9], X[9], JrPhi[9];
-  const double nrR[3] = {-rR[0], -rR[1], -rR[2]};
-  so3_jr_inv(rR, JrInv);
-  so3_jr_inv(nrR, JrInvNeg);
-#define JSET(row0, col0, Mat, sgn)                                                         \
-  for (int a = 0; a < 3; ++a)                                                              \
-    for (int b = 0; b < 3; ++b) J[24 * ((row0) + a) + (col0) + b] = (sgn) * (Mat)[3 * a + b]
-  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[3 * a + b] = dRc[3 * b + a];
-  mm(JrInv, M, M2);
-  JSET(0, 0, M2, 1.0);
-  JSET(0, 9, JrInvNeg, -1.0);
-  so3_jr(phi, JrPhi);
-  mm(JrInv, JrPhi, M); mm(M, pim + PIM_DR_DBG, M2);
-  JSET(0, 21, M2, 1.0);
-  skew(dPc, X); mm(RjtRi, X, M);
-  JSET(3, 0, M, -1.0);
-  JSET(3, 3, RjtRi, 1.0);
-  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[3 * a + b] = Rj[3 * b + a] * dt;
-  JSET(3, 6, M, 1.0);
-  skew(rP, X);
-  JSET(3, 9, X, 1.0);
-  for (int a = 0; a < 3; ++a) J[24 * (3 + a) + 12 + a] = -1.0;
-  mm(RjtRi, pim + PIM_DP_DBA, M); JSET(3, 18, M, 1.0);
-  mm(RjtRi, pim + PIM_DP_DBG, M); JSET(3, 21, M, 1.0);
-  skew(dVc, X); mm(RjtRi, X, M);
-  JSET(6, 0, M, -1.0);
-  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[3 * a + b] = Rj[3 * b + a];
-  JSET(6, 6, M, 1.0);
-  skew(rV, X);
-  JSET(6, 9, X, 1.0);
-  JSET(6, 15, M, -1.0);
-  mm(RjtRi, pim + PIM_DV_DBA, M); JSET(6, 18, M, 1.0);
-  mm(RjtRi, pim + PIM_DV_DBG, M); JSET(6, 21, M, 1.0);
-#undef JSET
-}
 
 // ---- the two node layouts ---------------------------------------------------------------------------------------------
 // ImuFactor columns (pose_i, vel_i, pose_j, vel_j, bias) -> (node, dim); node -1 = the shared-bias border
@@ -832,7 +705,10 @@ inline void expmap_jr(const double* w, double* R, double* Jr) {
   for (int i = 0; i < 9; ++i) Jr[i] = (i % 4 == 0 ? 1.0 : 0.0) - a * W[i] + b * W2[i];
 }
 
-void integrate(double* p, const double* smp, const double* acc_cov, const double* gyro_cov, const double* int_cov) {
+// Aout [81], Gout [9 x 6], cov2 [81] (may be null), for the 15 x 15 recursion of vus_imu_preintegrate_combined: the sample's
+// A and G = [B | C], and a second 9 x 9 covariance that takes the same step A cov2 A^T + Q9 as the record's, sum for sum
+void integrate(double* p, const double* smp, const double* acc_cov, const double* gyro_cov, const double* int_cov,
+               double* Aout = nullptr, double* Gout = nullptr, double* cov2 = nullptr) {
   const double dt = smp[6];
   const double a[3] = {smp[0] - p[BIAS], smp[1] - p[BIAS + 1], smp[2] - p[BIAS + 2]};
   const double w[3] = {(smp[3] - p[BIAS + 3]) * dt, (smp[4] - p[BIAS + 4]) * dt, (smp[5] - p[BIAS + 5]) * dt};
@@ -854,32 +730,39 @@ void integrate(double* p, const double* smp, const double* acc_cov, const double
       Cm[3 * r + c] = dt * Jr[3 * r + c];
     }
   for (int r = 0; r < 3; ++r) A[9 * (3 + r) + 6 + r] = dt;
-  double* cov = p + COV;
-  double T[81], N[81];
-  for (int r = 0; r < 9; ++r)
-    for (int c = 0; c < 9; ++c) {
-      double v = 0.0;
-      for (int k = 0; k < 9; ++k) v += A[9 * r + k] * cov[9 * k + c];
-      T[9 * r + c] = v;
-    }
-  for (int r = 0; r < 9; ++r)
-    for (int c = 0; c < 9; ++c) {
-      double v = 0.0;
-      for (int k = 0; k < 9; ++k) v += T[9 * r + k] * A[9 * c + k];
-      N[9 * r + c] = v;
-    }
-  auto add_noise = [&](const double* G, const double* Q) {      // N += G (Q / dt) G^T, G 9x3
-    double GQ[27];
+  if (Aout) std::memcpy(Aout, A, sizeof(A));
+  if (Gout)
     for (int r = 0; r < 9; ++r)
-      for (int c = 0; c < 3; ++c) GQ[3 * r + c] = (G[3 * r] * Q[c] + G[3 * r + 1] * Q[3 + c] + G[3 * r + 2] * Q[6 + c]) / dt;
+      for (int c = 0; c < 3; ++c) { Gout[6 * r + c] = Bm[3 * r + c]; Gout[6 * r + 3 + c] = Cm[3 * r + c]; }
+  auto propagate = [&](double* cov) {      // cov <- A cov A^T + Q9
+    double T[81], N[81];
     for (int r = 0; r < 9; ++r)
-      for (int c = 0; c < 9; ++c) N[9 * r + c] += GQ[3 * r] * G[3 * c] + GQ[3 * r + 1] * G[3 * c + 1] + GQ[3 * r + 2] * G[3 * c + 2];
+      for (int c = 0; c < 9; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 9; ++k) v += A[9 * r + k] * cov[9 * k + c];
+        T[9 * r + c] = v;
+      }
+    for (int r = 0; r < 9; ++r)
+      for (int c = 0; c < 9; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 9; ++k) v += T[9 * r + k] * A[9 * c + k];
+        N[9 * r + c] = v;
+      }
+    auto add_noise = [&](const double* G, const double* Q) {      // N += G (Q / dt) G^T, G 9x3
+      double GQ[27];
+      for (int r = 0; r < 9; ++r)
+        for (int c = 0; c < 3; ++c) GQ[3 * r + c] = (G[3 * r] * Q[c] + G[3 * r + 1] * Q[3 + c] + G[3 * r + 2] * Q[6 + c]) / dt;
+      for (int r = 0; r < 9; ++r)
+        for (int c = 0; c < 9; ++c) N[9 * r + c] += GQ[3 * r] * G[3 * c] + GQ[3 * r + 1] * G[3 * c + 1] + GQ[3 * r + 2] * G[3 * c + 2];
+    };
+    add_noise(Bm, acc_cov);
+    add_noise(Cm, gyro_cov);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) N[9 * (3 + r) + 3 + c] += int_cov[3 * r + c] * dt;
+    std::memcpy(cov, N, sizeof(N));
   };
-  add_noise(Bm, acc_cov);
-  add_noise(Cm, gyro_cov);
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) N[9 * (3 + r) + 3 + c] += int_cov[3 * r + c] * dt;
-  std::memcpy(cov, N, sizeof(N));
+  propagate(p + COV);
+  if (cov2) propagate(cov2);
   // bias Jacobians, then the deltas (every update uses the OLD dR, dV)
   double t[9], tmp[9];
   mul33(RaX, p + DR_DBG, t);
@@ -902,27 +785,66 @@ void integrate(double* p, const double* smp, const double* acc_cov, const double
   p[DT] += dt;
 }
 
-// W = L^-1, cov = L L^T
+// W = L^-1, cov = L L^T (N x N); W is written only when cov is positive definite
+template <int N>
 bool whitening(const double* cov, double* W) {
-  double L[81] = {0.0};
-  for (int c = 0; c < 9; ++c) {
-    double d = cov[10 * c];
-    for (int k = 0; k < c; ++k) d -= L[9 * c + k] * L[9 * c + k];
+  double L[N * N] = {0.0};
+  for (int c = 0; c < N; ++c) {
+    double d = cov[(N + 1) * c];
+    for (int k = 0; k < c; ++k) d -= L[N * c + k] * L[N * c + k];
     if (!(d > 0.0)) return false;
-    L[10 * c] = std::sqrt(d);
-    for (int r = c + 1; r < 9; ++r) {
-      double v = cov[9 * r + c];
-      for (int k = 0; k < c; ++k) v -= L[9 * r + k] * L[9 * c + k];
-      L[9 * r + c] = v / L[10 * c];
+    L[(N + 1) * c] = std::sqrt(d);
+    for (int r = c + 1; r < N; ++r) {
+      double v = cov[N * r + c];
+      for (int k = 0; k < c; ++k) v -= L[N * r + k] * L[N * c + k];
+      L[N * r + c] = v / L[(N + 1) * c];
     }
   }
-  for (int c = 0; c < 9; ++c)          // column c of L^-1 by forward substitution
-    for (int r = 0; r < 9; ++r) {
+  for (int c = 0; c < N; ++c)          // column c of L^-1 by forward substitution
+    for (int r = 0; r < N; ++r) {
       double v = (r == c) ? 1.0 : 0.0;
-      for (int k = 0; k < r; ++k) v -= L[9 * r + k] * W[9 * k + c];
-      W[9 * r + c] = v / L[10 * r];
+      for (int k = 0; k < r; ++k) v -= L[N * r + k] * W[N * k + c];
+      W[N * r + c] = v / L[(N + 1) * r];
     }
   return true;
+}
+
+// One sample of the 15 x 15 recursion Sigma <- F Sigma F^T + Q, F = [[A, G], [0, I]], around pim::integrate: with
+// Sigma = [[S, C], [C^T, V]] the record's own update gives A S A^T + Q9 in ITS summation order (so V = C = 0 leaves the
+// record's covariance bit for bit), then S += A C G^T + (A C G^T)^T + G V G^T, C <- A C + G V, V += bias covariances * dt.
+void integrate_combined(double* p, double* S15, const double* smp, const double* acc_cov, const double* gyro_cov,
+                        const double* int_cov, const double* ba_cov, const double* bg_cov) {
+  double S9[81], A[81], G[54];
+  for (int r = 0; r < 9; ++r)
+    for (int c = 0; c < 9; ++c) S9[9 * r + c] = S15[15 * r + c];
+  integrate(p, smp, acc_cov, gyro_cov, int_cov, A, G, S9);     // the record as vus_imu_preintegrate leaves it; S9 = A S A^T + Q9
+  const double dt = smp[6];
+  double C[54], V[36], AC[54], GV[54];
+  for (int r = 0; r < 9; ++r)
+    for (int c = 0; c < 6; ++c) C[6 * r + c] = S15[15 * r + 9 + c];
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) V[6 * r + c] = S15[15 * (9 + r) + 9 + c];
+  for (int r = 0; r < 9; ++r)
+    for (int c = 0; c < 6; ++c) {
+      double ac = 0.0, gv = 0.0;
+      for (int k = 0; k < 9; ++k) ac += A[9 * r + k] * C[6 * k + c];
+      for (int k = 0; k < 6; ++k) gv += G[6 * r + k] * V[6 * k + c];
+      AC[6 * r + c] = ac;
+      GV[6 * r + c] = gv;
+    }
+  for (int r = 0; r < 9; ++r)
+    for (int c = 0; c < 9; ++c) {
+      double x = 0.0;      // (A C G^T)[r][c] + (A C G^T)[c][r] + (G V G^T)[r][c]
+      for (int k = 0; k < 6; ++k) x += AC[6 * r + k] * G[6 * c + k] + AC[6 * c + k] * G[6 * r + k] + GV[6 * r + k] * G[6 * c + k];
+      S15[15 * r + c] = S9[9 * r + c] + x;
+    }
+  for (int r = 0; r < 9; ++r)
+    for (int c = 0; c < 6; ++c) S15[15 * r + 9 + c] = S15[15 * (9 + c) + r] = AC[6 * r + c] + GV[6 * r + c];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      S15[15 * (9 + r) + 9 + c] += ba_cov[3 * r + c] * dt;
+      S15[15 * (12 + r) + 12 + c] += bg_cov[3 * r + c] * dt;
+    }
 }
 }  // namespace pim
 }  // namespace
@@ -935,6 +857,39 @@ extern "C" int vus_imu_preintegrate(double* pim_rec, const double* samples, int 
     VUS_REQUIRE(samples[7 * i + 6] > 0.0, "sample %d: dt=%g is not positive", i, samples[7 * i + 6]);
     pim::integrate(pim_rec, samples + 7 * (size_t)i, acc_cov, gyro_cov, int_cov);
   }
-  if (whiten) VUS_REQUIRE(pim::whitening(pim_rec + pim::COV, whiten), "preintegrated covariance is not positive definite");
+  if (whiten) VUS_REQUIRE(pim::whitening<9>(pim_rec + pim::COV, whiten), "preintegrated covariance is not positive definite");
+  return VUS_OK;
+}
+
+extern "C" int vus_imu_preintegrate_combined(double* pim_rec, double* cov15, const double* samples, int n, const double* acc_cov,
+                                             const double* gyro_cov, const double* int_cov, const double* bias_acc_cov,
+                                             const double* bias_omega_cov, double* whiten) {
+  VUS_REQUIRE(pim_rec && cov15 && acc_cov && gyro_cov && int_cov && bias_acc_cov && bias_omega_cov, "null buffer");
+  VUS_REQUIRE(n >= 0 && (samples != nullptr || n == 0), "n=%d", n);
+  for (int i = 0; i < n; ++i) {
+    VUS_REQUIRE(samples[7 * i + 6] > 0.0, "sample %d: dt=%g is not positive", i, samples[7 * i + 6]);
+    pim::integrate_combined(pim_rec, cov15, samples + 7 * (size_t)i, acc_cov, gyro_cov, int_cov, bias_acc_cov, bias_omega_cov);
+  }
+  if (whiten) {       // of the RESIDUAL's covariance T cov15 T^T, T = diag(I, dR^T, dR^T, I, I): its p and v rows are in frame j
+    const double* dR = pim_rec + pim::DR;
+    double T[225] = {0.0}, TS[225], Sr[225];
+    for (int k = 0; k < 15; ++k) T[16 * k] = 1.0;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) T[15 * (3 + r) + 3 + c] = T[15 * (6 + r) + 6 + c] = dR[3 * c + r];
+    for (int r = 0; r < 15; ++r)
+      for (int c = 0; c < 15; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 15; ++k) v += T[15 * r + k] * cov15[15 * k + c];
+        TS[15 * r + c] = v;
+      }
+    for (int r = 0; r < 15; ++r)
+      for (int c = 0; c < 15; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 15; ++k) v += TS[15 * r + k] * T[15 * c + k];
+        Sr[15 * r + c] = v;
+      }
+    VUS_REQUIRE(pim::whitening<15>(Sr, whiten), "combined preintegrated covariance is not positive definite (a zero bias "
+                "covariance leaves its bias block singular)");
+  }
   return VUS_OK;
 }

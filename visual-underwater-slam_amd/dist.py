@@ -190,8 +190,11 @@ class ShardedStereoBASolver:
 
     def __init__(self, obs_pose, obs_point, meas, n_poses, n_points, K, sigma, prior_pose=None, prior_T=None,
                  prior_sigmas=None, device="cuda:0", loss=None, between=None, body_P_sensor=None, mono=None,
-                 point_priors=None, pose_meas=None, window_prior=None):
+                 point_priors=None, pose_meas=None, window_prior=None, combined=None):
         from .ba import StereoBAProblem, StereoBASolver
+        if combined is not None:
+            raise NotImplementedError("CombinedImuFactor (ba.CombinedImuFactors) is not supported by the landmark-sharded "
+                                      "solver: use NavBiasBASolver(problem, nav, combined=...) on one GPU")
         if window_prior is not None:
             single = "NavBiasBASolver" if type(window_prior).__name__ == "NavWindowPrior" else "StereoBASolver"
             raise NotImplementedError(f"a dense prior over a window (ba.{type(window_prior).__name__}) is not supported by the "

@@ -13,7 +13,8 @@ runs on the MI355X kernels (ba.py / csrc/ba.hip).
 Scope: GenericStereoFactor3D, GenericProjectionFactorCal3_S2, PriorFactorPose3, PriorFactorVector,
 the partial absolute measurements on a pose GPSFactor, GPSFactorArm, PoseTranslationPrior3D and PoseRotationPrior3D
 (position, position of a transponder off the body origin, attitude; include/vus_pose_meas.h), ImuFactor (with
-PreintegratedImuMeasurements) and the DVL velocity factor (DvlVelocityFactor, the well-formed
+PreintegratedImuMeasurements), CombinedImuFactor (with PreintegratedCombinedMeasurements; one bias per keyframe,
+include/vus_combined_imu.h) and the DVL velocity factor (DvlVelocityFactor, the well-formed
 replacement of the reference's CustomFactor) are solved on the GPU.  A generic gtsam.CustomFactor
 (arbitrary Python callback) can be constructed and added, but optimize() refuses it, loudly.
 
@@ -33,7 +34,8 @@ from .symbol_shorthand import symbol, symbolChr, symbolIndex  # noqa: F401
 __all__ = [
     "Point3", "Rot3", "Pose3", "Cal3_S2Stereo", "Cal3_S2", "StereoPoint2", "noiseModel", "imuBias",
     "GenericStereoFactor3D", "PriorFactorPose3", "PriorFactorVector", "PriorFactorPoint3",
-    "PriorFactorConstantBias", "BetweenFactorConstantBias", "BetweenFactorPose3", "ImuFactor", "CustomFactor", "DvlVelocityFactor",
+    "PriorFactorConstantBias", "BetweenFactorConstantBias", "BetweenFactorPose3", "ImuFactor", "CombinedImuFactor", "PreintegrationCombinedParams",
+    "PreintegratedCombinedMeasurements", "CustomFactor", "DvlVelocityFactor",
     "PreintegrationParams", "PreintegratedImuMeasurements", "NavState", "ISAM2", "ConstantTwistScenario",
     "PinholeCameraCal3_S2",
     "NonlinearFactorGraph", "Values", "LevenbergMarquardtParams", "LevenbergMarquardtOptimizer",
@@ -1067,6 +1069,93 @@ class ImuFactor(_Factor):
         self.pim = pim._pre.packed()
         self.W = pim._pre.whitening().reshape(-1)
         self.gravity = np.asarray(pim.params.n_gravity, dtype=float).copy()
+
+
+class PreintegrationCombinedParams(PreintegrationParams):
+    """gtsam.PreintegrationCombinedParams: PreintegrationParams plus the continuous-time bias random walk.  STATED DEVIATION:
+    the uncertainty of the bias estimate used during preintegration (biasAccOmegaInt in gtsam 4.0 / 4.1, biasAccOmegaInit in
+    4.2) is not modelled; its default here is zero (upstream 4.0: the identity) and its setters accept only zero."""
+
+    def __init__(self, n_gravity):
+        super().__init__(n_gravity)
+        self.biasAccCovariance = np.eye(3)
+        self.biasOmegaCovariance = np.eye(3)
+        self.biasAccOmegaInt = np.zeros((6, 6))
+
+    @staticmethod
+    def MakeSharedU(g=9.81):
+        return PreintegrationCombinedParams([0.0, 0.0, -float(g)])
+
+    @staticmethod
+    def MakeSharedD(g=9.81):
+        return PreintegrationCombinedParams([0.0, 0.0, float(g)])
+
+    def setBiasAccCovariance(self, c):
+        self.biasAccCovariance = np.asarray(c, dtype=float)
+
+    def setBiasOmegaCovariance(self, c):
+        self.biasOmegaCovariance = np.asarray(c, dtype=float)
+
+    def _set_bias_init(self, c, setter):
+        c = np.asarray(c, dtype=float)
+        if c.shape != (6, 6):
+            raise RuntimeError(f"{setter}: a 6 x 6 matrix is expected, not an array of shape {c.shape}")
+        if c.any():
+            raise NotImplementedError(f"{setter}: the uncertainty of the bias estimate used during preintegration is not "
+                                      "modelled by the combined preintegration; only the all-zero matrix is accepted")
+        self.biasAccOmegaInt = np.zeros((6, 6))
+
+    def setBiasAccOmegaInt(self, c):                                     # gtsam 4.0 / 4.1
+        self._set_bias_init(c, "setBiasAccOmegaInt")
+
+    def setBiasAccOmegaInit(self, c):                                    # gtsam 4.2
+        self._set_bias_init(c, "setBiasAccOmegaInit")
+
+
+class PreintegratedCombinedMeasurements(PreintegratedImuMeasurements):
+    """gtsam.PreintegratedCombinedMeasurements(params, bias): the preintegration of PreintegratedImuMeasurements with the bias
+    random walk of the same interval; preintMeasCov() is 15 x 15 in the error order (theta, p, v, b_a, b_g) (imu.py)."""
+
+    def __init__(self, params: PreintegrationCombinedParams, bias: Optional[_ConstantBias] = None):
+        from .imu import CombinedPreintegrator
+        if not isinstance(params, PreintegrationCombinedParams):
+            raise RuntimeError("PreintegratedCombinedMeasurements needs PreintegrationCombinedParams")
+        self.params, self.bias = params, bias or _ConstantBias()
+        self._pre = CombinedPreintegrator(self.bias.vector(), params.accelerometerCovariance, params.gyroscopeCovariance,
+                                          params.integrationCovariance, params.biasAccCovariance, params.biasOmegaCovariance)
+
+    def preintMeasCov(self):
+        return self._pre.cov15.copy()
+
+
+class CombinedImuFactor(_Factor):
+    """CombinedImuFactor(pose_i, vel_i, pose_j, vel_j, bias_i, bias_j, pim): the IMU measurement and the bias walk of one
+    keyframe interval as ONE 15-row factor under the full covariance of pim (include/vus_combined_imu.h).  Like gtsam, the
+    factor copies the preintegrated measurement at construction.  Its noise model is that covariance and nothing else."""
+
+    def __init__(self, pose_i, vel_i, pose_j, vel_j, bias_i, bias_j, pim: PreintegratedCombinedMeasurements, model=None):
+        super().__init__([pose_i, vel_i, pose_j, vel_j, bias_i, bias_j])
+        if model is not None:
+            self.cloneWithNewNoiseModel(model)
+        if not isinstance(pim, PreintegratedCombinedMeasurements):
+            raise RuntimeError("CombinedImuFactor needs PreintegratedCombinedMeasurements")
+        if int(bias_i) == int(bias_j):
+            raise NotImplementedError(f"CombinedImuFactor: bias_i and bias_j are both {symbol_shorthand.key_string(int(bias_i))} -- that is the "
+                                      "shared-bias layout, where a bias cannot walk; give the factor B(i) and B(i+1), or use "
+                                      "ImuFactor with the one shared bias")
+        if pim._pre.dt <= 0.0:
+            raise RuntimeError("CombinedImuFactor: the preintegrated interval is empty (no IMU sample between the keyframes)")
+        if pim.params.use2ndOrderCoriolis or np.any(pim.params.omegaCoriolis != 0):
+            raise NotImplementedError("Coriolis terms are not implemented (batch.py:186-187 disables them)")
+        self.pim = pim._pre.packed()
+        self.W = pim._pre.whitening().reshape(-1)
+        self.cov = pim._pre.cov15.copy()
+        self.gravity = np.asarray(pim.params.n_gravity, dtype=float).copy()
+
+    def cloneWithNewNoiseModel(self, model):
+        kind = "a robust noise model" if isinstance(model, _Robust) else "a replaced noise model"
+        raise NotImplementedError(f"CombinedImuFactor: {kind} is not supported -- the factor whitens with the 15 x 15 covariance "
+                                  "of its PreintegratedCombinedMeasurements")
 
 
 class DvlVelocityFactor(_Factor):

@@ -153,13 +153,13 @@ def _pack_graph(graph, values, device=None, per_keyframe=False):
     from . import (GenericStereoFactor3D, StereoFactorBlock, PriorFactorPose3, PriorFactorVector, Pose3,
                    ImuFactor, CustomFactor, DvlVelocityFactor, _ConstantBias, PriorFactorConstantBias,
                    BetweenFactorConstantBias, BetweenFactorPose3, GenericProjectionFactorCal3_S2, ProjectionFactorBlock,
-                   _PoseMeasFactor, LinearContainerFactor)
+                   _PoseMeasFactor, LinearContainerFactor, CombinedImuFactor)
     container = None
     meas, pkeys, lkeys = [], [], []
     mono_n = []                     # per part of meas / pkeys / lkeys: 0 for a stereo part, its length for a mono part
     mono = dict(sigma=None, calib=None, loss=None, sensor=None)
     between_f, pose_meas_f = [], []
-    imu_f, dvl_f, bias_f = [], [], []
+    imu_f, dvl_f, bias_f, cimu_f = [], [], [], []
     from . import _Robust
     from . import _same_sensor
     model_sigma, calib, loss, sensor = None, None, None, None
@@ -234,6 +234,8 @@ def _pack_graph(graph, values, device=None, per_keyframe=False):
             prior_vec.append(f)
         elif isinstance(f, ImuFactor):
             imu_f.append(f)
+        elif isinstance(f, CombinedImuFactor):
+            cimu_f.append(f)
         elif isinstance(f, DvlVelocityFactor):
             dvl_f.append(f)
         elif isinstance(f, (PriorFactorConstantBias, BetweenFactorConstantBias)):
@@ -343,13 +345,13 @@ def _pack_graph(graph, values, device=None, per_keyframe=False):
     elif container is not None:     # -> ba.WindowPrior: (first pose index, x0 [m, 12], H, gradient, constant)
         window = dict(zip(("first", "x0", "H", "g", "c"), container._window(pose_keys)))
     nav = None
-    if imu_f or dvl_f or bias_f or nav_window is not None:
+    if imu_f or dvl_f or bias_f or cimu_f or nav_window is not None:
         if window is not None:
             raise NotImplementedError("a LinearContainerFactor over Pose3 keys next to inertial factors (ImuFactor, "
                                       "DvlVelocityFactor, bias factors) is not supported: that dense prior serves the pose-only "
                                       "layout; an inertial window takes one over X(i), V(i), B(i)")
         nav, prior_vec = _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f,
-                                   per_keyframe=per_keyframe or nav_window is not None)
+                                   per_keyframe=per_keyframe or nav_window is not None, cimu_f=cimu_f)
     aux = _AuxPriors()
     pp_idx, pp_mean, pp_sig = [], [], []
     for f in prior_vec:
@@ -420,10 +422,11 @@ def _pack_pose_meas(pose_keys, pose_meas_f):
                 sigmas=np.asarray(sig, float).reshape(-1, 3), losses=losses, keys=np.asarray(keys, np.int64))
 
 
-def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyframe=False):
+def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyframe=False, cimu_f=()):
     """Velocity / bias side of the graph (batch.py:274-293): every pose X(i) needs a velocity V(i) with the same
     index; either one shared bias key (batch.py:238 passes B(0) to every ImuFactor) or, when the graph has bias factors
-    or several bias keys or `per_keyframe` asks for it, one bias B(i) per keyframe (_pack_bias_walk)."""
+    or several bias keys or a CombinedImuFactor (`cimu_f`, packed by _pack_combined) or `per_keyframe` asks for it, one bias
+    B(i) per keyframe (_pack_bias_walk)."""
     from . import _ConstantBias
     pidx = {int(k): i for i, k in enumerate(pose_keys.tolist())}
     vel_keys = []
@@ -437,7 +440,7 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyfram
     if vels.shape[1] != 3:
         raise RuntimeError("velocity variables must be 3-vectors")
     bias_keys = sorted({f._keys[4] for f in imu_f})
-    per_keyframe = bool(per_keyframe) or bool(bias_f) or len(bias_keys) > 1
+    per_keyframe = bool(per_keyframe) or bool(bias_f) or len(bias_keys) > 1 or bool(cimu_f)
     if per_keyframe:
         bias_keys, biases, bbetween, bprior = _pack_bias_walk(values, pose_keys, imu_f, bias_f)
     bias_key = bias_keys[0] if bias_keys and not per_keyframe else None
@@ -455,6 +458,9 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyfram
             raise NotImplementedError("all ImuFactors must share one gravity vector")
         grav = f.gravity
         imu_i.append(pidx[ki]); imu_j.append(pidx[kj]); pims.append(f.pim); Ws.append(f.W)
+    combined = None
+    if cimu_f:
+        combined, grav = _pack_combined(cimu_f, pidx, vidx, bias_keys, grav)
     dvl_p, dvl_m, dvl_s = [], [], []
     for f in dvl_f:
         kv, kx = f._keys
@@ -470,7 +476,7 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyfram
             rest.append(f)
     nav = dict(vel_keys=vel_keys, bias_key=bias_key, vels=vels, bias=bias, per_keyframe=per_keyframe,
                bias_keys=bias_keys if per_keyframe else None, bbetween=bbetween if per_keyframe else None,
-               bprior=bprior if per_keyframe else None,
+               bprior=bprior if per_keyframe else None, combined=combined,
                gravity=grav if grav is not None else np.array([0.0, 0.0, -9.81]),
                imu=(np.asarray(imu_i, np.int32), np.asarray(imu_j, np.int32), np.asarray(pims, float).reshape(-1, 148),
                     np.asarray(Ws, float).reshape(-1, 81)) if imu_f else None,
@@ -478,6 +484,30 @@ def _pack_nav(values, pose_keys, imu_f, dvl_f, prior_vec, bias_f=(), per_keyfram
                vprior=(np.asarray(vp_i, np.int32), np.asarray(vp_v, float).reshape(-1, 3),
                        np.asarray(vp_s, float).reshape(-1, 3)) if vp_i else None)
     return nav, rest
+
+
+def _pack_combined(cimu_f, pidx, vidx, bias_keys, grav):
+    """CombinedImuFactor -> (i [n], pim [n, 148], W [n, 225]) for ba.CombinedImuFactors and the graph's gravity: every
+    factor on X(i), V(i), X(i+1), V(i+1), B(i), B(i+1) of consecutive keyframes.  Anything else is refused with the reason."""
+    name = _sym.key_string
+    ci, pims, Ws = [], [], []
+    for f in cimu_f:
+        ki, kvi, kj, kvj, kbi, kbj = f._keys
+        what = f"CombinedImuFactor({name(ki)}, {name(kvi)}, {name(kj)}, {name(kvj)}, {name(kbi)}, {name(kbj)})"
+        if ki not in pidx or kj not in pidx or vidx.get(kvi) != pidx[ki] or vidx.get(kvj) != pidx[kj]:
+            raise RuntimeError(f"{what}: its pose / velocity keys are not X(i), V(i), X(j), V(j) of the Values")
+        i, j = pidx[ki], pidx[kj]
+        if j != i + 1:
+            raise NotImplementedError(f"{what}: a CombinedImuFactor between non-consecutive keyframes is not supported (the "
+                                      "band holds the couplings of neighbouring keyframes only)")
+        if kbi != bias_keys[i] or kbj != bias_keys[j]:
+            raise NotImplementedError(f"{what}: its biases must be {name(bias_keys[i])} and {name(bias_keys[j])}, the biases of "
+                                      "its two keyframes")
+        if grav is not None and not np.array_equal(grav, f.gravity):
+            raise NotImplementedError("all ImuFactors and CombinedImuFactors must share one gravity vector")
+        grav = f.gravity
+        ci.append(i); pims.append(f.pim); Ws.append(f.W)
+    return (np.asarray(ci, np.int32), np.asarray(pims, float).reshape(-1, 148), np.asarray(Ws, float).reshape(-1, 225)), grav
 
 
 def _pack_bias_walk(values, pose_keys, imu_f, bias_f):
@@ -542,7 +572,7 @@ def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
     the band follows the rest.  min_span: the band is at least this many poses wide (a fixed-lag smoother's sub-problem,
     whose marginal must fit the band); a LinearContainerFactor's width feeds the band in the same way."""
     from ..ba import (StereoBAProblem, StereoBASolver, NavBASolver, NavFactors, NavBiasBASolver, NavBiasFactors,
-                      BetweenFactors, PointPriors, PoseMeasurements, WindowPrior, NavWindowPrior)
+                      BetweenFactors, PointPriors, PoseMeasurements, WindowPrior, NavWindowPrior, CombinedImuFactors)
     nav = pg.get("nav")
     btw = pg.get("between")
     walk = bool(nav) and nav.get("per_keyframe", False)
@@ -558,12 +588,14 @@ def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
     # an inertial prior over m keyframes needs 3 m - 1 nodes (B of the last against X of the first): m poses' worth
     between_span = max(between_span, int(min_span), len(win["x0"]) - 1 if win is not None else 0,
                        len(nwin["x0"]) if nwin is not None else 0)
+    cimu = nav.get("combined") if nav else None
+    extra = dict(combined_imu=True) if cimu is not None else {}         # without one the problem is built as before
     prob =StereoBAProblem(pg["pose_idx"], pg["lm_idx"], pg["meas"], n_poses, len(pg["lm_keys"]),
                            pg["K"], pg["sigma"], prior_pose=pg["prior_idx"], prior_T=pg["prior_T"],
                            prior_sigmas=pg["prior_sigmas"], device=device, pose_stride=stride,
                            loss=pg.get("loss"), between_span=between_span,
                            body_P_sensor=pg.get("body_P_sensor"), mono=pg.get("mono"), mono_K=pg.get("mono_K"),
-                           mono_sigma=pg.get("mono_sigma"))
+                           mono_sigma=pg.get("mono_sigma"), **extra)
     # a factor the landmark band already covers stays in the band whatever long_span says
     max_span = None if long_span is None else max(int(long_span), prob.band // stride)
     bf = BetweenFactors(btw["i"], btw["j"], btw["meas"], btw["sigmas"], n_poses, pose_stride=stride,
@@ -579,7 +611,10 @@ def _build_solver(pg, device="cuda:0", long_span=None, min_span=0):
                             bprior=nav["bprior"], device=device)
         nw = NavWindowPrior(nwin["first"], nwin["x0"], nwin["v0"], nwin["b0"], nwin["H"], nwin["g"], nwin["c"], n_poses,
                             device=device) if nwin is not None else None
-        return prob, NavBiasBASolver(prob, nf, bf, pf, mf, window_prior=nw)
+        if cimu is None:
+            return prob, NavBiasBASolver(prob, nf, bf, pf, mf, window_prior=nw)
+        cf = CombinedImuFactors(nav["gravity"], cimu[0], cimu[1], cimu[2], device=device)
+        return prob, NavBiasBASolver(prob, nf, bf, pf, mf, window_prior=nw, combined=cf)
     if nav:
         nf = NavFactors(nav["gravity"], imu=nav["imu"], dvl=nav["dvl"], vprior=nav["vprior"], device=device)
         return prob, NavBASolver(prob, nf, bf, pf, mf)
@@ -602,6 +637,8 @@ def graph_error(graph, values) -> float:
     if pg.get("nav"):
         vels, bias = torch.from_numpy(pg["nav"]["vels"]).to(dev), torch.from_numpy(pg["nav"]["bias"]).to(dev)
         e += sv.nav_error(poses, vels, bias)
+        if pg["nav"].get("combined") is not None:
+            e += sv.cimu_error(poses, vels, bias)
         if pg.get("nav_window_prior") is not None:
             e += sv.nav_window_prior_error(poses, vels, bias)
     return e + pg["aux"].error()

@@ -137,6 +137,10 @@ class BatchFixedLagSmoother:
         t0 = time.perf_counter()
         new = list(newFactors._factors) if newFactors is not None else []
         for f in new:
+            if isinstance(f, _g.CombinedImuFactor):
+                raise NotImplementedError("BatchFixedLagSmoother: CombinedImuFactor is not supported -- marginalising keyframes "
+                                          "out of a graph that holds one is not implemented; use ImuFactor and "
+                                          "BetweenFactorConstantBias in the smoother")
             if isinstance(f, _g.CustomFactor):
                 raise NotImplementedError(f"BatchFixedLagSmoother: {type(f).__name__} is not supported -- of the inertial "
                                           "factors the smoother takes ImuFactor, DvlVelocityFactor and the bias factors")
